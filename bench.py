@@ -2,6 +2,16 @@
 """Benchmark of the per-pixel ray-trace path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dragon|demo] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
+
+A plain run measures the headline and nothing else: it sets up, warms up, times the K steps, writes the
+outputs of the last timed step when --dump-outputs is given (DIR/accumulation.npy: the HDR accumulation
+image a caller of Renderer.render() reads, float32 H x W x 4 -- a seeded pixel sample where the image is
+above 48 MiB, with DIR/accumulation_pixel_index.npy; DIR/ray_counts.npy: rays, hits, misses and pixels of
+the timed steps, float64; elements that are not finite -- a long run can leave NaN pixels, as the reference
+does -- are written as 0 and listed in DIR/<name>_nonfinite.npy), and prints the one JSON line.  Everything else described below (the
+secondary workloads, the forest leg, the roofline and its counter passes, the CPU baseline, the N > 1
+gather check) runs only with --full.
 
 One STEP = one pass of the hot path over one batch of input: FRAMES_PER_STEP = 16 consecutive
 Renderer.render() frames (raytrace + accumulate passes, 1 sample per pixel each, whole image, 8
@@ -24,7 +34,7 @@ N ways.  `--scaling weak` grows the image with N instead (N=2: 1920x2160, N=4: 3
 N=8: 3840x4320) so that every GPU always renders 1920x1080 pixels per frame.
 
 Prints ONE JSON line on rank 0: metric Mrays/s (rays = raySceneIntersect calls, counted exactly
-by the kernel), plus
+by the kernel), plus, with --full,
   roofline     : the dominant kernel (the persistent raytrace kernel) against the roof that binds it.
                  It is NOT HBM-bound on this workload (the 181 MB scene sits in the 256 MiB Infinity
                  Cache; the algorithmic byte rate SURVEY.md 8(d) defines exceeds the HBM peak): what
@@ -495,6 +505,42 @@ def roofline_block(m, pmc, source, num_cus):
     return block
 
 
+DUMP_IMAGE_BYTES = 48 << 20     # --dump-outputs: above this the accumulation image is written as a seeded sample of its pixels
+NONFINITE_LISTED = 1 << 19      # --dump-outputs: non-finite elements listed one by one (16 bytes each), at most
+
+
+def write_outputs(directory, outputs):
+    """--dump-outputs: DIR/<name>.npy for each array of the last timed step.  An accumulation image larger than DUMP_IMAGE_BYTES
+    (weak scaling at N >= 4) is cut to a fixed sample of its pixels (seed 0, sorted), with the row-major pixel indices beside it.
+    Non-finite elements are written as 0 and recorded in DIR/<name>_nonfinite.npy (only written when there are any)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = dict(outputs)
+    image = arrays["accumulation"]
+    if image.nbytes > DUMP_IMAGE_BYTES:
+        flat = image.reshape(-1, image.shape[-1])
+        n = DUMP_IMAGE_BYTES // (flat.shape[1] * flat.itemsize + 8)          # (the pixel and its float64 index)
+        index = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=n, replace=False))
+        arrays["accumulation"] = np.ascontiguousarray(flat[index])
+        arrays["accumulation_pixel_index"] = index.astype(np.float64)
+    for name, a in list(arrays.items()):
+        bad = ~np.isfinite(a)
+        if bad.any():
+            # the reference's own arithmetic can leave NaN in a pixel for good (rand() == 0 in its Box-Muller step: log(0)), and the
+            # project keeps its bits: such elements are written as 0 and listed exactly beside the array -- flat element index and
+            # 1 = NaN, 2 = +inf, 3 = -inf -- so that every written value is finite and nothing is lost
+            flat = a.reshape(-1)
+            where = np.flatnonzero(bad)
+            code = np.where(np.isnan(flat[where]), 1.0, np.where(flat[where] > 0, 2.0, 3.0))
+            listed = np.stack([where.astype(np.float64), code], axis=1)
+            if len(listed) > NONFINITE_LISTED:        # (a broken build: the first ones, then a row (-1, how many in all))
+                listed = np.concatenate([listed[:NONFINITE_LISTED], [[-1.0, float(len(listed))]]])
+            arrays[name + "_nonfinite"] = listed
+            arrays[name] = np.where(bad, np.zeros((), a.dtype), a)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher around it (round-5 verdict: that command died here).  This process
     becomes the launcher and never touches the GPU: it builds (compilers only), picks a free rendezvous port on 127.0.0.1 and
@@ -555,6 +601,10 @@ def main():
     ap.add_argument("--workload", default="dragon", choices=["demo", "dragon", "closeup", "forest"])
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"])
     ap.add_argument("--variant", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements and checks: demo / close-up / presenting legs, the "
+                                                        "forest leg, the roofline with its rocprofv3 counter passes, the CPU baseline, the N > 1 "
+                                                        "gather check (the --no-* options below switch single ones off again)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (children of this process)")
     ap.add_argument("--no-also", action="store_true", help="skip the secondary measurements (demo scene, close-up camera)")
@@ -651,9 +701,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(workload, steps, warmup, gather, size=None, present=False):
+    def measure(workload, steps, warmup, gather, size=None, present=False, outputs=False):
         """The timed job for one workload: `warmup` untimed steps, then EXACTLY `steps` steps of 16 frames
-        (+ the one gather when N > 1) between barrier + synchronize on both sides."""
+        (+ the one gather when N > 1) between barrier + synchronize on both sides.  outputs: rank 0 keeps what the last
+        timed step left for a caller (the whole accumulation image, gathered, and the ray counts) in m["outputs"]."""
         width, height = size or (base_width, base_height)
         stream = torch.cuda.Stream()       # the context's main stream
         tile_rank, tile_world = (int(v) for v in args.tile.split("/")) if args.tile else (rank, world)
@@ -771,11 +822,24 @@ def main():
                        + f"; lean build, {waves if waves else 'five or six'} waves per SIMD" + (" (80 registers: launches of >= 1.5 M jobs)" if waves == 6 else " (96 registers)" if waves == 5 else "")
                        + "; YMAX = the one-axis culling condition where the scene's margins allow it; batched frames)")
         m["lean"], m["waves_per_simd"], m["workgroups"] = last["lean"], waves, wg
+        if outputs and rank == 0:
+            import numpy as np
+            from mi3pt_host import tiles
+            if use_group:
+                image = ctx.read_texture(capi.TEX_ACCUMULATION)
+            elif send is not None:
+                got = gathered_host if rehearsal else [g.cpu().numpy() for g in gathered]
+                parts = [np.asarray(got[r])[: capi.tile_local_rows(height, r, world, BLOCK_ROWS)] for r in range(world)]
+                image = tiles.deinterleave_rows(parts, height, world, BLOCK_ROWS)
+            else:
+                image = accum.cpu().numpy()          # (--tile: the rank's own rows, in local order)
+            m["outputs"] = {"accumulation": np.ascontiguousarray(image, np.float32),
+                            "ray_counts": np.array([total[k] for k in ("rays", "hits", "misses", "pixels")], np.float64)}
         # ---- is the gathered image the right image?  (outside the timed region; round-4 verdict: the N > 1 line gathered and
         # discarded.)  Rank 0 renders the shares of two OTHER ranks again, alone, on its own GPU -- every row, every frame of the
         # job (warm-up included: the accumulation image is the mean since frame 2) -- and compares them bit for bit with what
         # arrived; its own rows against its own image.  A rank's pixels depend on nothing but (global pixel, frame).
-        if gather and not args.tile and not args.no_gather_check and (send is not None or use_group):
+        if args.full and gather and not args.tile and not args.no_gather_check and (send is not None or use_group):
             verdict = None
             if rank == 0:
                 import numpy as np
@@ -807,9 +871,11 @@ def main():
             ctx.bind_accumulation(None, 0)
         return m
 
-    m = measure(args.workload, args.steps, args.warmup, gather=True)
+    m = measure(args.workload, args.steps, args.warmup, gather=True, outputs=bool(args.dump_outputs))
     job = m["job"]
     out = None
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, m["outputs"])
     if rank == 0:
         rays, elapsed, steps = m["total"]["rays"], m["elapsed"], max(args.steps, 1)
         out = {
@@ -848,7 +914,7 @@ def main():
 
     # ---- secondary workloads (N = 1): BASELINE.json configs[1], the default demo mesh; and the headline scene seen from
     # close up (the model fills the frame: deep walks on every pixel, next to the sky-and-floor-dominated stated view)
-    if world == 1 and args.workload == "dragon" and not args.no_also and not args.tile:
+    if args.full and world == 1 and args.workload == "dragon" and not args.no_also and not args.tile:
         out["also"] = {}
         for name in ("demo", "closeup"):
             a = measure(name, args.steps, args.warmup, gather=False)
@@ -876,11 +942,11 @@ def main():
     # ---- the forest leg (N = 1): config 5's scene -- 10 M triangles, 2.08 GB, the only one larger than the 256 MiB
     # Infinity Cache, i.e. the one on which "HBM GB/s against peak" is the question -- at 1920x1080, with its own counter passes
     forest = None
-    if world == 1 and args.workload == "dragon" and not args.no_forest and not args.tile and not args.image:
+    if args.full and world == 1 and args.workload == "dragon" and not args.no_forest and not args.tile and not args.image:
         forest = measure("forest", FOREST_STEPS, FOREST_WARMUP, gather=False, size=FOREST_IMAGE)
         forest["job"].ctx.close()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline: counter passes of this very command line (children; the timed job is over)
         log = []
         pmc, source = {}, None
@@ -937,10 +1003,11 @@ def main():
                                     "round trips, and its waves wait for memory more than they issue; frac is the vector-ALU lane-op fraction, as for the other workloads")
             if flog:
                 out["forest"]["roofline"]["pmc_log"] = flog
-        if args.tile:
-            out["config"]["parallelism"] = f"EXPERIMENT: rank {args.tile} of a tile split rendered alone on one GPU, no gather"
         if world == 1 and not args.no_cpu_baseline and not args.tile:
             out["cpu_baseline"] = cpu_baseline(job)
+    if rank == 0:
+        if args.tile:
+            out["config"]["parallelism"] = f"EXPERIMENT: rank {args.tile} of a tile split rendered alone on one GPU, no gather"
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if use_dist:

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd $ROOT
 for r in $(seq 1 ${1:-3}); do
   for L in ${LIBS:-webgpu-pathtracer_amd/libmi3pt.so}; do
-    MI3PT_LIBRARY=$ROOT/$L python bench.py --no-pmc --no-cpu-baseline --no-forest --steps 20 --warmup 5 2>/dev/null | python -c "
+    MI3PT_LIBRARY=$ROOT/$L python bench.py --full --no-pmc --no-cpu-baseline --no-forest --steps 20 --warmup 5 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readline())
 print('$L: dragon %.0f  demo %.0f' % (j['value'], j['also']['demo']['value']))"

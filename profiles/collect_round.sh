@@ -41,14 +41,14 @@ from mi3pt_host import scenes
 scenes.synthetic_env().tofile('/tmp/env.f32')"
 node webgpu-pathtracer_amd/js/tools/bench_render_loop.js --env /tmp/env.f32 --frames 64 > $OUT/${TAG}_node_render_loop.json 2>&1
 echo "timelines + loop bench done"
-bash profiles/rocprof_stats.sh $TAG
-python bench.py --no-forest > $OUT/${TAG}_dragon_1080p_bench.json 2> $OUT/${TAG}_dragon_bench.err
+bash profiles/rocprof_stats.sh $TAG $OUT
+python bench.py --full --no-forest > $OUT/${TAG}_dragon_1080p_bench.json 2> $OUT/${TAG}_dragon_bench.err
 echo "bench (default args) done: $(cut -c1-120 $OUT/${TAG}_dragon_1080p_bench.json)"
 sleep 30
-python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_dragon_1080p_bench_driver_args.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_dragon_1080p_bench_driver_args.json 2>/dev/null
 echo "bench (driver args) done: $(cut -c1-120 $OUT/${TAG}_dragon_1080p_bench_driver_args.json)"
 sleep 30
-python bench.py --workload demo --no-forest > $OUT/${TAG}_demo_1080p_bench.json 2>/dev/null
+python bench.py --full --workload demo --no-forest > $OUT/${TAG}_demo_1080p_bench.json 2>/dev/null
 echo "bench (demo) done: $(cut -c1-120 $OUT/${TAG}_demo_1080p_bench.json)"
 STEPS=20; WARM=5
 bash profiles/pmc_passes.sh gpurun_out/${TAG}_pmc_dragon --steps $STEPS --warmup $WARM

@@ -9,7 +9,7 @@ cd $ROOT
 mkdir -p gpurun_out
 : > gpurun_out/knob_sweep2.log
 for K in "$@"; do
-  L=$(env $K python bench.py --no-pmc --no-cpu-baseline --steps 12 2>/dev/null | python -c "
+  L=$(env $K python bench.py --full --no-pmc --no-cpu-baseline --steps 12 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readline())
 print('dragon %.0f  demo %.0f  ms_per_step %.3f kernel_ms %.3f' % (j['value'], j['also']['demo']['value'], j['ms_per_step'], j['roofline']['kernel_ms']))")

@@ -9,7 +9,7 @@ cd $ROOT
 mkdir -p gpurun_out
 TILE=${TILE:-0/8}
 for K in "$@"; do
-  L=$(env $K python bench.py --no-pmc --no-cpu-baseline --no-also --steps 20 --warmup 5 --tile $TILE 2>/dev/null | python -c "
+  L=$(env $K python bench.py --full --no-pmc --no-cpu-baseline --no-also --steps 20 --warmup 5 --tile $TILE 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readline())
 print('%.3f ms for the job, frames/launch %s kernel_ms %.3f' % (j['ms_per_step'] * j['steps'], j['roofline']['frames_per_launch'], j['roofline']['kernel_ms']))")

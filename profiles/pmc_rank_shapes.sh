@@ -12,7 +12,7 @@ cd $ROOT
 for ARGS in "--steps 20 --warmup 5" "--steps 16 --warmup 2"; do
   A=$(echo $ARGS | tr -d ' -')
   for T in 0/2 1/4 2/4 0/8 3/8 7/8; do
-    python bench.py $ARGS --tile $T --no-cpu-baseline --no-also --no-forest > $OUT/tile_$(echo $T | tr / of)_$A.json 2> $OUT/tile_$(echo $T | tr / of)_$A.err
+    python bench.py $ARGS --tile $T --full --no-cpu-baseline --no-also --no-forest > $OUT/tile_$(echo $T | tr / of)_$A.json 2> $OUT/tile_$(echo $T | tr / of)_$A.err
     echo "tile $T $ARGS: $(cut -c1-100 $OUT/tile_$(echo $T | tr / of)_$A.json)"
   done
 done

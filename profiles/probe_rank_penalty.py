@@ -17,7 +17,7 @@ with_pmc = (sys.argv[1:] or ["pmc"])[0] == "pmc"
 
 
 def run(tile, rows, pmc):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-also", "--no-forest", "--steps", str(STEPS), "--warmup", str(WARM)]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-also", "--no-forest", "--steps", str(STEPS), "--warmup", str(WARM)]
     if not pmc:
         cmd.append("--no-pmc")
     if tile:

@@ -1,12 +1,14 @@
 """bench.py end to end: the one JSON line the driver reads (metric / value / unit / n_gpus / steps /
-warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config + roofline
-+ cpu_baseline), for N = 1 and -- as a rehearsal of the multi-GPU path on one device, two ranks
+warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config; with --full
+also roofline + cpu_baseline), for N = 1 and -- as a rehearsal of the multi-GPU path on one device, two ranks
 over gloo -- for N = 2."""
 import json
 import os
 import subprocess
 import sys
+import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +28,7 @@ def test_single_gpu_line():
     """The driver's own arguments (--steps 20 --warmup 5; a step = 16 frames, up to sixteen steps per launch): the headline is
     the ~870k-triangle scene the target is quoted on; the roofline fraction comes from counter passes
     of this very command line and is a fraction; the launch statistics are consistent with the wall clock."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full"],
                        capture_output=True, text=True, timeout=1100, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _line(r.stdout)
@@ -88,6 +90,32 @@ def test_single_gpu_line():
     assert "1" in cpu["thread_scaling_Mrays_per_s"] and cpu["value"] == max(cpu["thread_scaling_Mrays_per_s"].values())
 
 
+def test_plain_line_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it, and the run spends less than 30 s outside its
+    steps (build check, torch, the ~870k-triangle scene and its BVH, uploads); --dump-outputs writes what the last timed step left
+    for a caller (the accumulation image, the ray counts of the timed steps), the same bits from run to run."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        t0 = time.monotonic()
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        wall = time.monotonic() - t0
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _line(r.stdout)
+        assert "dragon-class" in j["config"]["workload"] and wall - (3 + 1) * j["ms_per_step"] / 1e3 < 30.0, wall
+        assert (j["metric"], j["unit"], j["higher_is_better"], j["dtype"], j["steps"], j["warmup"]) == ("Mrays/s", "Mrays/s", True, "f32", 3, 1)
+        assert j["value"] > 100 and abs(j["value"] - j["config"]["rays_per_step"] / j["ms_per_step"] / 1e3) / j["value"] < 0.01
+        assert not {"roofline", "also", "forest", "cpu_baseline", "gather_check"} & set(j)
+        assert sorted(os.listdir(d)) == ["accumulation.npy", "ray_counts.npy"]
+        img, counts = np.load(d / "accumulation.npy"), np.load(d / "ray_counts.npy")
+        assert img.dtype == np.float32 and img.shape == (1080, 1920, 4) and np.isfinite(img).all() and img[..., :3].max() > 0
+        assert counts.dtype == np.float64 and counts[0] // 3 == j["config"]["rays_per_step"] and counts[0] == counts[1] + counts[2]
+        assert counts[3] == 1920 * 1080 * 3 * 16
+        dumps.append((img, counts))
+    assert np.array_equal(dumps[0][0].view(np.uint32), dumps[1][0].view(np.uint32)) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
 PLAIN = [sys.executable, os.path.join(ROOT, "bench.py")]          # `python bench.py --gpus N`: bench.py launches its own ranks (round-5 verdict, next #1)
 TORCHRUN = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
             "--master-port", "29533", os.path.join(ROOT, "bench.py")]   # the launcher form of the contract: keeps working
@@ -98,7 +126,7 @@ TORCHRUN = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--npro
 def test_two_rank_rehearsal_line(launcher, scaling, image):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["MI3PT_BENCH_REHEARSAL"] = "1"
-    r = subprocess.run([*launcher, "--gpus", "2", "--steps", "4", "--warmup", "1", "--scaling", scaling, "--workload", "demo"],
+    r = subprocess.run([*launcher, "--gpus", "2", "--steps", "4", "--warmup", "1", "--scaling", scaling, "--workload", "demo", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
@@ -123,7 +151,7 @@ def test_two_rank_rehearsal_of_the_headline_job_carries_a_roofline():
     time from rank 0's live HIP events -- and the gathered image is verified."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["MI3PT_BENCH_REHEARSAL"] = "1"
-    r = subprocess.run([*PLAIN, "--gpus", "2", "--steps", "20", "--warmup", "5"],          # exactly the BENCH record's command shape, N = 2
+    r = subprocess.run([*PLAIN, "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],          # exactly the BENCH record's command shape, N = 2
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
@@ -145,7 +173,7 @@ def test_rccl_path_with_a_world_of_one():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["MI3PT_BENCH_RCCL_SELFTEST"] = "1"
     args = ["--steps", "4", "--warmup", "1", "--workload", "demo", "--no-pmc", "--no-cpu-baseline", "--no-also", "--no-forest"]
-    r = subprocess.run([*PLAIN, *args], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    r = subprocess.run([*PLAIN, *args, "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
     assert "RCCL" in j["rccl_selftest"] and j["n_gpus"] == 1
@@ -162,7 +190,7 @@ def test_device_group_rehearsal_line():
     with both members on the box's one GPU.  Same job, same rays as two processes over torch.distributed."""
     env = dict(os.environ, MI3PT_BENCH_REHEARSAL="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--group", "--steps", "4", "--warmup", "1", "--workload", "demo",
-                        "--no-pmc", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--no-pmc", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
     assert (j["n_gpus"], j["steps"], j["scaling"]) == (2, 4, "strong") and j["config"]["image"] == [1920, 1080]
