@@ -46,7 +46,8 @@ extern "C" {
  * new exports mi3pt_tile_global_row, mi3pt_tile_owner; new options MI3PT_OPT_GATE_TIMEOUT_MS, MI3PT_OPT_GATE_RELEASES, MI3PT_OPT_CAMERA_BASE,
  * MI3PT_OPT_PACKET_ORDER, MI3PT_OPT_SIX_WAVES (22 .. 27); MI3PT_OPT_WAVES_PER_CU reads up to 24 (six waves per SIMD). */
 /* 4 (round 6): mi3pt_set_rows and mi3pt_measure_tile_cost are GONE (contiguous cost-balanced bands: measured 7 % slower than the dealt
- * 8-row blocks in round 4 and kept since as dead surface); mi3pt_set_kernel_variant accepts 14 (the eight-wide walk: an option). */
+ * 8-row blocks in round 4 and kept since as dead surface); mi3pt_set_kernel_variant accepts 14 (the eight-wide walk: an option).
+ * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31). */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -368,6 +369,10 @@ typedef enum mi3pt_option {
                                    * (five waves per SIMD, like the shipped one) instead of the four-wave diagnostic twin (profiles/wave_timeline.py) */
     MI3PT_OPT_GATHER_STAGED = 20, /* device group: 1 = every member's rows reach the presenting context through pinned host memory -- the
                                    * path the gather takes where peer access is unavailable or a direct copy failed (forced: tests) */
+    MI3PT_OPT_SKY_TILES = 31,       /* 8x8 tiles whose camera rays provably reach no geometry (mi3pt_host_sky_tiles) are shaded by a streaming kernel
+                                   * at full wave width instead of being given to the persistent kernel as jobs; batched launches of the lean
+                                   * culling walks, pinhole camera, one sample per frame.  Same bits, same rays / hits / misses / pixels; 0 = every
+                                   * tile is traced; 1 = the streaming kernel is enqueued in front of the persistent one, 2 = behind it (1) */
     MI3PT_OPT_COST_ORDER = 17  /* a launch's jobs in the order of the tiles' measured cost, costliest first: one launch adds up the path
                                 * segments per 8x8 tile, later launches with the same uniforms run the
                                 * cheapest quarter of the tiles last (1), or every tile costliest first (2).  Default 0: measured +0.3 % on
@@ -463,6 +468,15 @@ int mi3pt_host_env_cdf(const float *rgba, int width, int height, float *cdf_rgba
  * leaves reached, 1 if a context would offer variant 14 for this tree (levels within the walk's stack).  MI3PT_ERR_STATE with the
  * reason in mi3pt_last_error when the tree does not admit the packets or a check fails. */
 int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes, const void *triangles, size_t triangles_bytes, int greedy, uint64_t out[6]);
+/* The EMPTY TILES of a view (no device): the 8x8 tiles of rank `rank`'s share of a width x height image (tiles_x = ceil(width / 8), rows of
+ * tiles over the rank's LOCAL rows, row-major) in which no pixel's camera ray, for any frame's jitter, can pass the reference's slab
+ * test on any box of a cut of the tree `nodes` (48-byte records) -- such a ray reaches no leaf, the path is one miss.  A context
+ * shades these tiles with a streaming kernel instead of tracing them (MI3PT_OPT_SKY_TILES; PROOFS.md section 5).  `raytrace_uniforms`: the
+ * 96-byte block.  empty_out[tile] = 1 / 0, `capacity` bytes; *ntiles_out = tiles (empty_out may be NULL to ask for the size only).
+ * All zero unless aperture == 0, no camera coordinate is -0, samplesPerFrame == 1, maxBounces >= 1, the camera lies in front of
+ * every cut box and every box of the tree contains its children's. */
+int mi3pt_host_sky_tiles(const void *nodes, size_t nodes_bytes, const void *raytrace_uniforms, int width, int height,
+                         int rank, int nranks, int block_rows, uint8_t *empty_out, size_t capacity, size_t *ntiles_out);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,28 @@ struct mi3pt_ctx {
     uint8_t cam_base_key[2][80] = {};
     bool cam_base_valid[2] = { false, false };
     bool cam_base_enabled = true;        // MI3PT_OPT_CAMERA_BASE
+    // The empty tiles of the view (pt_host_sky.cpp; PROOFS.md section 5): 8x8 tiles whose camera rays reach no geometry are not jobs of the
+    // persistent kernel -- a streaming kernel shades them (launch_batch: sky_prepare).  sky_cut: the boxes of a cut of the uploaded tree
+    // (mi3pt_upload_bvh); the classification is cached under the camera-base key + what else it depends on + the scene's version, on
+    // the host (one per view) and as a device list per launch parity: [active tiles, ascending | empty tiles].
+#ifndef PT_SKY_TILES_DEFAULT
+#define PT_SKY_TILES_DEFAULT 1           // (A/B builds: 0 / 2)
+#endif
+    int sky_tiles = PT_SKY_TILES_DEFAULT; // MI3PT_OPT_SKY_TILES: 0 off, 1 on (the streaming kernel in front of the persistent one), 2 on (behind it)
+    std::vector<float> sky_cut;
+    bool sky_cut_ok = false;
+    uint8_t sky_key[104] = {}, sky_seen_key[104] = {};
+    bool sky_host_valid = false;
+    std::vector<uint32_t> sky_host;      // the list for sky_key
+    int sky_host_active = 0;
+    uint64_t sky_host_pixels = 0;        // in-bounds pixels of the empty tiles
+    uint32_t *d_sky_list[2] = { nullptr, nullptr };
+    size_t sky_list_cap[2] = { 0, 0 };
+    uint8_t sky_dev_key[2][104] = {};
+    bool sky_dev_valid[2] = { false, false };
+    std::vector<uint32_t> sky_staged[2]; // what the last copy into d_sky_list[par] reads (kept until sky_copied[par])
+    hipEvent_t sky_copied[2] = {};
+    bool sky_copied_valid[2] = { false, false };
     int collapse = -1;                   // MI3PT_OPT_COLLAPSE: 1 = the SAH-optimal grouping of the tree's nodes into wide packets, 0 = the greedy one of rounds 2 - 5, -1 = greedy for the 4-ary packets, optimal for the 8-ary ones (what each measured best with)
     int six_waves = -1;                  // MI3PT_OPT_SIX_WAVES: the compressed-wide walk's build, -1 = by the size of the launch (pt::RtLaunch::six_waves)
     int packet_order = 0;                // MI3PT_OPT_PACKET_ORDER: numbering of the wide packets in memory (prepare_cull): 0 breadth-first, 1 depth-first, 2 treelets
@@ -141,7 +163,10 @@ struct mi3pt_ctx {
     bool output_is_accum = false;
     uint64_t *d_block_counters = nullptr;
     uint32_t *d_tile_counter = nullptr;
-    int job_reverse = 1;                 // MI3PT_JOB_REVERSE, see RtLaunch::job_reverse (the top band last: +0.5 % with the sky up there)
+#ifndef PT_JOB_REVERSE_DEFAULT
+#define PT_JOB_REVERSE_DEFAULT 1         // (A/B builds: 0)
+#endif
+    int job_reverse = PT_JOB_REVERSE_DEFAULT; // MI3PT_JOB_REVERSE, see RtLaunch::job_reverse (the top band last: +0.5 % with the sky up there)
     int job_group = -1;                  // MI3PT_JOB_GROUP, see RtLaunch::job_group; -1 = chosen per tile set in build_launch
     int tri_pair = 1;                    // MI3PT_TRI_PAIR, see RtLaunch::tri_pair
     int job_chunk = PT_DEFAULT_JOB_CHUNK;    // job tickets per draw from the queue (MI3PT_JOB_CHUNK; 1 = one atomic per job)
@@ -513,6 +538,7 @@ extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
             CREATE_TRY(hipStreamCreateWithFlags(&ctx->rt_stream[k], hipStreamNonBlocking));
         }
         CREATE_TRY(hipEventCreateWithFlags(&ctx->rt_done[k], hipEventDisableTiming));
+        CREATE_TRY(hipEventCreateWithFlags(&ctx->sky_copied[k], hipEventDisableTiming));
     }
     for (int k = 0; k < 3; k++) CREATE_TRY(hipEventCreateWithFlags(&ctx->acc_done[k], hipEventDisableTiming));
     CREATE_TRY(hipEventCreateWithFlags(&ctx->main_mark, hipEventDisableTiming));
@@ -640,6 +666,9 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     for (int k = 0; k < 2; k++) {
         if (ctx->rt_stream[k]) (void)hipStreamDestroy(ctx->rt_stream[k]);
         if (ctx->rt_done[k]) (void)hipEventDestroy(ctx->rt_done[k]);
+        if (ctx->sky_copied[k]) (void)hipEventDestroy(ctx->sky_copied[k]);
+        if (ctx->d_sky_list[k]) (void)hipFree(ctx->d_sky_list[k]);
+        ctx->d_sky_list[k] = nullptr;
     }
     for (int k = 0; k < 3; k++)
         if (ctx->acc_done[k]) (void)hipEventDestroy(ctx->acc_done[k]);
@@ -753,6 +782,10 @@ extern "C" int mi3pt_debug_set_option(mi3pt_ctx *ctx, int option, int value)
     case MI3PT_OPT_WIDE: ctx->wide_enabled = value != 0; break;
     case MI3PT_OPT_GATE: ctx->gate_enabled = value != 0 && ctx->d_drain_flag != nullptr; if (ctx->gate_enabled) { ctx->gate_releases = 0; ctx->gate_stalls_in_a_row = 0; } break;
     case MI3PT_OPT_CAMERA_BASE: ctx->cam_base_enabled = value != 0; break;
+    case MI3PT_OPT_SKY_TILES:
+        if (value < 0 || value > 2) return pt_set_error(MI3PT_ERR_INVALID, "MI3PT_OPT_SKY_TILES: 0, 1 or 2");
+        ctx->sky_tiles = value;
+        break;
     case MI3PT_OPT_SIX_WAVES: ctx->six_waves = value < 0 ? -1 : (value != 0 ? 1 : 0); break;
     case MI3PT_OPT_WALK_ADAPT: ctx->walk_adapt = value != 0; if (!ctx->walk_adapt) ctx->deep_by_view = false; break;
     case MI3PT_OPT_COLLAPSE:
@@ -819,6 +852,7 @@ extern "C" int mi3pt_debug_get_option(mi3pt_ctx *ctx, int option, int *value)
     case MI3PT_OPT_WIDE: *value = ctx->wide_enabled ? 1 : 0; break;
     case MI3PT_OPT_GATE: *value = ctx->gate_enabled ? 1 : 0; break;
     case MI3PT_OPT_CAMERA_BASE: *value = ctx->cam_base_enabled ? 1 : 0; break;
+    case MI3PT_OPT_SKY_TILES: *value = ctx->sky_tiles; break;
     case MI3PT_OPT_SIX_WAVES: *value = ctx->six_waves; break;
     case MI3PT_OPT_COLLAPSE: *value = ctx->collapse; break;
     case MI3PT_OPT_WALK_ADAPT: *value = ctx->walk_adapt; break;
@@ -1131,6 +1165,9 @@ extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes
     ctx->root_ref = ref_of(0);
     ctx->scene_flags = node_box_safe(src, 0) ? 1u : 0u;
     ctx->max_tri_ref = max_tri;
+    // the cut behind the empty tiles of a view: the nesting of EVERY node's box is checked (the collapse checks it for the nodes it absorbs only)
+    ctx->sky_cut_ok = tree_proper && pt::sky_cut_of(src, n, ctx->sky_cut);
+    ctx->sky_host_valid = false;
     ctx->cull_dirty = true;
     ctx->cost_state = 0;            // (the tiles' costs were measured on another scene)
     ctx->layout_active = false;
@@ -2054,6 +2091,7 @@ static pt::RtLaunch build_launch(const mi3pt_ctx *ctx, const uint8_t *u, const p
     L.num_cus = ctx->num_cus;
     L.service = nullptr;          // (batched launches: a slot of the context's ring, see launch_batch)
     L.cam_base = nullptr;         // (batched launches: launch_batch)
+    L.ntiles_active = 0;          // (batched launches: launch_batch, sky_prepare)
     L.park = ctx->d_park;
     L.six_waves = ctx->six_waves;
     L.tile_cost = nullptr;        // (batched launches: launch_batch)
@@ -2245,6 +2283,91 @@ static void adapt_walk(mi3pt_ctx *ctx)
     else if (per_ray <= WALK_ADAPT_LEAVE) ctx->deep_by_view = false;
 }
 
+// The empty tiles of this launch's view: sets L.tile_perm / L.ntiles_active to the list of the other tiles and returns the device list
+// of the empty ones through *sky_list / *sky_count / *sky_samples (0: every tile is traced, the launch is what it was).  The split is
+// used by the lean builds of the culling walks only (variants 9 - 14: their box-test counter is not pinned; 1 - 8 keep the oracle's exact
+// counts and so trace every tile; the diagnostic twins and the per-pixel kernels keep tracing every pixel -- they are the on-device
+// check), with the camera base at hand, without a cost order.  The host's classification (a millisecond or two at 1080p) runs at
+// once for a launch of SKY_MIN_FRAMES frames or more, which hides it; a shallower launch -- an interactive host -- gets it once its camera
+// has stood still for a launch, so that a host that moves the camera every frame never pays for it.
+#define SKY_MIN_FRAMES 8
+static int sky_prepare(mi3pt_ctx *ctx, pt::RtLaunch &L, const uint8_t *u_rt, int par, int n, hipStream_t rs,
+                       const uint32_t **sky_list, int *sky_count, uint64_t *sky_samples)
+{
+    *sky_list = nullptr; *sky_count = 0; *sky_samples = 0;
+    const pt::RtRoute &r = ctx->last_route;
+    if (!ctx->sky_tiles || !ctx->sky_cut_ok || ctx->env_sampling || !L.cam_base || L.tile_perm || L.tile_cost ||
+        !(r.kind == 1 && r.lean && r.variant >= 9 && r.variant <= 14))
+        return MI3PT_OK;
+    const int ntiles = pt::raytrace_grid_blocks(L.tile);
+    if (ntiles < 2) return MI3PT_OK;
+    uint8_t key[104];
+    std::memset(key, 0, sizeof key);
+    std::memcpy(key, u_rt, 12);                       // resolution, aspect
+    std::memcpy(key + 12, u_rt + 32, 40);             // camera position, direction, fov, focal distance, aperture (32 .. 72)
+    std::memcpy(key + 52, u_rt + 16, 8);              // maxBounces, samplesPerFrame
+    const int32_t tl[6] = { L.tile.tex_w, L.tile.tex_h, L.tile.local_rows, L.tile.rank, L.tile.nranks, L.tile.block_rows };
+    std::memcpy(key + 60, tl, sizeof tl);
+    std::memcpy(key + 88, &ctx->scene_epoch, 8);
+    if (!ctx->sky_host_valid || std::memcmp(key, ctx->sky_key, sizeof key) != 0) {
+        const bool stood_still = std::memcmp(key, ctx->sky_seen_key, sizeof key) == 0;
+        std::memcpy(ctx->sky_seen_key, key, sizeof key);
+        if (n < SKY_MIN_FRAMES && !stood_still) return MI3PT_OK;
+        std::vector<uint8_t> empty;
+        (void)pt::sky_classify(ctx->sky_cut, true, u_rt, L.tile.tex_w, L.tile.local_rows, L.tile.tex_h,
+                               L.tile.rank, L.tile.nranks, L.tile.block_rows, empty);
+        ctx->sky_host.assign((size_t)ntiles, 0u);
+        size_t at = 0;
+        for (int t = 0; t < ntiles; t++) if (!empty[(size_t)t]) ctx->sky_host[at++] = (uint32_t)t;
+        ctx->sky_host_active = (int)at;
+        // the in-bounds pixels of the empty tiles (the refill's test, raytrace.wgsl:425-427): each is one ray, one miss, one pixel per frame
+        const double rx = ldf(u_rt, 0), ry = ldf(u_rt, 4);
+        const long long res_w = rx >= 1.0 ? (long long)std::min(rx, 4294967295.0) : 0, res_h = ry >= 1.0 ? (long long)std::min(ry, 4294967295.0) : 0;
+        const int tiles_x = (L.tile.tex_w + 7) / 8;
+        uint64_t pixels = 0;
+        for (int t = 0; t < ntiles; t++) {
+            if (!empty[(size_t)t]) continue;
+            ctx->sky_host[at++] = (uint32_t)t;
+            const int trow = t / tiles_x, tcol = t - trow * tiles_x;
+            int cols = 0;
+            for (int px = tcol * 8; px < tcol * 8 + 8; px++) cols += px < L.tile.tex_w && (long long)px < res_w ? 1 : 0;
+            for (int ply = trow * 8; ply < trow * 8 + 8; ply++) {
+                if (ply >= L.tile.local_rows) continue;
+                const int pgy = L.tile.nranks <= 1 ? ply : mi3pt_tile_global_row(ply, L.tile.rank, L.tile.nranks, L.tile.block_rows);
+                if (pgy >= 0 && pgy < L.tile.tex_h && (long long)pgy < res_h) pixels += (uint64_t)cols;
+            }
+        }
+        ctx->sky_host_pixels = pixels;
+        std::memcpy(ctx->sky_key, key, sizeof key);
+        ctx->sky_host_valid = true;
+    }
+    const int active = ctx->sky_host_active, nempty = ntiles - active;
+    if (nempty <= 0 || active <= 0) return MI3PT_OK;          // (nothing to take out -- or nothing left: such a launch stays whole)
+    if (!ctx->sky_dev_valid[par] || std::memcmp(key, ctx->sky_dev_key[par], sizeof key) != 0) {
+        if (ctx->sky_copied_valid[par]) HIP_TRY(hipEventSynchronize(ctx->sky_copied[par]));      // (long done: this parity's previous view)
+        if (ctx->sky_list_cap[par] < (size_t)ntiles) {
+            uint32_t *fresh = nullptr;
+            if (hipMalloc((void **)&fresh, (size_t)ntiles * 4) != hipSuccess) { (void)hipGetLastError(); return MI3PT_OK; }      // no memory: no split
+            if (ctx->d_sky_list[par]) (void)hipFree(ctx->d_sky_list[par]);          // (hipFree waits for the device: nothing still reads it)
+            ctx->d_sky_list[par] = fresh;
+            ctx->sky_list_cap[par] = (size_t)ntiles;
+        }
+        ctx->sky_dev_valid[par] = false;
+        ctx->sky_staged[par] = ctx->sky_host;
+        HIP_TRY(hipMemcpyAsync(ctx->d_sky_list[par], ctx->sky_staged[par].data(), (size_t)ntiles * 4, hipMemcpyHostToDevice, rs));
+        HIP_TRY(hipEventRecord(ctx->sky_copied[par], rs));
+        ctx->sky_copied_valid[par] = true;
+        std::memcpy(ctx->sky_dev_key[par], key, sizeof key);
+        ctx->sky_dev_valid[par] = true;
+    }
+    L.tile_perm = ctx->d_sky_list[par];
+    L.ntiles_active = active;
+    *sky_list = ctx->d_sky_list[par] + active;
+    *sky_count = nempty;
+    *sky_samples = ctx->sky_host_pixels * (uint64_t)n;
+    return MI3PT_OK;
+}
+
 static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, int n)
 {
     adapt_walk(ctx);
@@ -2272,11 +2395,6 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     if (ctx->acc_done_valid[set]) HIP_TRY(hipStreamWaitEvent(rs, ctx->acc_done[set], 0));
     L.radiance = ctx->d_slots[set];
     L.nframes = n;
-    // the walk threshold by the view (adapt_walk): the deep-walk build for a launch of the shipped walk long enough to run its six-wave form
-    // (>= 250 k jobs: a short launch -- an interactive host's single frames -- is all ramp and drain, and keeps the ordinary build)
-    if (ctx->deep_by_view && ctx->walk_min == 0 && L.walk_min == PT_DEFAULT_WALK_MIN && pick_variant(ctx) == 13 &&
-        (long long)pt::raytrace_grid_blocks(L.tile) * n >= 250000)
-        L.walk_min = PT_DEEP_WALK_MIN;
     L.block_counters = ctx->d_block_counters + (size_t)par * ctx->nblocks * pt::CNT_COUNT;
     L.tile_counter = ctx->d_tile_counter + par * 32;
     L.stack_overflow = ctx->d_stack_overflow + (size_t)par * pt::PT_MAX_RESIDENT_WAVES * pt::SM_OVERFLOW_ENTRIES * 64;
@@ -2337,12 +2455,30 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
             L.cam_base = ctx->d_cam_base[par];
         }
     }
+    // the tiles whose camera rays reach no geometry leave the job list
+    const uint32_t *sky_list = nullptr;
+    int sky_count = 0;
+    uint64_t sky_samples = 0;
+    if (launches)
+        if (int rc = sky_prepare(ctx, L, first.u_rt, par, n, rs, &sky_list, &sky_count, &sky_samples)) return rc;
+    // the walk threshold by the view (adapt_walk): the deep-walk build for a launch of the shipped walk long enough to run its six-wave form
+    // (>= 250 k jobs: a short launch -- an interactive host's single frames -- is all ramp and drain, and keeps the ordinary build.  Counted in
+    // tiles of the FRAME, empty ones included: which of the two builds a view gets does not depend on how much sky it shows --
+    // tests/test_gpu_configs.py::test_walk_threshold_follows_the_view pins the sequence; the grid and the six-wave choice count the real jobs)
+    if (ctx->deep_by_view && ctx->walk_min == 0 && L.walk_min == PT_DEFAULT_WALK_MIN && pick_variant(ctx) == 13 &&
+        (long long)pt::raytrace_grid_blocks(L.tile) * n >= 250000)
+        L.walk_min = PT_DEEP_WALK_MIN;
+    ctx->last_route = pt::raytrace_route(L, pick_variant(ctx));          // (the grid and the build follow the number of jobs)
     pt::launch_raytrace_setup(L, false, pick_variant(ctx), rs);
     if (ctx->timing) {
         HIP_TRY(hipEventRecord(ctx->ev_rt[par][0], rs));
         if (!ctx->span_started) { HIP_TRY(hipEventRecord(ctx->ev_span_start, rs)); ctx->span_started = true; }
     }
+    // (in front of the persistent kernel: it runs while the predecessor's last paths drain -- +0.4 % over behind it, where it would follow this
+    // launch's own drain: profiles/sky_tiles_ab.log)
+    if (sky_count && ctx->sky_tiles != 2) pt::launch_sky_samples(L, sky_list, sky_count, sky_samples, rs);
     pt::launch_raytrace(L, false, pick_variant(ctx), rs);
+    if (sky_count && ctx->sky_tiles == 2) pt::launch_sky_samples(L, sky_list, sky_count, sky_samples, rs);
     if (publish_after && !ctx->debug_suppress_drain && hipStreamWriteValue32(rs, ctx->d_drain_flag, publish_after, 0) != hipSuccess) {
         (void)hipGetLastError();
         ctx->gate_enabled = false;          // (the next batch enqueues no wait; a batch already held is released by ctx_wait)
@@ -2365,14 +2501,14 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
         ctx->ev_rt_frames[par] = n;
         ctx->ev_rt_newest = par;
     }
-    HIP_TRY(hipEventRecord(ctx->rt_done[par], rs));
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->rt_done[par], 0));
-    // what this launch cost per ray, for the choice of a later launch's build (adapt_walk): behind the launch on its own stream, after the event
-    // the ordered mean waits for
+    // what this launch cost per ray, for the choice of a later launch's build (adapt_walk): behind the launch on its own stream, in front of the
+    // event the ordered mean waits for -- the report is there at every sync point (the rays of the empty tiles' samples are in the same counter set)
     if (ctx->walk_adapt && ctx->h_walk_stats && launches && ctx->last_route.kind == 1 && ctx->last_route.lean && ctx->last_route.variant == 13 && ctx->walk_min == 0) {
         pt::launch_walk_stats(L.block_counters, ctx->nblocks, ctx->d_walk_prev + 2 * par, ctx->d_walk_stats + 4 * par, ++ctx->walk_stats_seq, rs);
         (void)hipGetLastError();
     }
+    HIP_TRY(hipEventRecord(ctx->rt_done[par], rs));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->rt_done[par], 0));
     // The ordered mean, a run of frames at a time: a run ends with a frame whose canvas is wanted (EXACT presentation) or
     // with the launch -- all n frames in one pass unless frames present, one pass + one fullscreen pass per presenting frame.
     ctx->last_radiance = L.radiance + (size_t)(n - 1) * L.slot_pixels;
@@ -3115,6 +3251,7 @@ static int clone_scene(mi3pt_ctx *dst, const mi3pt_ctx *src)
     dst->wide_leaf_cap = src->wide_leaf_cap; dst->wide_root = src->wide_root;
     dst->layout = src->layout; dst->layout_dirty = src->layout_dirty; dst->layout_active = src->layout_active;
     dst->cost_state = 0;
+    dst->sky_cut = src->sky_cut; dst->sky_cut_ok = src->sky_cut_ok; dst->sky_host_valid = false;
     dst->main_dirty = true;
     dst->scene_epoch++;
     return MI3PT_OK;

@@ -61,3 +61,10 @@ struct Cw8Build {
 };
 bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per triangle: a, pad, b, pad, c, pad */, size_t nt,
                const std::vector<float> &wmax, Cw8Build &out, bool greedy = false);
+// pt_host_sky.cpp: the tiles whose camera rays can reach no geometry (PROOFS.md section 5).  sky_cut_of: a cut of the tree as boxes (6 floats
+// each), false if a node's box does not contain its children's; sky_classify: empty[tile] = 1 per 8x8 tile of this rank's image, returns the count
+namespace pt {
+bool sky_cut_of(const uint8_t *src, size_t n, std::vector<float> &boxes);
+size_t sky_classify(const std::vector<float> &boxes, bool have_cut, const uint8_t *u, int width, int local_rows, int height,
+                    int rank, int nranks, int block_rows, std::vector<uint8_t> &empty);
+}

@@ -286,6 +286,8 @@ struct RtLaunch {
     const uint32_t *tile_perm;   // state-machine kernel, or null: position in the job order -> tile of the frame; the context sorts
                                  // the tiles by measured cost, costliest first, so that a launch's last tickets are its cheapest
                                  // tiles and the drain after the queue has run empty is short (any order renders the same bits)
+    int32_t ntiles_active;       // state-machine kernel: 0 = every tile of the frame is a job; n > 0 = only the first n positions of tile_perm are (the
+                                 // context has taken out the tiles whose camera rays reach no geometry: k_sky_samples shades those)
     const float4 *cam_base;      // state-machine kernel, or null: per texel of this rank's image, cam_pos + dir0 * focalDistance -- the part of
                                  // cameraToRay (raytrace.wgsl:219-238, 446) that depends on the PIXEL only, formed once per camera by
                                  // launch_camera_base instead of once per frame of a batch in the service step (same operations, same bits)
@@ -323,7 +325,11 @@ void launch_debug_math(int fn, const float *a, const float *b, float *out, size_
 // out[1] = box tests, out[2] = rays, then (after a system-scope fence) out[0] = seq.  `prev` (2 x u64, device) carries the sums.
 void launch_walk_stats(const uint64_t *counters, int nblocks, uint64_t *prev, uint64_t *out, uint64_t seq, hipStream_t s);
 int raytrace_grid_blocks(const Tile &tile);
-int raytrace_persistent_blocks(const Tile &tile, int nframes, int waves_per_cu, int num_cus, bool tuned = false, int waves_per_simd = 0);
+int raytrace_persistent_blocks(const Tile &tile, int nframes, int waves_per_cu, int num_cus, bool tuned = false, int waves_per_simd = 0, int job_tiles = 0);
+int raytrace_job_tiles(const RtLaunch &L);      // tiles of a frame that are jobs of the state-machine kernel: all, or RtLaunch::ntiles_active
+// the samples of `ntiles` listed tiles (device array) x L.nframes whose camera rays reach no geometry, shaded at full width (needs
+// L.cam_base); `samples`: the in-bounds pixels among them x frames, for the launch's counters
+void launch_sky_samples(const RtLaunch &L, const uint32_t *tiles, int ntiles, uint64_t samples, hipStream_t s);
 // packs the three position vectors of `ntris` 112-byte triangle records into 48-byte rows (the context's cull analysis)
 void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipStream_t s);
 // writes NodePacket::cull of `npackets` packets from a dense array (the context's cull analysis)

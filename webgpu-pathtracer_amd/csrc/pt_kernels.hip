@@ -638,6 +638,33 @@ PT_DEV f3 sample_env(const float4 *env, int W, int H, float u, float v)
     return r;
 }
 
+// A path segment that hit nothing, raytrace.wgsl:396-407: the environment along `d`, weighted by the path's throughput.  (The
+// environment texture is 1024 x 512 by the API: renderer.ts:76-85, mi3pt_upload_environment.)  Shared by the state-machine kernel's
+// service step and k_sky_samples.
+PT_DEV f3 miss_light(const float4 *env, const f3 &d, float sinr, float cosr, const f3 &ray_color, const f3 &light, float env_intensity)
+{
+    float u, v;
+    env_uv_from_dir(d, sinr, cosr, u, v);
+    const f3 e = sample_env(env, ENV_W, ENV_H, u, v);
+    return light + (ray_color * e) * env_intensity;
+}
+
+// The seed of a (pixel, frame) sample, raytrace.wgsl:435-436
+PT_DEV uint32_t sample_seed(uint32_t px, uint32_t pgy, uint32_t res_w, uint32_t frame)
+{
+    return (px + pgy * res_w) + frame * 719393u + PT_SEED;
+}
+
+// The focal point of a camera path, raytrace.wgsl:443-446: the pixel's base point (cam_pos + dir0 * focalDistance) plus a point of the
+// unit disk scaled to (1 / res_x, 1 / res_y, 0) -- in WORLD x, y
+PT_DEV f3 camera_focal_point(uint32_t &seed, const f3 &fbase, float inv_res_x, float inv_res_y)
+{
+    float jx, jy;
+    rand_point_in_circle(seed, jx, jy);
+    const f3 jitter = F3(jx * inv_res_x, jy * inv_res_y, 0.0f);
+    return fbase + jitter;
+}
+
 // textureSampleLevel(environmentCDFTexture, nearest sampler, clamp-to-edge): renderer.ts:82-85
 PT_DEV float4 cdf_texel(const float4 *cdf, int W, int H, float u, float v)
 {
@@ -1179,7 +1206,9 @@ PT_DEV RtService compute_service(const RtLaunch &L, bool scene_has_nodes)
                  __float_as_uint(un.cam_pos[1]) != 0x80000000u && __float_as_uint(un.cam_pos[2]) != 0x80000000u) ? 1 : 0;
     S.tiles_x = (L.tile.tex_w + 7) >> 3;
     // A launch covers L.nframes consecutive frames: job = (frame slot, 8x8 tile)
-    S.ntiles_frame = S.tiles_x * ((L.tile.local_rows + 7) >> 3);
+    // (L.ntiles_active > 0: only the first so many positions of L.tile_perm are jobs -- the context has taken the tiles whose camera
+    // rays reach no geometry out of the list: k_sky_samples shades them)
+    S.ntiles_frame = L.ntiles_active > 0 ? L.ntiles_active : S.tiles_x * ((L.tile.local_rows + 7) >> 3);
     S.ntiles = S.ntiles_frame * L.nframes;
     S.grp_jobs = (L.job_group > 0 && L.job_group < S.ntiles_frame) ? L.job_group * L.nframes : 0;
     S.grp_full = S.grp_jobs ? S.ntiles_frame / L.job_group : 0;
@@ -2197,13 +2226,7 @@ __global__ void __launch_bounds__(64, DIAG ? SM_OTHER_WAVES_PER_SIMD : WAVES) k_
             if (wave_times) st_switch(4);
 #endif
             PT_SERVICE_PART();
-            if (shade_miss) {         // :396-407
-                
-                float u, v;
-                env_uv_from_dir(d, sinr, cosr, u, v);
-                const f3 env = sample_env(sc.env, ENV_W, ENV_H, u, v);      // (the environment texture is 1024 x 512 by the API: renderer.ts:76-85, mi3pt_upload_environment)
-                light = light + (ray_color * env) * un.env_intensity;
-            }
+            if (shade_miss) light = miss_light(sc.env, d, sinr, cosr, ray_color, light, un.env_intensity);        // :396-407
             PT_SERVICE_PART();
             if (shade_hit || shade_miss) {
                 mode = M_DEAD;        // until a path / segment is started below
@@ -2289,7 +2312,7 @@ __global__ void __launch_bounds__(64, DIAG ? SM_OTHER_WAVES_PER_SIMD : WAVES) k_
                                     (uint32_t)px < res_w && (uint32_t)pgy < res_h;     // :425-427
                     if (ok) {
                         got_job = true;
-                        seed = ((uint32_t)px + (uint32_t)pgy * res_w) + (un.frame + (uint32_t)fslot) * 719393u + PT_SEED;    // :435-436
+                        seed = sample_seed((uint32_t)px, (uint32_t)pgy, res_w, un.frame + (uint32_t)fslot);
                         // the pixel's coordinates are only needed for the camera ray, formed in this very step;
                         // what a lane carries through its walks: texel index, frame slot << 16 | bounce
                         job_px = (uint32_t)px; job_py = (uint32_t)pgy;
@@ -2341,10 +2364,8 @@ __global__ void __launch_bounds__(64, DIAG ? SM_OTHER_WAVES_PER_SIMD : WAVES) k_
                     const f3 dir0 = camera_direction(cf, un.aspect, uvx, uvy);
                     fbase = cam_pos + dir0 * un.focal_distance;
                 }
-                float jx, jy, kx, ky;
-                rand_point_in_circle(seed, jx, jy);
-                const f3 jitter = F3(jx * inv_res_x, jy * inv_res_y, 0.0f);
-                const f3 focal = fbase + jitter;
+                float kx, ky;
+                const f3 focal = camera_focal_point(seed, fbase, inv_res_x, inv_res_y);
                 if (pinhole) {
                     // aperture == 0 (the reference's default, scene.ts:9): the lens offset is (+-0, +-0, 0) whatever the
                     // disk sample is (finite * 0), and cam_pos + (+-0) == cam_pos bit for bit unless a coordinate of
@@ -2500,9 +2521,9 @@ __global__ void __launch_bounds__(64, DIAG ? SM_OTHER_WAVES_PER_SIMD : WAVES) k_
     }
 }
 
-int raytrace_persistent_blocks(const Tile &tile, int nframes, int waves_per_cu, int num_cus, bool tuned, int waves_per_simd)
+int raytrace_persistent_blocks(const Tile &tile, int nframes, int waves_per_cu, int num_cus, bool tuned, int waves_per_simd, int job_tiles)
 {
-    const int ntiles = raytrace_grid_blocks(tile);
+    const int ntiles = job_tiles > 0 ? job_tiles : raytrace_grid_blocks(tile);
     if (num_cus <= 0) num_cus = 256;
     if (waves_per_simd <= 0) waves_per_simd = tuned ? SM_TUNED_WAVES_PER_SIMD : SM_OTHER_WAVES_PER_SIMD;
     if (waves_per_cu > 4 * waves_per_simd) waves_per_cu = 0;          // (more than the build can keep resident: its own width)
@@ -2535,6 +2556,12 @@ int raytrace_grid_blocks(const Tile &tile)
     const int tiles_x = (tile.tex_w + 7) / 8;
     const int tiles_y = (tile.local_rows + 7) / 8;
     return tiles_x * tiles_y;
+}
+
+// Tiles of a frame that the state-machine kernel is given as jobs: all of them, or the launch's active list
+int raytrace_job_tiles(const RtLaunch &L)
+{
+    return L.ntiles_active > 0 ? L.ntiles_active : raytrace_grid_blocks(L.tile);
 }
 
 // Frame slot and bounce share a word in the state-machine kernel, and the sample count of a multi-sample frame is a float in the
@@ -2620,7 +2647,7 @@ static int route_waves_per_simd(const RtLaunch &L, const RtRoute &r)
         if (L.wave_times && L.diag_lite) return SM_TUNED_WAVES_PER_SIMD;      // (the lean build + lane counts: five)
 #endif
         if (L.six_waves >= 0) return L.six_waves ? SM_SIX_WAVES_PER_SIMD : SM_TUNED_WAVES_PER_SIMD;
-        const long long jobs = (long long)raytrace_grid_blocks(L.tile) * (L.nframes > 0 ? L.nframes : 1);
+        const long long jobs = (long long)raytrace_job_tiles(L) * (L.nframes > 0 ? L.nframes : 1);
         // (a job of a very large tree -- the walk_min-44 builds -- is an order of magnitude longer)
         return jobs >= (L.walk_min == PT_DEEP_WALK_MIN ? PT_SIX_WAVES_MIN_JOBS / 10 : PT_SIX_WAVES_MIN_JOBS) ? SM_SIX_WAVES_PER_SIMD : SM_TUNED_WAVES_PER_SIMD;
     }
@@ -2628,7 +2655,7 @@ static int route_waves_per_simd(const RtLaunch &L, const RtRoute &r)
 }
 static int persistent_blocks_for(const RtLaunch &L, const RtRoute &r)
 {
-    return raytrace_persistent_blocks(L.tile, L.nframes, L.waves_per_cu, L.num_cus, r.kind == 1 && r.lean, route_waves_per_simd(L, r));
+    return raytrace_persistent_blocks(L.tile, L.nframes, L.waves_per_cu, L.num_cus, r.kind == 1 && r.lean, route_waves_per_simd(L, r), L.ntiles_active);
 }
 RtRoute raytrace_route(const RtLaunch &L, int variant)
 {
@@ -3233,6 +3260,53 @@ __global__ void __launch_bounds__(256) k_debug_math(int fn, const float *__restr
     default: r = x / y; break;
     }
     out[i] = r;
+}
+
+// The samples of a launch whose camera rays provably reach no geometry (the context's empty tiles: pt_host_sky.cpp, PROOFS.md section 5): one
+// thread per (pixel of an empty 8x8 tile, frame slot), every lane live -- inside the state machine such a sample takes a job, a segment
+// start and a node step that fails every child, and is served twice at half a wave's width.  The same device functions in the same
+// order as that kernel's path for a pinhole camera, one sample per frame: seed, the focal point's disk sample, the two rand() of the
+// lens sample, the ray from RtLaunch::cam_base, the miss, the store.  A block is one tile x four frame slots.  `samples`: in-bounds pixels
+// of the listed tiles x frames, one ray, one miss and one pixel each, added to the launch's counter set by the first thread (the launch
+// stream orders this kernel against the persistent kernel that writes the same set).
+__global__ void __launch_bounds__(256) k_sky_samples(const RtLaunch L, const uint32_t *__restrict__ tiles, uint64_t samples)
+{
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && L.block_counters) {
+        L.block_counters[CNT_RAYS] += samples; L.block_counters[CNT_MISS] += samples; L.block_counters[CNT_PIXELS] += samples;
+    }
+    const RtUniforms &un = L.un;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int fslot = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6);
+    if (fslot >= L.nframes) return;
+    const int tiles_x = (L.tile.tex_w + 7) >> 3;
+    const int ftile = (int)tiles[blockIdx.x];
+    const int trow = ftile / tiles_x;
+    const int px = (ftile - trow * tiles_x) * 8 + (lane & 7);
+    const int ply = trow * 8 + (lane >> 3);
+    const int pgy = local_to_global_row(ply, L.tile);
+    const uint32_t res_w = (uint32_t)un.res_x, res_h = (uint32_t)un.res_y;
+    const bool ok = px < L.tile.tex_w && ply < L.tile.local_rows && pgy < L.tile.tex_h &&
+                    (uint32_t)px < res_w && (uint32_t)pgy < res_h;     // (the refill's test, raytrace.wgsl:425-427)
+    if (!ok) return;
+    uint32_t seed = sample_seed((uint32_t)px, (uint32_t)pgy, res_w, un.frame + (uint32_t)fslot);
+    const uint32_t gx = (uint32_t)ply * (uint32_t)L.tile.tex_w + (uint32_t)px;
+    const f3 fbase = xyz(L.cam_base[gx]);
+    const f3 focal = camera_focal_point(seed, fbase, 1.0f / un.res_x, 1.0f / un.res_y);
+    (void)rand1(seed);           // (the lens sample of a pinhole camera: its two rand() calls, for the seed)
+    (void)rand1(seed);
+    const f3 o = F3(un.cam_pos[0], un.cam_pos[1], un.cam_pos[2]);
+    const f3 d = normalize(focal - o);
+    float sinr, cosr;
+    ptm::sincos(un.env_rotation, sinr, cosr);
+    const f3 light = miss_light(L.scene.env, d, sinr, cosr, F3(1.0f, 1.0f, 1.0f), F3(0.0f, 0.0f, 0.0f), un.env_intensity);
+    const f3 pix = F3(0.0f, 0.0f, 0.0f) + light;
+    write_radiance(L, gx, (uint32_t)fslot, pix);
+}
+
+void launch_sky_samples(const RtLaunch &L, const uint32_t *tiles, int ntiles, uint64_t samples, hipStream_t s)
+{
+    if (ntiles <= 0 || L.nframes <= 0 || !L.cam_base || !tiles) return;
+    hipLaunchKernelGGL(k_sky_samples, dim3((unsigned)ntiles, (unsigned)((L.nframes + 3) / 4)), dim3(256), 0, s, L, tiles, samples);
 }
 
 // What the launch that has just run COST per ray, for the host's choice of the next launch's build (pt_context.hip: adapt_walk): the

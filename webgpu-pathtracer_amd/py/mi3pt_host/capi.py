@@ -24,7 +24,7 @@ PRESENT_EXACT, PRESENT_LATEST = 0, 1
 (OPT_WALK_MIN, OPT_LEAF_MIN, OPT_SHADE_SPLIT, OPT_TAIL_POLICY, OPT_TOP_PACKETS, OPT_TRI_PAIR, OPT_JOB_REVERSE, OPT_JOB_GROUP,
  OPT_JOB_CHUNK, OPT_BATCH_LIMIT, OPT_BATCH, OPT_WAVES_PER_CU, OPT_CULL, OPT_WIDE, OPT_GATE, OPT_SLOT_SETS, OPT_PIPELINE,
  OPT_COST_ORDER, OPT_PRESENT_DEPTH, OPT_HOST_ANALYSES, OPT_GATHER_STAGED, OPT_DIAG_LITE,
- OPT_GATE_TIMEOUT_MS, OPT_GATE_RELEASES, OPT_DEBUG_SUPPRESS_DRAIN, OPT_CAMERA_BASE, OPT_PACKET_ORDER, OPT_SIX_WAVES, OPT_COLLAPSE, OPT_LAST_BUILD, OPT_WALK_ADAPT) = range(31)
+ OPT_GATE_TIMEOUT_MS, OPT_GATE_RELEASES, OPT_DEBUG_SUPPRESS_DRAIN, OPT_CAMERA_BASE, OPT_PACKET_ORDER, OPT_SIX_WAVES, OPT_COLLAPSE, OPT_LAST_BUILD, OPT_WALK_ADAPT, OPT_SKY_TILES) = range(32)
 COUNTER_NAMES = ("rays", "box_tests", "tri_tests", "hits", "misses", "stack_overflows", "pixels", "reserved")
 
 # every symbol include/mi3pt.h declares; tests/test_capi_symbols.py checks the header
@@ -41,7 +41,7 @@ SYMBOLS = (
     "mi3pt_set_env_sampling", "mi3pt_device_build_bvh",
     "mi3pt_set_pipelining", "mi3pt_flush", "mi3pt_set_present_mode", "mi3pt_raytrace_launch_span", "mi3pt_batch_capacity", "mi3pt_debug_active_variant", "mi3pt_debug_last_launch", "mi3pt_submit_frames", "mi3pt_debug_set_packet_layout",
     "mi3pt_debug_intersect", "mi3pt_debug_math", "mi3pt_debug_wave_times", "mi3pt_host_build_bvh", "mi3pt_host_build_bvh_f64",
-    "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
+    "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
     "mi3pt_create_group", "mi3pt_group_size", "mi3pt_group_member",
     "mi3pt_tile_global_row", "mi3pt_tile_owner",
 )
@@ -118,6 +118,7 @@ def load_library(path=None):
     lib.mi3pt_host_build_bvh_f64.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_int]
     lib.mi3pt_host_env_cdf.argtypes = [c_void_p, c_int, c_int, c_void_p]
     lib.mi3pt_host_eight_wide_check.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p]
+    lib.mi3pt_host_sky_tiles.argtypes = [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
     lib.mi3pt_device_count.argtypes = [ctypes.POINTER(c_int)]
     lib.mi3pt_device_name.argtypes = [c_int, ctypes.c_char_p, c_size_t]
     lib.mi3pt_tile_local_rows.argtypes = [c_int, c_int, c_int, c_int]
@@ -193,6 +194,20 @@ def host_build_bvh_f64(positions, nthreads=0):
     count = ctypes.c_size_t(0)
     _check(lib, lib.mi3pt_host_build_bvh_f64(_ptr(pos), n, _ptr(nodes), nodes.nbytes, ctypes.byref(count), nthreads))
     return nodes[:count.value]
+
+
+def host_sky_tiles(nodes, raytrace_uniforms, width, height, rank=0, nranks=1, block_rows=8):
+    """mi3pt_host_sky_tiles: the 8x8 tiles of a rank's image whose camera rays can reach no geometry, as a (tile rows, tile
+    columns) array of 0 / 1 over the rank's local rows."""
+    lib = load_library()
+    nd = np.ascontiguousarray(nodes)
+    un = np.frombuffer(bytes(raytrace_uniforms), np.uint8).copy()
+    n = ctypes.c_size_t(0)
+    _check(lib, lib.mi3pt_host_sky_tiles(_ptr(nd), nd.nbytes, _ptr(un), width, height, rank, nranks, block_rows, None, 0, ctypes.byref(n)))
+    out = np.zeros(max(n.value, 1), np.uint8)
+    _check(lib, lib.mi3pt_host_sky_tiles(_ptr(nd), nd.nbytes, _ptr(un), width, height, rank, nranks, block_rows, _ptr(out), out.nbytes, ctypes.byref(n)))
+    tiles_x = (width + 7) // 8
+    return out[:n.value].reshape(-1, tiles_x)
 
 
 def host_eight_wide_check(nodes, triangles, greedy=False):
