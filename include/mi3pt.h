@@ -47,7 +47,8 @@ extern "C" {
  * MI3PT_OPT_PACKET_ORDER, MI3PT_OPT_SIX_WAVES (22 .. 27); MI3PT_OPT_WAVES_PER_CU reads up to 24 (six waves per SIMD). */
 /* 4 (round 6): mi3pt_set_rows and mi3pt_measure_tile_cost are GONE (contiguous cost-balanced bands: measured 7 % slower than the dealt
  * 8-row blocks in round 4 and kept since as dead surface); mi3pt_set_kernel_variant accepts 14 (the eight-wide walk: an option).
- * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31). */
+ * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31);
+ * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3). */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -72,7 +73,9 @@ typedef enum mi3pt_status {
 typedef enum mi3pt_pass {
     MI3PT_PASS_RAYTRACE = 0,
     MI3PT_PASS_ACCUMULATE = 1,
-    MI3PT_PASS_FULLSCREEN = 2
+    MI3PT_PASS_FULLSCREEN = 2,
+    MI3PT_PASS_AOV = 3           /* -- no counterpart: the first-hit feature images (mi3pt_render_aovs).  Known to
+                                    mi3pt_pass_time_us only; it has no uniform block (mi3pt_set_uniforms refuses it) */
 } mi3pt_pass;
 
 #define MI3PT_SUBMIT_RAYTRACE 1u
@@ -88,6 +91,25 @@ typedef enum mi3pt_texture {
     MI3PT_TEX_CANVAS = 2         /* the fullscreen pass's colour attachment, as float RGBA
                                     (canvas_w x canvas_h, row 0 = top) */
 } mi3pt_texture;
+
+/* The feature images of the FIRST HIT (AOVs, a G-buffer), mi3pt_render_aovs.  The reference renders none; each is defined by
+ * the reference's own functions: the un-jittered camera ray of the texel (getUv raytrace.wgsl:247-250, cameraToRay :217-245)
+ * and its closest hit (raySceneIntersect :205-211; the hit record of rayTriangleIntersect :78-116).  Each image is
+ * local_rows x width x 16 bytes, rows and tile compaction exactly as MI3PT_TEX_OUTPUT, fp32 / i32 whatever mi3pt_set_storage says.
+ *                                   hit                                                   miss (and texels outside `resolution`)
+ *   ALBEDO    4 x f32   materials[hit.material].color.rgb (raytrace.wgsl:31-38), 1.0      0, 0, 0, 0
+ *   NORMAL    4 x f32   hit.normal.xyz as :105-112 forms it (interpolated, normalised,    0, 0, 0, 0
+ *                       world space, NOT flipped towards the ray), 0.0
+ *   POSITION  4 x f32   hit.position.xyz (origin + t * direction, :111), t                0, 0, 0, 1e20 (the miss record's t, INF, :155)
+ *   IDS       4 x i32   triangle index (into the uploaded 112-byte records),              -1, -1, 0, 0
+ *                       materialIndex (:49), 1, 0 */
+typedef enum mi3pt_aov {
+    MI3PT_AOV_ALBEDO = 0,
+    MI3PT_AOV_NORMAL = 1,
+    MI3PT_AOV_POSITION = 2,
+    MI3PT_AOV_IDS = 3,
+    MI3PT_AOV_COUNT = 4
+} mi3pt_aov;
 
 /* texel storage of output / accumulation textures */
 typedef enum mi3pt_storage {
@@ -228,6 +250,32 @@ int mi3pt_flush(mi3pt_ctx *ctx);
  * it holds this many).  A caller that wants launches of one shape flushes at a divisor of its job. */
 int mi3pt_batch_capacity(mi3pt_ctx *ctx, int *frames);
 
+/* ---- first-hit feature images -- no counterpart in the reference (see mi3pt_aov for what each image holds).
+ * mi3pt_render_aovs renders the images named in aov_mask, an OR of (1u << mi3pt_aov), from the raytrace uniform block (96 B,
+ * raytrace.wgsl:66-75) and the scene AS THEY ARE AT THE CALL; asynchronous and stream ordered like mi3pt_submit.  For every texel
+ * of this context's share (local row ly = image row gy of mi3pt_set_tile's deal, column x):
+ *   inside the rectangle -- x < u32(resolution.x) and gy < u32(resolution.y), the bounds test of raytrace.wgsl:425-427 --
+ *     uv = (x / resolution.x, gy / resolution.y), ray = cameraToRay(camera, uv), hit = raySceneIntersect(ray): the closest t, of
+ *     equal t the leaf the reference's walk visits first, best-so-far after the 64-entry abort (:167-171).  No jitter, no lens, no
+ *     rand(): frame, maxBounces, samplesPerFrame, focalDistance, aperture, the environment and the other passes' blocks do not enter;
+ *   outside: the miss values.  Every call defines every texel of every image it was asked for.
+ * It is NOT a raytrace pass: nothing is added to mi3pt_get_counters, mi3pt_debug_last_launch / MI3PT_OPT_LAST_BUILD keep naming the
+ * last SAMPLE launch, and queued sample frames stay queued -- the pass runs beside them, what they render is bit-identical with or
+ * without it.  Images are allocated at the first call that asks for them and freed by mi3pt_resize / mi3pt_destroy (a context that
+ * never asks allocates nothing).  Images rendered earlier are not altered by later uploads or uniform changes.
+ *   MI3PT_ERR_STATE before mi3pt_resize or for an inconsistent scene (as a raytrace submit); MI3PT_ERR_INVALID for a mask of 0 or
+ *   with unknown bits.
+ * mi3pt_read_aov (blocking) copies image `which` to dst: nbytes = rows x width x 16.  mi3pt_aov_device_ptr hands out the device
+ * image itself (zero copy, e.g. for a torch tensor; valid until the next mi3pt_resize; order your reads behind the context's
+ * stream or call mi3pt_sync first).  Both: MI3PT_ERR_STATE for an image not rendered since the last resize, MI3PT_ERR_INVALID for
+ * a wrong nbytes / unknown image.  Tile split: rows = this rank's compact rows.  Device group: the render goes to every member,
+ * and these two GATHER the whole height x width image onto devices[0] like the accumulation image (two strided copies per member;
+ * staged through pinned memory under MI3PT_OPT_GATHER_STAGED or without peer access).
+ * With timing enabled, mi3pt_pass_time_us(MI3PT_PASS_AOV) is the device time of the most recent call (a group: the slowest member's). ---- */
+int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask);
+int mi3pt_read_aov(mi3pt_ctx *ctx, int which /* mi3pt_aov */, void *dst, size_t nbytes);
+int mi3pt_aov_device_ptr(mi3pt_ctx *ctx, int which /* mi3pt_aov */, void **dev_ptr, size_t *nbytes);
+
 /* ---- read-back (the capability a headless drop-in needs; the reference only has
  * canvas.toDataURL, main.ts:351-356).  Blocking.  dst holds rows x width x 4 floats
  * (rows = local rows for OUTPUT / ACCUMULATION, canvas height for CANVAS). ---- */
@@ -314,7 +362,7 @@ int mi3pt_set_kernel_variant(mi3pt_ctx *ctx, int variant);
  * which voids its proof) -- those exist in no release object. */
 typedef enum mi3pt_option {
     MI3PT_OPT_WALK_MIN = 0,    /* walk while at least this many lanes are walking (32) */
-    MI3PT_OPT_LEAF_MIN = 1,    /* run a triangle step once this many lanes have a leaf parked (24) */
+    MI3PT_OPT_LEAF_MIN = 1,    /* run a triangle step once this many lanes have a leaf parked (24); also the vote of mi3pt_render_aovs' culled walk */
     MI3PT_OPT_SHADE_SPLIT = 2, /* service step: serve the larger of the hit / miss groups, the other only with >= n lanes (64) */
     MI3PT_OPT_TAIL_POLICY = 3, /* drain-phase scheduling bits (7) */
     MI3PT_OPT_TOP_PACKETS = 4, /* kernel variants 6 / 8: node packets staged in LDS per wave */

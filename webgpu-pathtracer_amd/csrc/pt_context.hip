@@ -264,6 +264,17 @@ struct mi3pt_ctx {
     bool timing = false;
     hipEvent_t ev[3][2] = {};
     bool ev_recorded[3] = { false, false, false };
+
+    // First-hit feature images (mi3pt_render_aovs): each local_rows x width x 16 B, allocated by the first call that asks for it and
+    // freed with the textures; aov_valid: rendered (a group's presenting context: gathered) since the last resize.  The pass runs on
+    // the context's stream BESIDE the sample path: it reads the scene, writes these images and touches nothing a sample launch reads
+    // or writes, so the frame queue is neither flushed nor ordered against it.
+    float4 *d_aov[MI3PT_AOV_COUNT] = {};
+    bool aov_valid[MI3PT_AOV_COUNT] = {};
+    hipEvent_t ev_aov[2] = {};           // created with the first timed call
+    bool ev_aov_recorded = false;
+    int walk_stack_worst = 64;           // mi3pt_upload_bvh: entries the reference walk's stack can hold at most on this tree (64: unknown, or the abort can fire)
+    int wide_stack_worst = 64;           // prepare_cull: the wide walks' node stack, order-independent worst case (internal packets only; <= SM_CULL_STACK_MAX where wide_ok)
 };
 
 // Most frames one launch may cover.  A single GPU batches 16 (the drain tail of a persistent
@@ -307,6 +318,9 @@ static int group_pass_time(mi3pt_ctx *g, int pass, float *us);
 static int group_launch_stats(mi3pt_ctx *g, int reset, double *total_ms, uint64_t *launches, uint64_t *frames);
 static int group_launch_span(mi3pt_ctx *g, double *span_ms);
 static int group_counters(mi3pt_ctx *g, uint64_t *out);
+static int group_render_aovs(mi3pt_ctx *g, unsigned aov_mask);
+static int group_read_aov(mi3pt_ctx *g, int which, void *dst, size_t nbytes);
+static int group_aov_ptr(mi3pt_ctx *g, int which, void **dev_ptr, size_t *nbytes);
 static int group_unsupported(const char *what);
 static int group_set_option(mi3pt_ctx *g, int option, int value);
 // one call applied to every member (and, where marked, to the presenting context too)
@@ -632,6 +646,12 @@ static void free_textures(mi3pt_ctx *ctx)
     ctx->d_canvas8 = nullptr;
     ctx->d_block_counters = nullptr;
     ctx->nblocks = 0;
+    for (int k = 0; k < MI3PT_AOV_COUNT; k++) {
+        if (ctx->d_aov[k]) (void)hipFree(ctx->d_aov[k]);
+        ctx->d_aov[k] = nullptr;
+        ctx->aov_valid[k] = false;
+    }
+    ctx->ev_aov_recorded = false;
 }
 
 extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
@@ -673,6 +693,8 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     for (int k = 0; k < 3; k++)
         if (ctx->acc_done[k]) (void)hipEventDestroy(ctx->acc_done[k]);
     if (ctx->main_mark) (void)hipEventDestroy(ctx->main_mark);
+    for (int k = 0; k < 2; k++)
+        if (ctx->ev_aov[k]) (void)hipEventDestroy(ctx->ev_aov[k]);
     if (ctx->ev_span_start) (void)hipEventDestroy(ctx->ev_span_start);
     if (ctx->cost_event) (void)hipEventDestroy(ctx->cost_event);
     for (int k = 0; k < 2; k++)
@@ -1092,6 +1114,7 @@ extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes
     std::vector<uint32_t> leaf_rank((size_t)(max_tri + 1 > 0 ? max_tri + 1 : 1), 0xffffffffu);
     int leaf_cap = 0;
     bool cull_stack_ok = false, tree_proper = false;
+    size_t walk_worst = 64;
     {
         std::vector<uint32_t> st;
         std::vector<uint8_t> seen(n, 0);
@@ -1128,6 +1151,7 @@ extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes
         // nodes only in the deferred walk) from the bottom, parked leaves from the top.
         if (proper && worst < 64 && (int)worst_internal <= pt::SM_LDS_DEPTH - 4) leaf_cap = pt::SM_LDS_DEPTH - (int)worst_internal;
         tree_proper = proper && worst < 64;
+        walk_worst = worst;             // (every box hit: the real walk's stack is a subset of this one's at every node it visits)
         (void)visited;      // nodes the root does not reach are never walked by the reference either
         // The culling walks push the nearer child last, so ANY child may be the one that is descended
         // first with all its internal siblings still stacked: occupancy(child) = occupancy(parent) - 1 +
@@ -1160,6 +1184,7 @@ extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes
     ctx->leaf_cap = leaf_cap;
     ctx->cull_stack_ok = cull_stack_ok;
     ctx->tree_proper = tree_proper;
+    ctx->walk_stack_worst = tree_proper ? (int)walk_worst : 64;
     ctx->nnodes = n;
     ctx->npackets = npackets;
     ctx->root_ref = ref_of(0);
@@ -1894,6 +1919,7 @@ static int prepare_cull(mi3pt_ctx *ctx)
             ctx->nwide = wp.size();
             ctx->wide_leaf_cap = pt::SM_CULL_LEAF_CAP;
             ctx->wide_root = 0;
+            ctx->wide_stack_worst = (int)worst;
             ctx->wide_ok = true;
             ctx->wide_root_nested = nested[0] != 0;
         }
@@ -2858,6 +2884,90 @@ extern "C" int mi3pt_bind_accumulation(mi3pt_ctx *ctx, void *dev_ptr, size_t nby
     return MI3PT_OK;
 }
 
+// ---- first-hit feature images (include/mi3pt.h: mi3pt_aov, mi3pt_render_aovs) ----
+// Not require_idle: the queued sample frames stay queued and keep their batching.  The pass is enqueued on the context's stream;
+// every path that frees or replaces a scene buffer waits for that stream first (replace_buffer, clone_scene, mi3pt_resize).
+extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
+{
+    PT_GROUP(ctx, group_render_aovs(ctx, aov_mask));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_render_aovs before resize");
+    if (aov_mask == 0 || (aov_mask >> MI3PT_AOV_COUNT)) return pt_set_error(MI3PT_ERR_INVALID, "aov_mask must be a non-empty OR of (1u << mi3pt_aov)");
+    if (int rc = check_scene(ctx)) return rc;
+    if (int rc = prepare_layout(ctx)) return rc;    // (what a raytrace submit does: no-ops unless the scene changed -- and then no frame is queued)
+    if (int rc = prepare_cull(ctx)) return rc;
+    const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
+    for (int k = 0; k < MI3PT_AOV_COUNT; k++)
+        if (((aov_mask >> k) & 1u) && !ctx->d_aov[k]) HIP_TRY(hipMalloc((void **)&ctx->d_aov[k], tex_bytes ? tex_bytes : 16));
+    pt::AovLaunch A;
+    A.scene = scene_refs(ctx);
+    const uint8_t *u = ctx->u_rt;
+    A.un.res_x = ldf(u, 0); A.un.res_y = ldf(u, 4); A.un.aspect = ldf(u, 8);
+    A.un.frame = 0; A.un.max_bounces = 0; A.un.samples_per_frame = 0;          // (do not enter)
+    for (int k = 0; k < 3; k++) { A.un.cam_pos[k] = ldf(u, 32 + 4 * k); A.un.cam_dir[k] = ldf(u, 48 + 4 * k); }
+    A.un.fov = ldf(u, 60); A.un.focal_distance = 0.0f; A.un.aperture = 0.0f; A.un.env_intensity = 0.0f; A.un.env_rotation = 0.0f;
+    A.tile = tile_of(ctx);
+    for (int k = 0; k < MI3PT_AOV_COUNT; k++) A.image[k] = ((aov_mask >> k) & 1u) ? ctx->d_aov[k] : nullptr;
+    // The walk.  Where `auto` would render sample frames with the shipped walk (variant 13: the scene admits distance culling and the
+    // compressed wide packets, MI3PT_OPT_CULL / MI3PT_OPT_WIDE are on, no debug layout), the first-hit walk on that walk's data.
+    // Else the reference's un-culled one on node / triangle packets with the prepared-reciprocal slab test (what the probe runs;
+    // bit-identical on every tree the context accepts).  The debug packet layout renumbers the triangles its packets name: there
+    // the walk on the uploaded records runs, so that the ids image holds uploaded indices.  One set of bits whichever runs.
+    int walk = 3, stack_worst = ctx->walk_stack_worst;
+    const bool culled = !ctx->env_sampling && !ctx->layout_active && ctx->cull_enabled && ctx->wide_enabled && ctx->cull_stack_ok &&
+                        ctx->cull_ok && !ctx->cull_dirty && ctx->wide_ok && ctx->cwide_ok && ctx->d_leaf_rank;
+    if (culled) { walk = 13; stack_worst = ctx->wide_stack_worst; }
+    else if (ctx->layout_active) { walk = 1; A.scene.tris = static_cast<const float4 *>(ctx->d_tris); }
+    if (tex_bytes) {
+        if (ctx->timing) {
+            for (int k = 0; k < 2; k++)
+                if (!ctx->ev_aov[k]) HIP_TRY(hipEventCreate(&ctx->ev_aov[k]));
+            HIP_TRY(hipEventRecord(ctx->ev_aov[0], ctx->stream));
+        }
+        pt::launch_aovs(A, walk, stack_worst, ctx->leaf_min, ctx->stream);
+        HIP_TRY(hipGetLastError());
+        if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev_aov[1], ctx->stream)); ctx->ev_aov_recorded = true; }
+    }
+    for (int k = 0; k < MI3PT_AOV_COUNT; k++)
+        if ((aov_mask >> k) & 1u) ctx->aov_valid[k] = true;
+    return MI3PT_OK;
+}
+
+static int aov_image(mi3pt_ctx *ctx, int which, const char *what)
+{
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
+    if (which < 0 || which >= MI3PT_AOV_COUNT) return pt_set_error(MI3PT_ERR_INVALID, "unknown feature image");
+    if (!ctx->aov_valid[which] || !ctx->d_aov[which])
+        return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": this image has not been rendered since the last resize (mi3pt_render_aovs)");
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_read_aov(mi3pt_ctx *ctx, int which, void *dst, size_t nbytes)
+{
+    PT_GROUP(ctx, group_read_aov(ctx, which, dst, nbytes));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = aov_image(ctx, which, "mi3pt_read_aov")) return rc;
+    const size_t need = (size_t)ctx->local_rows * ctx->width * 16;
+    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
+    if (need == 0) return MI3PT_OK;
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
+    HIP_TRY(hipMemcpyAsync(dst, ctx->d_aov[which], need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_aov_device_ptr(mi3pt_ctx *ctx, int which, void **dev_ptr, size_t *nbytes)
+{
+    PT_GROUP(ctx, group_aov_ptr(ctx, which, dev_ptr, nbytes));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = aov_image(ctx, which, "mi3pt_aov_device_ptr")) return rc;
+    *dev_ptr = ctx->d_aov[which];
+    if (nbytes) *nbytes = (size_t)ctx->local_rows * ctx->width * 16;
+    return MI3PT_OK;
+}
+
 extern "C" int mi3pt_enable_timing(mi3pt_ctx *ctx, int enabled)
 {
     PT_GROUP_ALL(ctx, true, mi3pt_enable_timing(m, enabled));
@@ -2870,6 +2980,14 @@ extern "C" int mi3pt_pass_time_us(mi3pt_ctx *ctx, int pass, float *microseconds)
 {
     PT_GROUP(ctx, group_pass_time(ctx, pass, microseconds));
     if (int rc = require_idle(ctx)) return rc;
+    if (microseconds && pass == MI3PT_PASS_AOV) {
+        if (!ctx->ev_aov_recorded) return pt_set_error(MI3PT_ERR_STATE, "no timed mi3pt_render_aovs since the last resize");
+        HIP_TRY(ctx_event_sync(ctx, ctx->ev_aov[1]));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_aov[0], ctx->ev_aov[1]));
+        *microseconds = ms * 1000.0f;
+        return MI3PT_OK;
+    }
     if (!microseconds || pass < 0 || pass > 2) return pt_set_error(MI3PT_ERR_INVALID, "bad argument");
     if (pass == MI3PT_PASS_RAYTRACE && !ctx->ev_recorded[0] && (ctx->ev_rt_pending[0] || ctx->ev_rt_pending[1] || ctx->rt_launches)) {
         // batched launch: the most recent batch's kernel time divided by its frames (the older
@@ -3082,6 +3200,9 @@ struct GroupState {
     std::vector<char> peer_direct;
     void *stage = nullptr;        // pinned host buffer of stage_bytes (allocated when first needed)
     size_t stage_bytes = 0;
+    // first-hit feature images: which the members hold (rendered since the last resize), and which of those the presenting
+    // context's whole image is a current copy of
+    bool aov_rendered[MI3PT_AOV_COUNT] = {}, aov_gathered[MI3PT_AOV_COUNT] = {};
 };
 
 template <class F>
@@ -3175,12 +3296,14 @@ static int group_resize(mi3pt_ctx *g, int width, int height)
 {
     GroupState *gs = g->group;
     gs->width = gs->height = 0;
+    for (int k = 0; k < MI3PT_AOV_COUNT; k++) gs->aov_rendered[k] = gs->aov_gathered[k] = false;
     if (int rc = group_each(g, true, [&](mi3pt_ctx *m) { return mi3pt_resize(m, width, height); })) return rc;
     gs->width = width;
     gs->height = height;
     g->width = width; g->height = height;
     gs->gathered = true;          // every image is zero
     gs->want_present = false;
+    for (int k = 0; k < MI3PT_AOV_COUNT; k++) gs->aov_rendered[k] = gs->aov_gathered[k] = false;
     return MI3PT_OK;
 }
 
@@ -3245,6 +3368,7 @@ static int clone_scene(mi3pt_ctx *dst, const mi3pt_ctx *src)
     dst->root_ref = src->root_ref; dst->scene_flags = src->scene_flags; dst->wide_root_nested = src->wide_root_nested;
     dst->max_tri_ref = src->max_tri_ref; dst->max_mat_ref = src->max_mat_ref;
     dst->leaf_cap = src->leaf_cap; dst->cull_stack_ok = src->cull_stack_ok; dst->tree_proper = src->tree_proper;
+    dst->walk_stack_worst = src->walk_stack_worst; dst->wide_stack_worst = src->wide_stack_worst;
     dst->cull_dirty = src->cull_dirty; dst->cull_ok = src->cull_ok; dst->cull_ka = src->cull_ka; dst->cull_kb = src->cull_kb;
     dst->auto_wide_variant = src->auto_wide_variant; dst->wide_ok = src->wide_ok; dst->cwide_ok = src->cwide_ok; dst->nwide = src->nwide;
     dst->cw8_ok = src->cw8_ok; dst->cw8_tried = src->cw8_tried; dst->ncw8 = src->ncw8; dst->cw8_records = src->cw8_records; dst->cw8_height = src->cw8_height;
@@ -3304,14 +3428,15 @@ static int group_sync(mi3pt_ctx *g)
 // geometry: source pitch = one block, destination pitch = n blocks) on the presenting context's stream -- peer DMA over xGMI.
 // Otherwise: staged through pinned host memory (a device-to-host copy on the member's device, then the same strided copy from
 // the host buffer).
-static int gather_member(GroupState *gs, int i, bool direct)
+// (aov < 0: the accumulation image; else that feature image, mi3pt_read_aov of a group)
+static int gather_member(GroupState *gs, int i, bool direct, int aov = -1)
 {
     mi3pt_ctx *p = gs->present;
     const mi3pt_ctx *m = gs->members[(size_t)i];
     const int n = (int)gs->members.size(), br = gs->block_rows, W = gs->width, H = gs->height;
     const size_t row_bytes = (size_t)W * 16, block_bytes = row_bytes * (size_t)br;
-    uint8_t *dst = reinterpret_cast<uint8_t *>(p->d_accum);
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(m->d_accum);
+    uint8_t *dst = reinterpret_cast<uint8_t *>(aov < 0 ? p->d_accum : p->d_aov[aov]);
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(aov < 0 ? m->d_accum : m->d_aov[aov]);
     const int rows = m->local_rows;
     if (rows == 0) return MI3PT_OK;
     const int full = rows / br, tail = rows - full * br;      // whole blocks, rows of a last partial block (the image's bottom edge)
@@ -3345,6 +3470,8 @@ static int gather_member(GroupState *gs, int i, bool direct)
     return MI3PT_OK;
 }
 
+static int gather_copies(GroupState *gs, int aov);
+
 static int group_gather(mi3pt_ctx *g)
 {
     GroupState *gs = g->group;
@@ -3353,12 +3480,24 @@ static int group_gather(mi3pt_ctx *g)
     if (int rc = group_sync(g)) return rc;
     mi3pt_ctx *p = gs->present;
     if (int rc = require_idle(p)) return rc;
+    if (int rc = gather_copies(gs, -1)) return rc;
+    p->output_is_accum = true;      // like the copy-back of accumulate.ts:171-175
+    p->main_dirty = true;
+    p->accum_version++;
+    gs->gathered = true;
+    return MI3PT_OK;
+}
+
+// the copies of a gather (the members' work has been waited for): the accumulation image (aov < 0) or a feature image
+static int gather_copies(GroupState *gs, int aov)
+{
+    mi3pt_ctx *p = gs->present;
     const int n = (int)gs->members.size();
     for (int attempt = 0; attempt < 2; attempt++) {
         // direct copies first, all in flight together on the presenting stream (n - 1 transfers on n - 1 links into one root) ...
         for (int i = 0; i < n; i++) {
             if (!gs->peer_direct[(size_t)i]) continue;
-            if (gather_member(gs, i, true) != MI3PT_OK) { (void)hipGetLastError(); gs->peer_direct[(size_t)i] = 0; }
+            if (gather_member(gs, i, true, aov) != MI3PT_OK) { (void)hipGetLastError(); gs->peer_direct[(size_t)i] = 0; }
         }
         if (ctx_stream_sync(p, p->stream) == hipSuccess) break;
         // ... a rect copy between two devices can also fail asynchronously (round-3 advice): nothing this pass wrote is trusted;
@@ -3372,14 +3511,62 @@ static int group_gather(mi3pt_ctx *g)
     // ... then whatever cannot be addressed directly, staged through pinned host memory
     for (int i = 0; i < n; i++)
         if (!gs->peer_direct[(size_t)i])
-            if (int rc = gather_member(gs, i, false)) return rc;
+            if (int rc = gather_member(gs, i, false, aov)) return rc;
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(ctx_stream_sync(p, p->stream));
-    p->output_is_accum = true;      // like the copy-back of accumulate.ts:171-175
-    p->main_dirty = true;
-    p->accum_version++;
-    gs->gathered = true;
     return MI3PT_OK;
+}
+
+// ---- first-hit feature images of a group: rendered by every member for its rows, gathered when read ----
+static int group_render_aovs(mi3pt_ctx *g, unsigned aov_mask)
+{
+    GroupState *gs = g->group;
+    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_render_aovs before resize");
+    if (aov_mask == 0 || (aov_mask >> MI3PT_AOV_COUNT)) return pt_set_error(MI3PT_ERR_INVALID, "aov_mask must be a non-empty OR of (1u << mi3pt_aov)");
+    if (int rc = group_sync_scene(g)) return rc;
+    if (int rc = group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_render_aovs(m, aov_mask); })) return rc;
+    for (int k = 0; k < MI3PT_AOV_COUNT; k++)
+        if ((aov_mask >> k) & 1u) { gs->aov_rendered[k] = true; gs->aov_gathered[k] = false; }
+    return MI3PT_OK;
+}
+
+static int group_gather_aov(mi3pt_ctx *g, int which, const char *what)
+{
+    GroupState *gs = g->group;
+    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
+    if (which < 0 || which >= MI3PT_AOV_COUNT) return pt_set_error(MI3PT_ERR_INVALID, "unknown feature image");
+    if (!gs->aov_rendered[which])
+        return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": this image has not been rendered since the last resize (mi3pt_render_aovs)");
+    if (gs->aov_gathered[which]) return MI3PT_OK;
+    mi3pt_ctx *p = gs->present;
+    // the members' passes (their own streams; their frame queues stay as they are), then the copies
+    for (mi3pt_ctx *m : gs->members) {
+        if (int rc = require_ctx(m)) return rc;
+        HIP_TRY(ctx_stream_sync(m, m->stream));
+    }
+    if (int rc = require_ctx(p)) return rc;
+    if (!p->d_aov[which]) HIP_TRY(hipMalloc((void **)&p->d_aov[which], (size_t)gs->width * gs->height * 16));
+    if (int rc = gather_copies(gs, which)) return rc;
+    p->aov_valid[which] = true;
+    gs->aov_gathered[which] = true;
+    return MI3PT_OK;
+}
+
+static int group_read_aov(mi3pt_ctx *g, int which, void *dst, size_t nbytes)
+{
+    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (g->group->width && which >= 0 && which < MI3PT_AOV_COUNT && g->group->aov_rendered[which] &&
+        nbytes != (size_t)g->group->width * g->group->height * 16)
+        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (a group reads whole images: height x width x 16 bytes)");
+    if (int rc = group_gather_aov(g, which, "mi3pt_read_aov")) return rc;
+    return mi3pt_read_aov(g->group->present, which, dst, nbytes);
+}
+
+static int group_aov_ptr(mi3pt_ctx *g, int which, void **dev_ptr, size_t *nbytes)
+{
+    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = group_gather_aov(g, which, "mi3pt_aov_device_ptr")) return rc;
+    return mi3pt_aov_device_ptr(g->group->present, which, dev_ptr, nbytes);
 }
 
 static int group_draw_canvas(mi3pt_ctx *g)
@@ -3534,6 +3721,7 @@ static int group_set_option(mi3pt_ctx *g, int option, int value)
         for (size_t i = 0; i < gs->peer_direct.size(); i++)
             gs->peer_direct[i] = value ? 0 : (gs->members[i]->device == gs->present->device ? 1 : gs->peer_direct[i]);
         gs->gathered = false;
+        for (bool &a : gs->aov_gathered) a = false;
         return MI3PT_OK;
     }
     return group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_debug_set_option(m, option, value); });

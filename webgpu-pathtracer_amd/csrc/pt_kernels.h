@@ -330,6 +330,17 @@ int raytrace_job_tiles(const RtLaunch &L);      // tiles of a frame that are job
 // the samples of `ntiles` listed tiles (device array) x L.nframes whose camera rays reach no geometry, shaded at full width (needs
 // L.cam_base); `samples`: the in-bounds pixels among them x frames, for the launch's counters
 void launch_sky_samples(const RtLaunch &L, const uint32_t *tiles, int ntiles, uint64_t samples, hipStream_t s);
+// First-hit feature images (include/mi3pt.h: mi3pt_aov, mi3pt_render_aovs): one un-jittered camera ray per texel of the rank's rows.
+struct AovLaunch {
+    SceneRefs scene;
+    RtUniforms un;               // resolution, aspect, camera position / direction, fov; the rest does not enter
+    Tile tile;
+    float4 *image[4];            // indexed by mi3pt_aov (albedo, normal, position + t, ids as four i32); null = not asked for
+};
+// walk: 3 = the reference's walk on node / triangle packets (prepared-reciprocal slab test), 1 = on the uploaded records,
+// 13 = first hit only on the shipped walk's compressed wide packets, near first, with distance culling (needs scene.cwide,
+// scene.tripk64, the culling constants); stack_worst: entries that walk's (node) stack can hold at most on this tree (64 = unknown)
+void launch_aovs(const AovLaunch &A, int walk, int stack_worst, int leaf_min, hipStream_t s);      // (leaf_min: walk 13's triangle-step vote)
 // packs the three position vectors of `ntris` 112-byte triangle records into 48-byte rows (the context's cull analysis)
 void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipStream_t s);
 // writes NodePacket::cull of `npackets` packets from a dense array (the context's cull analysis)

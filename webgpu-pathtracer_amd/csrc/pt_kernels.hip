@@ -3369,6 +3369,230 @@ void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipSt
     hipLaunchKernelGGL(k_pack_vertices, dim3((ntris + 255u) / 256u), dim3(256), 0, s, tris, out, ntris);
 }
 
+// ---------------------------------------------------------------------------------
+// First-hit feature images (include/mi3pt.h: mi3pt_aov): per texel of the rank's rows the UN-JITTERED camera ray -- getUv,
+// raytrace.wgsl:247-250, and cameraToRay, :217-245, of the texel itself: no disk sample, no lens, no rand() -- and its closest
+// hit, raySceneIntersect (:205-211).  One wave per 8x8 tile, like k_raytrace: the 64 primary rays of a tile share their origin and
+// leave through one small solid angle, which is as coherent as rays get, so the wave walks in lockstep with few idle lanes and a
+// plain grid (no persistent loop, no refill) keeps the CUs full.  The walk is traverse<> as the probe kernel runs it -- the
+// reference's tests in the reference's order: closest t, of equal t the first visited leaf, best-so-far after the 64-entry
+// abort -- and finish_hit forms position and normal; nothing here is shared with k_raytrace_sm.  The stack is [entry][lane] in LDS:
+// DEPTH = 64 entries (16 KiB, ten waves per CU), or 32 (8 KiB, twenty) where the context has shown at upload that the walk's
+// stack cannot hold more than 32 entries on this tree.  Only the images asked for are formed and written (the mask is
+// wave-uniform: scalar branches), one 16-byte store per texel and image; texels outside `resolution` get the miss values.
+// ---------------------------------------------------------------------------------
+// the texel's values in the images asked for (the mask is wave-uniform: scalar branches), one 16-byte store each
+PT_DEV void aov_store(const AovLaunch &A, size_t idx, const f3 &o, const f3 &d, const Best &best)
+{
+    const bool hit = best.tri >= 0;
+    f3 position = F3(0.0f, 0.0f, 0.0f), normal = F3(0.0f, 0.0f, 0.0f);
+    int32_t mi = -1;
+    if (hit) finish_hit(A.scene, o, d, best, position, normal, mi);
+    if (A.image[0]) {
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (hit) { const float4 m0 = A.scene.mats[(size_t)mi * 4]; c = make_float4(m0.x, m0.y, m0.z, 1.0f); }      // Material.color, raytrace.wgsl:31-38
+        A.image[0][idx] = c;
+    }
+    if (A.image[1]) A.image[1][idx] = make_float4(normal.x, normal.y, normal.z, 0.0f);
+    if (A.image[2]) A.image[2][idx] = make_float4(position.x, position.y, position.z, best.t);
+    if (A.image[3]) A.image[3][idx] = make_float4(__int_as_float(best.tri), __int_as_float(mi), __int_as_float(hit ? 1 : 0), __int_as_float(0));
+}
+
+template <int VARIANT, int DEPTH>
+__global__ void __launch_bounds__(64) k_aov(const AovLaunch A)
+{
+    __shared__ uint32_t stack_lds[DEPTH * 64];
+    const int lane = threadIdx.x;
+    const int tiles_x = (A.tile.tex_w + 7) >> 3;
+    const int tile_y = (int)blockIdx.x / tiles_x, tile_x = (int)blockIdx.x - tile_y * tiles_x;
+    const int gx = tile_x * 8 + (lane & 7);
+    const int ly = tile_y * 8 + (lane >> 3);
+    if (gx >= A.tile.tex_w || ly >= A.tile.local_rows) return;      // no such texel (no wave-wide operation follows)
+    const int gy = local_to_global_row(ly, A.tile);
+    // raytrace.wgsl:425-427
+    const bool inside = gy < A.tile.tex_h && (uint32_t)gx < (uint32_t)A.un.res_x && (uint32_t)gy < (uint32_t)A.un.res_y;
+    const f3 o = F3(A.un.cam_pos[0], A.un.cam_pos[1], A.un.cam_pos[2]);
+    f3 d = F3(0.0f, 0.0f, 0.0f);
+    Best best;
+    best.t = PT_INF; best.u = 0.0f; best.v = 0.0f; best.tri = -1;
+    if (inside) {
+        const float uvx = (float)gx / A.un.res_x;            // getUv, :247-250
+        const float uvy = (float)gy / A.un.res_y;
+        const CameraFrame cf = camera_frame(A.un);           // (wave-uniform)
+        d = camera_direction(cf, A.un.aspect, uvx, uvy);
+        Counters cnt = { 0, 0, 0, 0, 0, 0, 0, 0 };
+        traverse<VARIANT>(A.scene, o, d, stack_lds + lane, best, cnt);
+    }
+    aov_store(A, (size_t)ly * A.tile.tex_w + gx, o, d, best);
+}
+
+// The same images from the SHIPPED walk's data, where the context has it (what `auto` resolves to variant 13 on: compressed 4-ary
+// packets, 64-byte triangle records with the leaf's own box, the culling constants): closest hit only, children near first, a child
+// skipped when its box starts provably behind the closest hit so far.  Every decision is made by the device functions the shipped
+// walk makes it with -- cwide_hit on the decoded planes (never rejects what the reference's test passes), leaf_box_hit (the
+// reference's test of the leaf's own box, exact), ray_triangle_flat_e, cull_setup and the three-axis culling condition (S) of
+// PROOFS.md section 1, equal t resolved by the leaf's rank in the reference's visiting order -- in the arrangement of
+// k_raytrace_sm's compressed-wide node and triangle steps; nothing new needs proving, and nothing of that kernel is touched.
+// Per lane: a node stack (internal packets only) from the bottom of its LDS column and a leaf list of AOV_LCAP entries at the top;
+// the wave votes between a node step and a triangle step like the deferred-leaf walks (leaf_min: MI3PT_OPT_LEAF_MIN).  The column is
+// DYNAMIC shared memory of exactly `entries` x 256 B: the order-independent worst case of the node stack that the context computed for
+// this tree's wide packets, plus the leaf list -- residency goes by the tree (160 KiB / that per CU), not by the 64 entries of the abort.
+constexpr int AOV_LCAP = 8;
+__global__ void __launch_bounds__(64) k_aov_cull(const AovLaunch A, const int ENTRIES, const int leaf_min)
+{
+    extern __shared__ uint32_t stack_lds[];
+    const int NCAP = ENTRIES - AOV_LCAP;
+    const SceneRefs &sc = A.scene;
+    const int lane = threadIdx.x;
+    uint32_t *const stack = stack_lds + lane;
+    const int tiles_x = (A.tile.tex_w + 7) >> 3;
+    const int tile_y = (int)blockIdx.x / tiles_x, tile_x = (int)blockIdx.x - tile_y * tiles_x;
+    const int gx = tile_x * 8 + (lane & 7);
+    const int ly = tile_y * 8 + (lane >> 3);
+    const bool texel = gx < A.tile.tex_w && ly < A.tile.local_rows;
+    const int gy = local_to_global_row(ly, A.tile);
+    // raytrace.wgsl:425-427
+    const bool inside = texel && gy < A.tile.tex_h && (uint32_t)gx < (uint32_t)A.un.res_x && (uint32_t)gy < (uint32_t)A.un.res_y;
+    const f3 o = F3(A.un.cam_pos[0], A.un.cam_pos[1], A.un.cam_pos[2]);
+    f3 d = F3(0.0f, 0.0f, 0.0f);
+    Best best;
+    best.t = PT_INF; best.u = 0.0f; best.v = 0.0f; best.tri = -1;
+    int sp = 0, nl = 0;
+    RayPre pre;
+    pre.ix = pre.iy = pre.iz = 0.0f; pre.flags = 8u;
+    float cull_ka = __builtin_inff(), cull_kb = __builtin_inff();
+    if (inside) {
+        const float uvx = (float)gx / A.un.res_x;            // getUv, :247-250
+        const float uvy = (float)gy / A.un.res_y;
+        const CameraFrame cf = camera_frame(A.un);           // (wave-uniform)
+        d = camera_direction(cf, A.un.aspect, uvx, uvy);
+        // (a ray with a NaN hits nothing in the reference -- every acceptance test of raytrace.wgsl:78-116 is false -- the known answer, as
+        // in the shipped culling walks)
+        const bool nan_ray = !(d.x == d.x) || !(d.y == d.y) || !(d.z == d.z) || !(o.x == o.x) || !(o.y == o.y) || !(o.z == o.z);
+        if (sc.nnodes != 0 && !nan_ray) {
+            pre = ray_prepare(o, d, sc.flags);
+            cull_setup(d, pre, sc.cull_ka, sc.cull_kb, cull_ka, cull_kb);
+            // the root test of rayBVHIntersect (raytrace.wgsl:157-159); where the root's box contains its children's, the first node step
+            // rejects whatever it would reject (the slab test is monotone under nesting)
+            bool enter = (sc.flags & 2u) != 0u;
+            if (!enter) {
+                const float4 n0 = sc.nodes[0], n1 = sc.nodes[1];
+                enter = ray_aabb_pre(o, d, pre, (sc.flags & 1u) == 0u, n0.x, n0.y, n0.z, n1.x, n1.y, n1.z);
+            }
+            if (enter) { stack[0] = sc.wide_root; sp = 1; }
+        }
+    }
+    for (;;) {
+        const bool has_node = sp > 0, has_leaf = nl > 0;
+        const int n_node = (int)__popcll(__ballot(has_node)), n_leaf = (int)__popcll(__ballot(has_leaf));
+        if (n_node == 0 && n_leaf == 0) break;
+        const bool full = __ballot(nl > AOV_LCAP - 4) != 0ull;      // a node step may park four more
+        if (full || n_node == 0 || n_leaf >= leaf_min) {
+            if (has_leaf) {
+                // a parked leaf is a CANDIDATE (its packet's box was rounded outward): the reference tests the triangle iff the leaf's own
+                // box passes its exact test -- made here, from the 64-byte record that carries that box
+                nl--;
+                const uint32_t ti = stack[(ENTRIES - 1 - nl) * 64];
+                const float4 pa = sc.tripk64[(size_t)ti * 4 + 0], pb = sc.tripk64[(size_t)ti * 4 + 1];
+                const float4 pc = sc.tripk64[(size_t)ti * 4 + 2], pd = sc.tripk64[(size_t)ti * 4 + 3];
+                float t, u, v;
+                const bool inbox = leaf_box_hit(o, d, pre, __float_as_uint(pd.w) != 0u, F3(pc.y, pc.z, pc.w), F3(pd.x, pd.y, pd.z));
+                const bool hit = ray_triangle_flat_e(o, d, F3(pa.x, pa.y, pa.z), F3(pa.w, pb.x, pb.y), F3(pb.z, pb.w, pc.x), t, u, v) && inbox;
+                bool take = hit && t < best.t;
+                if (hit && t == best.t && best.tri >= 0) take = sc.leaf_rank[ti] < sc.leaf_rank[best.tri];      // the earlier leaf of the reference order wins
+                best.t = take ? t : best.t; best.u = take ? u : best.u; best.v = take ? v : best.v;
+                best.tri = take ? (int32_t)ti : best.tri;
+            }
+        } else if (has_node) {
+            sp--;
+            const uint32_t ref = stack[sp * 64];
+            const float4 *P = sc.cwide + (size_t)ref * 4;
+            const float4 c0 = P[0], c1 = P[1], c2 = P[2], c3 = P[3];
+            uint32_t cr[4] = { __float_as_uint(c3.x), __float_as_uint(c3.y), __float_as_uint(c3.z), __float_as_uint(c3.w) };
+            const uint32_t meta = __float_as_uint(c0.w);
+            const uint32_t w01 = __float_as_uint(c2.z), w23 = __float_as_uint(c2.w);
+            const uint32_t lx = __float_as_uint(c1.x), lyq = __float_as_uint(c1.y), lz = __float_as_uint(c1.z);
+            const uint32_t hx = __float_as_uint(c1.w), hy = __float_as_uint(c2.x), hz = __float_as_uint(c2.y);
+            const float cx = __uint_as_float((meta & 0xffu) << 23), cy = __uint_as_float(((meta >> 8) & 0xffu) << 23), cz = __uint_as_float(((meta >> 16) & 0xffu) << 23);
+            bool hit[4];
+            float key[4];
+            f3 tn[4];
+            // (a ray on the plain-division path: never skipped -- its culling constants are +inf -- and the order of no consequence)
+            tn[0] = tn[1] = tn[2] = tn[3] = F3(-PT_INF, -PT_INF, -PT_INF);
+            key[0] = key[1] = key[2] = key[3] = -PT_INF;
+            if ((pre.flags & 8u) == 0u) {
+                // one fma per quotient on the decoded planes, near / far plane per axis by the sign of the ray's reciprocal: k_raytrace_sm's
+                // compressed-wide node step, operation for operation (see there and cwide_hit)
+                const float Ax = (c0.x - o.x) * pre.ix, Ay = (c0.y - o.y) * pre.iy, Az = (c0.z - o.z) * pre.iz;
+                const float Bx = cx * pre.ix, By = cy * pre.iy, Bz = cz * pre.iz;
+                const bool nx_ = pre.ix < 0.0f, ny_ = pre.iy < 0.0f, nz_ = pre.iz < 0.0f;
+                const uint32_t ex = nx_ ? hx : lx, fx = nx_ ? lx : hx, ey = ny_ ? hy : lyq, fy = ny_ ? lyq : hy, ez = nz_ ? hz : lz, fz = nz_ ? lz : hz;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const float ax_ = fmaf((float)((ex >> (8 * k)) & 0xffu), Bx, Ax), bx_ = fmaf((float)((fx >> (8 * k)) & 0xffu), Bx, Ax);
+                    const float ay_ = fmaf((float)((ey >> (8 * k)) & 0xffu), By, Ay), by_ = fmaf((float)((fy >> (8 * k)) & 0xffu), By, Ay);
+                    const float az_ = fmaf((float)((ez >> (8 * k)) & 0xffu), Bz, Az), bz_ = fmaf((float)((fz >> (8 * k)) & 0xffu), Bz, Az);
+                    const float f_ = fminf(fminf(bx_, by_), bz_);
+                    tn[k] = F3(ax_, ay_, az_);
+                    key[k] = fmaxf(fmaxf(ax_, ay_), az_);
+                    hit[k] = cwide_hit(key[k], f_);
+                }
+            } else {
+                // the reference's test on the decoded box, which contains the child's (see k_raytrace_sm): conservative too
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    hit[k] = ray_aabb(o, d, fmaf((float)((lx >> (8 * k)) & 0xffu), cx, c0.x), fmaf((float)((lyq >> (8 * k)) & 0xffu), cy, c0.y), fmaf((float)((lz >> (8 * k)) & 0xffu), cz, c0.z),
+                                      fmaf((float)((hx >> (8 * k)) & 0xffu), cx, c0.x), fmaf((float)((hy >> (8 * k)) & 0xffu), cy, c0.y), fmaf((float)((hz >> (8 * k)) & 0xffu), cz, c0.z));
+            }
+            // distance bound per child (condition (S) on all three axes), as k_raytrace_sm forms it
+            const float rc = fmaf(cull_ka, best.t, cull_kb);
+            const float bt = best.t * 1.00000095367431640625f;
+            const float wgt[4] = { __uint_as_float(w01 & 0xffff0000u), __uint_as_float(w01 << 16),
+                                   __uint_as_float(w23 & 0xffff0000u), __uint_as_float(w23 << 16) };
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float dk = wgt[k] * rc;
+                const float tc = fmaxf(fmaxf(fmaf(-dk, fabsf(pre.ix), tn[k].x), fmaf(-dk, fabsf(pre.iy), tn[k].y)), fmaf(-dk, fabsf(pre.iz), tn[k].z));
+                cr[k] = (hit[k] && !(tc > bt)) ? cr[k] : PT_REF_NONE;
+            }
+            // far first, near last (popped first): sort the four entries by entry distance, descending
+#define PT_CSWAP(A_, B_)                                                                       \
+            {                                                                                  \
+                const bool sw = key[A_] < key[B_];                                             \
+                const float ka_ = sw ? key[B_] : key[A_], kb_ = sw ? key[A_] : key[B_];        \
+                const uint32_t ra_ = sw ? cr[B_] : cr[A_], rb_ = sw ? cr[A_] : cr[B_];         \
+                key[A_] = ka_; key[B_] = kb_; cr[A_] = ra_; cr[B_] = rb_;                      \
+            }
+            PT_CSWAP(0, 1) PT_CSWAP(2, 3) PT_CSWAP(0, 2) PT_CSWAP(1, 3) PT_CSWAP(1, 2)
+#undef PT_CSWAP
+            // nl <= AOV_LCAP - 4 before the step (the `full` rule): four leaf slots are free; the node stack stays below NCAP by the
+            // context's bound (the comparison is a guard that never fires)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t r = cr[k];
+                if (r == PT_REF_NONE) continue;
+                if (r & PT_REF_LEAF) { stack[(ENTRIES - 1 - nl) * 64] = r & 0x7fffffffu; nl++; }
+                else if (sp < NCAP) { stack[sp * 64] = r; sp++; }
+            }
+        }
+    }
+    if (texel) aov_store(A, (size_t)ly * A.tile.tex_w + gx, o, d, best);
+}
+
+void launch_aovs(const AovLaunch &A, int walk, int stack_worst, int leaf_min, hipStream_t s)
+{
+    const int tiles = raytrace_grid_blocks(A.tile);
+    if (tiles <= 0) return;
+    const dim3 grid((unsigned)tiles), block(64);
+    if (walk == 13 && A.scene.cwide && A.scene.tripk64 && A.scene.leaf_rank) {
+        const int entries = (stack_worst < 1 ? 1 : (stack_worst > SM_CULL_STACK_MAX ? SM_CULL_STACK_MAX : stack_worst)) + AOV_LCAP;
+        hipLaunchKernelGGL(k_aov_cull, grid, block, (size_t)entries * 256, s, A, entries, leaf_min < 1 ? 1 : leaf_min);
+    }
+    else if (walk == 1) hipLaunchKernelGGL((k_aov<1, PT_MAX_STACK>), grid, block, 0, s, A);
+    else if (stack_worst <= 32) hipLaunchKernelGGL((k_aov<3, 32>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((k_aov<3, PT_MAX_STACK>), grid, block, 0, s, A);
+}
+
 void launch_debug_math(int fn, const float *a, const float *b, float *out, size_t n, hipStream_t s)
 {
     if (n == 0) return;

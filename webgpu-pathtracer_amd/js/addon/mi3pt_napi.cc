@@ -381,6 +381,34 @@ napi_value ReadTexture(napi_env env, napi_callback_info info)
     return ta;
 }
 
+// renderAovs(ctx, mask): the first-hit feature images named in mask (OR of 1 << mi3pt_aov); asynchronous
+napi_value RenderAovs(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t mask;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &mask)) return nullptr;
+    MI3PT_TRY(mi3pt_render_aovs(ctx, (unsigned)mask));
+    return undefined(env);
+}
+
+// readAov(ctx, which, ntexels) -> Float32Array of ntexels x 4 (Int32Array for MI3PT_AOV_IDS)
+napi_value ReadAov(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t which, ntexels;
+    if (!get_args(env, info, a, 3) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &which) ||
+        !get_i32(env, a.v[2], &ntexels) || ntexels < 0)
+        return nullptr;
+    void *data = nullptr;
+    napi_value ab, ta;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)ntexels * 16, &data, &ab));
+    MI3PT_TRY(mi3pt_read_aov(ctx, which, data, (size_t)ntexels * 16));
+    NAPI_OK(napi_create_typedarray(env, which == MI3PT_AOV_IDS ? napi_int32_array : napi_float32_array, (size_t)ntexels * 4, ab, 0, &ta));
+    return ta;
+}
+
 // writeTexture(ctx, which, Float32Array) : GPUQueue.writeTexture for the HDR images
 napi_value WriteTexture(napi_env env, napi_callback_info info)
 {
@@ -574,7 +602,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "enableTiming", EnableTiming }, { "passTimeUs", PassTimeUs }, { "getCounters", GetCounters },
         { "resetCounters", ResetCounters }, { "hostBuildBvhF64", HostBuildBvhF64 }, { "hostBuildBvh", HostBuildBvh },
         { "hostEnvCdf", HostEnvCdf }, { "setPipelining", SetPipelining }, { "setPresentMode", SetPresentMode }, { "setEnvSampling", SetEnvSampling }, { "deviceBuildBvh", DeviceBuildBvh }, { "writeTexture", WriteTexture },
-        { "raytraceLaunchStats", RaytraceLaunchStats },
+        { "raytraceLaunchStats", RaytraceLaunchStats }, { "renderAovs", RenderAovs }, { "readAov", ReadAov },
     };
     for (const auto &f : fns) {
         napi_value v;

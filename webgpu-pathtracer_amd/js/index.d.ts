@@ -114,6 +114,11 @@ export class Renderer {
   readOutput(): Float32Array; readAccumulation(): Float32Array;
   /** the fullscreen pass's target, row 0 = top */
   readCanvasFloat(): Float32Array; readCanvas(): Uint8Array;
+  /** first-hit feature images of the un-jittered camera rays (camera and scene of the last update()); default: all four */
+  renderAovs(names?: Array<'albedo' | 'normal' | 'position' | 'ids'>): void;
+  /** localRows x width x 4, row 0 = bottom: albedo rgb 1 | normal xyz 0 | position xyz t | (Int32Array) triangle, material, hit, 0 */
+  readAov(name: 'albedo' | 'normal' | 'position'): Float32Array;
+  readAov(name: 'ids'): Int32Array;
   counters(): { rays: number; boxTests: number; triTests: number; hits: number; misses: number; stackOverflows: number; pixels: number };
   /** src/main.ts:351-356: the presented canvas as PNG bytes (written to `file` when given) */
   screenshot(file?: string): Buffer;
@@ -140,3 +145,4 @@ export function whiteMaterial(): RaytracingMaterial;
 export function placeModel(model: Object3D, material?: RaytracingMaterial): Object3D;
 export function boundsOfObject(object: Object3D): { min: Vector3; max: Vector3 };
 export function encodePNG(rgba: Uint8Array, width: number, height: number): Buffer;
+export const AOV_NAMES: Array<'albedo' | 'normal' | 'position' | 'ids'>;

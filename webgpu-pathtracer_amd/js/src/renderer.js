@@ -13,6 +13,7 @@ const { FullscreenPass } = require('./passes/fullscreen');
 const { FloatType } = require('./scene');
 
 const TEX_OUTPUT = 0, TEX_ACCUMULATION = 1, TEX_CANVAS = 2;
+const AOV_NAMES = ['albedo', 'normal', 'position', 'ids'];      // mi3pt_aov, include/mi3pt.h
 
 let nativeModule = null;
 function loadNative() {
@@ -199,6 +200,25 @@ class Renderer {
   readCanvasFloat() { return this.native.readTexture(this.handle, TEX_CANVAS, this._height * this._width * 4); }
   readCanvas() { return this.native.readCanvasRgba8(this.handle, this._height * this._width * 4); }
   counters() { return this.native.getCounters(this.handle); }
+  // ---- first-hit feature images (no counterpart in the reference): albedo, normal, position (+ t), ids of the un-jittered camera
+  // ray's closest hit, with the camera and scene of the last update() at the current resolution.  Not a sample frame: `frame`, the
+  // accumulation image and the counters are untouched.  names: a subset of AOV_NAMES (default: all four).
+  renderAovs(names) {
+    let mask = 0;
+    for (const name of (names || AOV_NAMES)) {
+      const k = AOV_NAMES.indexOf(name);
+      if (k < 0) throw new Error('renderAovs: unknown feature image "' + name + '" (' + AOV_NAMES.join(', ') + ')');
+      mask |= 1 << k;
+    }
+    this.passes.raytrace.update();               // resolution / aspect as render() would send them
+    this.native.renderAovs(this.handle, mask);
+  }
+  // localRows x width x 4: Float32Array, Int32Array for 'ids' (triangle, material, hit, 0); row 0 = bottom of the picture
+  readAov(name) {
+    const k = AOV_NAMES.indexOf(name);
+    if (k < 0) throw new Error('readAov: unknown feature image "' + name + '" (' + AOV_NAMES.join(', ') + ')');
+    return this.native.readAov(this.handle, k, this.localRows * this._width);
+  }
   // main.ts:351-356 (canvas.toDataURL("image/png")): the presented canvas as a PNG file
   screenshot(file) {
     const png = encodePNG(this.readCanvas(), this._width, this._height);
@@ -251,4 +271,4 @@ function encodePNG(rgba, width, height) {
     chunk('IDAT', zlib.deflateSync(raw)), chunk('IEND', Buffer.alloc(0))]);
 }
 
-module.exports = { Renderer, loadNative, encodePNG };
+module.exports = { Renderer, loadNative, encodePNG, AOV_NAMES };

@@ -5,6 +5,8 @@
 //   --hdr file.hdr     a Radiance map (1024x512) instead of raw float texels (main.ts:41-46)
 //   --model file.glb   replace the default meshes by a loaded model (.glb/.gltf/.obj), main.ts:251-279
 //   --devices 0,1,2    a device group: Renderer.create({ devices: [0, 1, 2] }) -- the same loop on several GPUs
+//   --aovs             also the first-hit feature images: <prefix>_albedo.png, <prefix>_normal.png (0.5 n + 0.5) and
+//                      <prefix>_position.f32 (raw RGBA float: position xyz, t; row 0 = bottom)
 // Writes <prefix>.acc.f32 (accumulation, RGBA float), <prefix>.canvas.rgba8 and prints a
 // JSON summary.  Needs a HIP device.
 const fs = require('fs');
@@ -56,6 +58,24 @@ async function main() {
   fs.writeFileSync(out + '.acc.f32', Buffer.from(acc.buffer));
   fs.writeFileSync(out + '.canvas.rgba8', Buffer.from(canvas.buffer));
   renderer.screenshot(out + '.png');
+  if (process.argv.includes('--aovs')) {
+    renderer.renderAovs(['albedo', 'normal', 'position']);
+    const toPng = (img, fn) => {                     // rows flipped: the canvas has row 0 at the top
+      const px = new Uint8Array(width * height * 4);
+      for (let y = 0; y < height; y++) {
+        for (let x = 0; x < width; x++) {
+          const s = ((height - 1 - y) * width + x) * 4, d = (y * width + x) * 4;
+          for (let c = 0; c < 3; c++) px[d + c] = Math.max(0, Math.min(255, Math.round(255 * fn(img[s + c], img, s))));
+          px[d + 3] = 255;
+        }
+      }
+      return pt.encodePNG(px, width, height);
+    };
+    const normal = renderer.readAov('normal');
+    fs.writeFileSync(out + '_albedo.png', toPng(renderer.readAov('albedo'), (v) => v));
+    fs.writeFileSync(out + '_normal.png', toPng(normal, (v, img, s) => (img[s] === 0 && img[s + 1] === 0 && img[s + 2] === 0 ? 0 : 0.5 * v + 0.5)));
+    fs.writeFileSync(out + '_position.f32', Buffer.from(renderer.readAov('position').buffer));
+  }
   const summary = {
     width, height, frames, status: renderer.status, frame: renderer.frame, events,
     counters: renderer.counters(), stats: renderer.passes.raytrace.stats, wall_ms: ms,

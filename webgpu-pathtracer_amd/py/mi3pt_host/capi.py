@@ -16,6 +16,11 @@ PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__fil
 LIB_PATH = os.environ.get("MI3PT_LIBRARY") or os.path.join(PKG_ROOT, "libmi3pt.so")
 
 PASS_RAYTRACE, PASS_ACCUMULATE, PASS_FULLSCREEN = 0, 1, 2
+PASS_AOV = 3          # mi3pt_pass_time_us only: the first-hit feature images have no uniform block
+# mi3pt_aov: the first-hit feature images (render_aovs takes an OR of 1 << AOV_*)
+AOV_ALBEDO, AOV_NORMAL, AOV_POSITION, AOV_IDS, AOV_COUNT = 0, 1, 2, 3, 4
+AOV_ALL = (1 << AOV_COUNT) - 1
+AOV_NAMES = ("albedo", "normal", "position", "ids")
 SUBMIT_RAYTRACE, SUBMIT_ACCUMULATE, SUBMIT_FULLSCREEN = 1, 2, 4
 TEX_OUTPUT, TEX_ACCUMULATION, TEX_CANVAS = 0, 1, 2
 STORAGE_F32, STORAGE_F16 = 0, 1
@@ -44,6 +49,7 @@ SYMBOLS = (
     "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
     "mi3pt_create_group", "mi3pt_group_size", "mi3pt_group_member",
     "mi3pt_tile_global_row", "mi3pt_tile_owner",
+    "mi3pt_render_aovs", "mi3pt_read_aov", "mi3pt_aov_device_ptr",
 )
 
 
@@ -94,6 +100,9 @@ def load_library(path=None):
     lib.mi3pt_write_texture.argtypes = [c_void_p, c_int, c_void_p, c_size_t]
     lib.mi3pt_accumulation_device_ptr.argtypes = [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]
     lib.mi3pt_bind_accumulation.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_render_aovs.argtypes = [c_void_p, ctypes.c_uint]
+    lib.mi3pt_read_aov.argtypes = [c_void_p, c_int, c_void_p, c_size_t]
+    lib.mi3pt_aov_device_ptr.argtypes = [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]
     lib.mi3pt_enable_timing.argtypes = [c_void_p, c_int]
     lib.mi3pt_pass_time_us.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]
     lib.mi3pt_raytrace_launch_stats.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
@@ -372,6 +381,25 @@ class Context:
     def accumulation_device_ptr(self):
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         self._c(self.lib.mi3pt_accumulation_device_ptr(self.handle, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def render_aovs(self, mask=AOV_ALL):
+        """Render the first-hit feature images named in `mask` (an OR of 1 << AOV_*) from the raytrace uniforms and the
+        scene as they are now; asynchronous.  Not a raytrace pass: counters and queued sample frames are untouched."""
+        self._c(self.lib.mi3pt_render_aovs(self.handle, int(mask)))
+
+    def read_aov(self, which):
+        """Feature image `which` as (rows, width, 4): float32, int32 for AOV_IDS.  rows = this rank's compact rows; a
+        device group returns the whole image."""
+        out = np.empty((self.local_rows, self.width, 4), np.int32 if which == AOV_IDS else np.float32)
+        self._c(self.lib.mi3pt_read_aov(self.handle, int(which), _ptr(out), out.nbytes))
+        return out
+
+    def aov_device_ptr(self, which):
+        """(device pointer, bytes) of feature image `which`, for zero-copy hand-off; sync() (or order your reads behind
+        the context's stream) before reading it."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._c(self.lib.mi3pt_aov_device_ptr(self.handle, int(which), ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
 
     def bind_accumulation(self, dev_ptr, nbytes):

@@ -352,6 +352,21 @@ class Renderer:
     def readCanvas(self):
         return self.ctx.read_canvas_rgba8()
 
+    # ---- first-hit feature images (no counterpart in the reference) ----
+    def renderAovs(self, names=None):
+        """Render the feature images of the first hit (capi.AOV_NAMES: albedo, normal, position, ids; None = all four)
+        with the camera and scene of the last update() at the current resolution.  Not a sample frame: `frame`, the
+        accumulation image and the counters are untouched."""
+        mask = 0
+        for name in (capi.AOV_NAMES if names is None else names):
+            mask |= 1 << capi.AOV_NAMES.index(name)
+        self.passes["raytrace"].update()           # resolution / aspect as render() would send them
+        self.ctx.render_aovs(mask)
+
+    def readAov(self, name):
+        """(rows, width, 4) float32 -- int32 for "ids" -- of a feature image rendered by renderAovs."""
+        return self.ctx.read_aov(capi.AOV_NAMES.index(name))
+
     def screenshot(self, path=None):
         """main.ts:351-356 (canvas.toDataURL("image/png")): the presented canvas as PNG bytes."""
         png = encode_png(self.readCanvas())
