@@ -105,3 +105,50 @@ def test_render_loop_throughput_under_node(built, env, tmp_path):
     assert legs["no_present"]["mrays_per_s"] >= 0.9 * legs["c_abi"]["mrays_per_s"]
     assert legs["present_latest"]["mrays_per_s"] >= 0.75 * legs["c_abi"]["mrays_per_s"]
     assert legs["present_exact"]["mrays_per_s"] < legs["present_latest"]["mrays_per_s"]
+
+
+def _ctypes_frames_with_device_tree(ctx, sc, tris, env, w=64, h=64, frames=(2, 3, 4), bounces=4):
+    """The render loop's frames through the C ABI, on the tree mi3pt_device_build_bvh gives for `tris`: (accumulation, canvas)"""
+    from mi3pt_host import capi
+    ctx.upload_triangles(tris)
+    nodes, _ = ctx.device_build_bvh()
+    ctx.upload_bvh(nodes)
+    ctx.upload_materials(sc.material_bytes)
+    ctx.upload_environment(env)
+    ctx.set_tile(0, 1, 8)
+    ctx.resize(w, h)
+    ctx.reset()
+    ctx.set_uniforms(capi.PASS_FULLSCREEN, pc.fs_uniforms(w, h, 1.0, 1, 1).tobytes())
+    for f in frames:
+        ctx.set_uniforms(capi.PASS_RAYTRACE, pc.rt_uniforms(sc, w, h, frame=f, bounces=bounces).tobytes())
+        ctx.set_uniforms(capi.PASS_ACCUMULATE, pc.acc_uniforms(w, h, f).tobytes())
+        ctx.submit(capi.SUBMIT_RAYTRACE | capi.SUBMIT_ACCUMULATE | capi.SUBMIT_FULLSCREEN)
+    acc, canvas = ctx.read_texture(capi.TEX_ACCUMULATION), ctx.read_canvas_rgba8()
+    pc.upload_scene(ctx, sc)
+    return len(nodes), acc, canvas
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("second_scene", [False, True], ids=["demo", "demo-then-submesh"])
+def test_render_loop_under_node_with_the_device_built_tree(built, gpu_ctx, demo, env, tmp_path, second_scene):
+    """Renderer.create({ deviceBvh: true }): updateScene uploads the triangles first and the tree built from them after -- the only
+    path in that order.  Its image and canvas equal the same frames through the C ABI on the tree mi3pt_device_build_bvh gives
+    (not the golden fixture: that is the SAH tree's, and ties in t may differ).  Second case: a second updateScene with fewer
+    triangles (the demo without its sphere) meets the stale tree of the first; it renders like the C ABI renders that sub-mesh."""
+    env_path = tmp_path / "env.f32"
+    env_path.write_bytes(env.tobytes())
+    out = str(tmp_path / "demo")
+    r = _node([os.path.join(JS, "tools", "render_demo.js"), "--env", str(env_path), "--width", "64", "--height", "64",
+               "--frames", "3", "--bounces", "4", "--out", out, "--device-bvh"] + (["--second-scene"] if second_scene else []))
+    assert r.returncode == 0, r.stdout + r.stderr
+    summary = json.loads(r.stdout.strip().splitlines()[-1])
+    assert summary["status"] == "idle" and summary["frame"] == 4
+    assert summary["first_stats"] == {"Triangles": 1998, "Materials": 2, "BVH Nodes": 3995}
+    tris = demo.triangles[:14] if second_scene else demo.triangles       # (plane 2 + box 12 triangles come first, the sphere last)
+    assert summary["stats"] == {"Triangles": len(tris), "Materials": 2, "BVH Nodes": 2 * len(tris) - 1}
+    nnodes, want_acc, want_canvas = _ctypes_frames_with_device_tree(gpu_ctx, demo, tris, env)
+    assert nnodes == 2 * len(tris) - 1
+    acc = np.frombuffer(open(out + ".acc.f32", "rb").read(), np.float32).reshape(64, 64, 4)
+    assert pc.same_bits(acc, want_acc), pc.describe_diff(acc, want_acc)
+    canvas = np.frombuffer(open(out + ".canvas.rgba8", "rb").read(), np.uint8).reshape(64, 64, 4)
+    assert np.array_equal(canvas, want_canvas)

@@ -7,6 +7,10 @@
 //   --devices 0,1,2    a device group: Renderer.create({ devices: [0, 1, 2] }) -- the same loop on several GPUs
 //   --aovs             also the first-hit feature images: <prefix>_albedo.png, <prefix>_normal.png (0.5 n + 0.5) and
 //                      <prefix>_position.f32 (raw RGBA float: position xyz, t; row 0 = bottom)
+//   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
+//   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
+//                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
+//                      second scene's
 // Writes <prefix>.acc.f32 (accumulation, RGBA float), <prefix>.canvas.rgba8 and prints a
 // JSON summary.  Needs a HIP device.
 const fs = require('fs');
@@ -30,8 +34,10 @@ async function main() {
   const diag = await pt.Renderer.diagnostic();
   if (!diag.supported) throw new Error('HIP device not found.');
   const devices = arg('devices', null);
-  const renderer = await pt.Renderer.create(devices ? { enableTimestampQuery: true, devices: devices.split(',').map((d) => parseInt(d, 10)) }
-    : { enableTimestampQuery: true });
+  const options = { enableTimestampQuery: true };
+  if (devices) options.devices = devices.split(',').map((d) => parseInt(d, 10));
+  if (process.argv.includes('--device-bvh')) options.deviceBvh = true;
+  const renderer = await pt.Renderer.create(options);
   const { scene, camera } = buildDefaultScene(envData);
   if (arg('hdr', null)) scene.environment = new pt.RGBELoader().setDataType(pt.FloatType).load(arg('hdr'));
   const modelPath = arg('model', null);
@@ -52,6 +58,13 @@ async function main() {
   renderer.resize(width, height);
   const t0 = Date.now();
   for (let i = 0; i < frames + 1; i++) renderer.render(scene, camera);     // the last call only presents
+  const firstStats = renderer.passes.raytrace.stats;
+  if (process.argv.includes('--second-scene')) {
+    scene.remove(scene.children[scene.children.length - 1]);
+    scene.needsUpdate = true;
+    renderer.reset();
+    for (let i = 0; i < frames + 1; i++) renderer.render(scene, camera);
+  }
   const acc = renderer.readAccumulation();
   const ms = Date.now() - t0;
   const canvas = renderer.readCanvas();
@@ -78,7 +91,7 @@ async function main() {
   }
   const summary = {
     width, height, frames, status: renderer.status, frame: renderer.frame, events,
-    counters: renderer.counters(), stats: renderer.passes.raytrace.stats, wall_ms: ms,
+    counters: renderer.counters(), stats: renderer.passes.raytrace.stats, first_stats: firstStats, wall_ms: ms,
     timings_us: { raytrace: renderer.timings.raytrace.value, accumulate: renderer.timings.accumulate.value,
       fullscreen: renderer.timings.fullscreen.value },
     device: diag.info.description,
