@@ -47,7 +47,7 @@ extern "C" {
  * MI3PT_OPT_PACKET_ORDER, MI3PT_OPT_SIX_WAVES (22 .. 27); MI3PT_OPT_WAVES_PER_CU reads up to 24 (six waves per SIMD). */
 /* 4 (round 6): mi3pt_set_rows and mi3pt_measure_tile_cost are GONE (contiguous cost-balanced bands: measured 7 % slower than the dealt
  * 8-row blocks in round 4 and kept since as dead surface); mi3pt_set_kernel_variant accepts 14 (the eight-wide walk: an option).
- * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31);
+ * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31); mi3pt_host_scene_compile;
  * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3). */
 #define MI3PT_ABI_VERSION 4
 
@@ -516,6 +516,19 @@ int mi3pt_host_env_cdf(const float *rgba, int width, int height, float *cdf_rgba
  * leaves reached, 1 if a context would offer variant 14 for this tree (levels within the walk's stack).  MI3PT_ERR_STATE with the
  * reason in mi3pt_last_error when the tree does not admit the packets or a check fails. */
 int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes, const void *triangles, size_t triangles_bytes, int greedy, uint64_t out[6]);
+/* Host-only scene compile (no device, no context): everything mi3pt_upload_bvh, mi3pt_upload_triangles and a context's lazy scene analysis
+ * compute for a tree (48-byte records) + triangles (112-byte records), by the same code, with every device buffer reduced to a 64-bit
+ * FNV-1a digest of its bytes.  collapse / packet_order: as MI3PT_OPT_COLLAPSE / MI3PT_OPT_PACKET_ORDER; want_eight_wide: also the packets
+ * of kernel variant 14.  out[0 .. MI3PT_SCENE_COMPILE_WORDS - 1]: 0 nodes, 1 triangles, 2 node packets, 3 leaf_cap, 4 tree_proper,
+ * 5 walk_stack_worst, 6 cull_stack_ok, 7 root_ref, 8 scene_flags, 9 max_tri_ref, 10 max_mat_ref, 11 analysed (1: the tree admits the
+ * culling walks and every leaf names an uploaded triangle -- 12 .. 23 and 27 .. 31 are 0 otherwise), 12 / 13 the bits of cull_ka /
+ * cull_kb, 14 wide_ok, 15 cwide_ok, 16 cw8_ok, 17 wide_root_nested, 18 wide_stack_worst, 19 auto_wide_variant, 20 wide packets, 21 8-wide
+ * packets, 22 8-wide records, 23 8-wide levels; digests (0: not built): 24 node packets with their final cull words, 25 leaf ranks, 26 48-byte
+ * triangle packets, 27 wide packets, 28 compressed packets, 29 64-byte records, 30 8-wide packets, 31 8-wide records.  MI3PT_ERR_INVALID with
+ * the upload's own message for a tree or triangles an upload would refuse. */
+#define MI3PT_SCENE_COMPILE_WORDS 32
+int mi3pt_host_scene_compile(const void *nodes, size_t nodes_bytes, const void *triangles, size_t triangles_bytes, int collapse, int packet_order,
+                             int want_eight_wide, uint64_t *out, size_t out_capacity);
 /* The EMPTY TILES of a view (no device): the 8x8 tiles of rank `rank`'s share of a width x height image (tiles_x = ceil(width / 8), rows of
  * tiles over the rank's LOCAL rows, row-major) in which no pixel's camera ray, for any frame's jitter, can pass the reference's slab
  * test on any box of a cut of the tree `nodes` (48-byte records) -- such a ray reaches no leaf, the path is one miss.  A context

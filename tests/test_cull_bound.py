@@ -5,7 +5,7 @@ adversarial ray / triangle pairs -- grazing incidence down to the 1e-6 determina
 slivers, coordinates far from the origin, un-normalised directions.  For every pair the code
 ACCEPTS with distance t, the point o + t d must lie within
     delta(E, L, t) = W(E) (u / EPSILON) (t |d|^2 + 1.65 L |d|),   u = 2^-24,
-of the triangle (E = |e1||e2|, L = |e1| + |e2|, W as in csrc/pt_context.hip prepare_cull), and the
+of the triangle (E = |e1||e2|, L = |e1| + |e2|, W as in csrc/pt_host_compile.cpp compile_walk), and the
 kernel's skip predicate, evaluated with the triangle's own bounding box, must not fire for
 best.t >= t.  A proof bounds the worst case; this test shows how much room the constants leave
 (observed: about 1/8 of the bound) and guards the formulas against transcription errors."""
@@ -45,7 +45,7 @@ def moller_trumbore_f32(o, d, a, b, c):
 
 
 def weight(E):
-    """W(E) = E c1(E) of prepare_cull (csrc/pt_context.hip); nan where the triangle is outside the analysis."""
+    """W(E) = E c1(E) of compile_walk (csrc/pt_host_compile.cpp); nan where the triangle is outside the analysis."""
     kappa = E * 2.0 / EPS
     A = 5.85 * U * kappa
     b = (1.0 + A) / (1.0 - A) + 1.0

@@ -1,7 +1,8 @@
 #!/bin/bash
 # AddressSanitizer + UndefinedBehaviorSanitizer over the CPU-side native code (no GPU sanitizer exists on this pool):
-# the host scene compile of libmi3pt.so (csrc/pt_host_scene.cpp: the reference's BVH builder and env CDF; csrc/pt_host_wide.cpp: the
-# SAH-optimal collapse and the eight-wide packets of kernel variant 14 with their self-check) and the CPU
+# the host scene compile of libmi3pt.so (csrc/pt_host_scene.cpp: the reference's BVH builder and env CDF; csrc/pt_host_compile.cpp: what
+# the uploads and a context's scene analysis hand to the device -- node packets, culling weights, the 4-ary packets of the shipped walk;
+# csrc/pt_host_wide.cpp: the SAH-optimal collapse and the eight-wide packets of kernel variant 14 with their self-check) and the CPU
 # oracle (oracle/pt_oracle.c: raytrace, accumulate, fullscreen).  Builds instrumented copies under /tmp and drives them
 # through ctypes.   usage: bash tests/tools/sanitize_cpu.sh        (about a minute; prints two "ok" lines)
 set -eu
@@ -14,7 +15,7 @@ cat > $W/stub.cpp <<'CPP'
 #include <cstdio>
 int pt_set_error(int code, const std::string &msg) { fprintf(stderr, "(expected) error %d: %s\n", code, msg.c_str()); return code; }
 CPP
-g++ $SAN -std=c++17 -w -I$ROOT/include -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ $ROOT/webgpu-pathtracer_amd/csrc/pt_host_scene.cpp $ROOT/webgpu-pathtracer_amd/csrc/pt_host_wide.cpp $W/stub.cpp -o $W/libhost.so -lpthread
+g++ $SAN -std=c++17 -w -I$ROOT/include -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ $ROOT/webgpu-pathtracer_amd/csrc/pt_host_scene.cpp $ROOT/webgpu-pathtracer_amd/csrc/pt_host_compile.cpp $ROOT/webgpu-pathtracer_amd/csrc/pt_host_wide.cpp $W/stub.cpp -o $W/libhost.so -lpthread
 gcc $SAN -std=c11 -ffp-contract=off -fno-fast-math -fopenmp $(grep -q -m1 fma /proc/cpuinfo && echo -mfma) -o $W/libptoracle.so $ROOT/oracle/pt_oracle.c -lm
 export LD_PRELOAD=$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=halt_on_error=1
 python3 - $W $ROOT <<'PY'
@@ -41,6 +42,14 @@ for n in (1, 2, 3, 7, 100, 5000, 200000):
     for greedy in (0, 1):
         rc = lib.mi3pt_host_eight_wide_check(nodes.ctypes.data_as(P), S(nodes.nbytes), tri.ctypes.data_as(P), S(tri.nbytes), greedy, out.ctypes.data_as(P))
         assert (rc == 0 and out[4] == n) if n > 1 else rc != 0, (n, greedy, rc, out)
+    # the whole scene compile over that tree as a context runs it, every grouping and packet numbering (pt_host_compile.cpp)
+    sc = np.zeros(32, np.uint64)
+    for collapse in (-1, 0, 1):
+        for order in (0, 1, 2):
+            rc = lib.mi3pt_host_scene_compile(nodes.ctypes.data_as(P), S(nodes.nbytes), tri.ctypes.data_as(P), S(tri.nbytes), collapse, order, 1, sc.ctypes.data_as(P), S(32))
+            assert rc == 0 and sc[2] == n - 1, (n, collapse, order, rc, sc)
+            if n > 1:
+                assert sc[11] == 1 and sc[14] == 1 and (n - 1 + 2) // 3 <= sc[20] <= n - 1, (n, collapse, order, sc)      # analysed, wide_ok; 4-ary packets: between all full and all binary
 for w, h in ((1, 1), (2, 1), (64, 32), (333, 77)):
     img = rng.random((h, w, 4), dtype=np.float32) * 10
     if w > 2:

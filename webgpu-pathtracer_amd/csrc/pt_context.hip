@@ -959,22 +959,6 @@ static int replace_buffer(mi3pt_ctx *ctx, void **dst, const void *bytes, size_t 
     return MI3PT_OK;
 }
 
-// The 48-byte intersection record of a 112-byte triangle record: a, the material index, and the edges b - a, c - a -- the two
-// subtractions Moller-Trumbore starts with (raytrace.wgsl:82-83), each ONE fp32 rounding (this is a float subtraction of two
-// floats: round-to-nearest-even, subnormals kept, like the device's v_sub_f32), so the kernels start from the same operands.
-static pt::TriPacket tri_packet_of(const uint8_t *rec)
-{
-    pt::TriPacket p;
-    for (int k = 0; k < 3; k++) {
-        const float a = ldf(rec, 4 * (size_t)k), b = ldf(rec, 16 + 4 * (size_t)k), c = ldf(rec, 32 + 4 * (size_t)k);
-        volatile float e1 = b - a, e2 = c - a;      // (volatile: each difference is rounded to binary32 here, whatever the host's evaluation method)
-        p.a[k] = a; p.e1[k] = e1; p.e2[k] = e2;
-    }
-    p.material = (uint32_t)ldi(rec, 92);
-    p.pad0 = p.pad1 = 0;
-    return p;
-}
-
 extern "C" int mi3pt_upload_triangles(mi3pt_ctx *ctx, const void *bytes, size_t nbytes)
 {
     PT_GROUP(ctx, mi3pt_upload_triangles(group_member0(ctx), bytes, nbytes));      // (a group's scene lives in member 0; the others receive device copies: group_sync_scene)
@@ -983,16 +967,9 @@ extern "C" int mi3pt_upload_triangles(mi3pt_ctx *ctx, const void *bytes, size_t 
         return pt_set_error(MI3PT_ERR_INVALID, "triangle bytes must be a non-zero multiple of 112");
     const size_t n = nbytes / MI3PT_TRIANGLE_STRIDE;
     if (n > 0x7fffffffu) return pt_set_error(MI3PT_ERR_INVALID, "too many triangles");
-    const uint8_t *src = static_cast<const uint8_t *>(bytes);
-    std::vector<pt::TriPacket> pk(n);
+    std::vector<pt::TriPacket> pk;
     int64_t max_mat = -1;
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t *t = src + i * MI3PT_TRIANGLE_STRIDE;
-        const int32_t mi = ldi(t, 92);
-        if (mi < 0) return pt_set_error(MI3PT_ERR_INVALID, "triangle with negative materialIndex");
-        pk[i] = tri_packet_of(t);
-        if (mi > max_mat) max_mat = mi;
-    }
+    if (const char *e = pt::compile_triangles(static_cast<const uint8_t *>(bytes), n, pk, max_mat)) return pt_set_error(MI3PT_ERR_INVALID, e);
     if (int rc = replace_buffer(ctx, &ctx->d_tris, bytes, nbytes)) return rc;
     if (int rc = replace_buffer(ctx, &ctx->d_tripk, pk.data(), n * sizeof(pt::TriPacket))) return rc;
     ctx->ntris = n;
@@ -1027,48 +1004,6 @@ extern "C" int mi3pt_upload_materials(mi3pt_ctx *ctx, const void *bytes, size_t 
 }
 
 
-// child reference of the packet walk: leaf -> 0x80000000 | triangle (renumbered by tri_new when given)
-static uint32_t child_ref(const uint8_t *src, const std::vector<uint32_t> &packet_of, const uint32_t *tri_new, int32_t child)
-{
-    if (child < 0) return pt::REF_NONE;
-    const uint8_t *r = src + (size_t)child * MI3PT_BVHNODE_STRIDE;
-    if (ldi(r, 28) == 1) {
-        const uint32_t ti = (uint32_t)ldi(r, 40);
-        return 0x80000000u | (tri_new ? tri_new[ti] : ti);
-    }
-    return packet_of[(size_t)child];
-}
-
-// One 64-byte packet per internal node, at the index packet_of[] gives it: bit copies of both
-// children's boxes, their references, the guard bits of the fast slab test.
-static void build_packets(const uint8_t *src, size_t n, const std::vector<uint32_t> &packet_of, size_t npackets,
-                          const uint32_t *tri_new, std::vector<pt::NodePacket> &pk)
-{
-    pk.assign(npackets ? npackets : 1, pt::NodePacket());
-    std::memset(pk.data(), 0, pk.size() * sizeof(pt::NodePacket));
-    for (auto &p : pk) p.cull = 0x7f807f80u;        // never skip, until the cull analysis has run
-    for (size_t i = 0; i < n; i++) {
-        if (packet_of[i] == pt::REF_NONE) continue;
-        const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-        pt::NodePacket &p = pk[packet_of[i]];
-        const int32_t left = ldi(r, 32), right = ldi(r, 36);
-        if (left >= 0) {
-            const uint8_t *c = src + (size_t)left * MI3PT_BVHNODE_STRIDE;
-            std::memcpy(p.lmin, c + 0, 12);
-            std::memcpy(p.lmax, c + 16, 12);
-        }
-        if (right >= 0) {
-            const uint8_t *c = src + (size_t)right * MI3PT_BVHNODE_STRIDE;
-            std::memcpy(p.rmin, c + 0, 12);
-            std::memcpy(p.rmax, c + 16, 12);
-        }
-        p.lref = child_ref(src, packet_of, tri_new, left);
-        p.rref = child_ref(src, packet_of, tri_new, right);
-        p.flags = ((left >= 0 && !node_box_safe(src, (size_t)left)) ? 1u : 0u) | ((right >= 0 && !node_box_safe(src, (size_t)right)) ? 2u : 0u) |
-                  ((left < 0 || right < 0) ? 4u : 0u);      // bit2: a child is missing (never from flattenBVH)
-    }
-}
-
 extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes)
 {
     PT_GROUP(ctx, mi3pt_upload_bvh(group_member0(ctx), bytes, nbytes));      // (a group's scene lives in member 0; the others receive device copies: group_sync_scene)
@@ -1078,120 +1013,22 @@ extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes
     const size_t n = nbytes / MI3PT_BVHNODE_STRIDE;
     if (n > 0x7fffffffu) return pt_set_error(MI3PT_ERR_INVALID, "too many BVH nodes");
     const uint8_t *src = static_cast<const uint8_t *>(bytes);
-    // Validate and number the internal nodes.  A child must come after its parent
-    // (true of flattenBVH's breadth-first order, raytrace.ts:667-678); that bounds the
-    // walk, so a malformed tree cannot hang the device.
-    std::vector<uint32_t> packet_of(n, pt::REF_NONE);
-    size_t npackets = 0;
-    int64_t max_tri = -1;
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-        if (ldi(r, 28) == 1) {
-            const int32_t ti = ldi(r, 40);
-            if (ti < 0) return pt_set_error(MI3PT_ERR_INVALID, "leaf node with negative triangleIndex");
-            if (ti > max_tri) max_tri = ti;
-        } else {
-            for (size_t off : { (size_t)32, (size_t)36 }) {
-                const int32_t c = ldi(r, off);
-                if (c >= 0 && ((size_t)c >= n || (size_t)c <= i))
-                    return pt_set_error(MI3PT_ERR_INVALID,
-                                        "BVH child index must be greater than its parent's and inside the buffer "
-                                        "(breadth-first order, raytrace.ts:667-694)");
-            }
-            packet_of[i] = (uint32_t)npackets++;
-        }
-    }
-    std::vector<pt::NodePacket> pk;
-    build_packets(src, n, packet_of, npackets, nullptr, pk);
-    auto ref_of = [&](int32_t child) -> uint32_t { return child_ref(src, packet_of, nullptr, child); };
-    // Order analysis for the deferred-leaf kernel (pt_kernels.hip, DEFER): the reference walk
-    // visits leaves in a fixed order (node, right subtree, left subtree: left is pushed first,
-    // raytrace.wgsl:184-198) and keeps the FIRST of equal-t hits.  If the buffer is a proper
-    // tree (every node reached exactly once, every triangle owned by at most one leaf, no
-    // missing child) that order is a per-triangle rank, and testing leaves in any order and
-    // resolving ties by rank gives the same hit -- provided the 64-entry abort cannot fire,
-    // i.e. the walk's worst-case stack occupancy (every box hit) stays below 64.
-    std::vector<uint32_t> leaf_rank((size_t)(max_tri + 1 > 0 ? max_tri + 1 : 1), 0xffffffffu);
-    int leaf_cap = 0;
-    bool cull_stack_ok = false, tree_proper = false;
-    size_t walk_worst = 64;
-    {
-        std::vector<uint32_t> st;
-        std::vector<uint8_t> seen(n, 0);
-        st.push_back(0);
-        size_t visited = 0, worst = 0, worst_internal = 0, internal = 0;     // stack occupancy: all entries / internal nodes only
-        uint32_t rank = 0;
-        bool proper = true;
-        auto is_leaf = [&](uint32_t node) { return ldi(src + (size_t)node * MI3PT_BVHNODE_STRIDE, 28) == 1; };
-        if (!is_leaf(0)) internal = 1;
-        while (!st.empty() && proper) {
-            if (st.size() > worst) worst = st.size();
-            if (internal > worst_internal) worst_internal = internal;
-            const uint32_t node = st.back();
-            st.pop_back();
-            if (seen[node]) { proper = false; break; }
-            seen[node] = 1;
-            visited++;
-            const uint8_t *r = src + (size_t)node * MI3PT_BVHNODE_STRIDE;
-            if (ldi(r, 28) == 1) {
-                const int32_t ti = ldi(r, 40);
-                if (leaf_rank[(size_t)ti] != 0xffffffffu) { proper = false; break; }
-                leaf_rank[(size_t)ti] = rank++;
-            } else {
-                internal--;
-                const int32_t left = ldi(r, 32), right = ldi(r, 36);
-                if (left < 0 || right < 0) { proper = false; break; }
-                st.push_back((uint32_t)left);
-                st.push_back((uint32_t)right);
-                internal += (is_leaf((uint32_t)left) ? 0 : 1) + (is_leaf((uint32_t)right) ? 0 : 1);
-            }
-        }
-        // The 64-entry abort (raytrace.wgsl:167-171) counts leaves too: it cannot fire while the
-        // worst case stays below 64.  LDS holds 32 entries per lane: the node stack (internal
-        // nodes only in the deferred walk) from the bottom, parked leaves from the top.
-        if (proper && worst < 64 && (int)worst_internal <= pt::SM_LDS_DEPTH - 4) leaf_cap = pt::SM_LDS_DEPTH - (int)worst_internal;
-        tree_proper = proper && worst < 64;
-        walk_worst = worst;             // (every box hit: the real walk's stack is a subset of this one's at every node it visits)
-        (void)visited;      // nodes the root does not reach are never walked by the reference either
-        // The culling walks push the nearer child last, so ANY child may be the one that is descended
-        // first with all its internal siblings still stacked: occupancy(child) = occupancy(parent) - 1 +
-        // (internal children of the parent).  The maximum over the tree bounds their node stack whatever
-        // the order; it has to fit the LDS slots plus the overflow slice (pt_kernels.h SM_CULL_STACK_MAX).
-        cull_stack_ok = false;
-        if (proper && worst < 64 && !is_leaf(0)) {
-            std::vector<std::pair<uint32_t, uint32_t>> work;
-            work.emplace_back(0u, 1u);
-            size_t worst_any = 1;
-            while (!work.empty()) {
-                const auto [node, occ] = work.back();
-                work.pop_back();
-                const uint8_t *r = src + (size_t)node * MI3PT_BVHNODE_STRIDE;
-                const uint32_t kids[2] = { (uint32_t)ldi(r, 32), (uint32_t)ldi(r, 36) };
-                const uint32_t m = (is_leaf(kids[0]) ? 0u : 1u) + (is_leaf(kids[1]) ? 0u : 1u);
-                for (uint32_t c : kids) {
-                    if (is_leaf(c)) continue;
-                    const uint32_t oc = occ - 1u + m;
-                    if (oc > worst_any) worst_any = oc;
-                    work.emplace_back(c, oc);
-                }
-            }
-            cull_stack_ok = worst_any <= (size_t)pt::SM_CULL_STACK_MAX;
-        }
-    }
+    pt::TreeCompile t;
+    if (const char *e = pt::compile_tree(src, n, t)) return pt_set_error(MI3PT_ERR_INVALID, e);
     if (int rc = replace_buffer(ctx, &ctx->d_nodes, bytes, nbytes)) return rc;
-    if (int rc = replace_buffer(ctx, &ctx->d_packets, pk.data(), pk.size() * sizeof(pt::NodePacket))) return rc;
-    if (int rc = replace_buffer(ctx, &ctx->d_leaf_rank, leaf_rank.data(), leaf_rank.size() * sizeof(uint32_t))) return rc;
-    ctx->leaf_cap = leaf_cap;
-    ctx->cull_stack_ok = cull_stack_ok;
-    ctx->tree_proper = tree_proper;
-    ctx->walk_stack_worst = tree_proper ? (int)walk_worst : 64;
+    if (int rc = replace_buffer(ctx, &ctx->d_packets, t.packets.data(), t.packets.size() * sizeof(pt::NodePacket))) return rc;
+    if (int rc = replace_buffer(ctx, &ctx->d_leaf_rank, t.leaf_rank.data(), t.leaf_rank.size() * sizeof(uint32_t))) return rc;
+    ctx->leaf_cap = t.leaf_cap;
+    ctx->cull_stack_ok = t.cull_stack_ok;
+    ctx->tree_proper = t.tree_proper;
+    ctx->walk_stack_worst = t.walk_stack_worst;
     ctx->nnodes = n;
-    ctx->npackets = npackets;
-    ctx->root_ref = ref_of(0);
-    ctx->scene_flags = node_box_safe(src, 0) ? 1u : 0u;
-    ctx->max_tri_ref = max_tri;
+    ctx->npackets = t.npackets;
+    ctx->root_ref = t.root_ref;
+    ctx->scene_flags = t.scene_flags;
+    ctx->max_tri_ref = t.max_tri_ref;
     // the cut behind the empty tiles of a view: the nesting of EVERY node's box is checked (the collapse checks it for the nodes it absorbs only)
-    ctx->sky_cut_ok = tree_proper && pt::sky_cut_of(src, n, ctx->sky_cut);
+    ctx->sky_cut_ok = t.tree_proper && pt::sky_cut_of(src, n, ctx->sky_cut);
     ctx->sky_host_valid = false;
     ctx->cull_dirty = true;
     ctx->cost_state = 0;            // (the tiles' costs were measured on another scene)
@@ -1439,7 +1276,7 @@ static int prepare_layout(mi3pt_ctx *ctx)
         if (tri_new[t] == 0xffffffffu) tri_new[t] = ntri++;
     if (npk != ctx->npackets || ntri != nt) return pt_set_error(MI3PT_ERR_STATE, "packet layout: counts do not match the upload");
     std::vector<pt::NodePacket> pk;
-    build_packets(src, n, packet_of, npk, tri_new.data(), pk);
+    pt::build_packets(src, n, packet_of, npk, tri_new.data(), pk);
     std::vector<uint8_t> tris_perm(tris.size());
     std::vector<pt::TriPacket> tripk(nt);
     std::vector<uint32_t> rank(nt);
@@ -1447,14 +1284,14 @@ static int prepare_layout(mi3pt_ctx *ctx)
         const uint8_t *rec = tris.data() + t * MI3PT_TRIANGLE_STRIDE;
         const size_t to = tri_new[t];
         std::memcpy(tris_perm.data() + to * MI3PT_TRIANGLE_STRIDE, rec, MI3PT_TRIANGLE_STRIDE);
-        tripk[to] = tri_packet_of(rec);
+        tripk[to] = pt::tri_packet_of(rec);
         rank[to] = (uint32_t)to;          // leaf-visiting order IS the new numbering
     }
     if (int rc = replace_buffer(ctx, &ctx->d_packets, pk.data(), pk.size() * sizeof(pt::NodePacket))) return rc;
     if (int rc = replace_buffer(ctx, &ctx->d_tripk, tripk.data(), nt * sizeof(pt::TriPacket))) return rc;
     if (int rc = replace_buffer(ctx, &ctx->d_leaf_rank, rank.data(), nt * sizeof(uint32_t))) return rc;
     if (int rc = replace_buffer(ctx, &ctx->d_tris_perm, tris_perm.data(), tris_perm.size())) return rc;
-    ctx->root_ref = child_ref(src, packet_of, tri_new.data(), 0);
+    ctx->root_ref = pt::child_ref(src, packet_of, tri_new.data(), 0);
     ctx->layout_active = true;
     ctx->layout_dirty = false;
     ctx->scene_epoch++;
@@ -1479,31 +1316,8 @@ extern "C" int mi3pt_debug_set_packet_layout(mi3pt_ctx *ctx, int layout)
     return MI3PT_OK;
 }
 
-// Analysis for the distance-culling walk (kernel variant 9; pt_kernels.hip k_raytrace_sm<.., CULL>,
-// proof in DESIGN.md section 3a).  The rounding error of the reference's Moller-Trumbore code
-// scales with E = |e1| * |e2| of the triangle (through kappa = E |d| / |det| <= 2 E / EPSILON for
-// |d| <= 2): a triangle it accepts with t <= tau lies within
-//     delta = W(E) * (u / EPSILON) * (tau |d|^2 + 1.65 L |d|),   W(E) = E * c1(E),  u = 2^-24,
-// of the point o + t d, with c1(E) = (11.7 b + 3.04) / (1 - (11.7 b + 1.02) u kappa),
-// b = (1 + A) / (1 - A) + 1, A = 5.85 u kappa (c1 = 26.4 for small triangles, growing with E),
-// and L = |e1| + |e2|.  Per child of every internal node this bounds W over the triangles below
-// that child and writes the two bounds, rounded up to 16 bits each, into the node packet.  A
-// child gets +infinity (never skipped) when something below it is outside the analysis: a
-// triangle too large for it (A >= 1/4 or the denominator below 1/2: E above ~0.17), one with
-// |e1| + |e2| above 16 x the scene's mean (it would loosen the L term for every other one), a
-// non-finite coordinate, or a box that does not contain what is below it (the walk bounds
-// distances by boxes; the reference does not care whether its boxes bound anything).  Runs when
-// the triangles or the tree changed, on the host, from the device's own copies of both.
-static inline uint32_t round_up_16(float f)
-{
-    uint32_t b;
-    std::memcpy(&b, &f, 4);
-    if (!(f == f) || (b & 0x7f800000u) == 0x7f800000u || (b >> 31)) return 0x7f80u;   // NaN / inf / negative: never skip
-    const uint32_t r = (b + 0xffffu) >> 16;
-    return r > 0x7f80u ? 0x7f80u : r;
-}
-
-
+// The lazy scene analysis behind the culling walks (kernel variants 9 .. 14): pt::compile_walk (pt_host_compile.cpp) on the device's own
+// copies of the tree and the vertices; runs when the triangles, the tree or an option that shapes the packets changed.
 static int prepare_cull(mi3pt_ctx *ctx)
 {
     if (!ctx->cull_dirty) return MI3PT_OK;
@@ -1517,487 +1331,65 @@ static int prepare_cull(mi3pt_ctx *ctx)
     std::vector<uint8_t> nodes(n * MI3PT_BVHNODE_STRIDE);
     // the three vertices of every triangle: the first 48 of every 112 bytes of the records, packed by a small kernel (the 48-B
     // triangle packets hold edges, not b and c; uploaded numbering -- the analysis does not run on a relabelled scene)
-    struct TriVerts { float a[3], pa, b[3], pb, c[3], pc; };
-    static_assert(sizeof(TriVerts) == 48, "three vec3f + padding (raytrace.wgsl:40-49)");
-    std::vector<TriVerts> tris(nt);
+    std::vector<pt::TriVerts> tris(nt);
     HIP_TRY(hipMemcpy(nodes.data(), ctx->d_nodes, nodes.size(), hipMemcpyDeviceToHost));
     {
         float4 *packed = nullptr;
-        HIP_TRY(hipMalloc((void **)&packed, nt * sizeof(TriVerts)));
+        HIP_TRY(hipMalloc((void **)&packed, nt * sizeof(pt::TriVerts)));
         pt::launch_pack_vertices(static_cast<const float4 *>(ctx->d_tris), packed, (uint32_t)nt, ctx->stream);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream, "read-back");      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-        if (e == hipSuccess) e = hipMemcpyAsync(tris.data(), packed, nt * sizeof(TriVerts), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tris.data(), packed, nt * sizeof(pt::TriVerts), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
         (void)hipFree(packed);
         if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("cull analysis: reading the vertices back: ") + hipGetErrorString(e));
     }
-    const uint8_t *src = nodes.data();
-    auto is_leaf = [&](size_t i) { return ldi(src + i * MI3PT_BVHNODE_STRIDE, 28) == 1; };
-
-    // per triangle: E and L in double from the fp32 vertices
-    auto tri_el = [&](size_t ti, double &E, double &Lsum) {
-        const TriVerts &t = tris[ti];
-        double e1 = 0, e2 = 0;
-        for (int k = 0; k < 3; k++) {
-            const double u = (double)t.b[k] - (double)t.a[k], v = (double)t.c[k] - (double)t.a[k];
-            e1 += u * u; e2 += v * v;
-        }
-        e1 = std::sqrt(e1); e2 = std::sqrt(e2);
-        E = e1 * e2; Lsum = e1 + e2;
-    };
-    double mean_l = 0.0;
-    size_t counted = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (!is_leaf(i)) continue;
-        const int32_t ti = ldi(src + i * MI3PT_BVHNODE_STRIDE, 40);
-        if (ti < 0 || (size_t)ti >= nt) return MI3PT_OK;      // check_scene reports it; no analysis
-        double E, Ls;
-        tri_el((size_t)ti, E, Ls);
-        if (Ls == Ls && Ls < 1e30) { mean_l += Ls; counted++; }
-    }
-    mean_l = counted ? mean_l / (double)counted : 0.0;
-    const double lcap = 16.0 * mean_l;
-    const double u = std::ldexp(1.0, -24), inv_eps = 1.0 / (double)1e-6f;
-    // W(E) = E * c1(E); < 0: the triangle is outside the analysis
-    auto weight = [&](double E) -> double {
-        const double kappa = E * 2.0 * inv_eps;
-        const double A = 5.85 * u * kappa;
-        if (!(A < 0.25)) return -1.0;
-        const double b = (1.0 + A) / (1.0 - A) + 1.0;
-        const double den = 1.0 - (11.7 * b + 1.02) * u * kappa;
-        if (!(den > 0.5)) return -1.0;
-        return E * (11.7 * b + 3.04) / den;
-    };
-
-    std::vector<float> wmax(n, 0.0f);       // +inf = never skip
-    const float inf = __builtin_inff();
-    double lmax = 0.0;
-    auto inside = [&](const uint8_t *outer, const float mn[3], const float mx[3]) {
-        for (int k = 0; k < 3; k++)
-            if (!(ldf(outer, 4 * k) <= mn[k] && ldf(outer, 16 + 4 * k) >= mx[k])) return false;     // false for NaNs too
-        return true;
-    };
-    for (size_t i = n; i-- > 0;) {          // children come after their parent (checked at upload)
-        const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-        if (is_leaf(i)) {
-            const TriVerts &t = tris[(size_t)ldi(r, 40)];
-            float mn[3], mx[3];
-            for (int k = 0; k < 3; k++) {
-                mn[k] = std::fmin(std::fmin(t.a[k], t.b[k]), t.c[k]);
-                mx[k] = std::fmax(std::fmax(t.a[k], t.b[k]), t.c[k]);
-            }
-            double E, Ls;
-            tri_el((size_t)ldi(r, 40), E, Ls);
-            const double W = (E == E && Ls == Ls) ? weight(E) : -1.0;
-            if (W >= 0.0 && Ls <= lcap && inside(r, mn, mx)) {
-                wmax[i] = (float)(W * (1.0 + 1e-6));
-                if ((double)wmax[i] < W) wmax[i] = std::nextafter(wmax[i], inf);
-                if (Ls > lmax) lmax = Ls;
-            } else {
-                wmax[i] = inf;
-            }
-        } else {
-            const int32_t left = ldi(r, 32), right = ldi(r, 36);
-            float e = 0.0f;
-            for (int32_t c : { left, right }) {
-                if (c < 0 || (size_t)c >= n) { e = inf; continue; }
-                const uint8_t *cr = src + (size_t)c * MI3PT_BVHNODE_STRIDE;
-                float mn[3], mx[3];
-                for (int k = 0; k < 3; k++) { mn[k] = ldf(cr, 4 * k); mx[k] = ldf(cr, 16 + 4 * k); }
-                if (!inside(r, mn, mx)) e = inf;
-                if (wmax[(size_t)c] > e) e = wmax[(size_t)c];
-            }
-            wmax[i] = e;
-        }
-    }
-    // packet numbering of mi3pt_upload_bvh: internal nodes in index order
-    std::vector<uint32_t> cull(ctx->npackets, 0x7f807f80u);
-    size_t pk = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (is_leaf(i)) continue;
-        const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-        const int32_t left = ldi(r, 32), right = ldi(r, 36);
-        const uint32_t hl = left >= 0 ? round_up_16(wmax[(size_t)left]) : 0x7f80u;
-        const uint32_t hr = right >= 0 ? round_up_16(wmax[(size_t)right]) : 0x7f80u;
-        if (pk < cull.size()) cull[pk] = (hl << 16) | hr;
-        pk++;
-    }
-    if (pk != ctx->npackets) return pt_set_error(MI3PT_ERR_STATE, "cull analysis: packet count mismatch");
-    uint32_t *d_cull = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_cull, cull.size() * 4));
-    hipError_t e = hipMemcpyAsync(d_cull, cull.data(), cull.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        pt::launch_patch_cull(static_cast<float4 *>(ctx->d_packets), d_cull, (uint32_t)ctx->npackets, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
-    (void)hipFree(d_cull);
-    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("cull analysis: ") + hipGetErrorString(e));
-    // scene constants of the bound: u / EPSILON and 1.65 L_max u / EPSILON, rounded up (the 1.001 covers the
-    // handful of fp32 roundings the kernel adds when it forms delta from them)
-    {
-        double scale = 1.0;
+    pt::WalkOptions opt;
+    opt.collapse = ctx->collapse;
+    opt.packet_order = ctx->packet_order;
+    // (the 8-wide packets only for a context that has asked for the walk: mi3pt_set_kernel_variant(ctx, 14) marks the analysis dirty when they are missing)
+    opt.eight_wide = ctx->variant == 14;
 #ifdef MI3PT_EXPERIMENTS
-        scale = ctx->exp_cull_scale;
+    opt.cull_scale = ctx->exp_cull_scale;
 #endif
-        const double ka = u * inv_eps * 1.001 * scale, kb = 1.65 * lmax * u * inv_eps * 1.001 * scale;
-        ctx->cull_ka = std::nextafter((float)ka, inf);
-        ctx->cull_kb = std::nextafter((float)kb, inf);
+    void **const buffer_of[] = { nullptr, &ctx->d_wide, &ctx->d_cwide, &ctx->d_tripk64, &ctx->d_cw8, &ctx->d_tripk8 };
+    auto upload = [&](pt::WalkBuffer kind, const void *data, size_t bytes) -> int {
+        if (kind != pt::WALK_CULL) return replace_buffer(ctx, buffer_of[kind], data, bytes);
+        // the first buffer out: from here on the device no longer holds the walks' packets of the scene before
+        ctx->wide_ok = ctx->cwide_ok = ctx->cw8_ok = false;
+        uint32_t *d_cull = nullptr;
+        HIP_TRY(hipMalloc((void **)&d_cull, bytes));
+        hipError_t e = hipMemcpyAsync(d_cull, data, bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) {
+            pt::launch_patch_cull(static_cast<float4 *>(ctx->d_packets), d_cull, (uint32_t)ctx->npackets, ctx->stream);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+        (void)hipFree(d_cull);
+        if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("cull analysis: ") + hipGetErrorString(e));
+        return MI3PT_OK;
+    };
+    pt::WalkCompile w;
+    if (int rc = pt::compile_walk(nodes.data(), n, tris.data(), nt, ctx->npackets, opt, upload, w)) return rc;
+    if (!w.analysed) return MI3PT_OK;       // a leaf names a triangle that was not uploaded: check_scene reports it; stays dirty
+    ctx->cull_ka = w.cull_ka; ctx->cull_kb = w.cull_kb;
+    ctx->wide_ok = w.wide_ok;
+    ctx->cwide_ok = w.cwide_ok;
+    if (w.wide_ok) {
+        ctx->nwide = w.nwide;
+        ctx->wide_leaf_cap = pt::SM_CULL_LEAF_CAP;
+        ctx->wide_root = 0;
+        ctx->wide_stack_worst = w.wide_stack_worst;
+        ctx->wide_root_nested = w.wide_root_nested;
     }
-    // ---- wide (4-ary) packets for the WIDE walk: absorb internal children into their parent, largest
-    // surface area first, while the node has fewer than four entries.  Only a child whose box contains
-    // its own children's boxes may be absorbed (pt_kernels.h, WidePacket: the monotonicity argument).
-    ctx->wide_ok = false;
-    if (!is_leaf(0)) {
-        std::vector<uint8_t> nested(n, 0);
-        for (size_t i = 0; i < n; i++) {
-            if (is_leaf(i)) continue;
-            const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-            bool ok = true;
-            for (int32_t c : { ldi(r, 32), ldi(r, 36) }) {
-                if (c < 0 || (size_t)c >= n) { ok = false; continue; }
-                const uint8_t *cr = src + (size_t)c * MI3PT_BVHNODE_STRIDE;
-                float mn[3], mx[3];
-                for (int k = 0; k < 3; k++) { mn[k] = ldf(cr, 4 * k); mx[k] = ldf(cr, 16 + 4 * k); }
-                if (!inside(r, mn, mx)) ok = false;
-            }
-            nested[i] = ok ? 1 : 0;
-        }
-        auto area = [&](size_t i) {
-            const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-            const double x = (double)ldf(r, 16) - ldf(r, 0), y = (double)ldf(r, 20) - ldf(r, 4), z = (double)ldf(r, 24) - ldf(r, 8);
-            const double a = x * y + x * z + y * z;
-            return a == a ? a : 0.0;
-        };
-        std::vector<uint32_t> wide_of(n, pt::REF_NONE);       // binary node -> wide packet index
-        std::vector<std::array<int32_t, 4>> kids;              // per wide packet: binary child nodes (-1: empty)
-        std::vector<uint32_t> owner;                           // per wide packet: the binary node it stands for
-        std::vector<uint32_t> queue;                           // breadth-first numbering
-        queue.push_back(0);
-        wide_of[0] = 0;
-        // (round 6) which descendants a packet holds: the SAH-optimal collapse (collapse_optimal above; a node whose box does not contain its
-        // children's is never opened) -- or, MI3PT_OPT_COLLAPSE = 0, the greedy one of rounds 2 - 5
-        WideCollapse plan4;
-        std::vector<int32_t> entries4;
-        bool optimal4 = ctx->collapse == 1;
-        if (optimal4) {
-            std::vector<uint8_t> closed(n, 0);
-            for (size_t i = 0; i < n; i++) closed[i] = nested[i] ? 0 : 1;
-            optimal4 = collapse_optimal(src, n, 4, &closed, plan4);
-        }
-        for (size_t qi = 0; qi < queue.size(); qi++) {
-            const uint32_t x = queue[qi];
-            const uint8_t *r = src + (size_t)x * MI3PT_BVHNODE_STRIDE;
-            int32_t set[4] = { ldi(r, 32), ldi(r, 36), -1, -1 };
-            int cnt = 2;
-            if (optimal4 && set[0] >= 0 && set[1] >= 0) {
-                plan4.children_of(x, entries4);
-                if (entries4.size() >= 2 && entries4.size() <= 4) {
-                    cnt = (int)entries4.size();
-                    for (int k = 0; k < cnt; k++) set[k] = entries4[(size_t)k];
-                }
-            } else
-            while (cnt < 4) {
-                int pick = -1;
-                double best_area = -1.0;
-                for (int k = 0; k < cnt; k++) {
-                    const int32_t c = set[k];
-                    if (c < 0 || is_leaf((size_t)c) || !nested[(size_t)c] || wide_of[(size_t)c] != pt::REF_NONE) continue;
-                    const double a = area((size_t)c);
-                    if (a > best_area) { best_area = a; pick = k; }
-                }
-                if (pick < 0) break;
-                const uint8_t *cr = src + (size_t)set[pick] * MI3PT_BVHNODE_STRIDE;
-                const int32_t cl = ldi(cr, 32), crr = ldi(cr, 36);
-                set[pick] = cl;
-                set[cnt++] = crr;
-            }
-            std::array<int32_t, 4> k4 = { set[0], set[1], set[2], set[3] };
-            kids.push_back(k4);
-            owner.push_back(x);
-            for (int k = 0; k < cnt; k++) {
-                const int32_t c = set[k];
-                if (c >= 0 && !is_leaf((size_t)c) && wide_of[(size_t)c] == pt::REF_NONE) {
-                    wide_of[(size_t)c] = (uint32_t)queue.size();
-                    queue.push_back((uint32_t)c);
-                }
-            }
-        }
-        // worst-case node-stack occupancy of the wide walk, whatever the order the children are pushed in
-        // (every box hit, nothing skipped, any child possibly descended first): internal entries only
-        size_t worst = 1;
-        {
-            std::vector<std::pair<uint32_t, uint32_t>> work;      // (wide packet, occupancy with it on top)
-            work.emplace_back(0u, 1u);
-            while (!work.empty()) {
-                const auto [w, occ] = work.back();
-                work.pop_back();
-                uint32_t ks[4];
-                uint32_t m = 0;
-                for (int k = 0; k < 4; k++) {
-                    const int32_t c = kids[w][k];
-                    if (c >= 0 && !is_leaf((size_t)c)) ks[m++] = wide_of[(size_t)c];
-                }
-                for (uint32_t i = 0; i < m; i++) {
-                    const uint32_t oc = occ - 1u + m;
-                    if (oc > worst) worst = oc;
-                    work.emplace_back(ks[i], oc);
-                }
-            }
-        }
-        if (worst <= (size_t)pt::SM_CULL_STACK_MAX && kids.size() < 0x7fffffffu) {
-            std::vector<pt::WidePacket> wp(kids.size());
-            std::memset(wp.data(), 0, wp.size() * sizeof(pt::WidePacket));
-            for (size_t w = 0; w < kids.size(); w++) {
-                pt::WidePacket &p = wp[w];
-                uint32_t cw[4] = { 0x7f80u, 0x7f80u, 0x7f80u, 0x7f80u };
-                for (int k = 0; k < 4; k++) {
-                    const int32_t c = kids[w][k];
-                    float *box = k < 2 ? p.b01 + 6 * k : p.b23 + 6 * (k - 2);
-                    if (c < 0) { p.ref[k] = pt::REF_NONE; continue; }
-                    const uint8_t *cr = src + (size_t)c * MI3PT_BVHNODE_STRIDE;
-                    std::memcpy(box, cr + 0, 12);
-                    std::memcpy(box + 3, cr + 16, 12);
-                    p.ref[k] = is_leaf((size_t)c) ? (0x80000000u | (uint32_t)ldi(cr, 40)) : wide_of[(size_t)c];
-                    cw[k] = round_up_16(wmax[(size_t)c]);
-                    if (!node_box_safe(src, (size_t)c)) p.flags |= 1u << k;
-                    p.flags += 16u;              // bits 4..6: the number of children (the walk's box-test count)
-                }
-                p.cull01 = (cw[0] << 16) | cw[1];
-                p.cull23 = (cw[2] << 16) | cw[3];
-            }
-            // ---- numbering of the packets in memory (MI3PT_OPT_PACKET_ORDER; the walk follows references, so any numbering with
-            // the root at 0 renders the same bits).  Breadth-first (the reference's flattenBVH order carried over, raytrace.ts:667-694)
-            // keeps each LEVEL together; depth-first (pre-order) keeps each SUBTREE together: the deep part of a walk -- most of the
-            // distinct packets it touches in a tree of millions -- then stays within a few pages; treelets: the top three levels of a
-            // subtree breadth-first (up to 21 packets, 1.3 KB), then each of its frontier subtrees the same way.
-            if (ctx->packet_order != 0 && wp.size() > 1) {
-                const size_t nw = wp.size();
-                std::vector<uint32_t> order;
-                order.reserve(nw);
-                auto internal_kids = [&](uint32_t w, uint32_t *out) { int m = 0; for (int k = 0; k < 4; k++) { const uint32_t r = wp[w].ref[k]; if (r != pt::REF_NONE && !(r & pt::REF_LEAF)) out[m++] = r; } return m; };
-                std::vector<uint32_t> work;
-                work.push_back(0u);
-                while (!work.empty()) {
-                    const uint32_t top = work.back();
-                    work.pop_back();
-                    if (ctx->packet_order == 1) {
-                        order.push_back(top);
-                        uint32_t ks[4];
-                        const int m = internal_kids(top, ks);
-                        for (int k = m - 1; k >= 0; k--) work.push_back(ks[k]);          // (first child next)
-                    } else {
-                        std::vector<uint32_t> level(1, top), next, frontier;
-                        for (int depth = 0; depth < 3; depth++) {
-                            next.clear();
-                            for (uint32_t w : level) {
-                                order.push_back(w);
-                                uint32_t ks[4];
-                                const int m = internal_kids(w, ks);
-                                for (int k = 0; k < m; k++) next.push_back(ks[k]);
-                            }
-                            level.swap(next);
-                        }
-                        for (size_t k = level.size(); k-- > 0;) work.push_back(level[k]);
-                    }
-                }
-                if (order.size() == nw) {
-                    std::vector<uint32_t> newid(nw);
-                    for (size_t i = 0; i < nw; i++) newid[order[i]] = (uint32_t)i;
-                    std::vector<pt::WidePacket> moved(nw);
-                    for (size_t w = 0; w < nw; w++) {
-                        pt::WidePacket q = wp[w];
-                        for (int k = 0; k < 4; k++)
-                            if (q.ref[k] != pt::REF_NONE && !(q.ref[k] & pt::REF_LEAF)) q.ref[k] = newid[q.ref[k]];
-                        moved[newid[w]] = q;
-                    }
-                    wp.swap(moved);
-                }
-            }
-            if (int rc = replace_buffer(ctx, &ctx->d_wide, wp.data(), wp.size() * sizeof(pt::WidePacket))) return rc;
-            // ---- compressed wide packets + 64-byte triangle records (kernel variant 13): the same packets with the boxes on a
-            // per-node 8-bit grid, rounded outward by at least one cell; the exact test moves to the leaf's own box, which travels
-            // with the triangle.  Offered when every internal box contains its children's (the reference then reaches a leaf iff
-            // the leaf's box passes) and every coordinate is finite and of ordinary magnitude.
-            ctx->cwide_ok = false;
-            {
-                bool ok = true;
-                for (size_t i = 0; i < n && ok; i++) {
-                    if (!is_leaf(i) && !nested[i]) ok = false;
-                    for (int k = 0; k < 6 && ok; k++) { const float v = ldf(src + i * MI3PT_BVHNODE_STRIDE, (size_t)(k < 3 ? 4 * k : 16 + 4 * (k - 3))); if (!(std::fabs(v) < 1e30f)) ok = false; }
-                }
-                std::vector<pt::CWidePacket> cp(ok ? wp.size() : 0);
-                for (size_t w = 0; w < cp.size() && ok; w++) {
-                    const pt::WidePacket &p = wp[w];
-                    pt::CWidePacket &c = cp[w];
-                    std::memset(&c, 0, sizeof c);
-                    const int nk = (int)((p.flags >> 4) & 7u);
-                    c.cull01 = p.cull01; c.cull23 = p.cull23;
-                    for (int k = 0; k < 4; k++) c.ref[k] = p.ref[k];
-                    uint32_t meta = (uint32_t)nk << 24;
-                    for (int ax = 0; ax < 3; ax++) {
-                        double lo = 1e300, hi = -1e300, maxabs = 0.0;
-                        auto box_of = [&](int k) { return k < 2 ? p.b01 + 6 * k : p.b23 + 6 * (k - 2); };
-                        for (int k = 0; k < 4; k++) {
-                            if (p.ref[k] == pt::REF_NONE) continue;
-                            const float *b = box_of(k);
-                            lo = std::min(lo, (double)b[ax]); hi = std::max(hi, (double)b[3 + ax]);
-                            maxabs = std::max({ maxabs, std::fabs((double)b[ax]), std::fabs((double)b[3 + ax]) });
-                        }
-                        if (!(lo <= hi)) { lo = hi = 0.0; }
-                        // cell = 2^e: the extent in at most 248 cells (2 below the lowest coordinate for the origin, 1 + 1 of outward rounding
-                        // on either side, 254 the largest index used), and no finer than 2^-20 of the largest coordinate (the origin and
-                        // the cell boundaries must be far above the fp32 grid of the coordinates themselves)
-                        int e = -100;
-                        if (hi > lo) e = std::max(e, (int)std::ceil(std::log2((hi - lo) / 248.0)));
-                        if (maxabs > 0.0) e = std::max(e, (int)std::floor(std::log2(maxabs)) - 20);
-                        double cell = std::ldexp(1.0, e);
-                        float o = 0.0f;
-                        for (;; e++, cell *= 2.0) {         // (at most a step or two: until the fp32 origin and every index fit)
-                            o = (float)(lo - 2.0 * cell);
-                            if ((double)o > lo - cell) continue;                         // the origin must leave room for a whole cell of outward rounding
-                            if (std::ceil((hi - (double)o) / cell) + 1.0 <= 254.0) break;
-                        }
-                        if (e + 127 < 1 || e + 127 > 254) { ok = false; break; }
-                        c.o[ax] = o;
-                        meta |= (uint32_t)(e + 127) << (8 * ax);
-                        uint32_t qlo = 0, qhi = 0;
-                        for (int k = 0; k < 4; k++) {
-                            uint32_t a = 255u, z = 0u;                                   // empty slot: an inverted box, never entered
-                            if (p.ref[k] != pt::REF_NONE) {
-                                const float *b = box_of(k);
-                                const double x0 = ((double)b[ax] - (double)o) / cell, x1 = ((double)b[3 + ax] - (double)o) / cell;     // exact: fp32 values, a power-of-two cell
-                                const double f0 = std::floor(x0) - 1.0, f1 = std::ceil(x1) + 1.0;
-                                if (!(f0 >= 0.0 && f1 <= 254.0 && f0 < f1)) { ok = false; break; }
-                                a = (uint32_t)f0; z = (uint32_t)f1;
-                                // ... and checked the way the kernel's plain-division path DECODES a plane, one fp32 fma: RN(o + cell q) is not
-                                // exact in general (o is an arbitrary fp32 value, not a multiple of the cell), but round-to-nearest is monotone and
-                                // the child's plane is itself an fp32 value, so a real plane a whole cell outside it cannot round to its inside.
-                                // Verified per plane rather than argued (round-4 advice): a packet that failed would send the tree to the exact packets.
-                                const float cf = (float)cell;
-                                if (!(std::fma((float)a, cf, o) <= b[ax] && std::fma((float)z, cf, o) >= b[3 + ax])) { ok = false; break; }
-                            }
-                            qlo |= a << (8 * k); qhi |= z << (8 * k);
-                        }
-                        c.qlo[ax] = qlo; c.qhi[ax] = qhi;
-                    }
-                    c.meta = meta;
-                }
-                std::vector<pt::TriPacket64> t64(ok ? nt : 0);
-                if (ok) {
-                    std::vector<uint8_t> seen(nt, 0);
-                    for (size_t i = 0; i < n; i++) {
-                        if (!is_leaf(i)) continue;
-                        const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-                        const size_t ti = (size_t)ldi(r, 40);
-                        const TriVerts &v = tris[ti];
-                        pt::TriPacket64 &q = t64[ti];
-                        for (int k = 0; k < 3; k++) {
-                            volatile float e1 = v.b[k] - v.a[k], e2 = v.c[k] - v.a[k];        // one fp32 rounding each (see tri_packet_of)
-                            q.a[k] = v.a[k]; q.e1[k] = e1; q.e2[k] = e2;
-                            q.bmin[k] = ldf(r, 4 * (size_t)k); q.bmax[k] = ldf(r, 16 + 4 * (size_t)k);
-                        }
-                        // (the word the 48-byte records keep the material index in: here a flag -- the leaf's box has a coordinate outside the
-                        // guard range of the reduced-instruction slab tests, e.g. the 1e-33 residues three.js leaves at a sphere's poles:
-                        // its exact test takes the plain divisions.  Internal boxes live on the packets' grids: no such range.)
-                        q.unsafe = node_box_safe(src, i) ? 0u : 1u;
-                        seen[ti] = 1;
-                    }
-                    for (size_t t = 0; t < nt; t++)
-                        if (!seen[t]) {        // a triangle no leaf refers to is never tested: an empty box keeps its record inert
-                            for (int k = 0; k < 3; k++) { t64[t].a[k] = t64[t].e1[k] = t64[t].e2[k] = 0.0f; t64[t].bmin[k] = 1.0f; t64[t].bmax[k] = -1.0f; }
-                            t64[t].unsafe = 0;
-                        }
-                }
-                if (ok) {
-                    if (int rc = replace_buffer(ctx, &ctx->d_cwide, cp.data(), cp.size() * sizeof(pt::CWidePacket))) return rc;
-                    if (int rc = replace_buffer(ctx, &ctx->d_tripk64, t64.data(), t64.size() * sizeof(pt::TriPacket64))) return rc;
-                    ctx->cwide_ok = true;
-                }
-            }
-            ctx->nwide = wp.size();
-            ctx->wide_leaf_cap = pt::SM_CULL_LEAF_CAP;
-            ctx->wide_root = 0;
-            ctx->wide_stack_worst = (int)worst;
-            ctx->wide_ok = true;
-            ctx->wide_root_nested = nested[0] != 0;
-        }
+    ctx->cw8_ok = w.cw8_ok;
+    ctx->cw8_tried = opt.eight_wide;
+    if (w.cw8_ok) {
+        ctx->ncw8 = w.ncw8;
+        ctx->cw8_height = w.cw8_height;
+        ctx->cw8_records = w.cw8_records;
     }
-    // ---- the 8-wide packets of kernel variant 14: its own preconditions -- every internal box contains its children's boxes, every
-    // coordinate is finite and of ordinary magnitude (what the compressed 4-ary packets ask for) -- and its own stack bound: the walk's
-    // node stack holds one entry per packet LEVEL, whatever the order (the 4-ary walk's bound, up to three entries per level, does not apply)
-    // Built only for a context that has asked for the walk (mi3pt_set_kernel_variant(ctx, 14) marks the analysis dirty when they are missing):
-    // an option nobody selected must not cost every scene's first submit the second collapse.
-    ctx->cw8_ok = false;
-    ctx->cw8_tried = ctx->variant == 14;
-    if (ctx->variant == 14 && !is_leaf(0) && nt < 0x7fffffffu) {
-        bool ok = true;
-        for (size_t i = 0; i < n && ok; i++) {
-            const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-            for (int k = 0; k < 6 && ok; k++) { const float v = ldf(r, (size_t)(k < 3 ? 4 * k : 16 + 4 * (k - 3))); if (!(std::fabs(v) < 1e30f)) ok = false; }
-            if (is_leaf(i)) continue;
-            for (int32_t c : { ldi(r, 32), ldi(r, 36) }) {
-                if (c < 0 || (size_t)c >= n) { ok = false; break; }
-                const uint8_t *cr = src + (size_t)c * MI3PT_BVHNODE_STRIDE;
-                float mn[3], mx[3];
-                for (int k = 0; k < 3; k++) { mn[k] = ldf(cr, 4 * k); mx[k] = ldf(cr, 16 + 4 * k); }
-                if (!inside(r, mn, mx)) ok = false;
-            }
-        }
-        Cw8Build b8;
-        if (ok && build_cw8(src, n, reinterpret_cast<const float *>(tris.data()), nt, wmax, b8, ctx->collapse == 0) &&
-            b8.height <= pt::SM_W8_MIN_LDS_NODES + pt::SM_W8_OVERFLOW_NODES) {
-            if (int rc = replace_buffer(ctx, &ctx->d_cw8, b8.packets.data(), b8.packets.size() * sizeof(pt::CW8Packet))) return rc;
-            if (int rc = replace_buffer(ctx, &ctx->d_tripk8, b8.records.data(), b8.records.size() * sizeof(pt::TriPacket64))) return rc;
-            ctx->cw8_ok = true;
-            ctx->ncw8 = b8.packets.size();
-            ctx->cw8_height = b8.height;
-            ctx->cw8_records = b8.records.size();
-        }
-    }
-    // ---- which wide walk `auto` means for this scene (variants 10 / 11 / 12 render the same bits; this is speed only).
-    // The filtered slab test (11, 12) saves ~45 of a wide step's ~290 vector instructions, but a box that is thin on an
-    // axis and entered through that face -- the two triangles of a floor, axis-aligned quads -- has a zero-length
-    // approximate interval and always takes the exact test on top: ~30 more instructions for the whole wave.  Estimate
-    // of such encounters per wide step: the surface-area share of the thin leaves (the chance that a ray through the
-    // root box meets the leaf's box) over the depth of the 4-ary tree.  Measured: demo scene 0.33 -> 10 is 1.5 % faster
-    // than 11; dragon-class 0.15 -> 11 is 2-3 % faster than 10 (profiles/r03_a_slab_filter_ab.log).
-    // The one-axis culling condition (12) is one operation per child instead of four but skips less; it is chosen when
-    // the margins it inflates are negligible anyway: 95th percentile of the leaves' W times k_a times 16 below 2^-10
-    // (dragon-class: 4e-4, +1.4 %; the 10 M-triangle forest: 0.5 -- there it doubles the boxes tested).
-    ctx->auto_wide_variant = 10;
-    if (ctx->wide_ok) {
-        const uint8_t *r0 = src;
-        double ext0[3], diag = 0.0;
-        for (int k = 0; k < 3; k++) { ext0[k] = (double)ldf(r0, 16 + 4 * k) - ldf(r0, 4 * k); diag += ext0[k] * ext0[k]; }
-        diag = std::sqrt(diag);
-        const double area0 = ext0[0] * ext0[1] + ext0[0] * ext0[2] + ext0[1] * ext0[2];
-        const double thin = std::ldexp(diag, -20);
-        double thin_share = 0.0;
-        std::vector<float> ws;
-        ws.reserve(nt);
-        for (size_t i = 0; i < n; i++) {
-            if (!is_leaf(i)) continue;
-            const uint8_t *r = src + i * MI3PT_BVHNODE_STRIDE;
-            const double x = (double)ldf(r, 16) - ldf(r, 0), y = (double)ldf(r, 20) - ldf(r, 4), z = (double)ldf(r, 24) - ldf(r, 8);
-            if ((x <= thin || y <= thin || z <= thin) && area0 > 0.0) {
-                const double a = (x * y + x * z + y * z) / area0;
-                if (a == a) thin_share += a < 1.0 ? a : 1.0;
-            }
-            if (wmax[i] < inf) ws.push_back(wmax[i]);
-        }
-        const double depth = std::log((double)(ctx->nwide > 4 ? ctx->nwide : 4)) / std::log(4.0);
-        const double thin_per_step = thin_share / depth;
-        double w95 = __builtin_inf();
-        if (!ws.empty()) {
-            const size_t k95 = (ws.size() - 1) * 95 / 100;
-            std::nth_element(ws.begin(), ws.begin() + (std::ptrdiff_t)k95, ws.end());
-            w95 = ws[k95];
-        }
-        const double margin = w95 * u * inv_eps * 16.0;
-        if (thin_per_step < 0.25) ctx->auto_wide_variant = margin < std::ldexp(1.0, -10) ? 12 : 11;
-    }
+    ctx->auto_wide_variant = w.auto_wide_variant;
     ctx->cull_ok = true;
     ctx->deep_by_view = false;           // (another scene: judged anew from its first launch)
     ctx->cull_dirty = false;

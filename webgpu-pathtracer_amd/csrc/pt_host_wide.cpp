@@ -2,7 +2,7 @@
 //   collapse_optimal               which descendants of a node its W-wide packet holds (SAH-optimal dynamic programme)
 //   build_cw8                      the eight-wide compressed packets + triangle records of kernel variant 14
 //   mi3pt_host_eight_wide_check    builds them and verifies the result independently of the builder (what the CPU tests call)
-// Called by the scene analysis (pt_context.hip: prepare_cull); covered by the CPU sanitizer builds (tests/tools/sanitize_cpu.sh).
+// Called by the scene compile (pt_host_compile.cpp: compile_walk); covered by the CPU sanitizer builds (tests/tools/sanitize_cpu.sh).
 #include "../../include/mi3pt.h"
 #include "pt_internal.h"
 
@@ -228,7 +228,7 @@ bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per
                     const double f0 = std::floor(x0) - 1.0, f1 = std::ceil(x1) + 1.0;
                     if (!(f0 >= 0.0 && f1 <= 254.0 && f0 < f1)) return false;
                     a = (uint32_t)f0; z = (uint32_t)f1;
-                    if (!(std::fma((float)a, cf, o) <= b0 && std::fma((float)z, cf, o) >= b1)) return false;      // (the plain-division path's decode: see CWidePacket's builder)
+                    if (!(std::fma((float)a, cf, o) <= b0 && std::fma((float)z, cf, o) >= b1)) return false;      // (the plain-division path's decode: see CWidePacket's builder, compile_walk)
                 }
                 c.qlo[ax][sl >> 2] |= a << (8 * (sl & 3));
                 c.qhi[ax][sl >> 2] |= z << (8 * (sl & 3));
@@ -288,24 +288,35 @@ bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per
     return true;
 }
 
-// Host-only check of the 8-wide packets (no device: `-m "not gpu"` tests call it): builds them for a tree + triangles in the reference's
-// layouts exactly as prepare_cull does (weights aside: all zero) and walks the result INDEPENDENTLY of the builder's bookkeeping -- every
-// leaf triangle of the tree reachable exactly once, every packet referenced exactly once, a leaf slot's record carrying that triangle's index
+// Host-only check of the 8-wide packets (no device: `-m "not gpu"` tests call it): obtains them for a tree + triangles in the reference's
+// layouts from the scene compile a context runs (pt_host_compile.cpp: compile_walk, real culling weights) and walks the result INDEPENDENTLY
+// of the builder's bookkeeping -- every leaf triangle of the tree reachable exactly once, every packet referenced exactly once, a leaf slot's record carrying that triangle's index
 // and its leaf's box bit for bit, every decoded child box (the fma the kernel's plain-division path uses) containing everything below it.
 // out[0..5] = packets, records, packet levels, children per packet x 1000, leaves reached, 1 if the kernel would be offered these packets.
 extern "C" int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes, const void *triangles, size_t triangles_bytes, int greedy, uint64_t out[6])
 {
-    if (!nodes || !triangles || !out || nodes_bytes % MI3PT_BVHNODE_STRIDE || triangles_bytes % MI3PT_TRIANGLE_STRIDE)
+    if (!nodes || !triangles || !out || nodes_bytes == 0 || nodes_bytes % MI3PT_BVHNODE_STRIDE || triangles_bytes % MI3PT_TRIANGLE_STRIDE)
         return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_host_eight_wide_check: bad argument");
     const size_t n = nodes_bytes / MI3PT_BVHNODE_STRIDE, nt = triangles_bytes / MI3PT_TRIANGLE_STRIDE;
     const uint8_t *src = static_cast<const uint8_t *>(nodes);
-    std::vector<float> verts(nt * 12, 0.0f);
-    for (size_t t = 0; t < nt; t++)
-        for (int v = 0; v < 3; v++) std::memcpy(&verts[t * 12 + 4 * (size_t)v], static_cast<const uint8_t *>(triangles) + t * MI3PT_TRIANGLE_STRIDE + 16 * (size_t)v, 12);
-    std::vector<float> wmax(n, 0.0f);
-    Cw8Build b;
     for (int k = 0; k < 6; k++) out[k] = 0;
-    if (!build_cw8(src, n, verts.data(), nt, wmax, b, greedy != 0)) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_host_eight_wide_check: the tree does not admit the 8-wide packets");
+    pt::TreeCompile tree;
+    if (const char *e = pt::compile_tree(src, n, tree)) return pt_set_error(MI3PT_ERR_INVALID, std::string("mi3pt_host_eight_wide_check: ") + e);
+    const std::vector<pt::TriVerts> tv = pt::triangle_verts(static_cast<const uint8_t *>(triangles), nt);
+    const float *verts = reinterpret_cast<const float *>(tv.data());
+    pt::WalkOptions opt;
+    opt.collapse = greedy ? 0 : 1;
+    opt.eight_wide = opt.eight_wide_any_height = true;
+    Cw8Build b;
+    auto keep = [&](pt::WalkBuffer kind, const void *p, size_t bytes) {
+        if (kind == pt::WALK_CW8) b.packets.assign(static_cast<const pt::CW8Packet *>(p), static_cast<const pt::CW8Packet *>(p) + bytes / sizeof(pt::CW8Packet));
+        if (kind == pt::WALK_TRI8) b.records.assign(static_cast<const pt::TriPacket64 *>(p), static_cast<const pt::TriPacket64 *>(p) + bytes / sizeof(pt::TriPacket64));
+        return 0;
+    };
+    pt::WalkCompile walk;
+    if (int rc = pt::compile_walk(src, n, tv.data(), nt, tree.npackets, opt, keep, walk)) return rc;
+    if (b.packets.empty()) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_host_eight_wide_check: the tree does not admit the 8-wide packets");
+    b.height = walk.cw8_height; b.mean_children = walk.cw8_mean_children;
     auto fail = [](const std::string &what) { return pt_set_error(MI3PT_ERR_STATE, "mi3pt_host_eight_wide_check: " + what); };
     // leaf of every triangle in the source tree
     std::vector<int64_t> leaf_of(nt, -1);
@@ -382,7 +393,7 @@ extern "C" int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes
     if (reached != nleaves) return fail("not every leaf is reachable");
     if (levels != b.height) return fail("the builder's height is not the tree's");
     out[0] = np; out[1] = b.records.size(); out[2] = (uint64_t)b.height; out[3] = (uint64_t)(b.mean_children * 1000.0 + 0.5); out[4] = reached;
-    out[5] = b.height <= pt::SM_W8_MIN_LDS_NODES + pt::SM_W8_OVERFLOW_NODES ? 1 : 0;
+    out[5] = walk.cw8_ok ? 1 : 0;
     return MI3PT_OK;
 }
 

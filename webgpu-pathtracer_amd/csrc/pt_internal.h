@@ -12,7 +12,7 @@ namespace pt {
 int lbvh_build(const void *d_tris, size_t n, void *nodes_out, float *build_ms, hipStream_t stream, std::string &err);
 }
 
-// ---- host-side helpers shared by pt_context.hip and pt_host_wide.cpp (plain C++: the CPU sanitizer builds cover them)
+// ---- host-side helpers shared by pt_context.hip and the pt_host_*.cpp files (plain C++: the CPU sanitizer builds cover them)
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -61,6 +61,60 @@ struct Cw8Build {
 };
 bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per triangle: a, pad, b, pad, c, pad */, size_t nt,
                const std::vector<float> &wmax, Cw8Build &out, bool greedy = false);
+// pt_host_compile.cpp: the scene compile -- what mi3pt_upload_bvh, mi3pt_upload_triangles and the context's lazy analysis (prepare_cull)
+// hand to the device, computed from the uploaded records alone
+#include <functional>
+namespace pt {
+// child reference of the packet walk: leaf -> 0x80000000 | triangle (renumbered by tri_new when given), else packet_of[]
+uint32_t child_ref(const uint8_t *src, const std::vector<uint32_t> &packet_of, const uint32_t *tri_new, int32_t child);
+// one 64-byte packet per internal node, at the index packet_of[] gives it: bit copies of both children's boxes, their references, the
+// guard bits of the fast slab test
+void build_packets(const uint8_t *src, size_t n, const std::vector<uint32_t> &packet_of, size_t npackets, const uint32_t *tri_new,
+                   std::vector<NodePacket> &pk);
+struct TreeCompile {
+    std::vector<uint32_t> packet_of;        // per node: its packet (internal nodes in index order), REF_NONE for a leaf
+    size_t npackets = 0;
+    std::vector<NodePacket> packets;
+    std::vector<uint32_t> leaf_rank;        // per triangle: its leaf's place in the reference's visiting order
+    int leaf_cap = 0, walk_stack_worst = 64;
+    bool tree_proper = false, cull_stack_ok = false;
+    uint32_t root_ref = REF_NONE, scene_flags = 0;
+    int64_t max_tri_ref = -1;
+};
+// nullptr, or why the tree is refused (MI3PT_ERR_INVALID)
+const char *compile_tree(const uint8_t *src, size_t n, TreeCompile &out);
+// the 48-byte intersection record of a 112-byte triangle record: a, the material index, and the edges b - a, c - a -- the two subtractions
+// Moller-Trumbore starts with (raytrace.wgsl:82-83), each ONE fp32 rounding (round-to-nearest-even, subnormals kept, like the device's
+// v_sub_f32), so the kernels start from the same operands
+TriPacket tri_packet_of(const uint8_t *rec);
+const char *compile_triangles(const uint8_t *src, size_t n, std::vector<TriPacket> &pk, int64_t &max_mat_ref);
+// the three vertices of a triangle: the first 48 of a record's 112 bytes (raytrace.wgsl:40-49)
+struct TriVerts { float a[3], pa, b[3], pb, c[3], pc; };
+static_assert(sizeof(TriVerts) == 48, "three vec3f + padding");
+std::vector<TriVerts> triangle_verts(const uint8_t *triangles, size_t nt);
+struct WalkOptions {
+    int collapse = -1, packet_order = 0;        // MI3PT_OPT_COLLAPSE, MI3PT_OPT_PACKET_ORDER
+    bool eight_wide = false;                    // build kernel variant 14's packets too
+    bool eight_wide_any_height = false;         // ... and emit them even when the walk's stack cannot hold their levels (the host-side self-check)
+    double cull_scale = 1.0;                    // < 1 VOIDS the proof of DESIGN.md 3a (experiment build only)
+};
+struct WalkCompile {
+    bool analysed = false;                      // false: a leaf names a triangle that was not uploaded -- nothing was emitted
+    float cull_ka = 0.0f, cull_kb = 0.0f;
+    bool wide_ok = false, cwide_ok = false, cw8_ok = false, wide_root_nested = false;
+    size_t nwide = 0, ncw8 = 0, cw8_records = 0;
+    int wide_stack_worst = 0, cw8_height = 0, auto_wide_variant = 10;
+    double cw8_mean_children = 0.0;
+};
+// the buffers of compile_walk, in the order they are emitted: uint32 cull words per node packet, WidePacket, CWidePacket, TriPacket64 per
+// triangle, CW8Packet, TriPacket64 per 8-wide record
+enum WalkBuffer { WALK_CULL, WALK_WIDE, WALK_CWIDE, WALK_TRI64, WALK_CW8, WALK_TRI8 };
+// called with each buffer as it becomes ready (valid during the call only: it is freed before the next stage); non-zero stops the compile
+using WalkSink = std::function<int(WalkBuffer kind, const void *data, size_t bytes)>;
+// 0, the sink's status, or MI3PT_ERR_STATE when npackets is not the tree's
+int compile_walk(const uint8_t *src, size_t n, const TriVerts *tris, size_t nt, size_t npackets, const WalkOptions &opt, const WalkSink &emit,
+                 WalkCompile &out);
+}
 // pt_host_sky.cpp: the tiles whose camera rays can reach no geometry (PROOFS.md section 5).  sky_cut_of: a cut of the tree as boxes (6 floats
 // each), false if a node's box does not contain its children's; sky_classify: empty[tile] = 1 per 8x8 tile of this rank's image, returns the count
 namespace pt {

@@ -46,7 +46,7 @@ SYMBOLS = (
     "mi3pt_set_env_sampling", "mi3pt_device_build_bvh",
     "mi3pt_set_pipelining", "mi3pt_flush", "mi3pt_set_present_mode", "mi3pt_raytrace_launch_span", "mi3pt_batch_capacity", "mi3pt_debug_active_variant", "mi3pt_debug_last_launch", "mi3pt_submit_frames", "mi3pt_debug_set_packet_layout",
     "mi3pt_debug_intersect", "mi3pt_debug_math", "mi3pt_debug_wave_times", "mi3pt_host_build_bvh", "mi3pt_host_build_bvh_f64",
-    "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
+    "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_host_scene_compile", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
     "mi3pt_create_group", "mi3pt_group_size", "mi3pt_group_member",
     "mi3pt_tile_global_row", "mi3pt_tile_owner",
     "mi3pt_render_aovs", "mi3pt_read_aov", "mi3pt_aov_device_ptr",
@@ -127,6 +127,7 @@ def load_library(path=None):
     lib.mi3pt_host_build_bvh_f64.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_int]
     lib.mi3pt_host_env_cdf.argtypes = [c_void_p, c_int, c_int, c_void_p]
     lib.mi3pt_host_eight_wide_check.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p]
+    lib.mi3pt_host_scene_compile.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_size_t]
     lib.mi3pt_host_sky_tiles.argtypes = [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
     lib.mi3pt_device_count.argtypes = [ctypes.POINTER(c_int)]
     lib.mi3pt_device_name.argtypes = [c_int, ctypes.c_char_p, c_size_t]
@@ -228,6 +229,26 @@ def host_eight_wide_check(nodes, triangles, greedy=False):
     _check(lib, lib.mi3pt_host_eight_wide_check(_ptr(nd), nd.nbytes, _ptr(tr), tr.nbytes, 1 if greedy else 0, _ptr(out)))
     return {"packets": int(out[0]), "records": int(out[1]), "levels": int(out[2]), "children_per_packet": out[3] / 1000.0,
             "leaves": int(out[4]), "offered": bool(out[5])}
+
+
+# what mi3pt_host_scene_compile fills in, in order (include/mi3pt.h): scalars, then one FNV-1a digest per device buffer (0: not built)
+SCENE_COMPILE_FIELDS = (
+    "nodes", "triangles", "packets", "leaf_cap", "tree_proper", "walk_stack_worst", "cull_stack_ok", "root_ref", "scene_flags",
+    "max_tri_ref", "max_mat_ref", "analysed", "cull_ka", "cull_kb", "wide_ok", "cwide_ok", "cw8_ok", "wide_root_nested",
+    "wide_stack_worst", "auto_wide_variant", "wide_packets", "cw8_packets", "cw8_records", "cw8_levels",
+    "digest_node_packets", "digest_leaf_rank", "digest_tri_packets", "digest_wide_packets", "digest_cwide_packets",
+    "digest_tri_records", "digest_cw8_packets", "digest_cw8_records")
+
+
+def host_scene_compile(nodes, triangles, collapse=-1, packet_order=0, want_eight_wide=False):
+    """mi3pt_host_scene_compile: what the uploads and a context's scene analysis compute for this tree + triangles, on the host;
+    dict of SCENE_COMPILE_FIELDS (ints; cull_ka / cull_kb as the bits of the float)."""
+    lib = load_library()
+    nd, tr = np.ascontiguousarray(nodes), np.ascontiguousarray(triangles)
+    out = np.zeros(len(SCENE_COMPILE_FIELDS), np.uint64)
+    _check(lib, lib.mi3pt_host_scene_compile(_ptr(nd), nd.nbytes, _ptr(tr), tr.nbytes, int(collapse), int(packet_order),
+                                             1 if want_eight_wide else 0, _ptr(out), len(out)))
+    return dict(zip(SCENE_COMPILE_FIELDS, (int(x) for x in out)))
 
 
 def host_env_cdf(rgba):
