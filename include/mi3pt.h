@@ -461,6 +461,19 @@ int mi3pt_set_pipelining(mi3pt_ctx *ctx, int enabled);
  * (hit, t, position xyz, normal xyz, materialIndex, box tests, triangle tests,
  * stack overflows) = raySceneIntersect, raytrace.wgsl:205-211. */
 int mi3pt_debug_intersect(mi3pt_ctx *ctx, const float *rays, size_t n, float *out);
+/* The same 12 floats per ray from the SHIPPED first-hit walk (what mi3pt_render_aovs runs where `auto` means kernel variant 13: compressed
+ * wide packets, distance culling, wave-voted node / leaf steps).  Slots 0-8 as above; 9: node steps of the ray's lane, 10: leaves whose own
+ * box passed the reference's test (each is a triangle test of the reference's walk), 11: 0.  Runs exactly when mi3pt_render_aovs would
+ * run that walk; otherwise MI3PT_ERR_STATE (never another walk in its place). */
+int mi3pt_debug_intersect_shipped(mi3pt_ctx *ctx, const float *rays, size_t n, float *out);
+/* The walks' primitive decisions on n independent pairs, by the kernels' own device functions.  rays: n x 6; out: n x 12; a slot that is
+ * not reported holds -1.
+ *   fn 0 (box), geom n x 7 = min xyz, max xyz, box_unsafe (0 / 1, the flag the upload sets per box):
+ *        0 ray_aabb, 1 ray_prepare().flags, 2 ray_aabb_pre, 3 leaf_box_hit; only when flags == 0 and box_unsafe == 0:
+ *        4 slab_margin > 0, 5 slab_hit, 6 cwide_hit (5 and 6 on slab_q0's own max3(tnear), tfar), 7 ray_aabb_fast, 8-10 tnear xyz, 11 tfar
+ *   fn 1 (triangle), geom n x 9 = a, b, c:  hit, t, u, v of ray_triangle (0-3), ray_triangle_e (4-7), ray_triangle_flat_e (8-11); the
+ *        edges of the last two are formed on the device as the upload forms them, fl(b - a), fl(c - a); t, u, v are meaningful where hit. */
+int mi3pt_debug_pairs(mi3pt_ctx *ctx, int fn, const float *rays, const float *geom, float *out, size_t n);
 /* An ALTERNATIVE tree, built on the device from the uploaded triangles: a linear
  * BVH (Morton codes, radix sort, Karras' parallel hierarchy, bottom-up fit) in the same 48-byte
  * records, pre-order numbered so that a child follows its parent; nodes_out (host) receives

@@ -122,7 +122,7 @@ static rt_uniforms parse_uniforms(const uint8_t *u)
 }
 
 typedef struct { v3 origin, direction; } ray_t;
-typedef struct { int hit; v3 position, normal; float t; int32_t material; } hit_t;
+typedef struct { int hit; v3 position, normal; float t; int32_t material; float u, v; /* barycentrics of an accepted hit (probes only) */ } hit_t;
 
 /* counters: 0 rays, 1 AABB tests (N_box), 2 triangle tests (N_tri), 3 hits,
  * 4 misses, 5 stack-overflow aborts, 6 pixel jobs, 7 reserved */
@@ -133,6 +133,7 @@ static hit_t ray_triangle(ray_t ray, const uint8_t *tri)
 {
     hit_t hit; hit.hit = 0; hit.position = V3(0, 0, 0); hit.normal = V3(0, 0, 0);
     hit.t = INF_; hit.material = ldi(tri, 92);
+    hit.u = 0.0f; hit.v = 0.0f;
     v3 a = ldv3(tri, 0), b = ldv3(tri, 16), c = ldv3(tri, 32);
     v3 edge1 = vsub(b, a);
     v3 edge2 = vsub(c, a);
@@ -151,6 +152,7 @@ static hit_t ray_triangle(ray_t ray, const uint8_t *tri)
     if (t > EPSILON) {
         hit.hit = 1;
         hit.t = t;
+        hit.u = u; hit.v = v;
         hit.position = vadd(ray.origin, vscale(ray.direction, t));
         v3 an = ldv3(tri, 48), bn = ldv3(tri, 64), cn = ldv3(tri, 80);
         hit.normal = vnormalize(vadd(vadd(vscale(an, w), vscale(bn, u)), vscale(cn, v)));
@@ -186,7 +188,7 @@ static int ray_aabb(ray_t ray, v3 bmin, v3 bmax)
 static hit_t ray_bvh(const orc_scene *sc, ray_t ray, int32_t root, uint64_t *cnt)
 {
     hit_t hit; hit.hit = 0; hit.position = V3(0, 0, 0); hit.normal = V3(0, 0, 0);
-    hit.t = INF_; hit.material = -1;
+    hit.t = INF_; hit.material = -1; hit.u = 0.0f; hit.v = 0.0f;
     const uint8_t *n0 = sc->nodes + (size_t)root * ORC_NODE_STRIDE;
     cnt[C_BOX]++;
     if (!ray_aabb(ray, ldv3(n0, 0), ldv3(n0, 16))) return hit;
@@ -226,7 +228,7 @@ static hit_t ray_scene(const orc_scene *sc, ray_t ray, uint64_t *cnt)
     cnt[C_RAYS]++;
     if (sc->nnodes == 0) {
         hit_t hit; hit.hit = 0; hit.position = V3(0, 0, 0); hit.normal = V3(0, 0, 0);
-        hit.t = INF_; hit.material = -1;
+        hit.t = INF_; hit.material = -1; hit.u = 0.0f; hit.v = 0.0f;
         return hit;
     }
     return ray_bvh(sc, ray, 0, cnt);
@@ -708,6 +710,42 @@ void orc_ray_scene(const orc_scene *sc, const float o[3], const float d[3], floa
     out[5] = h.normal.x; out[6] = h.normal.y; out[7] = h.normal.z;
     out[8] = (float)h.material;
     if (counters8) for (int k = 0; k < C_COUNT; k++) counters8[k] += cnt[k];
+}
+
+/* ---- the same three, batched (one call per test instead of one per pair) ---- */
+
+/* rays: n x 6 (origin, direction); boxes: n x 6 (min, max); out: n bytes, 0 / 1 */
+void orc_ray_aabb_n(const float *rays, const float *boxes, int64_t n, uint8_t *out)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++)
+        out[i] = (uint8_t)orc_ray_aabb(rays + i * 6, rays + i * 6 + 3, boxes + i * 6, boxes + i * 6 + 3);
+}
+
+/* abc: n x 9 (the three vertices); out: n x 4 = hit, t, u, v (t = INF, u = v = 0 without a hit) */
+void orc_ray_triangle_n(const float *rays, const float *abc, int64_t n, float *out)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        uint8_t tri[ORC_TRI_STRIDE];
+        memset(tri, 0, sizeof tri);
+        for (int k = 0; k < 3; k++) memcpy(tri + 16 * k, abc + i * 9 + 3 * k, 12);
+        ray_t r; r.origin = V3(rays[i * 6], rays[i * 6 + 1], rays[i * 6 + 2]);
+        r.direction = V3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+        hit_t h = ray_triangle(r, tri);
+        out[i * 4] = (float)h.hit; out[i * 4 + 1] = h.t; out[i * 4 + 2] = h.u; out[i * 4 + 3] = h.v;
+    }
+}
+
+/* out: n x 9 as orc_ray_scene; counts: n x 3 = box tests, triangle tests, stack overflows of each ray */
+void orc_ray_scene_n(const orc_scene *sc, const float *rays, int64_t n, float *out, uint64_t *counts)
+{
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t i = 0; i < n; i++) {
+        uint64_t cnt[C_COUNT]; memset(cnt, 0, sizeof cnt);
+        orc_ray_scene(sc, rays + i * 6, rays + i * 6 + 3, out + i * 9, cnt);
+        counts[i * 3] = cnt[C_BOX]; counts[i * 3 + 1] = cnt[C_TRI]; counts[i * 3 + 2] = cnt[C_OVERFLOW];
+    }
 }
 
 void orc_camera_ray(const uint8_t *uniforms96, float uvx, float uvy, float out6[6])

@@ -41,6 +41,9 @@ def lib():
         L.orc_ray_aabb.argtypes = [ctypes.c_void_p] * 4
         L.orc_ray_triangle.argtypes = [ctypes.c_void_p] * 4
         L.orc_ray_scene.argtypes = [ctypes.c_void_p] * 5
+        L.orc_ray_aabb_n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        L.orc_ray_triangle_n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        L.orc_ray_scene_n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
         L.orc_camera_ray.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
         L.orc_env_uv.argtypes = [ctypes.c_void_p] * 3
         L.orc_sample_env.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
@@ -209,6 +212,36 @@ def ray_scene(scene, o, d):
     cnt = np.zeros(8, np.uint64)
     lib().orc_ray_scene(ctypes.byref(scene.c), _p(o), _p(d), _p(out), _p(cnt))
     return out, dict(zip(COUNTER_NAMES, (int(x) for x in cnt)))
+
+
+def ray_aabb_n(rays, bmin, bmax):
+    """ray_aabb on n pairs: rays n x 6 (origin, direction), bmin / bmax n x 3 -> bool[n]."""
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    box = np.ascontiguousarray(np.concatenate([np.asarray(bmin, np.float32).reshape(-1, 3),
+                                               np.asarray(bmax, np.float32).reshape(-1, 3)], 1))
+    assert len(box) == len(r)
+    out = np.zeros(len(r), np.uint8)
+    lib().orc_ray_aabb_n(_p(r), _p(box), len(r), _p(out))
+    return out.astype(bool)
+
+
+def ray_triangle_n(rays, abc):
+    """ray_triangle on n pairs: rays n x 6, abc n x 9 (or n x 3 x 3) -> float32[n, 4] = hit, t, u, v."""
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    g = np.ascontiguousarray(abc, np.float32).reshape(-1, 9)
+    assert len(g) == len(r)
+    out = np.zeros((len(r), 4), np.float32)
+    lib().orc_ray_triangle_n(_p(r), _p(g), len(r), _p(out))
+    return out
+
+
+def ray_scene_n(scene, rays):
+    """ray_scene on n rays -> (float32[n, 9], uint64[n, 3] = box tests, triangle tests, stack overflows per ray)."""
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    out = np.zeros((len(r), 9), np.float32)
+    cnt = np.zeros((len(r), 3), np.uint64)
+    lib().orc_ray_scene_n(ctypes.byref(scene.c), _p(r), len(r), _p(out), _p(cnt))
+    return out, cnt
 
 
 def camera_ray(uniforms96, uvx, uvy):

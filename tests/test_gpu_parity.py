@@ -138,6 +138,17 @@ def test_ray_scene_intersect_matches_oracle(gpu_ctx, orc, demo, env, variant):
         assert pc.same_bits(got[i, :9], want), f"ray {i} {r}: gpu {got[i]} oracle {want}"
         assert (int(got[i, 9]), int(got[i, 10]), int(got[i, 11])) == \
             (cnt["box_tests"], cnt["tri_tests"], cnt["stack_overflows"]), f"ray {i} counters"
+    # the ray families of the walk probes (tests/walk_probe_inputs.py: incoherent rays, origins on node planes, leaf-box corners,
+    # triangle edges and vertices, the guard range, NaN / inf / zero directions): the same two assertions per ray, the oracle batched
+    import walk_probe_inputs as wpi
+    for name, rays in wpi.scene_rays(demo.nodes, demo.triangles).items():
+        got = ctx.debug_intersect(rays)
+        want, cnt = orc.ray_scene_n(osc, rays)
+        for i in range(len(rays)):
+            if not pc.same_bits(got[i, :9], want[i]):
+                raise AssertionError(f"{name} ray {i} {rays[i]}: gpu {got[i]} oracle {want[i]}")
+        assert (got[:, 9:12].astype(np.uint64) == cnt).all(), \
+            f"{name} counters, first at ray {int(np.flatnonzero((got[:, 9:12].astype(np.uint64) != cnt).any(1))[0])}"
     ctx.set_kernel_variant(0)
 
 

@@ -2277,6 +2277,14 @@ extern "C" int mi3pt_bind_accumulation(mi3pt_ctx *ctx, void *dev_ptr, size_t nby
 }
 
 // ---- first-hit feature images (include/mi3pt.h: mi3pt_aov, mi3pt_render_aovs) ----
+// Whether a first-hit pass walks the shipped walk's data (walk 13) -- after prepare_layout and prepare_cull: asked by mi3pt_render_aovs and
+// by the probe of that walk, mi3pt_debug_intersect_shipped.
+static bool first_hit_walk_is_shipped(const mi3pt_ctx *ctx)
+{
+    return !ctx->env_sampling && !ctx->layout_active && ctx->cull_enabled && ctx->wide_enabled && ctx->cull_stack_ok &&
+           ctx->cull_ok && !ctx->cull_dirty && ctx->wide_ok && ctx->cwide_ok && ctx->d_leaf_rank;
+}
+
 // Not require_idle: the queued sample frames stay queued and keep their batching.  The pass is enqueued on the context's stream;
 // every path that frees or replaces a scene buffer waits for that stream first (replace_buffer, clone_scene, mi3pt_resize).
 extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
@@ -2306,9 +2314,7 @@ extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
     // bit-identical on every tree the context accepts).  The debug packet layout renumbers the triangles its packets name: there
     // the walk on the uploaded records runs, so that the ids image holds uploaded indices.  One set of bits whichever runs.
     int walk = 3, stack_worst = ctx->walk_stack_worst;
-    const bool culled = !ctx->env_sampling && !ctx->layout_active && ctx->cull_enabled && ctx->wide_enabled && ctx->cull_stack_ok &&
-                        ctx->cull_ok && !ctx->cull_dirty && ctx->wide_ok && ctx->cwide_ok && ctx->d_leaf_rank;
-    if (culled) { walk = 13; stack_worst = ctx->wide_stack_worst; }
+    if (first_hit_walk_is_shipped(ctx)) { walk = 13; stack_worst = ctx->wide_stack_worst; }
     else if (ctx->layout_active) { walk = 1; A.scene.tris = static_cast<const float4 *>(ctx->d_tris); }
     if (tex_bytes) {
         if (ctx->timing) {
@@ -2515,6 +2521,67 @@ extern "C" int mi3pt_debug_intersect(mi3pt_ctx *ctx, const float *rays, size_t n
     (void)hipFree(d_rays);
     (void)hipFree(d_out);
     if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_intersect: ") + hipGetErrorString(e));
+    return MI3PT_OK;
+}
+
+// the shipped first-hit walk (k_aov_cull's loop) on rays from memory; never another walk in its place
+extern "C" int mi3pt_debug_intersect_shipped(mi3pt_ctx *ctx, const float *rays, size_t n, float *out)
+{
+    PT_GROUP(ctx, mi3pt_debug_intersect_shipped(group_member0(ctx), rays, n, out));
+    if (int rc = require_idle(ctx)) return rc;
+    if (!rays || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = check_scene(ctx)) return rc;
+    if (int rc = prepare_layout(ctx)) return rc;    // (what mi3pt_render_aovs does before it picks its walk)
+    if (int rc = prepare_cull(ctx)) return rc;
+    const pt::SceneRefs scene = scene_refs(ctx);
+    if (!first_hit_walk_is_shipped(ctx) || !scene.cwide || !scene.tripk64 || !scene.leaf_rank)
+        return pt_set_error(MI3PT_ERR_STATE, "debug_intersect_shipped: mi3pt_render_aovs would not run the shipped first-hit walk on this scene / these options");
+    if (n == 0) return MI3PT_OK;
+    float *d_rays = nullptr, *d_out = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_rays, n * 24));
+    if (hipMalloc((void **)&d_out, n * 48) != hipSuccess) {
+        (void)hipFree(d_rays);
+        return pt_set_error(MI3PT_ERR_HIP, "hipMalloc failed");
+    }
+    hipError_t e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        pt::launch_debug_intersect_cull(scene, d_rays, n, d_out, ctx->wide_stack_worst, ctx->leaf_min, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream, "read-back");
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 48, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+    (void)hipFree(d_rays);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_intersect_shipped: ") + hipGetErrorString(e));
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_debug_pairs(mi3pt_ctx *ctx, int fn, const float *rays, const float *geom, float *out, size_t n)
+{
+    PT_GROUP(ctx, mi3pt_debug_pairs(group_member0(ctx), fn, rays, geom, out, n));
+    if (int rc = require_idle(ctx)) return rc;
+    if (!rays || !geom || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (fn != 0 && fn != 1) return pt_set_error(MI3PT_ERR_INVALID, "debug_pairs: fn must be 0 (box) or 1 (triangle)");
+    if (n == 0) return MI3PT_OK;
+    const size_t G = fn == 0 ? 7 : 9;
+    float *d_rays = nullptr, *d_geom = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_rays, n * 24);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_geom, n * G * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_out, n * 48);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_geom, geom, n * G * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        pt::launch_debug_pairs(fn, d_rays, d_geom, d_out, n, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream, "read-back");
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 48, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+    if (d_rays) (void)hipFree(d_rays);
+    if (d_geom) (void)hipFree(d_geom);
+    if (d_out) (void)hipFree(d_out);
+    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_pairs: ") + hipGetErrorString(e));
     return MI3PT_OK;
 }
 

@@ -321,6 +321,11 @@ void launch_fullscreen(const FsUniforms &fs, const float4 *tex, int tex_w, int t
 void launch_debug_intersect(const SceneRefs &scene, const float *rays, size_t n, float *out, int variant,
                             hipStream_t s);
 void launch_debug_math(int fn, const float *a, const float *b, float *out, size_t n, hipStream_t s);
+// fn 0: (ray, box) pairs, geom n x 7; fn 1: (ray, triangle) pairs, geom n x 9; out n x 12 (pt_kernels.hip, k_debug_pairs)
+void launch_debug_pairs(int fn, const float *rays, const float *geom, float *out, size_t n, hipStream_t s);
+// the first-hit walk on the shipped walk's data (k_aov_cull's loop) on n rays; needs scene.cwide, scene.tripk64 and scene.leaf_rank
+void launch_debug_intersect_cull(const SceneRefs &scene, const float *rays, size_t n, float *out, int stack_worst, int leaf_min,
+                                 hipStream_t s);
 // Box tests and rays of one counter set ([nblocks][CNT_COUNT]) since the previous call for that set, into host-visible memory:
 // out[1] = box tests, out[2] = rays, then (after a system-scope fence) out[0] = seq.  `prev` (2 x u64, device) carries the sums.
 void launch_walk_stats(const uint64_t *counters, int nblocks, uint64_t *prev, uint64_t *out, uint64_t seq, hipStream_t s);

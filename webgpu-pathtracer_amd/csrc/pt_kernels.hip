@@ -3233,6 +3233,63 @@ void launch_debug_intersect(const SceneRefs &scene, const float *rays, size_t n,
     else hipLaunchKernelGGL(k_debug_intersect<1>, grid, block, 0, s, scene, rays, n, out);
 }
 
+// The walks' primitive decisions on arbitrary (ray, box) / (ray, triangle) pairs, one thread per pair, by the device functions the kernels
+// call (include/mi3pt.h: mi3pt_debug_pairs).  12 floats per pair; a slot that is not reported holds -1.
+//   fn 0, geom = mn xyz, mx xyz, box_unsafe:  ray_aabb, ray_prepare().flags, ray_aabb_pre, leaf_box_hit; and for a ray and a box on the
+//         fast path (flags == 0 && !box_unsafe):  slab_margin > 0, slab_hit, cwide_hit -- the last two on slab_q0's own (max3(tnear), tfar)
+//         --, ray_aabb_fast, tnear xyz, tfar
+//   fn 1, geom = a, b, c:  hit, t, u, v of ray_triangle, of ray_triangle_e and of ray_triangle_flat_e, the edges formed here as the upload
+//         forms them: fl(b - a), fl(c - a)
+__global__ void __launch_bounds__(256) k_debug_pairs(int fn, const float *__restrict__ rays, const float *__restrict__ geom,
+                                                     float *__restrict__ out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const f3 o = F3(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
+    const f3 d = F3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+    float *r = out + i * 12;
+    if (fn == 0) {
+        const float *g = geom + i * 7;
+        const f3 mn = F3(g[0], g[1], g[2]), mx = F3(g[3], g[4], g[5]);
+        const bool box_unsafe = g[6] != 0.0f;
+        const RayPre pre = ray_prepare(o, d, 0u);
+        r[0] = ray_aabb(o, d, mn.x, mn.y, mn.z, mx.x, mx.y, mx.z) ? 1.0f : 0.0f;
+        r[1] = (float)pre.flags;
+        r[2] = ray_aabb_pre(o, d, pre, box_unsafe, mn.x, mn.y, mn.z, mx.x, mx.y, mx.z) ? 1.0f : 0.0f;
+        r[3] = leaf_box_hit(o, d, pre, box_unsafe, mn, mx) ? 1.0f : 0.0f;
+        for (int k = 4; k < 12; k++) r[k] = -1.0f;
+        if (pre.flags == 0u && !box_unsafe) {
+            f3 tn;
+            float tf;
+            slab_q0(o, pre, mn.x, mn.y, mn.z, mx.x, mx.y, mx.z, tn, tf);
+            const float key = fmaxf(fmaxf(tn.x, tn.y), tn.z);
+            r[4] = slab_margin(key, tf) > 0.0f ? 1.0f : 0.0f;
+            r[5] = slab_hit(key, tf) ? 1.0f : 0.0f;
+            r[6] = cwide_hit(key, tf) ? 1.0f : 0.0f;
+            r[7] = ray_aabb_fast(o, d, pre, mn.x, mn.y, mn.z, mx.x, mx.y, mx.z) ? 1.0f : 0.0f;
+            r[8] = tn.x; r[9] = tn.y; r[10] = tn.z; r[11] = tf;
+        }
+    } else {
+        const float *g = geom + i * 9;
+        const f3 a = F3(g[0], g[1], g[2]), b = F3(g[3], g[4], g[5]), c = F3(g[6], g[7], g[8]);
+        const f3 e1 = b - a, e2 = c - a;
+        float t = 0.0f, u = 0.0f, v = 0.0f;
+        r[0] = ray_triangle(o, d, a, b, c, t, u, v) ? 1.0f : 0.0f;
+        r[1] = t; r[2] = u; r[3] = v;
+        t = u = v = 0.0f;
+        r[4] = ray_triangle_e(o, d, a, e1, e2, t, u, v) ? 1.0f : 0.0f;
+        r[5] = t; r[6] = u; r[7] = v;
+        r[8] = ray_triangle_flat_e(o, d, a, e1, e2, t, u, v) ? 1.0f : 0.0f;
+        r[9] = t; r[10] = u; r[11] = v;
+    }
+}
+
+void launch_debug_pairs(int fn, const float *rays, const float *geom, float *out, size_t n, hipStream_t s)
+{
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fn, rays, geom, out, n);
+}
+
 __global__ void __launch_bounds__(256) k_debug_math(int fn, const float *__restrict__ a,
                                                     const float *__restrict__ b, float *__restrict__ out, size_t n)
 {
@@ -3438,34 +3495,21 @@ __global__ void __launch_bounds__(64) k_aov(const AovLaunch A)
 // DYNAMIC shared memory of exactly `entries` x 256 B: the order-independent worst case of the node stack that the context computed for
 // this tree's wide packets, plus the leaf list -- residency goes by the tree (160 KiB / that per CU), not by the 64 entries of the abort.
 constexpr int AOV_LCAP = 8;
-__global__ void __launch_bounds__(64) k_aov_cull(const AovLaunch A, const int ENTRIES, const int leaf_min)
+// The walk itself, from the ray preparation to empty stacks, for ONE lane of a wave whose 64 lanes all call it (the loop ballots): `stack` is
+// the lane's LDS column, `active` false for a lane without a ray (it votes and does nothing).  Leaves the closest hit in `best`.  COUNT (the
+// probe kernel, k_debug_intersect_cull): the lane's node steps and the parked leaves whose own box passed -- the triangles the reference
+// tests too -- are counted; k_aov_cull compiles without them.
+template <bool COUNT>
+PT_DEV void first_hit_cull(const SceneRefs &sc, const f3 &o, const f3 &d, const bool active, uint32_t *const stack, const int ENTRIES,
+                           const int leaf_min, Best &best, uint32_t &node_steps, uint32_t &leaves_passed)
 {
-    extern __shared__ uint32_t stack_lds[];
     const int NCAP = ENTRIES - AOV_LCAP;
-    const SceneRefs &sc = A.scene;
-    const int lane = threadIdx.x;
-    uint32_t *const stack = stack_lds + lane;
-    const int tiles_x = (A.tile.tex_w + 7) >> 3;
-    const int tile_y = (int)blockIdx.x / tiles_x, tile_x = (int)blockIdx.x - tile_y * tiles_x;
-    const int gx = tile_x * 8 + (lane & 7);
-    const int ly = tile_y * 8 + (lane >> 3);
-    const bool texel = gx < A.tile.tex_w && ly < A.tile.local_rows;
-    const int gy = local_to_global_row(ly, A.tile);
-    // raytrace.wgsl:425-427
-    const bool inside = texel && gy < A.tile.tex_h && (uint32_t)gx < (uint32_t)A.un.res_x && (uint32_t)gy < (uint32_t)A.un.res_y;
-    const f3 o = F3(A.un.cam_pos[0], A.un.cam_pos[1], A.un.cam_pos[2]);
-    f3 d = F3(0.0f, 0.0f, 0.0f);
-    Best best;
     best.t = PT_INF; best.u = 0.0f; best.v = 0.0f; best.tri = -1;
     int sp = 0, nl = 0;
     RayPre pre;
     pre.ix = pre.iy = pre.iz = 0.0f; pre.flags = 8u;
     float cull_ka = __builtin_inff(), cull_kb = __builtin_inff();
-    if (inside) {
-        const float uvx = (float)gx / A.un.res_x;            // getUv, :247-250
-        const float uvy = (float)gy / A.un.res_y;
-        const CameraFrame cf = camera_frame(A.un);           // (wave-uniform)
-        d = camera_direction(cf, A.un.aspect, uvx, uvy);
+    if (active) {
         // (a ray with a NaN hits nothing in the reference -- every acceptance test of raytrace.wgsl:78-116 is false -- the known answer, as
         // in the shipped culling walks)
         const bool nan_ray = !(d.x == d.x) || !(d.y == d.y) || !(d.z == d.z) || !(o.x == o.x) || !(o.y == o.y) || !(o.z == o.z);
@@ -3498,12 +3542,14 @@ __global__ void __launch_bounds__(64) k_aov_cull(const AovLaunch A, const int EN
                 float t, u, v;
                 const bool inbox = leaf_box_hit(o, d, pre, __float_as_uint(pd.w) != 0u, F3(pc.y, pc.z, pc.w), F3(pd.x, pd.y, pd.z));
                 const bool hit = ray_triangle_flat_e(o, d, F3(pa.x, pa.y, pa.z), F3(pa.w, pb.x, pb.y), F3(pb.z, pb.w, pc.x), t, u, v) && inbox;
+                if constexpr (COUNT) leaves_passed += inbox ? 1u : 0u;
                 bool take = hit && t < best.t;
                 if (hit && t == best.t && best.tri >= 0) take = sc.leaf_rank[ti] < sc.leaf_rank[best.tri];      // the earlier leaf of the reference order wins
                 best.t = take ? t : best.t; best.u = take ? u : best.u; best.v = take ? v : best.v;
                 best.tri = take ? (int32_t)ti : best.tri;
             }
         } else if (has_node) {
+            if constexpr (COUNT) node_steps++;
             sp--;
             const uint32_t ref = stack[sp * 64];
             const float4 *P = sc.cwide + (size_t)ref * 4;
@@ -3576,7 +3622,77 @@ __global__ void __launch_bounds__(64) k_aov_cull(const AovLaunch A, const int EN
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(64) k_aov_cull(const AovLaunch A, const int ENTRIES, const int leaf_min)
+{
+    extern __shared__ uint32_t stack_lds[];
+    const int lane = threadIdx.x;
+    const int tiles_x = (A.tile.tex_w + 7) >> 3;
+    const int tile_y = (int)blockIdx.x / tiles_x, tile_x = (int)blockIdx.x - tile_y * tiles_x;
+    const int gx = tile_x * 8 + (lane & 7);
+    const int ly = tile_y * 8 + (lane >> 3);
+    const bool texel = gx < A.tile.tex_w && ly < A.tile.local_rows;
+    const int gy = local_to_global_row(ly, A.tile);
+    // raytrace.wgsl:425-427
+    const bool inside = texel && gy < A.tile.tex_h && (uint32_t)gx < (uint32_t)A.un.res_x && (uint32_t)gy < (uint32_t)A.un.res_y;
+    const f3 o = F3(A.un.cam_pos[0], A.un.cam_pos[1], A.un.cam_pos[2]);
+    f3 d = F3(0.0f, 0.0f, 0.0f);
+    if (inside) {
+        const float uvx = (float)gx / A.un.res_x;            // getUv, :247-250
+        const float uvy = (float)gy / A.un.res_y;
+        const CameraFrame cf = camera_frame(A.un);           // (wave-uniform)
+        d = camera_direction(cf, A.un.aspect, uvx, uvy);
+    }
+    Best best;
+    uint32_t node_steps = 0, leaves_passed = 0;      // (not counted here)
+    first_hit_cull<false>(A.scene, o, d, inside, stack_lds + lane, ENTRIES, leaf_min, best, node_steps, leaves_passed);
     if (texel) aov_store(A, (size_t)ly * A.tile.tex_w + gx, o, d, best);
+}
+
+// The same walk on rays from memory (include/mi3pt.h: mi3pt_debug_intersect_shipped), 64 per block: every lane of the wave enters the loop --
+// it ballots --, the lanes beyond n without a ray.  k_debug_intersect's 12 floats; slots 9 / 10: the lane's node steps and the leaves whose
+// own box passed, slot 11: 0.
+__global__ void __launch_bounds__(64) k_debug_intersect_cull(const SceneRefs sc, const float *__restrict__ rays, size_t n,
+                                                             float *__restrict__ out, const int ENTRIES, const int leaf_min)
+{
+    extern __shared__ uint32_t stack_lds[];
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const bool active = i < n;
+    f3 o = F3(0.0f, 0.0f, 0.0f), d = F3(0.0f, 0.0f, 0.0f);
+    if (active) {
+        o = F3(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
+        d = F3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+    }
+    Best best;
+    uint32_t node_steps = 0, leaves_passed = 0;
+    first_hit_cull<true>(sc, o, d, active, stack_lds + threadIdx.x, ENTRIES, leaf_min, best, node_steps, leaves_passed);
+    if (!active) return;
+    float *r = out + i * 12;
+    f3 position = F3(0.0f, 0.0f, 0.0f), normal = F3(0.0f, 0.0f, 0.0f);
+    int32_t mi = -1;
+    if (best.tri >= 0) finish_hit(sc, o, d, best, position, normal, mi);
+    r[0] = best.tri >= 0 ? 1.0f : 0.0f;
+    r[1] = best.t;
+    r[2] = position.x; r[3] = position.y; r[4] = position.z;
+    r[5] = normal.x; r[6] = normal.y; r[7] = normal.z;
+    r[8] = (float)mi;
+    r[9] = (float)node_steps; r[10] = (float)leaves_passed; r[11] = 0.0f;
+}
+
+// the LDS column of the first-hit walk: the node stack's worst case on this tree plus the leaf list
+static int aov_cull_entries(int stack_worst)
+{
+    return (stack_worst < 1 ? 1 : (stack_worst > SM_CULL_STACK_MAX ? SM_CULL_STACK_MAX : stack_worst)) + AOV_LCAP;
+}
+
+void launch_debug_intersect_cull(const SceneRefs &scene, const float *rays, size_t n, float *out, int stack_worst, int leaf_min,
+                                 hipStream_t s)
+{
+    if (n == 0) return;
+    const int entries = aov_cull_entries(stack_worst);
+    hipLaunchKernelGGL(k_debug_intersect_cull, dim3((unsigned)((n + 63) / 64)), dim3(64), (size_t)entries * 256, s, scene, rays, n, out,
+                       entries, leaf_min < 1 ? 1 : leaf_min);
 }
 
 void launch_aovs(const AovLaunch &A, int walk, int stack_worst, int leaf_min, hipStream_t s)
@@ -3585,7 +3701,7 @@ void launch_aovs(const AovLaunch &A, int walk, int stack_worst, int leaf_min, hi
     if (tiles <= 0) return;
     const dim3 grid((unsigned)tiles), block(64);
     if (walk == 13 && A.scene.cwide && A.scene.tripk64 && A.scene.leaf_rank) {
-        const int entries = (stack_worst < 1 ? 1 : (stack_worst > SM_CULL_STACK_MAX ? SM_CULL_STACK_MAX : stack_worst)) + AOV_LCAP;
+        const int entries = aov_cull_entries(stack_worst);
         hipLaunchKernelGGL(k_aov_cull, grid, block, (size_t)entries * 256, s, A, entries, leaf_min < 1 ? 1 : leaf_min);
     }
     else if (walk == 1) hipLaunchKernelGGL((k_aov<1, PT_MAX_STACK>), grid, block, 0, s, A);

@@ -45,7 +45,7 @@ SYMBOLS = (
     "mi3pt_pass_time_us", "mi3pt_raytrace_launch_stats", "mi3pt_get_counters", "mi3pt_reset_counters", "mi3pt_set_kernel_variant",
     "mi3pt_set_env_sampling", "mi3pt_device_build_bvh",
     "mi3pt_set_pipelining", "mi3pt_flush", "mi3pt_set_present_mode", "mi3pt_raytrace_launch_span", "mi3pt_batch_capacity", "mi3pt_debug_active_variant", "mi3pt_debug_last_launch", "mi3pt_submit_frames", "mi3pt_debug_set_packet_layout",
-    "mi3pt_debug_intersect", "mi3pt_debug_math", "mi3pt_debug_wave_times", "mi3pt_host_build_bvh", "mi3pt_host_build_bvh_f64",
+    "mi3pt_debug_intersect", "mi3pt_debug_intersect_shipped", "mi3pt_debug_pairs", "mi3pt_debug_math", "mi3pt_debug_wave_times", "mi3pt_host_build_bvh", "mi3pt_host_build_bvh_f64",
     "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_host_scene_compile", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
     "mi3pt_create_group", "mi3pt_group_size", "mi3pt_group_member",
     "mi3pt_tile_global_row", "mi3pt_tile_owner",
@@ -121,6 +121,8 @@ def load_library(path=None):
     lib.mi3pt_reset_counters.argtypes = [c_void_p]
     lib.mi3pt_debug_intersect.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mi3pt_debug_math.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_debug_intersect_shipped.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mi3pt_debug_pairs.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
     lib.mi3pt_device_build_bvh.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.mi3pt_debug_wave_times.argtypes = [c_void_p, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
     lib.mi3pt_host_build_bvh.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_int]
@@ -489,6 +491,23 @@ class Context:
         r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         out = np.empty((len(r), 12), np.float32)
         self._c(self.lib.mi3pt_debug_intersect(self.handle, _ptr(r), len(r), _ptr(out)))
+        return out
+
+    def debug_intersect_shipped(self, rays):
+        """debug_intersect's 12 floats per ray from the shipped first-hit walk (slots 9 / 10: node steps, leaves whose own box passed);
+        Mi3ptError (state) where mi3pt_render_aovs would not run that walk."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.empty((len(r), 12), np.float32)
+        self._c(self.lib.mi3pt_debug_intersect_shipped(self.handle, _ptr(r), len(r), _ptr(out)))
+        return out
+
+    def debug_pairs(self, fn, rays, geom):
+        """The kernels' box (fn 0, geom n x 7: min, max, box_unsafe) / triangle (fn 1, geom n x 9: a, b, c) decisions per pair: n x 12
+        (include/mi3pt.h: mi3pt_debug_pairs)."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        g = np.ascontiguousarray(geom, np.float32).reshape(len(r), 7 if fn == 0 else 9)
+        out = np.empty((len(r), 12), np.float32)
+        self._c(self.lib.mi3pt_debug_pairs(self.handle, fn, _ptr(r), _ptr(g), _ptr(out), len(r)))
         return out
 
     def enable_wave_times(self, enabled=True):
