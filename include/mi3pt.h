@@ -48,7 +48,8 @@ extern "C" {
 /* 4 (round 6): mi3pt_set_rows and mi3pt_measure_tile_cost are GONE (contiguous cost-balanced bands: measured 7 % slower than the dealt
  * 8-row blocks in round 4 and kept since as dead surface); mi3pt_set_kernel_variant accepts 14 (the eight-wide walk: an option).
  * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31); mi3pt_host_scene_compile;
- * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3). */
+ * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3); mi3pt_denoise_guided, mi3pt_read_guided,
+ * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4). */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -74,8 +75,10 @@ typedef enum mi3pt_pass {
     MI3PT_PASS_RAYTRACE = 0,
     MI3PT_PASS_ACCUMULATE = 1,
     MI3PT_PASS_FULLSCREEN = 2,
-    MI3PT_PASS_AOV = 3           /* -- no counterpart: the first-hit feature images (mi3pt_render_aovs).  Known to
+    MI3PT_PASS_AOV = 3,          /* -- no counterpart: the first-hit feature images (mi3pt_render_aovs).  Known to
                                     mi3pt_pass_time_us only; it has no uniform block (mi3pt_set_uniforms refuses it) */
+    MI3PT_PASS_GUIDED = 4        /* -- no counterpart: the feature-guided de-noise (mi3pt_denoise_guided), pack kernel and every level.
+                                    Known to mi3pt_pass_time_us only */
 } mi3pt_pass;
 
 #define MI3PT_SUBMIT_RAYTRACE 1u
@@ -275,6 +278,48 @@ int mi3pt_batch_capacity(mi3pt_ctx *ctx, int *frames);
 int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask);
 int mi3pt_read_aov(mi3pt_ctx *ctx, int which /* mi3pt_aov */, void *dst, size_t nbytes);
 int mi3pt_aov_device_ptr(mi3pt_ctx *ctx, int which /* mi3pt_aov */, void **dev_ptr, size_t *nbytes);
+
+/* ---- feature-guided de-noise of the running mean -- no counterpart in the reference (its only de-noiser is the colour-only bilateral of
+ * the fullscreen pass, fullscreen.wgsl:22-71).  An edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) over the accumulation
+ * image, guided by the four feature images of mi3pt_render_aovs.  Pinned arithmetic: fp32, round to nearest even, nothing contracted,
+ * correctly rounded division, the library's exp (mi3pt_debug_math fn 4).  Per texel p = (x, y) of the width x rows image:
+ *   c = rgb of MI3PT_TEX_ACCUMULATION, n = NORMAL.xyz, P = POSITION.xyz, a = ALBEDO.rgb, hit = word 2 of IDS;
+ *   inv_X = 1 / (sigma_X * sigma_X) in fp32, and 0 for sigma_X == 0 (the term is off).
+ * Level i = 0 .. levels - 1, step s = 1 << i, inv_c(i) = inv_color * 4^i (sigma_color halves per level); level i reads the output of level
+ * i - 1, level 0 reads c.  Taps q = p + s * (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner, h = [1/16, 1/4, 3/8, 1/4, 1/16].  A tap COUNTS
+ * iff q lies inside [0, width) x [0, rows) and hit(q) == hit(p); for each that counts, in that order:
+ *   dc = c_q - c_p     ec = ((dc.x*dc.x + dc.y*dc.y) + dc.z*dc.z) * inv_c(i)
+ *   dn = n_q - n_p     en = ((dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z) * inv_normal
+ *   da = a_q - a_p     ea = ((da.x*da.x + da.y*da.y) + da.z*da.z) * inv_albedo
+ *   dP = P_q - P_p     pd = (n_p.x*dP.x + n_p.y*dP.y) + n_p.z*dP.z;   ep = (pd * pd) * inv_plane
+ *   w  = exp(-(((ec + en) + ea) + ep)) * (h[dx] * h[dy])
+ *   den = den + w;   num.k = num.k + w * c_q.k      (k = r, g, b; both start at 0)
+ * Output: (num.r / den, num.g / den, num.b / den, c_p.w).  The centre tap always counts with w = 9/64, so den > 0 for finite inputs.
+ * NON-FINITE inputs (texels, features, or a sigma so small that 1 / (sigma * sigma) overflows) give unspecified values; they neither hang
+ * nor fault.
+ * mi3pt_denoise_guided filters the running mean as mi3pt_read_texture(MI3PT_TEX_ACCUMULATION) would return it at the call -- frames still
+ * queued are launched first, as for a read-back -- and the four feature images as they stand; asynchronous and stream ordered after that:
+ * one small pack kernel and one launch per level on the context's stream, between two images the context allocates at the first call and
+ * frees at mi3pt_resize / mi3pt_destroy.  It changes neither the accumulation image, nor the feature images, nor any counter; sample frames
+ * submitted afterwards accumulate as if it had not been called.  With MI3PT_GUIDED_PRESENT the canvas is then drawn from the FILTERED image
+ * by the fullscreen pass with its current uniforms, `denoise` taken as 0 (tone-map, scaling, RGBA8 as they are).
+ *   MI3PT_ERR_STATE before mi3pt_resize; unless all four feature images have been rendered since the last resize; for a context whose tile
+ *   is not the whole image (mi3pt_set_tile with more than one rank) and for a device group: five levels reach 32 rows up and down, the halo
+ *   exchange is NOT BUILT -- gather into a 1-rank context (mi3pt_write_texture) and filter there.
+ *   MI3PT_ERR_INVALID for levels outside 1 .. 5, a negative or non-finite sigma, unknown flag bits, a null pointer.
+ * mi3pt_read_guided (blocking) copies the filtered image to dst: nbytes = rows x width x 16.  mi3pt_guided_device_ptr hands out the device
+ * image (zero copy; valid until the next mi3pt_denoise_guided or mi3pt_resize; order your reads behind the context's stream or call
+ * mi3pt_sync first).  Both: MI3PT_ERR_STATE before the first filter since the last resize, MI3PT_ERR_INVALID for a null pointer / a wrong
+ * nbytes.  With timing enabled, mi3pt_pass_time_us(MI3PT_PASS_GUIDED) is the device time of the most recent filter (without the draw). ---- */
+typedef struct mi3pt_guided_params {
+    int levels;                  /* 1 .. 5 */
+    float sigma_color, sigma_normal, sigma_albedo, sigma_plane;   /* finite, >= 0; 0 = term off */
+    unsigned flags;              /* MI3PT_GUIDED_* */
+} mi3pt_guided_params;
+#define MI3PT_GUIDED_PRESENT 1u
+int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *params);
+int mi3pt_read_guided(mi3pt_ctx *ctx, void *dst, size_t nbytes);
+int mi3pt_guided_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes);
 
 /* ---- read-back (the capability a headless drop-in needs; the reference only has
  * canvas.toDataURL, main.ts:351-356).  Blocking.  dst holds rows x width x 4 floats

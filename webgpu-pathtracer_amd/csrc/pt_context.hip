@@ -273,6 +273,13 @@ struct mi3pt_ctx {
     bool aov_valid[MI3PT_AOV_COUNT] = {};
     hipEvent_t ev_aov[2] = {};           // created with the first timed call
     bool ev_aov_recorded = false;
+    // The feature-guided de-noise (mi3pt_denoise_guided): two ping-pong images and the packed normal + hit records, each local_rows x width
+    // x 16 B, allocated by the first call and freed with the textures; guided_result: the image the last level wrote (null: no filter since
+    // the last resize).
+    float4 *d_guided[2] = {}, *d_guided_nh = nullptr;
+    const float4 *guided_result = nullptr;
+    hipEvent_t ev_guided[2] = {};        // created with the first timed call
+    bool ev_guided_recorded = false;
     int walk_stack_worst = 64;           // mi3pt_upload_bvh: entries the reference walk's stack can hold at most on this tree (64: unknown, or the abort can fire)
     int wide_stack_worst = 64;           // prepare_cull: the wide walks' node stack, order-independent worst case (internal packets only; <= SM_CULL_STACK_MAX where wide_ok)
 };
@@ -652,6 +659,11 @@ static void free_textures(mi3pt_ctx *ctx)
         ctx->aov_valid[k] = false;
     }
     ctx->ev_aov_recorded = false;
+    for (void *p : { (void *)ctx->d_guided[0], (void *)ctx->d_guided[1], (void *)ctx->d_guided_nh })
+        if (p) (void)hipFree(p);
+    ctx->d_guided[0] = ctx->d_guided[1] = ctx->d_guided_nh = nullptr;
+    ctx->guided_result = nullptr;
+    ctx->ev_guided_recorded = false;
 }
 
 extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
@@ -695,6 +707,8 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     if (ctx->main_mark) (void)hipEventDestroy(ctx->main_mark);
     for (int k = 0; k < 2; k++)
         if (ctx->ev_aov[k]) (void)hipEventDestroy(ctx->ev_aov[k]);
+    for (int k = 0; k < 2; k++)
+        if (ctx->ev_guided[k]) (void)hipEventDestroy(ctx->ev_guided[k]);
     if (ctx->ev_span_start) (void)hipEventDestroy(ctx->ev_span_start);
     if (ctx->cost_event) (void)hipEventDestroy(ctx->cost_event);
     for (int k = 0; k < 2; k++)
@@ -2366,6 +2380,98 @@ extern "C" int mi3pt_aov_device_ptr(mi3pt_ctx *ctx, int which, void **dev_ptr, s
     return MI3PT_OK;
 }
 
+// ---- the feature-guided a-trous de-noise of the running mean (include/mi3pt.h: mi3pt_denoise_guided; pt_guided.hip) ----
+// 1 / (sigma * sigma) in fp32; a sigma of 0 switches its term off
+static float guided_inv(float sigma) { return sigma == 0.0f ? 0.0f : 1.0f / (sigma * sigma); }
+
+extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *params)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_denoise_guided: not built for a device group (the members would have to exchange a 32-row halo)"));
+    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (params->levels < 1 || params->levels > 5) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: levels must be 1 .. 5");
+    for (float sigma : { params->sigma_color, params->sigma_normal, params->sigma_albedo, params->sigma_plane })
+        if (!(sigma >= 0.0f) || std::isinf(sigma)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: every sigma must be finite and >= 0");
+    if (params->flags & ~MI3PT_GUIDED_PRESENT) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: unknown flag bits");
+    if (int rc = require_ctx(ctx)) return rc;
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided before resize");
+    if (ctx->partial())
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided needs the whole image: not built for a rank of a tile split (a 32-row halo would have to be exchanged)");
+    for (int k = 0; k < MI3PT_AOV_COUNT; k++)
+        if (!ctx->aov_valid[k] || !ctx->d_aov[k])
+            return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided: the four feature images have not all been rendered since the last resize (mi3pt_render_aovs)");
+    if (int rc = flush_pending(ctx)) return rc;      // the mean a read-back would return now: the accumulate passes run on this stream
+    const size_t texels = (size_t)ctx->local_rows * ctx->width, tex_bytes = texels * 16;
+    for (float4 **p : { &ctx->d_guided[0], &ctx->d_guided[1], &ctx->d_guided_nh })
+        if (!*p) HIP_TRY(hipMalloc((void **)p, tex_bytes ? tex_bytes : 16));
+    pt::GuidedLaunch G;
+    G.normal_hit = ctx->d_guided_nh; G.position = ctx->d_aov[MI3PT_AOV_POSITION]; G.albedo = ctx->d_aov[MI3PT_AOV_ALBEDO];
+    G.width = ctx->width; G.rows = ctx->local_rows;
+    G.inv_color = guided_inv(params->sigma_color); G.inv_normal = guided_inv(params->sigma_normal);
+    G.inv_albedo = guided_inv(params->sigma_albedo); G.inv_plane = guided_inv(params->sigma_plane);
+    if (ctx->timing) {
+        for (int k = 0; k < 2; k++)
+            if (!ctx->ev_guided[k]) HIP_TRY(hipEventCreate(&ctx->ev_guided[k]));
+        HIP_TRY(hipEventRecord(ctx->ev_guided[0], ctx->stream));
+    }
+    pt::launch_guided_pack(ctx->d_aov[MI3PT_AOV_NORMAL], ctx->d_aov[MI3PT_AOV_IDS], ctx->d_guided_nh, texels, ctx->stream);
+    const float4 *src = ctx->d_accum;
+    for (int level = 0; level < params->levels; level++) {
+        float4 *dst = ctx->d_guided[level & 1];
+        pt::launch_guided_level(G, src, dst, level, ctx->stream);
+        src = dst;
+    }
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev_guided[1], ctx->stream)); ctx->ev_guided_recorded = true; }
+    ctx->guided_result = src;
+    if (params->flags & MI3PT_GUIDED_PRESENT) {
+        // the fullscreen pass on the filtered image, with the pass's uniforms as they are and its own de-noiser off.  The canvas then shows
+        // no state of the running mean: the next fullscreen submit draws again whatever it showed before, and a draw still owed to queued
+        // frames (MI3PT_PRESENT_LATEST) is dropped -- those frames are in the mean this call filtered.
+        pt::FsUniforms fs;
+        const uint8_t *u_fs = ctx->u_fs;
+        fs.res_x = ldf(u_fs, 0); fs.res_y = ldf(u_fs, 4); fs.aspect = ldf(u_fs, 8);
+        fs.scaling = ldf(u_fs, 12); fs.denoise = 0u; fs.tonemapping = ldu(u_fs, 20);
+        pt::launch_fullscreen(fs, src, ctx->width, ctx->height, ctx->width, ctx->height, ctx->d_fs_taps, true, ctx->d_canvas, ctx->d_canvas8, ctx->stream);
+        HIP_TRY(hipGetLastError());
+        ctx->presented_version = 0;
+        ctx->want_present = false;
+    }
+    return MI3PT_OK;
+}
+
+static int guided_image(mi3pt_ctx *ctx, const char *what)
+{
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
+    if (!ctx->guided_result) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": nothing has been filtered since the last resize (mi3pt_denoise_guided)");
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_read_guided(mi3pt_ctx *ctx, void *dst, size_t nbytes)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_read_guided: mi3pt_denoise_guided is not built for a device group"));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = guided_image(ctx, "mi3pt_read_guided")) return rc;
+    const size_t need = (size_t)ctx->local_rows * ctx->width * 16;
+    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
+    if (need == 0) return MI3PT_OK;
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
+    HIP_TRY(hipMemcpyAsync(dst, ctx->guided_result, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_guided_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_guided_device_ptr: mi3pt_denoise_guided is not built for a device group"));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = guided_image(ctx, "mi3pt_guided_device_ptr")) return rc;
+    *dev_ptr = const_cast<float4 *>(ctx->guided_result);
+    if (nbytes) *nbytes = (size_t)ctx->local_rows * ctx->width * 16;
+    return MI3PT_OK;
+}
+
 extern "C" int mi3pt_enable_timing(mi3pt_ctx *ctx, int enabled)
 {
     PT_GROUP_ALL(ctx, true, mi3pt_enable_timing(m, enabled));
@@ -2383,6 +2489,14 @@ extern "C" int mi3pt_pass_time_us(mi3pt_ctx *ctx, int pass, float *microseconds)
         HIP_TRY(ctx_event_sync(ctx, ctx->ev_aov[1]));
         float ms = 0.0f;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_aov[0], ctx->ev_aov[1]));
+        *microseconds = ms * 1000.0f;
+        return MI3PT_OK;
+    }
+    if (microseconds && pass == MI3PT_PASS_GUIDED) {
+        if (!ctx->ev_guided_recorded) return pt_set_error(MI3PT_ERR_STATE, "no timed mi3pt_denoise_guided since the last resize");
+        HIP_TRY(ctx_event_sync(ctx, ctx->ev_guided[1]));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_guided[0], ctx->ev_guided[1]));
         *microseconds = ms * 1000.0f;
         return MI3PT_OK;
     }

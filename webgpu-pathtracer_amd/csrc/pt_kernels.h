@@ -346,6 +346,16 @@ struct AovLaunch {
 // 13 = first hit only on the shipped walk's compressed wide packets, near first, with distance culling (needs scene.cwide,
 // scene.tripk64, the culling constants); stack_worst: entries that walk's (node) stack can hold at most on this tree (64 = unknown)
 void launch_aovs(const AovLaunch &A, int walk, int stack_worst, int leaf_min, hipStream_t s);      // (leaf_min: walk 13's triangle-step vote)
+// The feature-guided a-trous de-noise (include/mi3pt.h: mi3pt_denoise_guided; pt_guided.hip).  normal_hit: launch_guided_pack's records
+// (normal.xyz, word 2 of the ids image); position / albedo: the feature images themselves; inv_*: 1 / (sigma * sigma), 0 = term off.
+struct GuidedLaunch {
+    const float4 *normal_hit, *position, *albedo;
+    int32_t width, rows;
+    float inv_color, inv_normal, inv_albedo, inv_plane;
+};
+void launch_guided_pack(const float4 *normal, const float4 *ids, float4 *out, size_t texels, hipStream_t s);
+// level `level` (step 1 << level, inv_color x 4^level) from src into dst, both rows x width
+void launch_guided_level(const GuidedLaunch &G, const float4 *src, float4 *dst, int level, hipStream_t s);
 // packs the three position vectors of `ntris` 112-byte triangle records into 48-byte rows (the context's cull analysis)
 void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipStream_t s);
 // writes NodePacket::cull of `npackets` packets from a dense array (the context's cull analysis)

@@ -409,6 +409,42 @@ napi_value ReadAov(napi_env env, napi_callback_info info)
     return ta;
 }
 
+// denoiseGuided(ctx, levels, sigmaColor, sigmaNormal, sigmaAlbedo, sigmaPlane, flags): mi3pt_denoise_guided; asynchronous
+napi_value DenoiseGuided(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t levels, flags;
+    double sigma[4];
+    if (!get_args(env, info, a, 7) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &levels) || !get_i32(env, a.v[6], &flags)) return nullptr;
+    for (int k = 0; k < 4; k++)
+        if (napi_get_value_double(env, a.v[2 + k], &sigma[k]) != napi_ok) {
+            napi_throw_type_error(env, nullptr, "expected a number");
+            return nullptr;
+        }
+    mi3pt_guided_params p;
+    p.levels = levels;
+    p.sigma_color = (float)sigma[0]; p.sigma_normal = (float)sigma[1]; p.sigma_albedo = (float)sigma[2]; p.sigma_plane = (float)sigma[3];
+    p.flags = (unsigned)flags;
+    MI3PT_TRY(mi3pt_denoise_guided(ctx, &p));
+    return undefined(env);
+}
+
+// readGuided(ctx, ntexels) -> Float32Array of ntexels x 4: the filtered image of the last denoiseGuided
+napi_value ReadGuided(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t ntexels;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &ntexels) || ntexels < 0) return nullptr;
+    void *data = nullptr;
+    napi_value ab, ta;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)ntexels * 16, &data, &ab));
+    MI3PT_TRY(mi3pt_read_guided(ctx, data, (size_t)ntexels * 16));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, (size_t)ntexels * 4, ab, 0, &ta));
+    return ta;
+}
+
 // writeTexture(ctx, which, Float32Array) : GPUQueue.writeTexture for the HDR images
 napi_value WriteTexture(napi_env env, napi_callback_info info)
 {
@@ -603,6 +639,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "resetCounters", ResetCounters }, { "hostBuildBvhF64", HostBuildBvhF64 }, { "hostBuildBvh", HostBuildBvh },
         { "hostEnvCdf", HostEnvCdf }, { "setPipelining", SetPipelining }, { "setPresentMode", SetPresentMode }, { "setEnvSampling", SetEnvSampling }, { "deviceBuildBvh", DeviceBuildBvh }, { "writeTexture", WriteTexture },
         { "raytraceLaunchStats", RaytraceLaunchStats }, { "renderAovs", RenderAovs }, { "readAov", ReadAov },
+        { "denoiseGuided", DenoiseGuided }, { "readGuided", ReadGuided },
     };
     for (const auto &f : fns) {
         napi_value v;

@@ -119,6 +119,12 @@ export class Renderer {
   /** localRows x width x 4, row 0 = bottom: albedo rgb 1 | normal xyz 0 | position xyz t | (Int32Array) triangle, material, hit, 0 */
   readAov(name: 'albedo' | 'normal' | 'position'): Float32Array;
   readAov(name: 'ids'): Int32Array;
+  /** feature-guided a-trous de-noise of the running mean (include/mi3pt.h: mi3pt_denoise_guided); renders the feature images itself when
+   *  none are current.  sigmaColor null: 2 / sqrt(frames in the mean).  present: also draw the canvas from the filtered image */
+  denoiseGuided(options?: { levels?: number; sigmaColor?: number | null; sigmaNormal?: number; sigmaAlbedo?: number; sigmaPlane?: number;
+    present?: boolean }): void;
+  /** localRows x width x 4, row 0 = bottom: the filtered image of the last denoiseGuided */
+  readGuided(): Float32Array;
   counters(): { rays: number; boxTests: number; triTests: number; hits: number; misses: number; stackOverflows: number; pixels: number };
   /** src/main.ts:351-356: the presented canvas as PNG bytes (written to `file` when given) */
   screenshot(file?: string): Buffer;

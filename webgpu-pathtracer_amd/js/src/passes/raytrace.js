@@ -132,6 +132,7 @@ class RaytracePass extends Pass {
     }
     native.uploadMaterials(handle, packed.materialBytes);
     scene.needsUpdate = false;
+    this.renderer._sceneVersion++;
     this.stats = { Triangles: flat.triangles.length, Materials: flat.materials.length, 'BVH Nodes': nodeBytes.length / 48 };
     if (this.renderer.options.verbose) console.table(this.stats);                     // raytrace.ts:528-532
   }

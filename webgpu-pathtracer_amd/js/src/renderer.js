@@ -49,6 +49,8 @@ class Renderer {
     this.samplesPerFrame = 1;
     this.status = 'idle';
     this.listeners = new Map();
+    this._sceneVersion = 0;      // scene uploads so far; with the camera and the size: what the feature images depend on
+    this._aovKey = null;         // ... as they were when all four feature images were last rendered (denoiseGuided)
     this.tile = args.tile || { rank: 0, nranks: 1, blockRows: 8 };
     if (this.options.enableTimestampQuery) this.native.enableTiming(this.handle, 1);
     this.passes = {
@@ -105,6 +107,7 @@ class Renderer {
     this._width = width;
     this._height = height;
     this.native.resize(this.handle, width, height);
+    this._aovKey = null;                         // (a resize frees the feature images)
     this.reset();
     this.emit('resize');
   }
@@ -212,7 +215,29 @@ class Renderer {
     }
     this.passes.raytrace.update();               // resolution / aspect as render() would send them
     this.native.renderAovs(this.handle, mask);
+    if (mask === 15) this._aovKey = this._aovKeyNow();
+    else if (this._aovKey !== this._aovKeyNow()) this._aovKey = null;      // (some images are of another view now)
   }
+  // what a feature image depends on: resolution, aspect, camera position / direction / fov (include/mi3pt.h), scene, size
+  _aovKeyNow() {
+    const u = Buffer.from(this.passes.raytrace.uniforms.bytes.buffer, this.passes.raytrace.uniforms.bytes.byteOffset, 96);
+    return [u.toString('hex', 0, 12), u.toString('hex', 32, 44), u.toString('hex', 48, 64), this._sceneVersion, this._width, this._height].join(':');
+  }
+  // ---- feature-guided de-noise of the running mean (no counterpart in the reference): the edge-avoiding a-trous filter of
+  // include/mi3pt.h (mi3pt_denoise_guided).  readGuided() returns the result; present: also draw the canvas from it.  sigmaColor
+  // undefined / null: 2 / sqrt(frames in the mean) -- the noise of the mean falls with the root of its frames.  The feature images are
+  // rendered first unless all four are current for the camera and scene of the last update() at this size.  The accumulation image is
+  // untouched.
+  denoiseGuided(options) {
+    const o = Object.assign({ levels: 3, sigmaColor: null, sigmaNormal: 0.35, sigmaAlbedo: 0.1, sigmaPlane: 0.05, present: false }, options || {});
+    this.passes.raytrace.update();
+    if (this._aovKey === null || this._aovKey !== this._aovKeyNow()) this.renderAovs();
+    const sigmaColor = o.sigmaColor === null || o.sigmaColor === undefined ? 2 / Math.sqrt(Math.max(1, this._frame - 1)) : o.sigmaColor;
+    if (o.present) this.passes.fullscreen.update();
+    this.native.denoiseGuided(this.handle, o.levels, sigmaColor, o.sigmaNormal, o.sigmaAlbedo, o.sigmaPlane, o.present ? 1 : 0);
+  }
+  // localRows x width x 4 floats: the filtered image of the last denoiseGuided; row 0 = bottom of the picture
+  readGuided() { return this.native.readGuided(this.handle, this.localRows * this._width); }
   // localRows x width x 4: Float32Array, Int32Array for 'ids' (triangle, material, hit, 0); row 0 = bottom of the picture
   readAov(name) {
     const k = AOV_NAMES.indexOf(name);

@@ -7,6 +7,8 @@
 //   --devices 0,1,2    a device group: Renderer.create({ devices: [0, 1, 2] }) -- the same loop on several GPUs
 //   --aovs             also the first-hit feature images: <prefix>_albedo.png, <prefix>_normal.png (0.5 n + 0.5) and
 //                      <prefix>_position.f32 (raw RGBA float: position xyz, t; row 0 = bottom)
+//   --guided           also the feature-guided de-noise of the final mean (renderer.denoiseGuided(), default parameters):
+//                      <prefix>_guided.f32 (raw RGBA float; row 0 = bottom) and <prefix>_guided.png (the canvas drawn from it)
 //   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
 //   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
 //                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
@@ -88,6 +90,11 @@ async function main() {
     fs.writeFileSync(out + '_albedo.png', toPng(renderer.readAov('albedo'), (v) => v));
     fs.writeFileSync(out + '_normal.png', toPng(normal, (v, img, s) => (img[s] === 0 && img[s + 1] === 0 && img[s + 2] === 0 ? 0 : 0.5 * v + 0.5)));
     fs.writeFileSync(out + '_position.f32', Buffer.from(renderer.readAov('position').buffer));
+  }
+  if (process.argv.includes('--guided')) {
+    renderer.denoiseGuided({ present: true });
+    fs.writeFileSync(out + '_guided.f32', Buffer.from(renderer.readGuided().buffer));
+    renderer.screenshot(out + '_guided.png');
   }
   const summary = {
     width, height, frames, status: renderer.status, frame: renderer.frame, events,

@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("MI3PT_LIBRARY") or os.path.join(PKG_ROOT, "libmi3pt.s
 
 PASS_RAYTRACE, PASS_ACCUMULATE, PASS_FULLSCREEN = 0, 1, 2
 PASS_AOV = 3          # mi3pt_pass_time_us only: the first-hit feature images have no uniform block
+PASS_GUIDED = 4       # mi3pt_pass_time_us only: the feature-guided de-noise (denoise_guided)
+GUIDED_PRESENT = 1    # mi3pt_guided_params.flags: draw the canvas from the filtered image
 # mi3pt_aov: the first-hit feature images (render_aovs takes an OR of 1 << AOV_*)
 AOV_ALBEDO, AOV_NORMAL, AOV_POSITION, AOV_IDS, AOV_COUNT = 0, 1, 2, 3, 4
 AOV_ALL = (1 << AOV_COUNT) - 1
@@ -50,7 +52,14 @@ SYMBOLS = (
     "mi3pt_create_group", "mi3pt_group_size", "mi3pt_group_member",
     "mi3pt_tile_global_row", "mi3pt_tile_owner",
     "mi3pt_render_aovs", "mi3pt_read_aov", "mi3pt_aov_device_ptr",
+    "mi3pt_denoise_guided", "mi3pt_read_guided", "mi3pt_guided_device_ptr",
 )
+
+
+class GuidedParams(ctypes.Structure):
+    """mi3pt_guided_params"""
+    _fields_ = [("levels", ctypes.c_int), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_albedo", ctypes.c_float), ("sigma_plane", ctypes.c_float), ("flags", ctypes.c_uint)]
 
 
 class Mi3ptError(RuntimeError):
@@ -103,6 +112,9 @@ def load_library(path=None):
     lib.mi3pt_render_aovs.argtypes = [c_void_p, ctypes.c_uint]
     lib.mi3pt_read_aov.argtypes = [c_void_p, c_int, c_void_p, c_size_t]
     lib.mi3pt_aov_device_ptr.argtypes = [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]
+    lib.mi3pt_denoise_guided.argtypes = [c_void_p, ctypes.POINTER(GuidedParams)]
+    lib.mi3pt_read_guided.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_guided_device_ptr.argtypes = [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]
     lib.mi3pt_enable_timing.argtypes = [c_void_p, c_int]
     lib.mi3pt_pass_time_us.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]
     lib.mi3pt_raytrace_launch_stats.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
@@ -423,6 +435,26 @@ class Context:
         the context's stream) before reading it."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         self._c(self.lib.mi3pt_aov_device_ptr(self.handle, int(which), ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def denoise_guided(self, levels=3, sigma_color=1.0, sigma_normal=0.35, sigma_albedo=0.1, sigma_plane=0.05, flags=0):
+        """Filter the running mean (every frame submitted so far) with the feature-guided a-trous filter of include/mi3pt.h;
+        needs all four feature images (render_aovs).  Asynchronous; the accumulation image is untouched.  flags:
+        GUIDED_PRESENT draws the canvas from the filtered image."""
+        p = GuidedParams(int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo), float(sigma_plane), int(flags))
+        self._c(self.lib.mi3pt_denoise_guided(self.handle, ctypes.byref(p)))
+
+    def read_guided(self):
+        """The filtered image of the last denoise_guided as (rows, width, 4) float32."""
+        out = np.empty((self.local_rows, self.width, 4), np.float32)
+        self._c(self.lib.mi3pt_read_guided(self.handle, _ptr(out), out.nbytes))
+        return out
+
+    def guided_device_ptr(self):
+        """(device pointer, bytes) of the filtered image, for zero-copy hand-off; sync() (or order your reads behind the
+        context's stream) before reading it.  Valid until the next denoise_guided or resize."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._c(self.lib.mi3pt_guided_device_ptr(self.handle, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
 
     def bind_accumulation(self, dev_ptr, nbytes):

@@ -126,6 +126,7 @@ class RaytracePass(Pass):
         ctx.upload_triangles(content.triangles)
         ctx.upload_materials(content.material_bytes)
         scene.needsUpdate = False
+        self.renderer._sceneVersion += 1
 
     def render(self, encoder):                    # raytrace.ts:696-708
         encoder.append(capi.SUBMIT_RAYTRACE)
@@ -190,6 +191,8 @@ class Renderer:
         self.status = "idle"
         self.listeners = {}
         self.presentEveryFrame = True      # headless hosts may skip the fullscreen pass
+        self._sceneVersion = 0             # scene uploads so far; with the camera and the size: what the feature images depend on
+        self._aovKey = None                # ... as they were when all four feature images were last rendered (denoiseGuided)
         self.passes = {"raytrace": RaytracePass(self), "accumulate": AccumulatePass(self),
                        "fullscreen": FullscreenPass(self)}
         if self.options["enableTimestampQuery"]:
@@ -226,6 +229,7 @@ class Renderer:
             return
         self._width, self._height = int(width), int(height)
         self.ctx.resize(self._width, self._height)
+        self._aovKey = None                        # (a resize frees the feature images)
         self.reset()
         self.emit("resize")
 
@@ -362,6 +366,35 @@ class Renderer:
             mask |= 1 << capi.AOV_NAMES.index(name)
         self.passes["raytrace"].update()           # resolution / aspect as render() would send them
         self.ctx.render_aovs(mask)
+        if mask == capi.AOV_ALL:
+            self._aovKey = self._aovKeyNow()
+        elif self._aovKey != self._aovKeyNow():
+            self._aovKey = None                    # (some images are of another view now)
+
+    def _aovKeyNow(self):
+        u = self.passes["raytrace"].uniforms.tobytes()
+        # what a feature image depends on: resolution, aspect, camera position / direction / fov (include/mi3pt.h), scene, size
+        return (u[0:12], u[32:44], u[48:64], self._sceneVersion, self._width, self._height)
+
+    # ---- feature-guided de-noise of the running mean (no counterpart in the reference) ----
+    def denoiseGuided(self, levels=3, sigmaColor=None, sigmaNormal=0.35, sigmaAlbedo=0.1, sigmaPlane=0.05, present=False):
+        """Filter the running mean with the edge-avoiding a-trous filter of include/mi3pt.h (mi3pt_denoise_guided); readGuided()
+        returns the result, present=True also draws the canvas from it.  sigmaColor None: 2 / sqrt(frames in the mean) -- the
+        noise of the mean falls with the root of its frames.  The feature images are rendered first unless all four are current
+        for the camera and scene of the last update() at this size.  The accumulation image is untouched."""
+        self.passes["raytrace"].update()
+        if self._aovKey is None or self._aovKey != self._aovKeyNow():
+            self.renderAovs()
+        if sigmaColor is None:
+            sigmaColor = 2.0 / math.sqrt(max(1, self._frame - 1))
+        if present:
+            self.passes["fullscreen"].update()
+        self.ctx.denoise_guided(levels, sigmaColor, sigmaNormal, sigmaAlbedo, sigmaPlane,
+                                capi.GUIDED_PRESENT if present else 0)
+
+    def readGuided(self):
+        """(rows, width, 4) float32: the filtered image of the last denoiseGuided."""
+        return self.ctx.read_guided()
 
     def readAov(self, name):
         """(rows, width, 4) float32 -- int32 for "ids" -- of a feature image rendered by renderAovs."""
