@@ -232,7 +232,19 @@ int mi3pt_set_uniforms(mi3pt_ctx *ctx, int pass /* mi3pt_pass */, const void *by
  * MI3PT_SUBMIT_*; passes run in the reference's order raytrace -> accumulate ->
  * fullscreen (raytrace.ts:696-708, accumulate.ts:154-176, fullscreen.ts:158-177).
  * RAYTRACE|ACCUMULATE in one submit runs as one fused kernel (bit-identical to
- * the two-pass result). ---- */
+ * the two-pass result).
+ * Non-finite and negative radiance is no special case anywhere: NaN, +-inf,
+ * negative and subnormal values that the reference's arithmetic produces --
+ * log(0) in randNormal when rand() returns exactly 0, emission or environment
+ * texels that overflow binary32 (or binary16 under MI3PT_STORAGE_F16), inf * 0
+ * in the throughput, material fields outside [0, 1] or NaN -- are carried
+ * exactly as that arithmetic carries them through the radiance storage, the
+ * running mean and the tone-map; the RGBA8 canvas maps NaN to 0 and clamps the
+ * rest to [0, 255].  The `frame` counters of the raytrace and the accumulate
+ * block are u32 and wrap modulo 2^32; an accumulate `frame` of 0 (or 1)
+ * anywhere, in the middle or at the end of a batch too, has weight 1 and
+ * restarts the mean.  Held to the oracle and to the executed shader on every
+ * kernel variant by tests/test_gpu_shading.py. ---- */
 int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask);
 /* `count` consecutive frames with one call: frame i is submitted with the raytrace and the
  * accumulate uniform `frame` fields at (their current value + i); afterwards both hold current +

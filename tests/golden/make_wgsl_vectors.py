@@ -29,6 +29,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import pt_oracle as orc            # noqa: E402  (pinned math only)
 from oracle import wgsl_interp as wi           # noqa: E402
 from mi3pt_host import layout, scenes          # noqa: E402
+import shading_cases as shading                 # noqa: E402  (tests/: the palette and the forced draws)
 
 F32 = np.float32
 
@@ -383,6 +384,44 @@ def main():
         res.append(img)
         print(f"fullscreen case {denoise, tonemap, scaling} done, {time.time() - t0:.1f} s", flush=True)
     out["fs_cases"], out["fs_out"] = np.array(cases, F32), np.array(res, F32)
+
+    # ------------------------------------------------------------------ raytrace.wgsl at the edges of shading
+    # (tests/shading_cases.py; behind everything else, and without a draw from `rng`, so that the vectors above stay as they are)
+    def bind_scene(sc):
+        rt.res["triangleBuffer"], rt.res["bvhBuffer"] = buffer(rt, "Triangle", sc.triangles), buffer(rt, "BVHNode", sc.nodes)
+        rt.res["materialBuffer"] = buffer(rt, "Material", np.frombuffer(sc.material_bytes.tobytes(), layout.MATERIAL))
+
+    # the 14-material palette: mix weights outside [0, 1], NaN metalness, emission that overflows (a NaN and two inf pixels)
+    bind_scene(shading.palette_scene())
+    lens = dict(aperture=demo.camera["aperture"], focal=demo.camera["focalDistance"])      # the scene's own camera, as ptcommon.rt_uniforms takes it
+    cfg = dict(w=16, h=12, frame=360, bounces=4, **lens)
+    u = set_uniforms(**cfg)
+    tex = wi.Texture(np.zeros((cfg["h"], cfg["w"], 4), F32))
+    rt.res["outputTexture"] = tex
+    for y in range(cfg["h"]):
+        for x in range(cfg["w"]):
+            rt.invoke("computeMain", [vec((x, y, 0), "u")])
+    img = np.zeros((cfg["h"], cfg["w"], 4), F32)
+    for (x, y), v in tex.stores.items():
+        img[y, x] = v
+    out["palette_uniforms"], out["palette_image"] = np.frombuffer(u.tobytes(), np.uint8), img
+    print(f"palette frame done, {time.time() - t0:.1f} s", flush=True)
+
+    # single pixels whose frame counter forces one draw of rand() (shading_cases.FORCED_CASES, in its order): log(0) in randNormal,
+    # a zero jitter radius, angles of 2 pi * 1.0, metalness 0 >= 0.0, metalness 1 >= 1.0
+    for i, name in enumerate(shading.FORCED_CASES):
+        key = f"forced{i}"
+        x, y = shading.FORCED_CASES[name][2]
+        sc = shading.one_material_scene(shading.FORCED_CASES[name][3])
+        bind_scene(sc)
+        u = set_uniforms(w=shading.W, h=shading.H, frame=shading.forced_case_frame(name), bounces=shading.PALETTE_BOUNCES, **lens)
+        tex = wi.Texture(np.zeros((shading.H, shading.W, 4), F32))
+        rt.res["outputTexture"] = tex
+        rt.invoke("computeMain", [vec((x, y, 0), "u")])
+        assert set(tex.stores) == {(x, y)}
+        out[key + "_uniforms"], out[key + "_materials"] = np.frombuffer(u.tobytes(), np.uint8), np.frombuffer(sc.material_bytes.tobytes(), np.uint8).copy()
+        out[key + "_pixel"], out[key + "_value"] = np.array([x, y], np.uint32), np.array(tex.stores[(x, y)], F32)
+    print(f"forced pixels done, {time.time() - t0:.1f} s", flush=True)
 
     np.savez_compressed(out_path, **out)
     print(f"wrote {out_path}: {len(out)} arrays, {os.path.getsize(out_path)} bytes, {time.time() - t0:.1f} s")

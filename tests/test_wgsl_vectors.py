@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import ptcommon as pc
+import shading_cases as sh
 from mi3pt_host import capi, layout, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -150,6 +151,45 @@ def test_dormant_environment_importance_sampling(orc, demo, env, vec):
     assert not bits_equal(plain, want) and cnt["misses"] > 50          # the mode really changes the image
 
 
+def test_palette_frame_matches_the_executed_shader(orc, env, vec):
+    """The 14 materials of tests/shading_cases.py (mix weights outside [0, 1], a NaN metalness, emission that overflows, a
+    throughput of 0 under an infinite emission) through the executed hit branch: one NaN pixel and two with an inf in this frame."""
+    sc = sh.palette_scene()
+    want = vec["palette_image"]
+    h, w = want.shape[:2]
+    got, cnt = orc.raytrace(pc.oracle_scene(orc, sc, env), vec["palette_uniforms"].tobytes(), w, h)
+    assert bits_equal(got, want), first_diff(got, want)
+    stats = sh.image_stats(want)
+    print(f"palette frame as executed: {stats}, {cnt['hits']} hits")
+    assert stats["nan"] >= 1 and stats["inf"] >= 2 and stats["finite_nonzero"] >= 150 and cnt["hits"] > 150
+
+
+def _forced_vectors(vec):
+    """(case name, scene, uniforms, x, y, value as executed) of every forced pixel; the vectors are those of the table as it is now."""
+    for i, name in enumerate(sh.FORCED_CASES):
+        material = sh.FORCED_CASES[name][3]
+        sc = sh.one_material_scene(material)
+        assert vec[f"forced{i}_materials"].tobytes() == sc.material_bytes.tobytes(), name
+        u = vec[f"forced{i}_uniforms"].tobytes()
+        assert u == pc.rt_uniforms(sc, sh.W, sh.H, frame=sh.forced_case_frame(name), bounces=sh.PALETTE_BOUNCES).tobytes(), name
+        x, y = (int(v) for v in vec[f"forced{i}_pixel"])
+        assert (x, y) == sh.FORCED_CASES[name][2]
+        yield name, sc, u, x, y, vec[f"forced{i}_value"]
+    assert f"forced{len(sh.FORCED_CASES)}_value" not in vec.files
+
+
+def test_forced_pixels_match_the_executed_shader(orc, env, vec):
+    """computeMain executed for the one pixel whose draw is forced to exactly 0 or exactly 1: what log(0), an angle of 2 pi * 1.0, a
+    zero radius and `metalness >= rand()` at equality do is the shader's own answer, and the oracle's."""
+    nan = 0
+    for name, sc, u, x, y, want in _forced_vectors(vec):
+        got, _ = orc.raytrace(pc.oracle_scene(orc, sc, env), u, sh.W, sh.H)
+        assert bits_equal(got[y, x], want), (name, got[y, x], want)
+        assert np.isnan(want[:3]).all() == (sh.FORCED_CASES[name][4] == "nan"), (name, want)
+        nan += int(np.isnan(want[:3]).all())
+    assert nan == 4
+
+
 # ---------------------------------------------------------------- accumulate.wgsl
 
 def test_accumulate_pass(orc, vec):
@@ -232,6 +272,24 @@ def test_device_frames_match_the_executed_shader(gpu_ctx, demo, env, vec):
     assert bits_equal(got, want), "importance-sampling frame: " + first_diff(got, want)
     ctx.submit(capi.SUBMIT_RAYTRACE)
     assert not bits_equal(ctx.read_texture(capi.TEX_OUTPUT), want)      # and off again
+    # the palette frame and the forced pixels of tests/shading_cases.py
+    sc = sh.palette_scene()
+    pc.upload_scene(ctx, sc, env)
+    want = vec["palette_image"]
+    h, w = want.shape[:2]
+    ctx.resize(w, h)
+    ctx.set_uniforms(capi.PASS_RAYTRACE, vec["palette_uniforms"].tobytes())
+    ctx.submit(capi.SUBMIT_RAYTRACE)
+    got = ctx.read_texture(capi.TEX_OUTPUT)
+    assert bits_equal(got, want), "palette frame: " + first_diff(got, want)
+    ctx.resize(sh.W, sh.H)
+    for name, sc, u, x, y, want in _forced_vectors(vec):
+        pc.upload_scene(ctx, sc, env)
+        ctx.set_uniforms(capi.PASS_RAYTRACE, u)
+        ctx.submit(capi.SUBMIT_RAYTRACE)
+        got = ctx.read_texture(capi.TEX_OUTPUT)[y, x]
+        assert bits_equal(got, want), (name, got, want)
+    pc.upload_scene(ctx, demo, env)
     tex = vec["fs_input"]
     h, w = tex.shape[:2]
     ctx.resize(w, h)
