@@ -333,6 +333,62 @@ int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *params);
 int mi3pt_read_guided(mi3pt_ctx *ctx, void *dst, size_t nbytes);
 int mi3pt_guided_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes);
 
+/* ---- the moments image: the spread of the frames around the running mean -- no counterpart in the reference (accumulate.wgsl keeps
+ * the mean alone).  Off by default.  While enabled every accumulate step also updates a second image beside the accumulation image:
+ * local_rows x width x 4 fp32 = (M2.r, M2.g, M2.b, n), ALWAYS fp32 whatever mi3pt_set_storage says, rows and tile compaction exactly
+ * those of the accumulation image.  Welford's update written around the reference's own mean -- for every accumulate step of a texel
+ * inside the accumulate block's rectangle (x < resolution.x and gy < resolution.y, accumulate.wgsl:14-16), with c = this frame's
+ * radiance rgb as the step reads it, p = the mean before the step, p' = the mean after it AS STORED (rounded to binary16 under
+ * MI3PT_STORAGE_F16), fp32, nothing contracted, k = r, g, b:
+ *   restart = (frame <= 1) || (enabled != 1)            exactly the steps whose weight is 1 (see mi3pt_submit)
+ *   restart:   M2.k = 0;   n = 1
+ *   otherwise: M2.k = M2.k + (c.k - p.k) * (c.k - p'.k);   n = n + 1
+ * Texels outside the rectangle are not touched.  n is an fp32 count: it stops growing at 2^24 = 16 777 216 steps.  Non-finite radiance
+ * is carried as this arithmetic carries it.  M2.k / (n - 1) is the sample variance of channel k, M2.k / (n (n - 1)) the variance of
+ * its mean -- what MI3PT_GUIDED_VARIANCE steers its colour weight by, and what a headless host needs to decide when to stop sampling.
+ * The mean, every counter and mi3pt_debug_last_launch are bit-identical with moments on and off: the image is kept by moments-keeping
+ * twins of the two accumulate kernels, in the same pass; the per-pixel kernel variants (1 / 2), which otherwise fold the accumulate
+ * pass into the raytrace kernel, run the two passes separately while moments are on (same bits).
+ * mi3pt_set_moments(1) allocates and zeroes the image (a context that never enables it allocates nothing and launches exactly what it
+ * launched before); mi3pt_resize re-allocates and zeroes it while enabled; mi3pt_reset zeroes it; mi3pt_write_texture and
+ * mi3pt_bind_accumulation (binding and un-binding) zero it (a mean that comes from outside has unknown spread -- mi3pt_write_moments
+ * afterwards restores a checkpoint); mi3pt_set_moments(0) and
+ * mi3pt_destroy free it.  Enable, disable and write launch the frame queue first.
+ * mi3pt_read_moments (blocking) copies the image to dst, mi3pt_write_moments loads it from src (checkpoint / resume, like
+ * mi3pt_write_texture): nbytes = rows x width x 16.  mi3pt_moments_device_ptr hands out the device image (zero copy; valid until the
+ * next mi3pt_resize or mi3pt_set_moments; order your reads behind the context's stream or call mi3pt_sync first).
+ *   MI3PT_ERR_STATE for read / write / ptr while disabled or before mi3pt_resize; MI3PT_ERR_INVALID for a wrong nbytes or a null pointer.
+ * Tile split: this rank's compact rows (the update is pointwise).  Device group: mi3pt_set_moments goes to every member; read and ptr
+ * GATHER the whole height x width image onto devices[0] like a feature image (the presenting context allocates its copy at the first
+ * read, not before); mi3pt_write_moments is refused (MI3PT_ERR_STATE). ---- */
+int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled);                       /* default 0 */
+int mi3pt_read_moments(mi3pt_ctx *ctx, void *dst, size_t nbytes);
+int mi3pt_write_moments(mi3pt_ctx *ctx, const void *src, size_t nbytes);
+int mi3pt_moments_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes);
+
+/* ---- MI3PT_GUIDED_VARIANCE: mi3pt_denoise_guided with the colour weight steered by the per-pixel variance of the mean -- the spatial
+ * filter of SVGF (Schied et al., "Spatiotemporal Variance-Guided Filtering", HPG 2017), variance carried from level to level.  Needs
+ * the moments image: MI3PT_ERR_STATE while mi3pt_set_moments is off -- on a context that has enabled it before; a context that has never
+ * called mi3pt_set_moments(ctx, 1) answers as it did before the flag existed, MI3PT_ERR_INVALID for an unknown flag bit (the flag is
+ * opt-in like the image; the message names mi3pt_set_moments).  Everything of mi3pt_denoise_guided's definition stands -- tap
+ * order, the hit rule, en / ea / ep, the h weights, the division, the exp -- except the colour term and what follows.
+ * One variance kernel per call, before the levels.  Per texel q of the moments image: s = (M2.r + M2.g) + M2.b;
+ *   v(q) = fmax(s / (n * (n - 1)), 0) for n >= 2 (fp32, the division correctly rounded once, fmax drops a NaN), 0 for n < 2
+ *   var_0(p) = (sum of g[dx] * g[dy] * v(q)) / (sum of g[dx] * g[dy])   over q = p + (dx, dy), dy = -1 .. 1 outer, dx = -1 .. 1 inner,
+ *   g = [1/4, 1/2, 1/4], counting the q inside the image with hit(q) == hit(p) (the centre always counts)
+ * -- the variance of the mean summed over rgb: |dc|^2 in expectation, up to a factor of 2.
+ * Level i, with k_c = sigma_color * sigma_color in fp32 and denom = k_c * var_i(p) + MI3PT_GUIDED_VARIANCE_EPS for the centre p:
+ *   ec = ((dc.x*dc.x + dc.y*dc.y) + dc.z*dc.z) / denom      (0 when sigma_color == 0; NO 4^i factor: the variance shrinks by itself)
+ *   w as before;   nv = nv + (w * w) * var_i(q)   beside den and num;   var_(i+1)(p) = nv / (den * den)
+ * Colour output as before, alpha included.  denom >= EPS > 0, so the exp's argument stays non-positive for finite inputs.
+ * mi3pt_read_guided returns the colour image as before; mi3pt_read_guided_variance (blocking) the last level's variance var_levels:
+ * nfloats = rows x width.  MI3PT_ERR_STATE unless the last filter since the last resize ran with the flag; MI3PT_ERR_INVALID for a null
+ * pointer / a wrong nfloats.  A rank of a tile split and a device group stay refused as above.  MI3PT_PASS_GUIDED's time includes the
+ * variance kernel. ---- */
+#define MI3PT_GUIDED_VARIANCE 2u
+#define MI3PT_GUIDED_VARIANCE_EPS 1e-8f
+int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfloats);
+
 /* ---- read-back (the capability a headless drop-in needs; the reference only has
  * canvas.toDataURL, main.ts:351-356).  Blocking.  dst holds rows x width x 4 floats
  * (rows = local rows for OUTPUT / ACCUMULATION, canvas height for CANVAS). ---- */

@@ -280,6 +280,15 @@ struct mi3pt_ctx {
     const float4 *guided_result = nullptr;
     hipEvent_t ev_guided[2] = {};        // created with the first timed call
     bool ev_guided_recorded = false;
+    // MI3PT_GUIDED_VARIANCE: two ping-pong variance images, local_rows x width floats, allocated by the first call with the flag and freed
+    // with the textures; guided_var_result: the one the last level wrote (null: the last filter ran without the flag)
+    float *d_guided_var[2] = {};
+    const float *guided_var_result = nullptr;
+    // The moments image (mi3pt_set_moments): local_rows x width x (M2.rgb, n) fp32 beside the accumulation image, kept by the
+    // moments-keeping accumulate kernels; allocated while `moments` is on and the context has textures.
+    bool moments = false;
+    bool moments_opted = false;          // mi3pt_set_moments(1) has been called: until then MI3PT_GUIDED_VARIANCE is an unknown flag bit, as it was before the image existed
+    float4 *d_moments = nullptr;
     int walk_stack_worst = 64;           // mi3pt_upload_bvh: entries the reference walk's stack can hold at most on this tree (64: unknown, or the abort can fire)
     int wide_stack_worst = 64;           // prepare_cull: the wide walks' node stack, order-independent worst case (internal packets only; <= SM_CULL_STACK_MAX where wide_ok)
 };
@@ -328,6 +337,9 @@ static int group_counters(mi3pt_ctx *g, uint64_t *out);
 static int group_render_aovs(mi3pt_ctx *g, unsigned aov_mask);
 static int group_read_aov(mi3pt_ctx *g, int which, void *dst, size_t nbytes);
 static int group_aov_ptr(mi3pt_ctx *g, int which, void **dev_ptr, size_t *nbytes);
+static int group_set_moments(mi3pt_ctx *g, int enabled);
+static int group_read_moments(mi3pt_ctx *g, void *dst, size_t nbytes);
+static int group_moments_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes);
 static int group_unsupported(const char *what);
 static int group_set_option(mi3pt_ctx *g, int option, int value);
 // one call applied to every member (and, where marked, to the presenting context too)
@@ -664,6 +676,11 @@ static void free_textures(mi3pt_ctx *ctx)
     ctx->d_guided[0] = ctx->d_guided[1] = ctx->d_guided_nh = nullptr;
     ctx->guided_result = nullptr;
     ctx->ev_guided_recorded = false;
+    for (void *p : { (void *)ctx->d_guided_var[0], (void *)ctx->d_guided_var[1], (void *)ctx->d_moments })
+        if (p) (void)hipFree(p);
+    ctx->d_guided_var[0] = ctx->d_guided_var[1] = nullptr;
+    ctx->guided_var_result = nullptr;
+    ctx->d_moments = nullptr;
 }
 
 extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
@@ -1098,6 +1115,7 @@ static int zero_textures(mi3pt_ctx *ctx)
         // (the batch slots need no clearing: a launch writes every texel the ordered mean reads)
         HIP_TRY(hipMemsetAsync(ctx->d_radiance, 0, tex_bytes, ctx->stream));
         HIP_TRY(hipMemsetAsync(ctx->d_accum, 0, tex_bytes, ctx->stream));
+        if (ctx->d_moments) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, tex_bytes, ctx->stream));
     }
     if (canvas_px) {
         HIP_TRY(hipMemsetAsync(ctx->d_canvas, 0, canvas_px * 16, ctx->stream));
@@ -1145,7 +1163,7 @@ extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
     const int nblocks = ntiles_frame > 0 ? std::max(ntiles_frame, pt::PT_MAX_RESIDENT_WAVES) : 0;
     // two counter sets: overlapping raytrace kernels of consecutive frames use alternate halves
     const size_t cbytes = 2 * (size_t)(nblocks ? nblocks : 1) * pt::CNT_COUNT * sizeof(uint64_t);
-    float4 *radiance = nullptr, *accum = nullptr, *canvas = nullptr;
+    float4 *radiance = nullptr, *accum = nullptr, *canvas = nullptr, *moments = nullptr;
     uint32_t *canvas8 = nullptr;
     uint64_t *counters = nullptr;
     hipError_t e = hipMalloc((void **)&radiance, tex_bytes ? tex_bytes : 16);
@@ -1153,10 +1171,11 @@ extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
     if (e == hipSuccess) e = hipMalloc((void **)&canvas, canvas_px * 16);
     if (e == hipSuccess) e = hipMalloc((void **)&canvas8, canvas_px * 4);
     if (e == hipSuccess) e = hipMalloc((void **)&counters, cbytes);
+    if (e == hipSuccess && ctx->moments) e = hipMalloc((void **)&moments, tex_bytes ? tex_bytes : 16);
     if (e == hipSuccess) e = hipMemsetAsync(counters, 0, cbytes, ctx->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        for (void *p : { (void *)radiance, (void *)accum, (void *)canvas, (void *)canvas8, (void *)counters })
+        for (void *p : { (void *)radiance, (void *)accum, (void *)canvas, (void *)canvas8, (void *)counters, (void *)moments })
             if (p) (void)hipFree(p);
         return pt_set_error(MI3PT_ERR_HIP, std::string("mi3pt_resize: allocating the textures failed: ") + hipGetErrorString(e));
     }
@@ -1164,6 +1183,7 @@ extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
     ctx->width = width; ctx->height = height; ctx->local_rows = local_rows;
     ctx->d_radiance = radiance; ctx->d_accum_own = accum; ctx->d_accum = accum;
     ctx->d_canvas = canvas; ctx->d_canvas8 = canvas8; ctx->d_block_counters = counters;
+    ctx->d_moments = moments;
     ctx->nblocks = nblocks;
     // batch depth: the limit for this tile split, capped so that the slot sets together take
     // at most a quarter of the memory that is free now (slots are allocated when first needed)
@@ -1952,7 +1972,10 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
         pt::AccUniforms a = acc;
         a.frame = acc.frame + (uint32_t)k;
         if (ctx->timing && last_run) HIP_TRY(hipEventRecord(ctx->ev[1][0], ctx->stream));
-        pt::launch_accumulate_batch(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, f16, ctx->stream);
+        if (ctx->d_moments)
+            pt::launch_accumulate_batch_moments(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, ctx->d_moments, f16, ctx->stream);
+        else
+            pt::launch_accumulate_batch(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, f16, ctx->stream);
         HIP_TRY(hipGetLastError());
         if (ctx->timing && last_run) { HIP_TRY(hipEventRecord(ctx->ev[1][1], ctx->stream)); ctx->ev_recorded[1] = true; }
         ctx->accum_version++;
@@ -2072,7 +2095,8 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
             pt::RtLaunch L = build_launch(ctx, ctx->u_rt, acc);
             // Fuse when the accumulate pass covers exactly the pixels the raytrace pass writes (the per-pixel kernels; the
             // state-machine kernel writes the frame's radiance and the accumulate pass follows as a kernel of its own: same bits).
-            const bool fused = do_acc && same_region && pt::raytrace_variant_fuses(variant);
+            // (not with the moments image: the per-pixel kernels do not keep it, the two passes run separately -- same bits)
+            const bool fused = do_acc && same_region && pt::raytrace_variant_fuses(variant) && !ctx->d_moments;
             // (the service block of a launch that runs at once: its own slot -- launches on the main stream follow each other,
             // and the batches launched before it are waited for by this stream)
             L.service = reinterpret_cast<pt::RtService *>(ctx->d_service + (size_t)SERVICE_SLOTS * service_slot_bytes());
@@ -2092,7 +2116,8 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
     }
     if (do_acc && !acc_done) {
         if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[1][0], ctx->stream));
-        pt::launch_accumulate(acc, tile, ctx->last_radiance, ctx->d_accum, f16, ctx->stream);
+        if (ctx->d_moments) pt::launch_accumulate_moments(acc, tile, ctx->last_radiance, ctx->d_accum, ctx->d_moments, f16, ctx->stream);
+        else pt::launch_accumulate(acc, tile, ctx->last_radiance, ctx->d_accum, f16, ctx->stream);
         HIP_TRY(hipGetLastError());
         if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev[1][1], ctx->stream)); ctx->ev_recorded[1] = true; }
         ctx->output_is_accum = true;   // accumulate.ts:171-175 copies the mean into outputTexture
@@ -2236,6 +2261,7 @@ extern "C" int mi3pt_write_texture(mi3pt_ctx *ctx, int which, const float *src, 
     if (need) {
         HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "write-back"));
         HIP_TRY(hipMemcpyAsync(ctx->d_accum, src, need * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (ctx->d_moments) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, need * 4, ctx->stream));      // (a mean from outside: its spread is unknown)
         HIP_TRY(ctx_stream_sync(ctx, ctx->stream));      // copy-on-call
     }
     ctx->output_is_accum = true;      // like the copy-back of accumulate.ts:171-175
@@ -2278,16 +2304,22 @@ extern "C" int mi3pt_bind_accumulation(mi3pt_ctx *ctx, void *dev_ptr, size_t nby
     HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
     ctx->main_dirty = true;
     ctx->accum_version++;
+    // (another image becomes the mean: like a mean written from outside, its spread is unknown -- the moments start over)
+    auto zero_moments = [&]() -> int {
+        const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
+        if (ctx->d_moments && tex_bytes) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, tex_bytes, ctx->stream));
+        return MI3PT_OK;
+    };
     if (!dev_ptr) {
         ctx->d_accum = ctx->d_accum_own;
-        return MI3PT_OK;
+        return zero_moments();
     }
     if (nbytes != (size_t)ctx->local_rows * ctx->width * 16)
         return pt_set_error(MI3PT_ERR_INVALID, "external accumulation buffer must be local_rows*width*16 bytes");
     if (reinterpret_cast<uintptr_t>(dev_ptr) % 16)
         return pt_set_error(MI3PT_ERR_INVALID, "external accumulation buffer must be 16-byte aligned");
     ctx->d_accum = static_cast<float4 *>(dev_ptr);
-    return MI3PT_OK;
+    return zero_moments();
 }
 
 // ---- first-hit feature images (include/mi3pt.h: mi3pt_aov, mi3pt_render_aovs) ----
@@ -2391,7 +2423,10 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     if (params->levels < 1 || params->levels > 5) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: levels must be 1 .. 5");
     for (float sigma : { params->sigma_color, params->sigma_normal, params->sigma_albedo, params->sigma_plane })
         if (!(sigma >= 0.0f) || std::isinf(sigma)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: every sigma must be finite and >= 0");
-    if (params->flags & ~MI3PT_GUIDED_PRESENT) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: unknown flag bits");
+    // (a context that never opted into the moments image answers as it always did: the variance bit is unknown to it)
+    if (params->flags & ~(MI3PT_GUIDED_PRESENT | (ctx->moments_opted ? MI3PT_GUIDED_VARIANCE : 0u)))
+        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: unknown flag bits (MI3PT_GUIDED_VARIANCE: only on a context that has enabled the moments image, mi3pt_set_moments)");
+    const bool by_variance = (params->flags & MI3PT_GUIDED_VARIANCE) != 0;
     if (int rc = require_ctx(ctx)) return rc;
     if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided before resize");
     if (ctx->partial())
@@ -2399,10 +2434,15 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     for (int k = 0; k < MI3PT_AOV_COUNT; k++)
         if (!ctx->aov_valid[k] || !ctx->d_aov[k])
             return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided: the four feature images have not all been rendered since the last resize (mi3pt_render_aovs)");
+    if (by_variance && !ctx->d_moments)
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided: MI3PT_GUIDED_VARIANCE needs the moments image (mi3pt_set_moments(ctx, 1) before the frames are accumulated)");
     if (int rc = flush_pending(ctx)) return rc;      // the mean a read-back would return now: the accumulate passes run on this stream
     const size_t texels = (size_t)ctx->local_rows * ctx->width, tex_bytes = texels * 16;
     for (float4 **p : { &ctx->d_guided[0], &ctx->d_guided[1], &ctx->d_guided_nh })
         if (!*p) HIP_TRY(hipMalloc((void **)p, tex_bytes ? tex_bytes : 16));
+    if (by_variance)
+        for (float *&p : ctx->d_guided_var)
+            if (!p) HIP_TRY(hipMalloc((void **)&p, texels ? texels * 4 : 16));
     pt::GuidedLaunch G;
     G.normal_hit = ctx->d_guided_nh; G.position = ctx->d_aov[MI3PT_AOV_POSITION]; G.albedo = ctx->d_aov[MI3PT_AOV_ALBEDO];
     G.width = ctx->width; G.rows = ctx->local_rows;
@@ -2415,14 +2455,27 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     }
     pt::launch_guided_pack(ctx->d_aov[MI3PT_AOV_NORMAL], ctx->d_aov[MI3PT_AOV_IDS], ctx->d_guided_nh, texels, ctx->stream);
     const float4 *src = ctx->d_accum;
+    const float *var = nullptr;
+    if (by_variance) {
+        // var_0 into the image level 0 does not write; level i then reads image (i + 1) & 1 and writes image i & 1
+        pt::launch_guided_variance(ctx->d_moments, ctx->d_guided_nh, ctx->d_guided_var[1], ctx->width, ctx->local_rows, ctx->stream);
+        var = ctx->d_guided_var[1];
+    }
     for (int level = 0; level < params->levels; level++) {
         float4 *dst = ctx->d_guided[level & 1];
-        pt::launch_guided_level(G, src, dst, level, ctx->stream);
+        if (by_variance) {
+            float *var_dst = ctx->d_guided_var[level & 1];
+            pt::launch_guided_level_variance(G, src, dst, var, var_dst, level, params->sigma_color, ctx->stream);
+            var = var_dst;
+        } else {
+            pt::launch_guided_level(G, src, dst, level, ctx->stream);
+        }
         src = dst;
     }
     HIP_TRY(hipGetLastError());
     if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev_guided[1], ctx->stream)); ctx->ev_guided_recorded = true; }
     ctx->guided_result = src;
+    ctx->guided_var_result = var;
     if (params->flags & MI3PT_GUIDED_PRESENT) {
         // the fullscreen pass on the filtered image, with the pass's uniforms as they are and its own de-noiser off.  The canvas then shows
         // no state of the running mean: the next fullscreen submit draws again whatever it showed before, and a draw still owed to queued
@@ -2468,6 +2521,104 @@ extern "C" int mi3pt_guided_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *n
     if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = guided_image(ctx, "mi3pt_guided_device_ptr")) return rc;
     *dev_ptr = const_cast<float4 *>(ctx->guided_result);
+    if (nbytes) *nbytes = (size_t)ctx->local_rows * ctx->width * 16;
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfloats)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_read_guided_variance: mi3pt_denoise_guided is not built for a device group"));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = guided_image(ctx, "mi3pt_read_guided_variance")) return rc;
+    if (!ctx->guided_var_result) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_guided_variance: the last filter ran without MI3PT_GUIDED_VARIANCE");
+    const size_t need = (size_t)ctx->local_rows * ctx->width;
+    if (nfloats != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width floats)");
+    if (need == 0) return MI3PT_OK;
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));
+    HIP_TRY(hipMemcpyAsync(dst, ctx->guided_var_result, need * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    return MI3PT_OK;
+}
+
+// ---- the moments image (include/mi3pt.h: mi3pt_set_moments; pt_kernels.hip: k_accumulate_moments, k_accumulate_batch_moments) ----
+extern "C" int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled)
+{
+    PT_GROUP(ctx, group_set_moments(ctx, enabled));
+    if (int rc = require_idle(ctx)) return rc;
+    const bool on = enabled != 0;
+    if (on == ctx->moments) return MI3PT_OK;
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));      // (the accumulate passes in flight read and write the image this frees)
+    if (!on) {
+        if (ctx->d_moments) (void)hipFree(ctx->d_moments);
+        ctx->d_moments = nullptr;
+        ctx->moments = false;
+        return MI3PT_OK;
+    }
+    if (ctx->width != 0) {
+        const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
+        float4 *image = nullptr;
+        HIP_TRY(hipMalloc((void **)&image, tex_bytes ? tex_bytes : 16));
+        if (tex_bytes) {
+            const hipError_t e = hipMemsetAsync(image, 0, tex_bytes, ctx->stream);
+            if (e != hipSuccess) {          // (nothing half enabled: the launches key on the pointer)
+                (void)hipGetLastError();
+                (void)hipFree(image);
+                return pt_set_error(MI3PT_ERR_HIP, std::string("mi3pt_set_moments: clearing the image failed: ") + hipGetErrorString(e));
+            }
+        }
+        ctx->d_moments = image;
+        ctx->main_dirty = true;
+    }
+    ctx->moments = ctx->moments_opted = true;      // (before mi3pt_resize: the image comes with the textures)
+    return MI3PT_OK;
+}
+
+static int moments_image(mi3pt_ctx *ctx, const char *what)
+{
+    if (!ctx->moments) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": the moments image is not enabled (mi3pt_set_moments)");
+    if (ctx->width == 0 || !ctx->d_moments) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_read_moments(mi3pt_ctx *ctx, void *dst, size_t nbytes)
+{
+    PT_GROUP(ctx, group_read_moments(ctx, dst, nbytes));
+    if (int rc = require_idle(ctx)) return rc;
+    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = moments_image(ctx, "mi3pt_read_moments")) return rc;
+    const size_t need = (size_t)ctx->local_rows * ctx->width * 16;
+    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
+    if (need == 0) return MI3PT_OK;
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
+    HIP_TRY(hipMemcpyAsync(dst, ctx->d_moments, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_write_moments(mi3pt_ctx *ctx, const void *src, size_t nbytes)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_write_moments: a device group keeps its members' moments images (write each member's rows: mi3pt_group_member)"));
+    if (int rc = require_idle(ctx)) return rc;
+    if (!src) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = moments_image(ctx, "mi3pt_write_moments")) return rc;
+    const size_t need = (size_t)ctx->local_rows * ctx->width * 16;
+    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "source size does not match the image (rows x width x 16 bytes)");
+    if (need == 0) return MI3PT_OK;
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "write-back"));
+    HIP_TRY(hipMemcpyAsync(ctx->d_moments, src, need, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));      // copy-on-call
+    ctx->main_dirty = true;
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_moments_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes)
+{
+    PT_GROUP(ctx, group_moments_ptr(ctx, dev_ptr, nbytes));
+    if (int rc = require_idle(ctx)) return rc;
+    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = moments_image(ctx, "mi3pt_moments_device_ptr")) return rc;
+    *dev_ptr = ctx->d_moments;
     if (nbytes) *nbytes = (size_t)ctx->local_rows * ctx->width * 16;
     return MI3PT_OK;
 }
@@ -3001,15 +3152,16 @@ static int group_sync(mi3pt_ctx *g)
 // geometry: source pitch = one block, destination pitch = n blocks) on the presenting context's stream -- peer DMA over xGMI.
 // Otherwise: staged through pinned host memory (a device-to-host copy on the member's device, then the same strided copy from
 // the host buffer).
-// (aov < 0: the accumulation image; else that feature image, mi3pt_read_aov of a group)
+// (aov == -1: the accumulation image; GATHER_MOMENTS: the moments image; else that feature image, mi3pt_read_aov of a group)
+static const int GATHER_MOMENTS = -2;
 static int gather_member(GroupState *gs, int i, bool direct, int aov = -1)
 {
     mi3pt_ctx *p = gs->present;
     const mi3pt_ctx *m = gs->members[(size_t)i];
     const int n = (int)gs->members.size(), br = gs->block_rows, W = gs->width, H = gs->height;
     const size_t row_bytes = (size_t)W * 16, block_bytes = row_bytes * (size_t)br;
-    uint8_t *dst = reinterpret_cast<uint8_t *>(aov < 0 ? p->d_accum : p->d_aov[aov]);
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(aov < 0 ? m->d_accum : m->d_aov[aov]);
+    uint8_t *dst = reinterpret_cast<uint8_t *>(aov == GATHER_MOMENTS ? p->d_moments : aov < 0 ? p->d_accum : p->d_aov[aov]);
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(aov == GATHER_MOMENTS ? m->d_moments : aov < 0 ? m->d_accum : m->d_aov[aov]);
     const int rows = m->local_rows;
     if (rows == 0) return MI3PT_OK;
     const int full = rows / br, tail = rows - full * br;      // whole blocks, rows of a last partial block (the image's bottom edge)
@@ -3140,6 +3292,56 @@ static int group_aov_ptr(mi3pt_ctx *g, int which, void **dev_ptr, size_t *nbytes
     if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = group_gather_aov(g, which, "mi3pt_aov_device_ptr")) return rc;
     return mi3pt_aov_device_ptr(g->group->present, which, dev_ptr, nbytes);
+}
+
+// ---- the moments image of a group: kept by every member for its rows; the presenting context's whole image is allocated by the first read
+// (like a feature image: group_gather_aov), freed by its resize (free_textures) and by mi3pt_set_moments(0), and gathered whenever it is read ----
+static int group_set_moments(mi3pt_ctx *g, int enabled)
+{
+    if (int rc = group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_set_moments(m, enabled); })) return rc;
+    mi3pt_ctx *p = g->group->present;
+    if (!enabled && p->d_moments) {
+        if (int rc = require_ctx(p)) return rc;
+        HIP_TRY(ctx_stream_sync(p, p->stream));
+        (void)hipFree(p->d_moments);
+        p->d_moments = nullptr;
+    }
+    return MI3PT_OK;
+}
+
+static int group_gather_moments(mi3pt_ctx *g, const char *what)
+{
+    GroupState *gs = g->group;
+    if (!gs->members[0]->moments) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": the moments image is not enabled (mi3pt_set_moments)");
+    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
+    if (int rc = group_sync(g)) return rc;
+    mi3pt_ctx *p = gs->present;
+    if (int rc = require_idle(p)) return rc;
+    if (!p->d_moments) HIP_TRY(hipMalloc((void **)&p->d_moments, (size_t)gs->width * gs->height * 16));
+    return gather_copies(gs, GATHER_MOMENTS);
+}
+
+static int group_read_moments(mi3pt_ctx *g, void *dst, size_t nbytes)
+{
+    GroupState *gs = g->group;
+    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    const size_t need = (size_t)gs->width * gs->height * 16;
+    if (gs->width && gs->members[0]->moments && nbytes != need)
+        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (a group reads whole images: height x width x 16 bytes)");
+    if (int rc = group_gather_moments(g, "mi3pt_read_moments")) return rc;
+    mi3pt_ctx *p = gs->present;
+    HIP_TRY(hipMemcpyAsync(dst, p->d_moments, need, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(ctx_stream_sync(p, p->stream));
+    return MI3PT_OK;
+}
+
+static int group_moments_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes)
+{
+    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = group_gather_moments(g, "mi3pt_moments_device_ptr")) return rc;
+    *dev_ptr = g->group->present->d_moments;
+    if (nbytes) *nbytes = (size_t)g->group->width * g->group->height * 16;
+    return MI3PT_OK;
 }
 
 static int group_draw_canvas(mi3pt_ctx *g)

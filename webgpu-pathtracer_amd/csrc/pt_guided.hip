@@ -9,6 +9,7 @@
 // inside a class the 5 x 5 taps are neighbours: a 256-thread block filters 16 x 16 texels of one class, copies the 20 x 20 texels of that
 // class around them (colour and features, 64 B per texel = 25 KB) into LDS once and runs the 25 taps from there -- every level is the same
 // kernel with the stride as an argument.  A texel outside the image is marked in its LDS record and never loaded.
+#include "../../include/mi3pt.h"
 #include "pt_kernels.h"
 #include "pt_devmath.h"
 
@@ -25,10 +26,15 @@ __global__ void __launch_bounds__(256) k_guided_pack(const float4 *__restrict__ 
     out[i] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(reinterpret_cast<const uint4 *>(ids)[i].z));       // (the flag's 32 bits: only ever compared as bits)
 }
 
-__global__ void __launch_bounds__(256) k_guided_level(const GuidedLaunch G, const float4 *__restrict__ src, float4 *__restrict__ dst, const int s,
-                                                      const float inv_c)
+// One level for one texel block.  VARIANCE (MI3PT_GUIDED_VARIANCE): the colour term is |dc|^2 / (k_c * var(p) + EPS) -- `color` = k_c, no 4^level
+// factor -- instead of |dc|^2 * `color` (= inv_c), and the variance is filtered with the squared weights beside the colour: it rides in the w
+// slot of the LDS colour record, so the centre's alpha comes from memory.  One body, so that the two kernels cannot drift apart; the plain
+// instantiation compiles to what it was (profiles/moments.log).
+template <bool VARIANCE>
+PT_DEV void guided_level(const GuidedLaunch &G, const float4 *__restrict__ src, float4 *__restrict__ dst, const float *__restrict__ var_src,
+                         float *__restrict__ var_dst, const int s, const float color, const int color_on)
 {
-    __shared__ float4 l_col[G_SPAN * G_SPAN];       // c.rgb, c.w
+    __shared__ float4 l_col[G_SPAN * G_SPAN];       // c.rgb, c.w (VARIANCE: the variance)
     __shared__ float4 l_nh[G_SPAN * G_SPAN];        // n.xyz, hit
     __shared__ float4 l_pos[G_SPAN * G_SPAN];       // P.xyz, w: bits 1 = inside the image
     __shared__ float4 l_alb[G_SPAN * G_SPAN];       // a.rgb
@@ -42,6 +48,7 @@ __global__ void __launch_bounds__(256) k_guided_level(const GuidedLaunch G, cons
         if (inside) {
             const size_t i = (size_t)y * (size_t)G.width + (size_t)x;
             c = src[i]; nh = G.normal_hit[i]; p = G.position[i]; a = G.albedo[i];
+            if (VARIANCE) c.w = var_src[i];
             p.w = __uint_as_float(1u);
         }
         l_col[e] = c; l_nh[e] = nh; l_pos[e] = p; l_alb[e] = a;
@@ -53,8 +60,9 @@ __global__ void __launch_bounds__(256) k_guided_level(const GuidedLaunch G, cons
     const int ec0 = (ly + G_HALO) * G_SPAN + lx + G_HALO;
     const float4 cp = l_col[ec0], np = l_nh[ec0], pp = l_pos[ec0], ap = l_alb[ec0];
     const uint32_t hit_p = __float_as_uint(np.w);
+    const float denom = VARIANCE ? color * cp.w + MI3PT_GUIDED_VARIANCE_EPS : 0.0f;
     const float h[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
-    float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
+    float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f, nv = 0.0f;
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++) {
 #pragma unroll
@@ -64,7 +72,8 @@ __global__ void __launch_bounds__(256) k_guided_level(const GuidedLaunch G, cons
             if (__float_as_uint(pq.w) != 1u || __float_as_uint(nq.w) != hit_p) continue;
             const float4 cq = l_col[e], aq = l_alb[e];
             const float dcx = cq.x - cp.x, dcy = cq.y - cp.y, dcz = cq.z - cp.z;
-            const float ec = ((dcx * dcx + dcy * dcy) + dcz * dcz) * inv_c;
+            const float dc2 = (dcx * dcx + dcy * dcy) + dcz * dcz;
+            const float ec = VARIANCE ? (color_on ? dc2 / denom : 0.0f) : dc2 * color;
             const float dnx = nq.x - np.x, dny = nq.y - np.y, dnz = nq.z - np.z;
             const float en = ((dnx * dnx + dny * dny) + dnz * dnz) * G.inv_normal;
             const float dax = aq.x - ap.x, day = aq.y - ap.y, daz = aq.z - ap.z;
@@ -75,9 +84,78 @@ __global__ void __launch_bounds__(256) k_guided_level(const GuidedLaunch G, cons
             const float w = ptm::exp1_nonpos(-(((ec + en) + ea) + ep)) * (h[dx + 2] * h[dy + 2]);
             den = den + w;
             nr = nr + w * cq.x; ng = ng + w * cq.y; nb = nb + w * cq.z;
+            if (VARIANCE) nv = nv + (w * w) * cq.w;
         }
     }
-    dst[(size_t)y * (size_t)G.width + (size_t)x] = make_float4(nr / den, ng / den, nb / den, cp.w);
+    const size_t i = (size_t)y * (size_t)G.width + (size_t)x;
+    dst[i] = make_float4(nr / den, ng / den, nb / den, VARIANCE ? src[i].w : cp.w);
+    if (VARIANCE) var_dst[i] = nv / (den * den);
+}
+
+__global__ void __launch_bounds__(256) k_guided_level(const GuidedLaunch G, const float4 *__restrict__ src, float4 *__restrict__ dst, const int s,
+                                                      const float inv_c)
+{
+    guided_level<false>(G, src, dst, nullptr, nullptr, s, inv_c, 1);
+}
+
+// ---- MI3PT_GUIDED_VARIANCE: the colour term steered by the per-pixel variance of the mean (SVGF's spatial filter: Schied et al.,
+// HPG 2017), from the moments image, carried from level to level: the variance kernel and guided_level's second instantiation. ----
+
+// v of one moments texel: the variance of the mean summed over rgb, 0 with fewer than two samples; fmaxf drops a NaN
+PT_DEV float moments_variance(const float4 m)
+{
+    const float sum = (m.x + m.y) + m.z;
+    return m.w >= 2.0f ? fmaxf(sum / (m.w * (m.w - 1.0f)), 0.0f) : 0.0f;
+}
+
+// var_0: v averaged over the 3 x 3 neighbours of the centre's hit class, g = [1/4, 1/2, 1/4]
+__global__ void __launch_bounds__(256) k_guided_variance(const float4 *__restrict__ moments, const float4 *__restrict__ normal_hit,
+                                                         float *__restrict__ var, const int width, const int rows)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)width * (size_t)rows) return;
+    const int y = (int)(i / (size_t)width), x = (int)(i - (size_t)y * (size_t)width);
+    const uint32_t hit_p = __float_as_uint(normal_hit[i].w);
+    const float g[3] = { 0.25f, 0.5f, 0.25f };
+    float num = 0.0f, den = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= width || qy < 0 || qy >= rows) continue;
+            const size_t q = (size_t)qy * (size_t)width + (size_t)qx;
+            if (__float_as_uint(normal_hit[q].w) != hit_p) continue;
+            const float w = g[dx + 1] * g[dy + 1];
+            num = num + w * moments_variance(moments[q]);
+            den = den + w;
+        }
+    }
+    var[i] = num / den;
+}
+
+__global__ void __launch_bounds__(256) k_guided_level_variance(const GuidedLaunch G, const float4 *__restrict__ src, float4 *__restrict__ dst,
+                                                               const float *__restrict__ var_src, float *__restrict__ var_dst, const int s,
+                                                               const float k_c, const int color_on)
+{
+    guided_level<true>(G, src, dst, var_src, var_dst, s, k_c, color_on);
+}
+
+void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, int width, int rows, hipStream_t s)
+{
+    const size_t texels = (size_t)width * (size_t)rows;
+    if (width <= 0 || rows <= 0) return;
+    hipLaunchKernelGGL(k_guided_variance, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, s, moments, normal_hit, var, width, rows);
+}
+
+void launch_guided_level_variance(const GuidedLaunch &G, const float4 *src, float4 *dst, const float *var_src, float *var_dst, int level,
+                                  float sigma_color, hipStream_t s)
+{
+    if (G.width <= 0 || G.rows <= 0) return;
+    const int step = 1 << level;
+    const int tx = ((G.width + step - 1) / step + G_TILE - 1) / G_TILE, ty = ((G.rows + step - 1) / step + G_TILE - 1) / G_TILE;      // (as launch_guided_level)
+    hipLaunchKernelGGL(k_guided_level_variance, dim3((unsigned)(tx * step), (unsigned)(ty * step)), dim3(256), 0, s, G, src, dst, var_src, var_dst,
+                       step, sigma_color * sigma_color, sigma_color == 0.0f ? 0 : 1);
 }
 
 void launch_guided_pack(const float4 *normal, const float4 *ids, float4 *out, size_t texels, hipStream_t s)

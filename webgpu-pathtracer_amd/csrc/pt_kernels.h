@@ -313,6 +313,11 @@ void launch_accumulate_batch(const AccUniforms &acc0, const Tile &tile, const fl
                              int nframes, float4 *accum, int store_f16, hipStream_t s);
 void launch_accumulate(const AccUniforms &acc, const Tile &tile, const float4 *input, float4 *accum,
                        int store_f16, hipStream_t s);
+// the same two passes, keeping the moments image (local_rows x width float4: M2.rgb, n; include/mi3pt.h: mi3pt_set_moments) beside the mean
+void launch_accumulate_batch_moments(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels,
+                                     int nframes, float4 *accum, float4 *moments, int store_f16, hipStream_t s);
+void launch_accumulate_moments(const AccUniforms &acc, const Tile &tile, const float4 *input, float4 *accum, float4 *moments,
+                               int store_f16, hipStream_t s);
 // `taps`: fullscreen_taps_bytes() of device memory (the de-noise pass's tap table); `taps_current`: an earlier call on
 // this stream has filled it from the same fs.res_x / fs.res_y
 size_t fullscreen_taps_bytes();
@@ -356,6 +361,11 @@ struct GuidedLaunch {
 void launch_guided_pack(const float4 *normal, const float4 *ids, float4 *out, size_t texels, hipStream_t s);
 // level `level` (step 1 << level, inv_color x 4^level) from src into dst, both rows x width
 void launch_guided_level(const GuidedLaunch &G, const float4 *src, float4 *dst, int level, hipStream_t s);
+// MI3PT_GUIDED_VARIANCE.  var (rows x width floats) = the 3 x 3 average of the moments image's variance of the mean; then level `level`
+// from src / var_src into dst / var_dst with the colour term |dc|^2 / (sigma_color^2 * var_src(p) + MI3PT_GUIDED_VARIANCE_EPS)
+void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, int width, int rows, hipStream_t s);
+void launch_guided_level_variance(const GuidedLaunch &G, const float4 *src, float4 *dst, const float *var_src, float *var_dst, int level,
+                                  float sigma_color, hipStream_t s);
 // packs the three position vectors of `ntris` 112-byte triangle records into 48-byte rows (the context's cull analysis)
 void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipStream_t s);
 // writes NodePacket::cull of `npackets` packets from a dense array (the context's cull analysis)

@@ -2842,6 +2842,83 @@ void launch_accumulate(const AccUniforms &acc, const Tile &tile, const float4 *i
 }
 
 // ---------------------------------------------------------------------------------
+// The moments image (include/mi3pt.h: mi3pt_set_moments): the two accumulate kernels above, keeping (M2.rgb, n) beside the mean in
+// the same pass.  Welford's update written around the mean as it is STORED: c the frame's radiance, p the mean before the step,
+// pn the mean after it (after store_round); a step of weight 1 (accumulate_texel) restarts the sums.  The mean's own arithmetic is
+// that of the kernels above, operation for operation.
+// ---------------------------------------------------------------------------------
+PT_DEV float4 moments_step(const AccUniforms &acc, f3 c, f3 p, f3 pn, float4 m)
+{
+    if (acc.frame <= 1u || acc.enabled != 1u) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    return make_float4(m.x + (c.x - p.x) * (c.x - pn.x), m.y + (c.y - p.y) * (c.y - pn.y), m.z + (c.z - p.z) * (c.z - pn.z), m.w + 1.0f);
+}
+
+__global__ void __launch_bounds__(256) k_accumulate_moments(const AccUniforms acc, const Tile tile, const float4 *__restrict__ input,
+                                                            float4 *__restrict__ accum, float4 *__restrict__ moments, int store_f16)
+{
+    const size_t n = (size_t)tile.local_rows * tile.tex_w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int ly = (int)(i / tile.tex_w);
+        const int gx = (int)(i - (size_t)ly * tile.tex_w);
+        const int gy = local_to_global_row(ly, tile);
+        if ((uint32_t)gx >= acc.res_w || (uint32_t)gy >= acc.res_h) continue;
+        const f3 c = xyz(input[i]), p = xyz(accum[i]);
+        const f3 nc = accumulate_texel(acc, c, p);
+        const f3 pn = F3(store_round(nc.x, store_f16), store_round(nc.y, store_f16), store_round(nc.z, store_f16));
+        accum[i] = make_float4(pn.x, pn.y, pn.z, 1.0f);
+        moments[i] = moments_step(acc, c, p, pn, moments[i]);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_accumulate_batch_moments(const AccUniforms acc0, const Tile tile, const float4 *__restrict__ slots,
+                                                                  size_t slot_pixels, int nframes, float4 *__restrict__ accum,
+                                                                  float4 *__restrict__ moments, int store_f16)
+{
+    const size_t n = (size_t)tile.local_rows * tile.tex_w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int ly = (int)(i / tile.tex_w);
+        const int gx = (int)(i - (size_t)ly * tile.tex_w);
+        const int gy = local_to_global_row(ly, tile);
+        if ((uint32_t)gx >= acc0.res_w || (uint32_t)gy >= acc0.res_h) continue;
+        f3 p = xyz(accum[i]);
+        float4 m = moments[i];
+        for (int k = 0; k < nframes; k++) {
+            AccUniforms a = acc0;
+            a.frame = acc0.frame + (uint32_t)k;
+            const f3 c = xyz(slots[(size_t)k * slot_pixels + i]);
+            const f3 nc = accumulate_texel(a, c, p);
+            const f3 pn = F3(store_round(nc.x, store_f16), store_round(nc.y, store_f16), store_round(nc.z, store_f16));
+            m = moments_step(a, c, p, pn, m);
+            p = pn;
+        }
+        accum[i] = make_float4(p.x, p.y, p.z, 1.0f);
+        moments[i] = m;
+    }
+}
+
+// (the grids of launch_accumulate_batch / launch_accumulate: capped, the kernels stride beyond)
+void launch_accumulate_batch_moments(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels,
+                                     int nframes, float4 *accum, float4 *moments, int store_f16, hipStream_t s)
+{
+    const size_t n = (size_t)tile.local_rows * tile.tex_w;
+    if (n == 0 || nframes <= 0) return;
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_accumulate_batch_moments, dim3(blocks), dim3(256), 0, s, acc0, tile, slots, slot_pixels, nframes,
+                       accum, moments, store_f16);
+}
+
+void launch_accumulate_moments(const AccUniforms &acc, const Tile &tile, const float4 *input, float4 *accum, float4 *moments,
+                               int store_f16, hipStream_t s)
+{
+    const size_t n = (size_t)tile.local_rows * tile.tex_w;
+    if (n == 0) return;
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(k_accumulate_moments, dim3(blocks), dim3(256), 0, s, acc, tile, input, accum, moments, store_f16);
+}
+
+// ---------------------------------------------------------------------------------
 // fullscreen.wgsl
 // ---------------------------------------------------------------------------------
 // repeat addressing: v mod n.  Sample positions stay within one period of the texture, so the

@@ -288,6 +288,7 @@ CTX_INT_FN(EnableTiming, mi3pt_enable_timing)
 CTX_INT_FN(SetPipelining, mi3pt_set_pipelining)
 CTX_INT_FN(SetPresentMode, mi3pt_set_present_mode)
 CTX_INT_FN(SetEnvSampling, mi3pt_set_env_sampling)
+CTX_INT_FN(SetMoments, mi3pt_set_moments)
 CTX_VOID_FN(Reset, mi3pt_reset)
 CTX_VOID_FN(Sync, mi3pt_sync)
 CTX_VOID_FN(Flush, mi3pt_flush)
@@ -441,6 +442,36 @@ napi_value ReadGuided(napi_env env, napi_callback_info info)
     napi_value ab, ta;
     NAPI_OK(napi_create_arraybuffer(env, (size_t)ntexels * 16, &data, &ab));
     MI3PT_TRY(mi3pt_read_guided(ctx, data, (size_t)ntexels * 16));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, (size_t)ntexels * 4, ab, 0, &ta));
+    return ta;
+}
+
+// readGuidedVariance(ctx, ntexels) -> Float32Array of ntexels: the last level's variance of the last denoiseGuided with MI3PT_GUIDED_VARIANCE
+napi_value ReadGuidedVariance(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t ntexels;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &ntexels) || ntexels < 0) return nullptr;
+    void *data = nullptr;
+    napi_value ab, ta;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)ntexels * 4, &data, &ab));
+    MI3PT_TRY(mi3pt_read_guided_variance(ctx, static_cast<float *>(data), (size_t)ntexels));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, (size_t)ntexels, ab, 0, &ta));
+    return ta;
+}
+
+// readMoments(ctx, ntexels) -> Float32Array of ntexels x 4: the moments image (M2.r, M2.g, M2.b, n)
+napi_value ReadMoments(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t ntexels;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &ntexels) || ntexels < 0) return nullptr;
+    void *data = nullptr;
+    napi_value ab, ta;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)ntexels * 16, &data, &ab));
+    MI3PT_TRY(mi3pt_read_moments(ctx, data, (size_t)ntexels * 16));
     NAPI_OK(napi_create_typedarray(env, napi_float32_array, (size_t)ntexels * 4, ab, 0, &ta));
     return ta;
 }
@@ -639,7 +670,8 @@ napi_value Init(napi_env env, napi_value exports)
         { "resetCounters", ResetCounters }, { "hostBuildBvhF64", HostBuildBvhF64 }, { "hostBuildBvh", HostBuildBvh },
         { "hostEnvCdf", HostEnvCdf }, { "setPipelining", SetPipelining }, { "setPresentMode", SetPresentMode }, { "setEnvSampling", SetEnvSampling }, { "deviceBuildBvh", DeviceBuildBvh }, { "writeTexture", WriteTexture },
         { "raytraceLaunchStats", RaytraceLaunchStats }, { "renderAovs", RenderAovs }, { "readAov", ReadAov },
-        { "denoiseGuided", DenoiseGuided }, { "readGuided", ReadGuided },
+        { "denoiseGuided", DenoiseGuided }, { "readGuided", ReadGuided }, { "readGuidedVariance", ReadGuidedVariance },
+        { "setMoments", SetMoments }, { "readMoments", ReadMoments },
     };
     for (const auto &f : fns) {
         napi_value v;

@@ -120,11 +120,20 @@ export class Renderer {
   readAov(name: 'albedo' | 'normal' | 'position'): Float32Array;
   readAov(name: 'ids'): Int32Array;
   /** feature-guided a-trous de-noise of the running mean (include/mi3pt.h: mi3pt_denoise_guided); renders the feature images itself when
-   *  none are current.  sigmaColor null: 2 / sqrt(frames in the mean).  present: also draw the canvas from the filtered image */
+   *  none are current.  sigmaColor null: 2 / sqrt(frames in the mean).  present: also draw the canvas from the filtered image.
+   *  variance true (MI3PT_GUIDED_VARIANCE; needs setMoments(true)): the colour weight follows the per-pixel variance of the mean and
+   *  sigmaColor null is 2; 'auto': true when the moments image is on and at least VARIANCE_AUTO_FRAMES frames are in the mean; default false */
   denoiseGuided(options?: { levels?: number; sigmaColor?: number | null; sigmaNormal?: number; sigmaAlbedo?: number; sigmaPlane?: number;
-    present?: boolean }): void;
+    present?: boolean; variance?: boolean | 'auto' }): void;
   /** localRows x width x 4, row 0 = bottom: the filtered image of the last denoiseGuided */
   readGuided(): Float32Array;
+  /** localRows x width, row 0 = bottom: the last level's variance of the last denoiseGuided({ variance: true }) */
+  readGuidedVariance(): Float32Array;
+  /** keep the moments image (M2.r, M2.g, M2.b, n: Welford's sums around the running mean; include/mi3pt.h: mi3pt_set_moments) beside the
+   *  accumulation image from now on; it starts at zero.  The mean is bit-identical with and without.  Default off */
+  setMoments(enabled: boolean): void;
+  /** localRows x width x 4, row 0 = bottom */
+  readMoments(): Float32Array;
   counters(): { rays: number; boxTests: number; triTests: number; hits: number; misses: number; stackOverflows: number; pixels: number };
   /** src/main.ts:351-356: the presented canvas as PNG bytes (written to `file` when given) */
   screenshot(file?: string): Buffer;
@@ -152,3 +161,5 @@ export function placeModel(model: Object3D, material?: RaytracingMaterial): Obje
 export function boundsOfObject(object: Object3D): { min: Vector3; max: Vector3 };
 export function encodePNG(rgba: Uint8Array, width: number, height: number): Buffer;
 export const AOV_NAMES: Array<'albedo' | 'normal' | 'position' | 'ids'>;
+/** denoiseGuided({ variance: 'auto' }) uses the variance mode from this many frames in the mean on */
+export const VARIANCE_AUTO_FRAMES: number;

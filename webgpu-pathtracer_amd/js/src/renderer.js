@@ -14,6 +14,7 @@ const { FloatType } = require('./scene');
 
 const TEX_OUTPUT = 0, TEX_ACCUMULATION = 1, TEX_CANVAS = 2;
 const AOV_NAMES = ['albedo', 'normal', 'position', 'ids'];      // mi3pt_aov, include/mi3pt.h
+const VARIANCE_AUTO_FRAMES = 8;      // denoiseGuided({ variance: 'auto' }): frames in the mean from which the per-pixel variance steers the filter (a choice: DESIGN.md 3)
 
 let nativeModule = null;
 function loadNative() {
@@ -51,6 +52,7 @@ class Renderer {
     this.listeners = new Map();
     this._sceneVersion = 0;      // scene uploads so far; with the camera and the size: what the feature images depend on
     this._aovKey = null;         // ... as they were when all four feature images were last rendered (denoiseGuided)
+    this._moments = false;       // setMoments: the moments image is kept beside the running mean
     this.tile = args.tile || { rank: 0, nranks: 1, blockRows: 8 };
     if (this.options.enableTimestampQuery) this.native.enableTiming(this.handle, 1);
     this.passes = {
@@ -228,14 +230,29 @@ class Renderer {
   // undefined / null: 2 / sqrt(frames in the mean) -- the noise of the mean falls with the root of its frames.  The feature images are
   // rendered first unless all four are current for the camera and scene of the last update() at this size.  The accumulation image is
   // untouched.
+  // variance: true (MI3PT_GUIDED_VARIANCE; needs setMoments(true) before the frames were sampled): the colour weight follows the per-pixel
+  // variance of the mean, sigmaColor defaults to 2, readGuidedVariance() returns the filtered variance; false (the default): as above;
+  // 'auto': true when the moments image is on and at least VARIANCE_AUTO_FRAMES frames are in the mean (below that a variance from so few
+  // samples is itself noise), false otherwise.
   denoiseGuided(options) {
-    const o = Object.assign({ levels: 3, sigmaColor: null, sigmaNormal: 0.35, sigmaAlbedo: 0.1, sigmaPlane: 0.05, present: false }, options || {});
+    const o = Object.assign({ levels: 3, sigmaColor: null, sigmaNormal: 0.35, sigmaAlbedo: 0.1, sigmaPlane: 0.05, present: false, variance: false }, options || {});
+    const frames = Math.max(1, this._frame - 1);
+    if (o.variance !== true && o.variance !== false && o.variance !== 'auto') throw new Error("denoiseGuided: variance must be true, false or 'auto'");
+    const variance = o.variance === 'auto' ? this._moments && frames >= VARIANCE_AUTO_FRAMES : o.variance;
     this.passes.raytrace.update();
     if (this._aovKey === null || this._aovKey !== this._aovKeyNow()) this.renderAovs();
-    const sigmaColor = o.sigmaColor === null || o.sigmaColor === undefined ? 2 / Math.sqrt(Math.max(1, this._frame - 1)) : o.sigmaColor;
+    const sigmaColor = o.sigmaColor === null || o.sigmaColor === undefined ? (variance ? 2 : 2 / Math.sqrt(frames)) : o.sigmaColor;
     if (o.present) this.passes.fullscreen.update();
-    this.native.denoiseGuided(this.handle, o.levels, sigmaColor, o.sigmaNormal, o.sigmaAlbedo, o.sigmaPlane, o.present ? 1 : 0);
+    this.native.denoiseGuided(this.handle, o.levels, sigmaColor, o.sigmaNormal, o.sigmaAlbedo, o.sigmaPlane, (o.present ? 1 : 0) | (variance ? 2 : 0));
   }
+  // localRows x width floats: the last level's variance of the last denoiseGuided({ variance: true })
+  readGuidedVariance() { return this.native.readGuidedVariance(this.handle, this.localRows * this._width); }
+  // ---- the moments image (no counterpart in the reference): (M2.r, M2.g, M2.b, n) -- Welford's sums around the running mean, include/mi3pt.h:
+  // mi3pt_set_moments -- kept beside the accumulation image from now on (it starts at zero: enable it before sampling starts, or reset()).
+  // The mean is bit-identical with and without.
+  setMoments(enabled) { this.native.setMoments(this.handle, enabled ? 1 : 0); this._moments = !!enabled; }
+  // localRows x width x 4 floats; row 0 = bottom of the picture
+  readMoments() { return this.native.readMoments(this.handle, this.localRows * this._width); }
   // localRows x width x 4 floats: the filtered image of the last denoiseGuided; row 0 = bottom of the picture
   readGuided() { return this.native.readGuided(this.handle, this.localRows * this._width); }
   // localRows x width x 4: Float32Array, Int32Array for 'ids' (triangle, material, hit, 0); row 0 = bottom of the picture
@@ -296,4 +313,4 @@ function encodePNG(rgba, width, height) {
     chunk('IDAT', zlib.deflateSync(raw)), chunk('IEND', Buffer.alloc(0))]);
 }
 
-module.exports = { Renderer, loadNative, encodePNG, AOV_NAMES };
+module.exports = { Renderer, loadNative, encodePNG, AOV_NAMES, VARIANCE_AUTO_FRAMES };

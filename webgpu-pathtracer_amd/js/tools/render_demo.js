@@ -9,6 +9,9 @@
 //                      <prefix>_position.f32 (raw RGBA float: position xyz, t; row 0 = bottom)
 //   --guided           also the feature-guided de-noise of the final mean (renderer.denoiseGuided(), default parameters):
 //                      <prefix>_guided.f32 (raw RGBA float; row 0 = bottom) and <prefix>_guided.png (the canvas drawn from it)
+//   --guided-variance  the moments image on from the start, then renderer.denoiseGuided({ variance: true, present: true }): the outputs of
+//                      --guided from the variance-guided filter, <prefix>_guided_variance.f32 (raw float, one per texel) and
+//                      <prefix>_moments.f32 (raw RGBA float: M2.rgb, n).  Not together with --guided: both write <prefix>_guided.*
 //   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
 //   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
 //                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
@@ -25,6 +28,8 @@ function arg(name, dflt) {
 }
 
 async function main() {
+  const guidedVariance = process.argv.includes('--guided-variance');
+  if (guidedVariance && process.argv.includes('--guided')) throw new Error('--guided and --guided-variance both write <prefix>_guided.f32 / .png: give one of them');
   const width = parseInt(arg('width', '256'), 10), height = parseInt(arg('height', '256'), 10);
   const frames = parseInt(arg('frames', '4'), 10), bounces = parseInt(arg('bounces', String(PARAMS.maxBounces)), 10);
   const envPath = arg('env', null), out = arg('out', 'demo');
@@ -57,6 +62,7 @@ async function main() {
   renderer.setUniforms('raytrace', { maxBounces: bounces, envMapIntensity: PARAMS.envMapIntensity });
   renderer.setUniforms('accumulate', { enabled: PARAMS.accumulate ? 1 : 0 });
   renderer.setUniforms('fullscreen', { denoise: PARAMS.denoise ? 1 : 0, tonemapping: PARAMS.tonemapping });
+  if (guidedVariance) renderer.setMoments(true);
   renderer.resize(width, height);
   const t0 = Date.now();
   for (let i = 0; i < frames + 1; i++) renderer.render(scene, camera);     // the last call only presents
@@ -94,6 +100,13 @@ async function main() {
   if (process.argv.includes('--guided')) {
     renderer.denoiseGuided({ present: true });
     fs.writeFileSync(out + '_guided.f32', Buffer.from(renderer.readGuided().buffer));
+    renderer.screenshot(out + '_guided.png');
+  }
+  if (guidedVariance) {
+    renderer.denoiseGuided({ variance: true, present: true });
+    fs.writeFileSync(out + '_guided.f32', Buffer.from(renderer.readGuided().buffer));
+    fs.writeFileSync(out + '_guided_variance.f32', Buffer.from(renderer.readGuidedVariance().buffer));
+    fs.writeFileSync(out + '_moments.f32', Buffer.from(renderer.readMoments().buffer));
     renderer.screenshot(out + '_guided.png');
   }
   const summary = {

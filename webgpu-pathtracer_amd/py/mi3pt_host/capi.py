@@ -19,6 +19,7 @@ PASS_RAYTRACE, PASS_ACCUMULATE, PASS_FULLSCREEN = 0, 1, 2
 PASS_AOV = 3          # mi3pt_pass_time_us only: the first-hit feature images have no uniform block
 PASS_GUIDED = 4       # mi3pt_pass_time_us only: the feature-guided de-noise (denoise_guided)
 GUIDED_PRESENT = 1    # mi3pt_guided_params.flags: draw the canvas from the filtered image
+GUIDED_VARIANCE = 2   # ... the colour weight steered by the per-pixel variance of the mean (needs set_moments(True))
 # mi3pt_aov: the first-hit feature images (render_aovs takes an OR of 1 << AOV_*)
 AOV_ALBEDO, AOV_NORMAL, AOV_POSITION, AOV_IDS, AOV_COUNT = 0, 1, 2, 3, 4
 AOV_ALL = (1 << AOV_COUNT) - 1
@@ -53,6 +54,7 @@ SYMBOLS = (
     "mi3pt_tile_global_row", "mi3pt_tile_owner",
     "mi3pt_render_aovs", "mi3pt_read_aov", "mi3pt_aov_device_ptr",
     "mi3pt_denoise_guided", "mi3pt_read_guided", "mi3pt_guided_device_ptr",
+    "mi3pt_set_moments", "mi3pt_read_moments", "mi3pt_write_moments", "mi3pt_moments_device_ptr", "mi3pt_read_guided_variance",
 )
 
 
@@ -115,6 +117,11 @@ def load_library(path=None):
     lib.mi3pt_denoise_guided.argtypes = [c_void_p, ctypes.POINTER(GuidedParams)]
     lib.mi3pt_read_guided.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.mi3pt_guided_device_ptr.argtypes = [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]
+    lib.mi3pt_set_moments.argtypes = [c_void_p, c_int]
+    lib.mi3pt_read_moments.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_write_moments.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_moments_device_ptr.argtypes = [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]
+    lib.mi3pt_read_guided_variance.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.mi3pt_enable_timing.argtypes = [c_void_p, c_int]
     lib.mi3pt_pass_time_us.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]
     lib.mi3pt_raytrace_launch_stats.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
@@ -455,6 +462,36 @@ class Context:
         context's stream) before reading it.  Valid until the next denoise_guided or resize."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         self._c(self.lib.mi3pt_guided_device_ptr(self.handle, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def read_guided_variance(self):
+        """The last level's variance image of a denoise_guided with GUIDED_VARIANCE as (rows, width) float32."""
+        out = np.empty((self.local_rows, self.width), np.float32)
+        self._c(self.lib.mi3pt_read_guided_variance(self.handle, _ptr(out), out.size))
+        return out
+
+    def set_moments(self, enabled=True):
+        """Keep the moments image (M2.rgb, n: Welford's sums around the running mean) beside the accumulation image from now
+        on; allocates and zeroes it, False frees it.  The mean is bit-identical with and without."""
+        self._c(self.lib.mi3pt_set_moments(self.handle, int(bool(enabled))))
+
+    def read_moments(self):
+        """The moments image as (rows, width, 4) float32: M2.r, M2.g, M2.b, n.  rows = this rank's compact rows; a device
+        group returns the whole image."""
+        out = np.empty((self.local_rows, self.width, 4), np.float32)
+        self._c(self.lib.mi3pt_read_moments(self.handle, _ptr(out), out.nbytes))
+        return out
+
+    def write_moments(self, image):
+        """Load a saved moments image (checkpoint / resume; after write_texture, which zeroes it)."""
+        a = np.ascontiguousarray(image, np.float32)
+        self._c(self.lib.mi3pt_write_moments(self.handle, _ptr(a), a.nbytes))
+
+    def moments_device_ptr(self):
+        """(device pointer, bytes) of the moments image, for zero-copy hand-off; sync() before reading it.  Valid until the
+        next resize or set_moments."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._c(self.lib.mi3pt_moments_device_ptr(self.handle, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
 
     def bind_accumulation(self, dev_ptr, nbytes):

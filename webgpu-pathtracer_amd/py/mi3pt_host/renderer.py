@@ -193,6 +193,7 @@ class Renderer:
         self.presentEveryFrame = True      # headless hosts may skip the fullscreen pass
         self._sceneVersion = 0             # scene uploads so far; with the camera and the size: what the feature images depend on
         self._aovKey = None                # ... as they were when all four feature images were last rendered (denoiseGuided)
+        self._moments = False              # setMoments: the moments image is kept beside the running mean
         self.passes = {"raytrace": RaytracePass(self), "accumulate": AccumulatePass(self),
                        "fullscreen": FullscreenPass(self)}
         if self.options["enableTimestampQuery"]:
@@ -377,20 +378,46 @@ class Renderer:
         return (u[0:12], u[32:44], u[48:64], self._sceneVersion, self._width, self._height)
 
     # ---- feature-guided de-noise of the running mean (no counterpart in the reference) ----
-    def denoiseGuided(self, levels=3, sigmaColor=None, sigmaNormal=0.35, sigmaAlbedo=0.1, sigmaPlane=0.05, present=False):
+    VARIANCE_AUTO_FRAMES = 8       # variance="auto": frames in the mean from which the per-pixel variance steers the filter (a choice: DESIGN.md 3)
+
+    def denoiseGuided(self, levels=3, sigmaColor=None, sigmaNormal=0.35, sigmaAlbedo=0.1, sigmaPlane=0.05, present=False, variance=False):
         """Filter the running mean with the edge-avoiding a-trous filter of include/mi3pt.h (mi3pt_denoise_guided); readGuided()
-        returns the result, present=True also draws the canvas from it.  sigmaColor None: 2 / sqrt(frames in the mean) -- the
-        noise of the mean falls with the root of its frames.  The feature images are rendered first unless all four are current
-        for the camera and scene of the last update() at this size.  The accumulation image is untouched."""
+        returns the result, present=True also draws the canvas from it.  variance False: sigmaColor None = 2 / sqrt(frames in the
+        mean) -- the noise of the mean falls with the root of its frames.  variance True (MI3PT_GUIDED_VARIANCE; needs
+        setMoments(True) before the frames were sampled): the colour weight follows the per-pixel variance of the mean, sigmaColor
+        None = 2, readGuidedVariance() returns the filtered variance.  variance "auto": True when the moments image is on and at
+        least VARIANCE_AUTO_FRAMES frames are in the mean (below that a variance from so few samples is itself noise), else False.
+        The feature images are rendered first unless all four are current for the camera and scene of the last update() at this
+        size.  The accumulation image is untouched."""
+        frames = max(1, self._frame - 1)
+        if variance == "auto":
+            variance = self._moments and frames >= self.VARIANCE_AUTO_FRAMES
+        elif not isinstance(variance, bool):
+            raise ValueError("variance must be True, False or 'auto'")
         self.passes["raytrace"].update()
         if self._aovKey is None or self._aovKey != self._aovKeyNow():
             self.renderAovs()
         if sigmaColor is None:
-            sigmaColor = 2.0 / math.sqrt(max(1, self._frame - 1))
+            sigmaColor = 2.0 if variance else 2.0 / math.sqrt(frames)
         if present:
             self.passes["fullscreen"].update()
         self.ctx.denoise_guided(levels, sigmaColor, sigmaNormal, sigmaAlbedo, sigmaPlane,
-                                capi.GUIDED_PRESENT if present else 0)
+                                (capi.GUIDED_PRESENT if present else 0) | (capi.GUIDED_VARIANCE if variance else 0))
+
+    def readGuidedVariance(self):
+        """(rows, width) float32: the last level's variance of the last denoiseGuided(variance=True)."""
+        return self.ctx.read_guided_variance()
+
+    # ---- the moments image: the spread of the frames around the running mean (no counterpart in the reference) ----
+    def setMoments(self, enabled=True):
+        """Keep (M2.rgb, n) -- Welford's sums around the running mean, include/mi3pt.h: mi3pt_set_moments -- beside the accumulation
+        image from now on (the image starts at zero: enable it before sampling starts, or reset()).  The mean is bit-identical."""
+        self.ctx.set_moments(bool(enabled))
+        self._moments = bool(enabled)
+
+    def readMoments(self):
+        """(rows, width, 4) float32: M2.r, M2.g, M2.b, n."""
+        return self.ctx.read_moments()
 
     def readGuided(self):
         """(rows, width, 4) float32: the filtered image of the last denoiseGuided."""
