@@ -23,8 +23,23 @@
  *   - uploads COPY at call time (queue.writeBuffer / writeTexture semantics); the
  *     caller keeps ownership of its memory.
  *   - mi3pt_submit() is asynchronous and stream ordered, like
- *     `device.queue.submit([encoder.finish()])` (renderer.ts:389-390); reads and
- *     mi3pt_sync() are the only blocking calls.
+ *     `device.queue.submit([encoder.finish()])` (renderer.ts:389-390).  A context has ONE stream -- its own, or the
+ *     caller's (mi3pt_set_stream) -- and everything that can be observed happens in that stream's order; the raytrace
+ *     kernels run on internal streams tied to it by events in both directions, which no caller can see.
+ *     STREAM ORDERED, returning before the device has run anything: mi3pt_submit, mi3pt_submit_frames, mi3pt_flush,
+ *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided.  mi3pt_set_uniforms, the setters of
+ *     modes and options and the *_device_ptr getters start no device work of their own (those that observe state launch
+ *     the frame queue first).  A host that has set its own stream may therefore enqueue its work in front of and behind
+ *     these calls on that stream -- fill a bound accumulation tensor, copy out of a *_device_ptr image -- and wait once.
+ *     BLOCKING (the host waits for the context's stream, at least): every upload and mi3pt_write_* (copy at call time),
+ *     mi3pt_resize (the internal streams too), mi3pt_set_stream (the stream it leaves), mi3pt_bind_accumulation,
+ *     mi3pt_set_moments when it changes the state, every mi3pt_read_*, mi3pt_sync, mi3pt_get_counters, mi3pt_pass_time_us,
+ *     mi3pt_raytrace_launch_stats / _span, the mi3pt_debug_* probes, mi3pt_device_build_bvh, mi3pt_destroy.
+ *     Three things make a stream-ordered call wait ONCE: the first raytrace submit or mi3pt_render_aovs after a scene
+ *     upload (or a change of kernel variant) compiles the scene and reads it back; the first call that needs an image
+ *     allocates it, and a launch deeper than any before on this context replaces its radiance slots (freeing waits for
+ *     the whole device, the caller's other streams included); with timing enabled a launch waits for the one two
+ *     before it.  A job of a shape the context has run before waits for nothing (tests/test_gpu_streams.py).
  *   - one host thread per context; no callbacks.
  *   - there is NO CPU fallback: without a HIP device mi3pt_create() fails with
  *     MI3PT_ERR_NO_DEVICE.  The mi3pt_host_* functions are the reference's own
@@ -184,8 +199,16 @@ int mi3pt_create_group(const int *devices, int ndevices, int block_rows, mi3pt_c
 int mi3pt_group_size(mi3pt_ctx *ctx, int *members);
 int mi3pt_group_member(mi3pt_ctx *ctx, int index, mi3pt_ctx **member);
 
-/* Run on a caller-owned hipStream_t (e.g. torch's current stream) instead of the
- * context's own; NULL restores the internal stream. */
+/* Run on a caller-owned hipStream_t instead of the context's own: from now on everything the conventions above call stream
+ * ordered is enqueued on it.  Launches what is queued on the stream the context leaves and BLOCKS until that stream is idle (not
+ * the new one: work already on hip_stream stays in front of whatever the context sends there).
+ * Handle 0 / NULL is NOT the HIP default stream: it restores the context's internal stream, which is created hipStreamNonBlocking
+ * and is ordered with nothing of the caller's -- in particular not with work on torch's default stream, whose handle
+ * (torch.cuda.current_stream().cuda_stream while no other stream is current) IS 0: a host that passes it gets MI3PT_OK and no
+ * ordering.  Pass a stream you created -- hipStreamCreate*; with torch a torch.cuda.Stream() s, made current for the tensor
+ * operations that go with the context's work (`with torch.cuda.stream(s):`), handle s.cuda_stream, as bench.py does.
+ * The stream stays the caller's: keep it alive until mi3pt_destroy or the next mi3pt_set_stream; mi3pt_destroy waits for it and
+ * leaves it usable.  Refused for a device group.  Held to the oracle by tests/test_gpu_streams.py. */
 int mi3pt_set_stream(mi3pt_ctx *ctx, void *hip_stream);
 int mi3pt_set_storage(mi3pt_ctx *ctx, int storage /* mi3pt_storage */);
 
