@@ -38,6 +38,36 @@ int pt_set_error(int code, const std::string &msg)
             return pt_set_error(MI3PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// GPU time of one pass: an event pair around it on the pass's stream, created by the first timed call (a context that never times a
+// pass creates none).  The batched raytrace launches keep their own events (ev_rt: per parity, folded into running totals).
+struct PassTimer {
+    hipEvent_t ev[2] = {};
+    bool recorded = false;
+    hipError_t begin(hipStream_t s)
+    {
+        for (hipEvent_t &e : ev)
+            if (!e)
+                if (hipError_t r = hipEventCreate(&e)) return r;
+        return hipEventRecord(ev[0], s);
+    }
+    hipError_t end(hipStream_t s)
+    {
+        const hipError_t r = hipEventRecord(ev[1], s);
+        recorded = r == hipSuccess;
+        return r;
+    }
+    int elapsed_us(mi3pt_ctx *ctx, float *us, const char *not_timed);      // (MI3PT_ERR_STATE with that text while nothing is recorded)
+    void forget() { recorded = false; }
+    void destroy()
+    {
+        for (hipEvent_t &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        recorded = false;
+    }
+};
+
 struct mi3pt_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -262,8 +292,7 @@ struct mi3pt_ctx {
     uint8_t presented_fs[MI3PT_FULLSCREEN_UNIFORMS_SIZE] = {};
 
     bool timing = false;
-    hipEvent_t ev[3][2] = {};
-    bool ev_recorded[3] = { false, false, false };
+    PassTimer pass_timer[3];             // raytrace (a launch mi3pt_submit runs at once), accumulate, fullscreen: of the last submit
 
     // First-hit feature images (mi3pt_render_aovs): each local_rows x width x 16 B, allocated by the first call that asks for it and
     // freed with the textures; aov_valid: rendered (a group's presenting context: gathered) since the last resize.  The pass runs on
@@ -271,15 +300,13 @@ struct mi3pt_ctx {
     // or writes, so the frame queue is neither flushed nor ordered against it.
     float4 *d_aov[MI3PT_AOV_COUNT] = {};
     bool aov_valid[MI3PT_AOV_COUNT] = {};
-    hipEvent_t ev_aov[2] = {};           // created with the first timed call
-    bool ev_aov_recorded = false;
+    PassTimer aov_timer;
     // The feature-guided de-noise (mi3pt_denoise_guided): two ping-pong images and the packed normal + hit records, each local_rows x width
     // x 16 B, allocated by the first call and freed with the textures; guided_result: the image the last level wrote (null: no filter since
     // the last resize).
     float4 *d_guided[2] = {}, *d_guided_nh = nullptr;
     const float4 *guided_result = nullptr;
-    hipEvent_t ev_guided[2] = {};        // created with the first timed call
-    bool ev_guided_recorded = false;
+    PassTimer guided_timer;
     // MI3PT_GUIDED_VARIANCE: two ping-pong variance images, local_rows x width floats, allocated by the first call with the flag and freed
     // with the textures; guided_var_result: the one the last level wrote (null: the last filter ran without the flag)
     float *d_guided_var[2] = {};
@@ -528,6 +555,50 @@ static hipError_t ctx_wait(mi3pt_ctx *ctx, hipStream_t s, hipEvent_t ev, const c
 static hipError_t ctx_stream_sync(mi3pt_ctx *ctx, hipStream_t s, const char *why = "stream wait") { return ctx_wait(ctx, s, nullptr, why); }
 static hipError_t ctx_event_sync(mi3pt_ctx *ctx, hipEvent_t ev, const char *why = "event wait") { return ctx_wait(ctx, nullptr, ev, why); }
 
+int PassTimer::elapsed_us(mi3pt_ctx *ctx, float *us, const char *not_timed)
+{
+    if (!recorded) return pt_set_error(MI3PT_ERR_STATE, not_timed);
+    HIP_TRY(ctx_event_sync(ctx, ev[1]));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    *us = ms * 1000.0f;
+    return MI3PT_OK;
+}
+
+// ---- image planes: the local_rows x width images of a context (radiance, mean, feature images, filter images, moments) ----
+static size_t plane_texels(const mi3pt_ctx *ctx) { return (size_t)ctx->local_rows * ctx->width; }
+static size_t plane_bytes(const mi3pt_ctx *ctx) { return plane_texels(ctx) * 16; }
+// (a rank without rows still owns a pointer per image: 16 bytes)
+template <class T> static hipError_t alloc_plane(T **plane, size_t nbytes) { return hipMalloc((void **)plane, nbytes ? nbytes : 16); }
+
+// Blocking copies between device memory on the context's stream and (pageable) host memory.  Such a copy blocks the host until the
+// stream gets there: the bounded wait comes first.  Nothing to copy: the stream is not touched.
+static hipError_t read_plane(mi3pt_ctx *ctx, const void *src, size_t nbytes, void *dst)
+{
+    if (nbytes == 0) return hipSuccess;
+    hipError_t e = ctx_stream_sync(ctx, ctx->stream, "read-back");
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+    return e;
+}
+
+static hipError_t write_plane(mi3pt_ctx *ctx, void *dst, const void *src, size_t nbytes)
+{
+    if (nbytes == 0) return hipSuccess;
+    hipError_t e = ctx_stream_sync(ctx, ctx->stream, "write-back");
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);      // copy-on-call
+    return e;
+}
+
+// what every *_device_ptr entry point ends with
+static int hand_out_plane(const mi3pt_ctx *ctx, const void *plane, void **dev_ptr, size_t *nbytes)
+{
+    *dev_ptr = const_cast<void *>(plane);
+    if (nbytes) *nbytes = plane_bytes(ctx);
+    return MI3PT_OK;
+}
+
 extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
 {
     if (!out_ctx) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
@@ -577,8 +648,6 @@ extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
     CREATE_TRY(hipEventCreateWithFlags(&ctx->main_mark, hipEventDisableTiming));
     for (int k = 0; k < 2; k++)
         for (int j = 0; j < 2; j++) CREATE_TRY(hipEventCreate(&ctx->ev_rt[k][j]));
-    for (int p = 0; p < 3; p++)
-        for (int k = 0; k < 2; k++) CREATE_TRY(hipEventCreate(&ctx->ev[p][k]));
     CREATE_TRY(hipEventCreate(&ctx->ev_span_start));
     CREATE_TRY(hipEventCreateWithFlags(&ctx->cost_event, hipEventDisableTiming));
     for (int k = 0; k < 2; k++) CREATE_TRY(hipEventCreateWithFlags(&ctx->perm_used[k], hipEventDisableTiming));
@@ -670,12 +739,12 @@ static void free_textures(mi3pt_ctx *ctx)
         ctx->d_aov[k] = nullptr;
         ctx->aov_valid[k] = false;
     }
-    ctx->ev_aov_recorded = false;
+    ctx->aov_timer.forget();
     for (void *p : { (void *)ctx->d_guided[0], (void *)ctx->d_guided[1], (void *)ctx->d_guided_nh })
         if (p) (void)hipFree(p);
     ctx->d_guided[0] = ctx->d_guided[1] = ctx->d_guided_nh = nullptr;
     ctx->guided_result = nullptr;
-    ctx->ev_guided_recorded = false;
+    ctx->guided_timer.forget();
     for (void *p : { (void *)ctx->d_guided_var[0], (void *)ctx->d_guided_var[1], (void *)ctx->d_moments })
         if (p) (void)hipFree(p);
     ctx->d_guided_var[0] = ctx->d_guided_var[1] = nullptr;
@@ -709,9 +778,7 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     for (void *p : { ctx->d_cw8, ctx->d_tripk8, ctx->d_cwide, ctx->d_tripk64, ctx->d_wide, ctx->d_tris, ctx->d_tris_perm, ctx->d_nodes, ctx->d_mats, ctx->d_env, ctx->d_cdf, ctx->d_packets, ctx->d_tripk, ctx->d_leaf_rank,
                      (void *)ctx->d_tile_counter, (void *)ctx->d_drain_flag, (void *)ctx->d_wave_times, (void *)ctx->d_stack_overflow, (void *)ctx->d_park, (void *)ctx->d_service, ctx->d_fs_taps })
         if (p) (void)hipFree(p);
-    for (int p = 0; p < 3; p++)
-        for (int k = 0; k < 2; k++)
-            if (ctx->ev[p][k]) (void)hipEventDestroy(ctx->ev[p][k]);
+    for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer }) t->destroy();
     for (int k = 0; k < 2; k++) {
         if (ctx->rt_stream[k]) (void)hipStreamDestroy(ctx->rt_stream[k]);
         if (ctx->rt_done[k]) (void)hipEventDestroy(ctx->rt_done[k]);
@@ -722,10 +789,6 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     for (int k = 0; k < 3; k++)
         if (ctx->acc_done[k]) (void)hipEventDestroy(ctx->acc_done[k]);
     if (ctx->main_mark) (void)hipEventDestroy(ctx->main_mark);
-    for (int k = 0; k < 2; k++)
-        if (ctx->ev_aov[k]) (void)hipEventDestroy(ctx->ev_aov[k]);
-    for (int k = 0; k < 2; k++)
-        if (ctx->ev_guided[k]) (void)hipEventDestroy(ctx->ev_guided[k]);
     if (ctx->ev_span_start) (void)hipEventDestroy(ctx->ev_span_start);
     if (ctx->cost_event) (void)hipEventDestroy(ctx->cost_event);
     for (int k = 0; k < 2; k++)
@@ -793,7 +856,7 @@ static void recompute_batch_cap(mi3pt_ctx *ctx)
     if (ctx->width == 0) return;
     // (a band of 1 / k of the image batches k times as many frames per launch, like a rank of a k-way tile split)
     ctx->batch_cap = batch_limit(ctx, ctx->nranks);
-    const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
+    const size_t tex_bytes = plane_bytes(ctx);
     size_t free_b = 0, total_b = 0;
     if (tex_bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         const size_t per_frame = (size_t)ctx->slot_sets * tex_bytes;
@@ -1109,7 +1172,7 @@ static pt::Tile tile_of(const mi3pt_ctx *ctx)
 
 static int zero_textures(mi3pt_ctx *ctx)
 {
-    const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
+    const size_t tex_bytes = plane_bytes(ctx);
     const size_t canvas_px = (size_t)ctx->width * ctx->height;
     if (tex_bytes) {
         // (the batch slots need no clearing: a launch writes every texel the ordered mean reads)
@@ -1166,12 +1229,12 @@ extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
     float4 *radiance = nullptr, *accum = nullptr, *canvas = nullptr, *moments = nullptr;
     uint32_t *canvas8 = nullptr;
     uint64_t *counters = nullptr;
-    hipError_t e = hipMalloc((void **)&radiance, tex_bytes ? tex_bytes : 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&accum, tex_bytes ? tex_bytes : 16);
+    hipError_t e = alloc_plane(&radiance, tex_bytes);
+    if (e == hipSuccess) e = alloc_plane(&accum, tex_bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&canvas, canvas_px * 16);
     if (e == hipSuccess) e = hipMalloc((void **)&canvas8, canvas_px * 4);
     if (e == hipSuccess) e = hipMalloc((void **)&counters, cbytes);
-    if (e == hipSuccess && ctx->moments) e = hipMalloc((void **)&moments, tex_bytes ? tex_bytes : 16);
+    if (e == hipSuccess && ctx->moments) e = alloc_plane(&moments, tex_bytes);
     if (e == hipSuccess) e = hipMemsetAsync(counters, 0, cbytes, ctx->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -1372,9 +1435,7 @@ static int prepare_cull(mi3pt_ctx *ctx)
         HIP_TRY(hipMalloc((void **)&packed, nt * sizeof(pt::TriVerts)));
         pt::launch_pack_vertices(static_cast<const float4 *>(ctx->d_tris), packed, (uint32_t)nt, ctx->stream);
         hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream, "read-back");      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-        if (e == hipSuccess) e = hipMemcpyAsync(tris.data(), packed, nt * sizeof(pt::TriVerts), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+        if (e == hipSuccess) e = read_plane(ctx, packed, nt * sizeof(pt::TriVerts), tris.data());
         (void)hipFree(packed);
         if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("cull analysis: reading the vertices back: ") + hipGetErrorString(e));
     }
@@ -1506,7 +1567,7 @@ static pt::RtLaunch build_launch(const mi3pt_ctx *ctx, const uint8_t *u, const p
     L.acc = acc;
     L.tile = tile_of(ctx);
     L.radiance = ctx->d_radiance;
-    L.slot_pixels = (size_t)ctx->local_rows * ctx->width;
+    L.slot_pixels = plane_texels(ctx);
     L.nframes = 1;
     L.accum = ctx->d_accum;
     L.block_counters = ctx->d_block_counters;
@@ -1582,7 +1643,7 @@ static int collect_rt_time(mi3pt_ctx *ctx, int par)
 static int ensure_slots(mi3pt_ctx *ctx, int par /* slot set */, int n)
 {
     if (ctx->slots_alloc[par] >= n) return MI3PT_OK;
-    const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
+    const size_t tex_bytes = plane_bytes(ctx);
     // one frame: one slot; up to eight: eight (a host that queues a few frames at a time does not pay for -- or wait
     // seconds for the allocation of -- 2 x 64 ... 256 full images it never fills); more: the full launch depth at
     // once, so that a batching caller allocates once and not again in the middle of its job
@@ -1600,11 +1661,11 @@ static int ensure_slots(mi3pt_ctx *ctx, int par /* slot set */, int n)
     }
     if (want < n) want = n;
     float4 *fresh = nullptr;
-    hipError_t e = hipMalloc((void **)&fresh, tex_bytes ? tex_bytes * (size_t)want : 16);
+    hipError_t e = alloc_plane(&fresh, tex_bytes * (size_t)want);
     if (e != hipSuccess && want > n) {          // not enough memory for the full depth: take what this batch needs
         (void)hipGetLastError();
         want = n;
-        e = hipMalloc((void **)&fresh, tex_bytes ? tex_bytes * (size_t)want : 16);
+        e = alloc_plane(&fresh, tex_bytes * (size_t)want);
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -1619,7 +1680,7 @@ static int ensure_slots(mi3pt_ctx *ctx, int par /* slot set */, int n)
         for (int other = 0; other < ctx->slot_sets; other++) {
             if (other == par || ctx->slots_alloc[other] >= want) continue;
             float4 *more = nullptr;
-            if (hipMalloc((void **)&more, tex_bytes ? tex_bytes * (size_t)want : 16) != hipSuccess) { (void)hipGetLastError(); break; }
+            if (alloc_plane(&more, tex_bytes * (size_t)want) != hipSuccess) { (void)hipGetLastError(); break; }
             if (ctx->d_slots[other]) (void)hipFree(ctx->d_slots[other]);
             ctx->d_slots[other] = more;
             ctx->slots_alloc[other] = want;
@@ -1971,13 +2032,10 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
         const bool last_run = e == n - 1;
         pt::AccUniforms a = acc;
         a.frame = acc.frame + (uint32_t)k;
-        if (ctx->timing && last_run) HIP_TRY(hipEventRecord(ctx->ev[1][0], ctx->stream));
-        if (ctx->d_moments)
-            pt::launch_accumulate_batch_moments(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, ctx->d_moments, f16, ctx->stream);
-        else
-            pt::launch_accumulate_batch(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, f16, ctx->stream);
+        if (ctx->timing && last_run) HIP_TRY(ctx->pass_timer[1].begin(ctx->stream));
+        pt::launch_accumulate_frames(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, ctx->d_moments, f16, 4096, ctx->stream);
         HIP_TRY(hipGetLastError());
-        if (ctx->timing && last_run) { HIP_TRY(hipEventRecord(ctx->ev[1][1], ctx->stream)); ctx->ev_recorded[1] = true; }
+        if (ctx->timing && last_run) HIP_TRY(ctx->pass_timer[1].end(ctx->stream));
         ctx->accum_version++;
         if (frames[e].present)
             if (int rc = run_fullscreen(ctx, frames[e].u_fs)) return rc;
@@ -2028,7 +2086,7 @@ static int run_fullscreen(mi3pt_ctx *ctx, const uint8_t *u_fs)
     fs.res_x = ldf(u_fs, 0); fs.res_y = ldf(u_fs, 4); fs.aspect = ldf(u_fs, 8);
     fs.scaling = ldf(u_fs, 12); fs.denoise = ldu(u_fs, 16); fs.tonemapping = ldu(u_fs, 20);
     const float4 *tex = ctx->output_is_accum ? ctx->d_accum : ctx->last_radiance;
-    if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[2][0], ctx->stream));
+    if (ctx->timing) HIP_TRY(ctx->pass_timer[2].begin(ctx->stream));
     // (bit patterns compared: a NaN uniform must not rebuild the table every frame, and -0 is not +0 for a quotient)
     const bool taps_current = ctx->fs_taps_valid && std::memcmp(ctx->fs_taps_res, &fs.res_x, 4) == 0 && std::memcmp(ctx->fs_taps_res + 1, &fs.res_y, 4) == 0;
     pt::launch_fullscreen(fs, tex, ctx->width, ctx->height, ctx->width, ctx->height, ctx->d_fs_taps, taps_current, ctx->d_canvas,
@@ -2038,7 +2096,7 @@ static int run_fullscreen(mi3pt_ctx *ctx, const uint8_t *u_fs)
         return pt_set_error(MI3PT_ERR_HIP, std::string("fullscreen launch: ") + hipGetErrorString(e));
     }
     if (fs.denoise == 1u) { ctx->fs_taps_res[0] = fs.res_x; ctx->fs_taps_res[1] = fs.res_y; ctx->fs_taps_valid = true; }
-    if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev[2][1], ctx->stream)); ctx->ev_recorded[2] = true; }
+    if (ctx->timing) HIP_TRY(ctx->pass_timer[2].end(ctx->stream));
     ctx->presented_version = ctx->accum_version;
     std::memcpy(ctx->presented_fs, u_fs, sizeof ctx->presented_fs);
     return MI3PT_OK;
@@ -2076,7 +2134,7 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
         std::memcpy(f.u_acc, ctx->u_acc, sizeof f.u_acc);
         if (!ctx->pending.empty() && !batch_compatible(ctx->pending.back(), f))
             if (int rc = flush_pending(ctx)) return rc;
-        if (ctx->pending.empty()) for (bool &r : ctx->ev_recorded) r = false;
+        if (ctx->pending.empty()) for (PassTimer &t : ctx->pass_timer) t.forget();
         int depth = ctx->batch_cap;
         if (do_fs && !lazy_present) {          // EXACT: this frame's canvas is drawn behind its mean (launch_batch)
             f.present = true;
@@ -2090,7 +2148,7 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
         acc_done = true;
     } else {
         if (int rc = flush_pending(ctx)) return rc;      // anything but a queued frame runs after the queue
-        for (bool &r : ctx->ev_recorded) r = false;
+        for (PassTimer &t : ctx->pass_timer) t.forget();
         if (do_rt) {
             pt::RtLaunch L = build_launch(ctx, ctx->u_rt, acc);
             // Fuse when the accumulate pass covers exactly the pixels the raytrace pass writes (the per-pixel kernels; the
@@ -2103,10 +2161,10 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
             L.block_counters = ctx->d_block_counters;
             ctx->last_route = pt::raytrace_route(L, variant);
             pt::launch_raytrace_setup(L, fused, variant, ctx->stream);
-            if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[0][0], ctx->stream));
+            if (ctx->timing) HIP_TRY(ctx->pass_timer[0].begin(ctx->stream));
             pt::launch_raytrace(L, fused, variant, ctx->stream);
             HIP_TRY(hipGetLastError());
-            if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev[0][1], ctx->stream)); ctx->ev_recorded[0] = true; }
+            if (ctx->timing) HIP_TRY(ctx->pass_timer[0].end(ctx->stream));
             ctx->last_radiance = ctx->d_radiance;
             ctx->output_is_accum = fused;
             ctx->main_dirty = true;     // a later batch must not overtake this kernel
@@ -2115,11 +2173,10 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
         }
     }
     if (do_acc && !acc_done) {
-        if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[1][0], ctx->stream));
-        if (ctx->d_moments) pt::launch_accumulate_moments(acc, tile, ctx->last_radiance, ctx->d_accum, ctx->d_moments, f16, ctx->stream);
-        else pt::launch_accumulate(acc, tile, ctx->last_radiance, ctx->d_accum, f16, ctx->stream);
+        if (ctx->timing) HIP_TRY(ctx->pass_timer[1].begin(ctx->stream));
+        pt::launch_accumulate_frames(acc, tile, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, 2048, ctx->stream);
         HIP_TRY(hipGetLastError());
-        if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev[1][1], ctx->stream)); ctx->ev_recorded[1] = true; }
+        if (ctx->timing) HIP_TRY(ctx->pass_timer[1].end(ctx->stream));
         ctx->output_is_accum = true;   // accumulate.ts:171-175 copies the mean into outputTexture
         ctx->main_dirty = true;
         ctx->accum_version++;
@@ -2223,11 +2280,11 @@ extern "C" int mi3pt_read_texture(mi3pt_ctx *ctx, int which, float *dst, size_t 
     switch (which) {
     case MI3PT_TEX_OUTPUT:
         src = ctx->output_is_accum ? ctx->d_accum : ctx->last_radiance;
-        need = (size_t)ctx->local_rows * ctx->width * 4;
+        need = plane_texels(ctx) * 4;
         break;
     case MI3PT_TEX_ACCUMULATION:
         src = ctx->d_accum;
-        need = (size_t)ctx->local_rows * ctx->width * 4;
+        need = plane_texels(ctx) * 4;
         break;
     case MI3PT_TEX_CANVAS:
         if (int rc = settle_canvas(ctx)) return rc;
@@ -2238,10 +2295,7 @@ extern "C" int mi3pt_read_texture(mi3pt_ctx *ctx, int which, float *dst, size_t 
         return pt_set_error(MI3PT_ERR_INVALID, "unknown texture");
     }
     if (nfloats != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the texture");
-    if (need == 0) return MI3PT_OK;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    HIP_TRY(hipMemcpyAsync(dst, src, need * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    HIP_TRY(read_plane(ctx, src, need * 4, dst));
     return MI3PT_OK;
 }
 
@@ -2256,14 +2310,10 @@ extern "C" int mi3pt_write_texture(mi3pt_ctx *ctx, int which, const float *src, 
     if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "write before resize");
     if (which != MI3PT_TEX_ACCUMULATION && which != MI3PT_TEX_OUTPUT)
         return pt_set_error(MI3PT_ERR_INVALID, "only the accumulation / output image can be written");
-    const size_t need = (size_t)ctx->local_rows * ctx->width * 4;
-    if (nfloats != need) return pt_set_error(MI3PT_ERR_INVALID, "source size does not match the texture");
-    if (need) {
-        HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "write-back"));
-        HIP_TRY(hipMemcpyAsync(ctx->d_accum, src, need * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (ctx->d_moments) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, need * 4, ctx->stream));      // (a mean from outside: its spread is unknown)
-        HIP_TRY(ctx_stream_sync(ctx, ctx->stream));      // copy-on-call
-    }
+    const size_t need = plane_bytes(ctx);
+    if (nfloats != need / 4) return pt_set_error(MI3PT_ERR_INVALID, "source size does not match the texture");
+    if (ctx->d_moments && need) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, need, ctx->stream));      // (a mean from outside: its spread is unknown)
+    HIP_TRY(write_plane(ctx, ctx->d_accum, src, need));
     ctx->output_is_accum = true;      // like the copy-back of accumulate.ts:171-175
     ctx->main_dirty = true;
     ctx->accum_version++;
@@ -2279,9 +2329,7 @@ extern "C" int mi3pt_read_canvas_rgba8(mi3pt_ctx *ctx, uint8_t *dst, size_t nbyt
     const size_t need = (size_t)ctx->width * ctx->height * 4;
     if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the canvas");
     if (int rc = settle_canvas(ctx)) return rc;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    HIP_TRY(hipMemcpyAsync(dst, ctx->d_canvas8, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    HIP_TRY(read_plane(ctx, ctx->d_canvas8, need, dst));
     return MI3PT_OK;
 }
 
@@ -2291,9 +2339,7 @@ extern "C" int mi3pt_accumulation_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, siz
     if (!ctx || !dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "no textures before resize");
     if (int rc = require_idle(ctx)) return rc;
-    *dev_ptr = ctx->d_accum;
-    if (nbytes) *nbytes = (size_t)ctx->local_rows * ctx->width * 16;
-    return MI3PT_OK;
+    return hand_out_plane(ctx, ctx->d_accum, dev_ptr, nbytes);
 }
 
 extern "C" int mi3pt_bind_accumulation(mi3pt_ctx *ctx, void *dev_ptr, size_t nbytes)
@@ -2306,15 +2352,14 @@ extern "C" int mi3pt_bind_accumulation(mi3pt_ctx *ctx, void *dev_ptr, size_t nby
     ctx->accum_version++;
     // (another image becomes the mean: like a mean written from outside, its spread is unknown -- the moments start over)
     auto zero_moments = [&]() -> int {
-        const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
-        if (ctx->d_moments && tex_bytes) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, tex_bytes, ctx->stream));
+        if (ctx->d_moments && plane_bytes(ctx)) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, plane_bytes(ctx), ctx->stream));
         return MI3PT_OK;
     };
     if (!dev_ptr) {
         ctx->d_accum = ctx->d_accum_own;
         return zero_moments();
     }
-    if (nbytes != (size_t)ctx->local_rows * ctx->width * 16)
+    if (nbytes != plane_bytes(ctx))
         return pt_set_error(MI3PT_ERR_INVALID, "external accumulation buffer must be local_rows*width*16 bytes");
     if (reinterpret_cast<uintptr_t>(dev_ptr) % 16)
         return pt_set_error(MI3PT_ERR_INVALID, "external accumulation buffer must be 16-byte aligned");
@@ -2342,9 +2387,9 @@ extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
     if (int rc = check_scene(ctx)) return rc;
     if (int rc = prepare_layout(ctx)) return rc;    // (what a raytrace submit does: no-ops unless the scene changed -- and then no frame is queued)
     if (int rc = prepare_cull(ctx)) return rc;
-    const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
+    const size_t tex_bytes = plane_bytes(ctx);
     for (int k = 0; k < MI3PT_AOV_COUNT; k++)
-        if (((aov_mask >> k) & 1u) && !ctx->d_aov[k]) HIP_TRY(hipMalloc((void **)&ctx->d_aov[k], tex_bytes ? tex_bytes : 16));
+        if (((aov_mask >> k) & 1u) && !ctx->d_aov[k]) HIP_TRY(alloc_plane(&ctx->d_aov[k], tex_bytes));
     pt::AovLaunch A;
     A.scene = scene_refs(ctx);
     const uint8_t *u = ctx->u_rt;
@@ -2363,14 +2408,10 @@ extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
     if (first_hit_walk_is_shipped(ctx)) { walk = 13; stack_worst = ctx->wide_stack_worst; }
     else if (ctx->layout_active) { walk = 1; A.scene.tris = static_cast<const float4 *>(ctx->d_tris); }
     if (tex_bytes) {
-        if (ctx->timing) {
-            for (int k = 0; k < 2; k++)
-                if (!ctx->ev_aov[k]) HIP_TRY(hipEventCreate(&ctx->ev_aov[k]));
-            HIP_TRY(hipEventRecord(ctx->ev_aov[0], ctx->stream));
-        }
+        if (ctx->timing) HIP_TRY(ctx->aov_timer.begin(ctx->stream));
         pt::launch_aovs(A, walk, stack_worst, ctx->leaf_min, ctx->stream);
         HIP_TRY(hipGetLastError());
-        if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev_aov[1], ctx->stream)); ctx->ev_aov_recorded = true; }
+        if (ctx->timing) HIP_TRY(ctx->aov_timer.end(ctx->stream));
     }
     for (int k = 0; k < MI3PT_AOV_COUNT; k++)
         if ((aov_mask >> k) & 1u) ctx->aov_valid[k] = true;
@@ -2392,12 +2433,8 @@ extern "C" int mi3pt_read_aov(mi3pt_ctx *ctx, int which, void *dst, size_t nbyte
     if (int rc = require_ctx(ctx)) return rc;
     if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = aov_image(ctx, which, "mi3pt_read_aov")) return rc;
-    const size_t need = (size_t)ctx->local_rows * ctx->width * 16;
-    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
-    if (need == 0) return MI3PT_OK;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    HIP_TRY(hipMemcpyAsync(dst, ctx->d_aov[which], need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    if (nbytes != plane_bytes(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
+    HIP_TRY(read_plane(ctx, ctx->d_aov[which], nbytes, dst));
     return MI3PT_OK;
 }
 
@@ -2407,9 +2444,7 @@ extern "C" int mi3pt_aov_device_ptr(mi3pt_ctx *ctx, int which, void **dev_ptr, s
     if (int rc = require_ctx(ctx)) return rc;
     if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = aov_image(ctx, which, "mi3pt_aov_device_ptr")) return rc;
-    *dev_ptr = ctx->d_aov[which];
-    if (nbytes) *nbytes = (size_t)ctx->local_rows * ctx->width * 16;
-    return MI3PT_OK;
+    return hand_out_plane(ctx, ctx->d_aov[which], dev_ptr, nbytes);
 }
 
 // ---- the feature-guided a-trous de-noise of the running mean (include/mi3pt.h: mi3pt_denoise_guided; pt_guided.hip) ----
@@ -2437,22 +2472,18 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     if (by_variance && !ctx->d_moments)
         return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided: MI3PT_GUIDED_VARIANCE needs the moments image (mi3pt_set_moments(ctx, 1) before the frames are accumulated)");
     if (int rc = flush_pending(ctx)) return rc;      // the mean a read-back would return now: the accumulate passes run on this stream
-    const size_t texels = (size_t)ctx->local_rows * ctx->width, tex_bytes = texels * 16;
+    const size_t texels = plane_texels(ctx);
     for (float4 **p : { &ctx->d_guided[0], &ctx->d_guided[1], &ctx->d_guided_nh })
-        if (!*p) HIP_TRY(hipMalloc((void **)p, tex_bytes ? tex_bytes : 16));
+        if (!*p) HIP_TRY(alloc_plane(p, plane_bytes(ctx)));
     if (by_variance)
         for (float *&p : ctx->d_guided_var)
-            if (!p) HIP_TRY(hipMalloc((void **)&p, texels ? texels * 4 : 16));
+            if (!p) HIP_TRY(alloc_plane(&p, texels * 4));
     pt::GuidedLaunch G;
     G.normal_hit = ctx->d_guided_nh; G.position = ctx->d_aov[MI3PT_AOV_POSITION]; G.albedo = ctx->d_aov[MI3PT_AOV_ALBEDO];
     G.width = ctx->width; G.rows = ctx->local_rows;
     G.inv_color = guided_inv(params->sigma_color); G.inv_normal = guided_inv(params->sigma_normal);
     G.inv_albedo = guided_inv(params->sigma_albedo); G.inv_plane = guided_inv(params->sigma_plane);
-    if (ctx->timing) {
-        for (int k = 0; k < 2; k++)
-            if (!ctx->ev_guided[k]) HIP_TRY(hipEventCreate(&ctx->ev_guided[k]));
-        HIP_TRY(hipEventRecord(ctx->ev_guided[0], ctx->stream));
-    }
+    if (ctx->timing) HIP_TRY(ctx->guided_timer.begin(ctx->stream));
     pt::launch_guided_pack(ctx->d_aov[MI3PT_AOV_NORMAL], ctx->d_aov[MI3PT_AOV_IDS], ctx->d_guided_nh, texels, ctx->stream);
     const float4 *src = ctx->d_accum;
     const float *var = nullptr;
@@ -2473,7 +2504,7 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
         src = dst;
     }
     HIP_TRY(hipGetLastError());
-    if (ctx->timing) { HIP_TRY(hipEventRecord(ctx->ev_guided[1], ctx->stream)); ctx->ev_guided_recorded = true; }
+    if (ctx->timing) HIP_TRY(ctx->guided_timer.end(ctx->stream));
     ctx->guided_result = src;
     ctx->guided_var_result = var;
     if (params->flags & MI3PT_GUIDED_PRESENT) {
@@ -2505,12 +2536,8 @@ extern "C" int mi3pt_read_guided(mi3pt_ctx *ctx, void *dst, size_t nbytes)
     if (int rc = require_ctx(ctx)) return rc;
     if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = guided_image(ctx, "mi3pt_read_guided")) return rc;
-    const size_t need = (size_t)ctx->local_rows * ctx->width * 16;
-    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
-    if (need == 0) return MI3PT_OK;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    HIP_TRY(hipMemcpyAsync(dst, ctx->guided_result, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    if (nbytes != plane_bytes(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
+    HIP_TRY(read_plane(ctx, ctx->guided_result, nbytes, dst));
     return MI3PT_OK;
 }
 
@@ -2520,9 +2547,7 @@ extern "C" int mi3pt_guided_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *n
     if (int rc = require_ctx(ctx)) return rc;
     if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = guided_image(ctx, "mi3pt_guided_device_ptr")) return rc;
-    *dev_ptr = const_cast<float4 *>(ctx->guided_result);
-    if (nbytes) *nbytes = (size_t)ctx->local_rows * ctx->width * 16;
-    return MI3PT_OK;
+    return hand_out_plane(ctx, ctx->guided_result, dev_ptr, nbytes);
 }
 
 extern "C" int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfloats)
@@ -2532,16 +2557,12 @@ extern "C" int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfl
     if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = guided_image(ctx, "mi3pt_read_guided_variance")) return rc;
     if (!ctx->guided_var_result) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_guided_variance: the last filter ran without MI3PT_GUIDED_VARIANCE");
-    const size_t need = (size_t)ctx->local_rows * ctx->width;
-    if (nfloats != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width floats)");
-    if (need == 0) return MI3PT_OK;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));
-    HIP_TRY(hipMemcpyAsync(dst, ctx->guided_var_result, need * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    if (nfloats != plane_texels(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width floats)");
+    HIP_TRY(read_plane(ctx, ctx->guided_var_result, nfloats * 4, dst));
     return MI3PT_OK;
 }
 
-// ---- the moments image (include/mi3pt.h: mi3pt_set_moments; pt_kernels.hip: k_accumulate_moments, k_accumulate_batch_moments) ----
+// ---- the moments image (include/mi3pt.h: mi3pt_set_moments; pt_kernels.hip: k_accumulate_frames<true>) ----
 extern "C" int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled)
 {
     PT_GROUP(ctx, group_set_moments(ctx, enabled));
@@ -2556,9 +2577,9 @@ extern "C" int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled)
         return MI3PT_OK;
     }
     if (ctx->width != 0) {
-        const size_t tex_bytes = (size_t)ctx->local_rows * ctx->width * 16;
+        const size_t tex_bytes = plane_bytes(ctx);
         float4 *image = nullptr;
-        HIP_TRY(hipMalloc((void **)&image, tex_bytes ? tex_bytes : 16));
+        HIP_TRY(alloc_plane(&image, tex_bytes));
         if (tex_bytes) {
             const hipError_t e = hipMemsetAsync(image, 0, tex_bytes, ctx->stream);
             if (e != hipSuccess) {          // (nothing half enabled: the launches key on the pointer)
@@ -2587,12 +2608,8 @@ extern "C" int mi3pt_read_moments(mi3pt_ctx *ctx, void *dst, size_t nbytes)
     if (int rc = require_idle(ctx)) return rc;
     if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = moments_image(ctx, "mi3pt_read_moments")) return rc;
-    const size_t need = (size_t)ctx->local_rows * ctx->width * 16;
-    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
-    if (need == 0) return MI3PT_OK;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    HIP_TRY(hipMemcpyAsync(dst, ctx->d_moments, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    if (nbytes != plane_bytes(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
+    HIP_TRY(read_plane(ctx, ctx->d_moments, nbytes, dst));
     return MI3PT_OK;
 }
 
@@ -2602,12 +2619,9 @@ extern "C" int mi3pt_write_moments(mi3pt_ctx *ctx, const void *src, size_t nbyte
     if (int rc = require_idle(ctx)) return rc;
     if (!src) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = moments_image(ctx, "mi3pt_write_moments")) return rc;
-    const size_t need = (size_t)ctx->local_rows * ctx->width * 16;
-    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "source size does not match the image (rows x width x 16 bytes)");
-    if (need == 0) return MI3PT_OK;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "write-back"));
-    HIP_TRY(hipMemcpyAsync(ctx->d_moments, src, need, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));      // copy-on-call
+    if (nbytes != plane_bytes(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "source size does not match the image (rows x width x 16 bytes)");
+    if (nbytes == 0) return MI3PT_OK;
+    HIP_TRY(write_plane(ctx, ctx->d_moments, src, nbytes));
     ctx->main_dirty = true;
     return MI3PT_OK;
 }
@@ -2618,9 +2632,7 @@ extern "C" int mi3pt_moments_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *
     if (int rc = require_idle(ctx)) return rc;
     if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = moments_image(ctx, "mi3pt_moments_device_ptr")) return rc;
-    *dev_ptr = ctx->d_moments;
-    if (nbytes) *nbytes = (size_t)ctx->local_rows * ctx->width * 16;
-    return MI3PT_OK;
+    return hand_out_plane(ctx, ctx->d_moments, dev_ptr, nbytes);
 }
 
 extern "C" int mi3pt_enable_timing(mi3pt_ctx *ctx, int enabled)
@@ -2635,24 +2647,10 @@ extern "C" int mi3pt_pass_time_us(mi3pt_ctx *ctx, int pass, float *microseconds)
 {
     PT_GROUP(ctx, group_pass_time(ctx, pass, microseconds));
     if (int rc = require_idle(ctx)) return rc;
-    if (microseconds && pass == MI3PT_PASS_AOV) {
-        if (!ctx->ev_aov_recorded) return pt_set_error(MI3PT_ERR_STATE, "no timed mi3pt_render_aovs since the last resize");
-        HIP_TRY(ctx_event_sync(ctx, ctx->ev_aov[1]));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_aov[0], ctx->ev_aov[1]));
-        *microseconds = ms * 1000.0f;
-        return MI3PT_OK;
-    }
-    if (microseconds && pass == MI3PT_PASS_GUIDED) {
-        if (!ctx->ev_guided_recorded) return pt_set_error(MI3PT_ERR_STATE, "no timed mi3pt_denoise_guided since the last resize");
-        HIP_TRY(ctx_event_sync(ctx, ctx->ev_guided[1]));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_guided[0], ctx->ev_guided[1]));
-        *microseconds = ms * 1000.0f;
-        return MI3PT_OK;
-    }
+    if (microseconds && pass == MI3PT_PASS_AOV) return ctx->aov_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_render_aovs since the last resize");
+    if (microseconds && pass == MI3PT_PASS_GUIDED) return ctx->guided_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_denoise_guided since the last resize");
     if (!microseconds || pass < 0 || pass > 2) return pt_set_error(MI3PT_ERR_INVALID, "bad argument");
-    if (pass == MI3PT_PASS_RAYTRACE && !ctx->ev_recorded[0] && (ctx->ev_rt_pending[0] || ctx->ev_rt_pending[1] || ctx->rt_launches)) {
+    if (pass == MI3PT_PASS_RAYTRACE && !ctx->pass_timer[0].recorded && (ctx->ev_rt_pending[0] || ctx->ev_rt_pending[1] || ctx->rt_launches)) {
         // batched launch: the most recent batch's kernel time divided by its frames (the older
         // parity is folded in first, so rt_last_ms ends up holding the newest launch)
         const int newest = ctx->ev_rt_newest;
@@ -2662,12 +2660,7 @@ extern "C" int mi3pt_pass_time_us(mi3pt_ctx *ctx, int pass, float *microseconds)
         *microseconds = (float)(ctx->rt_last_ms * 1000.0 / (frames > 0 ? frames : 1));
         return MI3PT_OK;
     }
-    if (!ctx->ev_recorded[pass]) return pt_set_error(MI3PT_ERR_STATE, "pass was not timed in the last submit");
-    HIP_TRY(ctx_event_sync(ctx, ctx->ev[pass][1]));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[pass][0], ctx->ev[pass][1]));
-    *microseconds = ms * 1000.0f;
-    return MI3PT_OK;
+    return ctx->pass_timer[pass].elapsed_us(ctx, microseconds, "pass was not timed in the last submit");
 }
 
 extern "C" int mi3pt_raytrace_launch_stats(mi3pt_ctx *ctx, int reset, double *total_ms, uint64_t *launches,
@@ -2714,9 +2707,7 @@ extern "C" int mi3pt_get_counters(mi3pt_ctx *ctx, uint64_t out[MI3PT_CNT_COUNT])
     for (int k = 0; k < MI3PT_CNT_COUNT; k++) out[k] = 0;
     if (ctx->nblocks == 0) return MI3PT_OK;
     std::vector<uint64_t> host(2 * (size_t)ctx->nblocks * pt::CNT_COUNT);
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    HIP_TRY(hipMemcpyAsync(host.data(), ctx->d_block_counters, host.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    HIP_TRY(read_plane(ctx, ctx->d_block_counters, host.size() * 8, host.data()));
     for (int b = 0; b < 2 * ctx->nblocks; b++)
         for (int k = 0; k < MI3PT_CNT_COUNT; k++) out[k] += host[(size_t)b * pt::CNT_COUNT + k];
     return MI3PT_OK;
@@ -2755,9 +2746,7 @@ extern "C" int mi3pt_debug_wave_times(mi3pt_ctx *ctx, int enable, uint64_t *out,
     }
     if (!ctx->d_wave_times) return pt_set_error(MI3PT_ERR_STATE, "wave times are not enabled");
     if (capacity_slots < (size_t)ctx->wave_times_slots) return pt_set_error(MI3PT_ERR_INVALID, "buffer too small");
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "read-back"));      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    HIP_TRY(hipMemcpyAsync(out, ctx->d_wave_times, (size_t)ctx->wave_times_slots * 128, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    HIP_TRY(read_plane(ctx, ctx->d_wave_times, (size_t)ctx->wave_times_slots * 128, out));
     if (slots_out) *slots_out = (size_t)ctx->wave_times_slots;
     return MI3PT_OK;
 }
@@ -2780,9 +2769,7 @@ extern "C" int mi3pt_debug_intersect(mi3pt_ctx *ctx, const float *rays, size_t n
         pt::launch_debug_intersect(scene_refs(ctx), d_rays, n, d_out, pick_walk(ctx), ctx->stream);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream, "read-back");      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 48, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+    if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
     (void)hipFree(d_rays);
     (void)hipFree(d_out);
     if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_intersect: ") + hipGetErrorString(e));
@@ -2813,9 +2800,7 @@ extern "C" int mi3pt_debug_intersect_shipped(mi3pt_ctx *ctx, const float *rays, 
         pt::launch_debug_intersect_cull(scene, d_rays, n, d_out, ctx->wide_stack_worst, ctx->leaf_min, ctx->stream);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream, "read-back");
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 48, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+    if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
     (void)hipFree(d_rays);
     (void)hipFree(d_out);
     if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_intersect_shipped: ") + hipGetErrorString(e));
@@ -2840,9 +2825,7 @@ extern "C" int mi3pt_debug_pairs(mi3pt_ctx *ctx, int fn, const float *rays, cons
         pt::launch_debug_pairs(fn, d_rays, d_geom, d_out, n, ctx->stream);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream, "read-back");
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 48, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+    if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
     if (d_rays) (void)hipFree(d_rays);
     if (d_geom) (void)hipFree(d_geom);
     if (d_out) (void)hipFree(d_out);
@@ -2882,9 +2865,7 @@ extern "C" int mi3pt_debug_math(mi3pt_ctx *ctx, int fn, const float *a, const fl
         pt::launch_debug_math(fn, d_a, d_b, d_o, n, ctx->stream);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream, "read-back");      // (a copy to pageable memory blocks the host until the stream gets there: the bounded wait comes first)
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
+    if (e == hipSuccess) e = read_plane(ctx, d_o, n * 4, out);
     if (d_a) (void)hipFree(d_a);
     if (d_b) (void)hipFree(d_b);
     if (d_o) (void)hipFree(d_o);
@@ -3021,6 +3002,7 @@ static int group_resize(mi3pt_ctx *g, int width, int height)
     GroupState *gs = g->group;
     gs->width = gs->height = 0;
     for (int k = 0; k < MI3PT_AOV_COUNT; k++) gs->aov_rendered[k] = gs->aov_gathered[k] = false;
+    gs->present->moments = false;      // (its resize frees the gathered moments image and must not allocate one of its own: group_gather_moments)
     if (int rc = group_each(g, true, [&](mi3pt_ctx *m) { return mi3pt_resize(m, width, height); })) return rc;
     gs->width = width;
     gs->height = height;
@@ -3152,16 +3134,15 @@ static int group_sync(mi3pt_ctx *g)
 // geometry: source pitch = one block, destination pitch = n blocks) on the presenting context's stream -- peer DMA over xGMI.
 // Otherwise: staged through pinned host memory (a device-to-host copy on the member's device, then the same strided copy from
 // the host buffer).
-// (aov == -1: the accumulation image; GATHER_MOMENTS: the moments image; else that feature image, mi3pt_read_aov of a group)
-static const int GATHER_MOMENTS = -2;
-static int gather_member(GroupState *gs, int i, bool direct, int aov = -1)
+// (member_plane: the member's rows of the image gathered; whole_plane: that image on the presenting context)
+static int gather_member(GroupState *gs, int i, bool direct, const float4 *member_plane, float4 *whole_plane)
 {
     mi3pt_ctx *p = gs->present;
     const mi3pt_ctx *m = gs->members[(size_t)i];
     const int n = (int)gs->members.size(), br = gs->block_rows, W = gs->width, H = gs->height;
     const size_t row_bytes = (size_t)W * 16, block_bytes = row_bytes * (size_t)br;
-    uint8_t *dst = reinterpret_cast<uint8_t *>(aov == GATHER_MOMENTS ? p->d_moments : aov < 0 ? p->d_accum : p->d_aov[aov]);
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(aov == GATHER_MOMENTS ? m->d_moments : aov < 0 ? m->d_accum : m->d_aov[aov]);
+    uint8_t *dst = reinterpret_cast<uint8_t *>(whole_plane);
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(member_plane);
     const int rows = m->local_rows;
     if (rows == 0) return MI3PT_OK;
     const int full = rows / br, tail = rows - full * br;      // whole blocks, rows of a last partial block (the image's bottom edge)
@@ -3195,26 +3176,8 @@ static int gather_member(GroupState *gs, int i, bool direct, int aov = -1)
     return MI3PT_OK;
 }
 
-static int gather_copies(GroupState *gs, int aov);
-
-static int group_gather(mi3pt_ctx *g)
-{
-    GroupState *gs = g->group;
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "read before resize");
-    if (gs->gathered) return MI3PT_OK;
-    if (int rc = group_sync(g)) return rc;
-    mi3pt_ctx *p = gs->present;
-    if (int rc = require_idle(p)) return rc;
-    if (int rc = gather_copies(gs, -1)) return rc;
-    p->output_is_accum = true;      // like the copy-back of accumulate.ts:171-175
-    p->main_dirty = true;
-    p->accum_version++;
-    gs->gathered = true;
-    return MI3PT_OK;
-}
-
-// the copies of a gather (the members' work has been waited for): the accumulation image (aov < 0) or a feature image
-static int gather_copies(GroupState *gs, int aov)
+// the copies of a gather (the members' work has been waited for); plane(ctx): the image gathered, as that context holds it
+template <class Plane> static int gather_copies(GroupState *gs, Plane plane)
 {
     mi3pt_ctx *p = gs->present;
     const int n = (int)gs->members.size();
@@ -3222,7 +3185,7 @@ static int gather_copies(GroupState *gs, int aov)
         // direct copies first, all in flight together on the presenting stream (n - 1 transfers on n - 1 links into one root) ...
         for (int i = 0; i < n; i++) {
             if (!gs->peer_direct[(size_t)i]) continue;
-            if (gather_member(gs, i, true, aov) != MI3PT_OK) { (void)hipGetLastError(); gs->peer_direct[(size_t)i] = 0; }
+            if (gather_member(gs, i, true, plane(gs->members[(size_t)i]), plane(p)) != MI3PT_OK) { (void)hipGetLastError(); gs->peer_direct[(size_t)i] = 0; }
         }
         if (ctx_stream_sync(p, p->stream) == hipSuccess) break;
         // ... a rect copy between two devices can also fail asynchronously (round-3 advice): nothing this pass wrote is trusted;
@@ -3236,9 +3199,35 @@ static int gather_copies(GroupState *gs, int aov)
     // ... then whatever cannot be addressed directly, staged through pinned host memory
     for (int i = 0; i < n; i++)
         if (!gs->peer_direct[(size_t)i])
-            if (int rc = gather_member(gs, i, false, aov)) return rc;
+            if (int rc = gather_member(gs, i, false, plane(gs->members[(size_t)i]), plane(p))) return rc;
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(ctx_stream_sync(p, p->stream));
+    return MI3PT_OK;
+}
+
+// A whole image the presenting context allocates when it is first gathered (a feature image, the moments image) and frees with its
+// textures.  wait_for_members: the members' work that writes the image, then the presenting context ready for the copies.
+template <class Plane, class Wait> static int gather_lazy_image(GroupState *gs, Plane plane, Wait wait_for_members)
+{
+    if (int rc = wait_for_members()) return rc;
+    mi3pt_ctx *p = gs->present;
+    if (!plane(p)) HIP_TRY(alloc_plane(&plane(p), plane_bytes(p)));
+    return gather_copies(gs, plane);
+}
+
+static int group_gather(mi3pt_ctx *g)
+{
+    GroupState *gs = g->group;
+    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "read before resize");
+    if (gs->gathered) return MI3PT_OK;
+    if (int rc = group_sync(g)) return rc;
+    mi3pt_ctx *p = gs->present;
+    if (int rc = require_idle(p)) return rc;
+    if (int rc = gather_copies(gs, [](mi3pt_ctx *c) -> float4 *& { return c->d_accum; })) return rc;
+    p->output_is_accum = true;      // like the copy-back of accumulate.ts:171-175
+    p->main_dirty = true;
+    p->accum_version++;
+    gs->gathered = true;
     return MI3PT_OK;
 }
 
@@ -3263,16 +3252,16 @@ static int group_gather_aov(mi3pt_ctx *g, int which, const char *what)
     if (!gs->aov_rendered[which])
         return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": this image has not been rendered since the last resize (mi3pt_render_aovs)");
     if (gs->aov_gathered[which]) return MI3PT_OK;
-    mi3pt_ctx *p = gs->present;
     // the members' passes (their own streams; their frame queues stay as they are), then the copies
-    for (mi3pt_ctx *m : gs->members) {
-        if (int rc = require_ctx(m)) return rc;
-        HIP_TRY(ctx_stream_sync(m, m->stream));
-    }
-    if (int rc = require_ctx(p)) return rc;
-    if (!p->d_aov[which]) HIP_TRY(hipMalloc((void **)&p->d_aov[which], (size_t)gs->width * gs->height * 16));
-    if (int rc = gather_copies(gs, which)) return rc;
-    p->aov_valid[which] = true;
+    auto members_streams = [&]() -> int {
+        for (mi3pt_ctx *m : gs->members) {
+            if (int rc = require_ctx(m)) return rc;
+            HIP_TRY(ctx_stream_sync(m, m->stream));
+        }
+        return require_ctx(gs->present);
+    };
+    if (int rc = gather_lazy_image(gs, [which](mi3pt_ctx *c) -> float4 *& { return c->d_aov[which]; }, members_streams)) return rc;
+    gs->present->aov_valid[which] = true;
     gs->aov_gathered[which] = true;
     return MI3PT_OK;
 }
@@ -3295,7 +3284,9 @@ static int group_aov_ptr(mi3pt_ctx *g, int which, void **dev_ptr, size_t *nbytes
 }
 
 // ---- the moments image of a group: kept by every member for its rows; the presenting context's whole image is allocated by the first read
-// (like a feature image: group_gather_aov), freed by its resize (free_textures) and by mi3pt_set_moments(0), and gathered whenever it is read ----
+// (like a feature image: group_gather_aov), freed by its resize (free_textures) and by mi3pt_set_moments(0), and gathered whenever it is read.
+// While it holds the gathered copy the presenting context counts as having moments enabled, so that its own mi3pt_read_moments and
+// mi3pt_moments_device_ptr serve the image; it never runs an accumulate pass, so it never keeps moments of its own ----
 static int group_set_moments(mi3pt_ctx *g, int enabled)
 {
     if (int rc = group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_set_moments(m, enabled); })) return rc;
@@ -3306,6 +3297,7 @@ static int group_set_moments(mi3pt_ctx *g, int enabled)
         (void)hipFree(p->d_moments);
         p->d_moments = nullptr;
     }
+    if (!enabled) p->moments = false;
     return MI3PT_OK;
 }
 
@@ -3314,11 +3306,13 @@ static int group_gather_moments(mi3pt_ctx *g, const char *what)
     GroupState *gs = g->group;
     if (!gs->members[0]->moments) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": the moments image is not enabled (mi3pt_set_moments)");
     if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
-    if (int rc = group_sync(g)) return rc;
-    mi3pt_ctx *p = gs->present;
-    if (int rc = require_idle(p)) return rc;
-    if (!p->d_moments) HIP_TRY(hipMalloc((void **)&p->d_moments, (size_t)gs->width * gs->height * 16));
-    return gather_copies(gs, GATHER_MOMENTS);
+    auto everything = [&]() -> int {
+        if (int rc = group_sync(g)) return rc;
+        return require_idle(gs->present);
+    };
+    if (int rc = gather_lazy_image(gs, [](mi3pt_ctx *c) -> float4 *& { return c->d_moments; }, everything)) return rc;
+    gs->present->moments = true;
+    return MI3PT_OK;
 }
 
 static int group_read_moments(mi3pt_ctx *g, void *dst, size_t nbytes)
@@ -3329,19 +3323,14 @@ static int group_read_moments(mi3pt_ctx *g, void *dst, size_t nbytes)
     if (gs->width && gs->members[0]->moments && nbytes != need)
         return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (a group reads whole images: height x width x 16 bytes)");
     if (int rc = group_gather_moments(g, "mi3pt_read_moments")) return rc;
-    mi3pt_ctx *p = gs->present;
-    HIP_TRY(hipMemcpyAsync(dst, p->d_moments, need, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(ctx_stream_sync(p, p->stream));
-    return MI3PT_OK;
+    return mi3pt_read_moments(gs->present, dst, nbytes);
 }
 
 static int group_moments_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes)
 {
     if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = group_gather_moments(g, "mi3pt_moments_device_ptr")) return rc;
-    *dev_ptr = g->group->present->d_moments;
-    if (nbytes) *nbytes = (size_t)g->group->width * g->group->height * 16;
-    return MI3PT_OK;
+    return mi3pt_moments_device_ptr(g->group->present, dev_ptr, nbytes);
 }
 
 static int group_draw_canvas(mi3pt_ctx *g)

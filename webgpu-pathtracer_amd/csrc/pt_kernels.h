@@ -309,15 +309,10 @@ void launch_raytrace_setup(const RtLaunch &L, bool fuse_accumulate, int variant,
 void launch_raytrace(const RtLaunch &L, bool fuse_accumulate, int variant, hipStream_t s);
 // fills `out` (tile.local_rows x tile.tex_w float4) for RtLaunch::cam_base from L.un / L.tile
 void launch_camera_base(const RtLaunch &L, float4 *out, hipStream_t s);
-void launch_accumulate_batch(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels,
-                             int nframes, float4 *accum, int store_f16, hipStream_t s);
-void launch_accumulate(const AccUniforms &acc, const Tile &tile, const float4 *input, float4 *accum,
-                       int store_f16, hipStream_t s);
-// the same two passes, keeping the moments image (local_rows x width float4: M2.rgb, n; include/mi3pt.h: mi3pt_set_moments) beside the mean
-void launch_accumulate_batch_moments(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels,
-                                     int nframes, float4 *accum, float4 *moments, int store_f16, hipStream_t s);
-void launch_accumulate_moments(const AccUniforms &acc, const Tile &tile, const float4 *input, float4 *accum, float4 *moments,
-                               int store_f16, hipStream_t s);
+// the running mean over nframes consecutive radiance slots (one frame: nframes 1, slot_pixels unused), at most max_blocks blocks of 256;
+// moments: null, or the moments image (local_rows x width float4: M2.rgb, n; include/mi3pt.h: mi3pt_set_moments) kept beside the mean
+void launch_accumulate_frames(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels, int nframes,
+                              float4 *accum, float4 *moments, int store_f16, int max_blocks, hipStream_t s);
 // `taps`: fullscreen_taps_bytes() of device memory (the de-noise pass's tap table); `taps_current`: an earlier call on
 // this stream has filled it from the same fs.res_x / fs.res_y
 size_t fullscreen_taps_bytes();

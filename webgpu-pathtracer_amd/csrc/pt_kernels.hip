@@ -27,7 +27,7 @@
 //       true: the diagnostic twin (step statistics, clock stamps, step-voting options at run time);
 //       TOPLDS / LITE and k_raytrace_persistent (variant 3): experiment builds only
 //   k_rt_service_setup         the launch-invariant scalars of the service step, one block per launch
-//   k_accumulate[_batch]       accumulate.wgsl computeMain (one frame / an ordered batch of frames)
+//   k_accumulate_frames        accumulate.wgsl computeMain (one frame / an ordered batch of frames; <true>: keeping the moments image)
 //   k_fullscreen[_setup]       fullscreen.wgsl fragmentMain (de-noise + tone-map) and its tap table
 //   k_pack_vertices, k_patch_cull   helpers of the context's cull analysis
 //   k_debug_intersect/_math    component probes for the parity tests
@@ -2778,101 +2778,23 @@ void launch_raytrace(const RtLaunch &L, bool fuse, int variant, hipStream_t s)
 // ---------------------------------------------------------------------------------
 // accumulate.wgsl:12-29 as its own pass
 // ---------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_accumulate(const AccUniforms acc, const Tile tile,
-                                                    const float4 *__restrict__ input,
-                                                    float4 *__restrict__ accum, int store_f16)
-{
-    const size_t n = (size_t)tile.local_rows * tile.tex_w;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int ly = (int)(i / tile.tex_w);
-        const int gx = (int)(i - (size_t)ly * tile.tex_w);
-        const int gy = local_to_global_row(ly, tile);
-        if ((uint32_t)gx >= acc.res_w || (uint32_t)gy >= acc.res_h) continue;
-        const float4 c = input[i];
-        const float4 p = accum[i];
-        const f3 nc = accumulate_texel(acc, xyz(c), xyz(p));
-        accum[i] = make_float4(store_round(nc.x, store_f16), store_round(nc.y, store_f16),
-                               store_round(nc.z, store_f16), 1.0f);
-    }
-}
-
-// The running mean over `nframes` consecutive frames' radiance slots, applied per pixel in
-// frame order (frame, frame+1, ...) -- the same sequence of accumulate.wgsl passes, with the
-// accumulator read and written once.
-__global__ void __launch_bounds__(256) k_accumulate_batch(const AccUniforms acc0, const Tile tile,
-                                                          const float4 *__restrict__ slots, size_t slot_pixels,
-                                                          int nframes, float4 *__restrict__ accum, int store_f16)
-{
-    const size_t n = (size_t)tile.local_rows * tile.tex_w;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int ly = (int)(i / tile.tex_w);
-        const int gx = (int)(i - (size_t)ly * tile.tex_w);
-        const int gy = local_to_global_row(ly, tile);
-        if ((uint32_t)gx >= acc0.res_w || (uint32_t)gy >= acc0.res_h) continue;
-        f3 p = xyz(accum[i]);
-        for (int k = 0; k < nframes; k++) {
-            AccUniforms a = acc0;
-            a.frame = acc0.frame + (uint32_t)k;
-            const f3 nc = accumulate_texel(a, xyz(slots[(size_t)k * slot_pixels + i]), p);
-            p = F3(store_round(nc.x, store_f16), store_round(nc.y, store_f16), store_round(nc.z, store_f16));
-        }
-        accum[i] = make_float4(p.x, p.y, p.z, 1.0f);
-    }
-}
-
-void launch_accumulate_batch(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels,
-                             int nframes, float4 *accum, int store_f16, hipStream_t s)
-{
-    const size_t n = (size_t)tile.local_rows * tile.tex_w;
-    if (n == 0 || nframes <= 0) return;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_accumulate_batch, dim3(blocks), dim3(256), 0, s, acc0, tile, slots, slot_pixels, nframes,
-                       accum, store_f16);
-}
-
-void launch_accumulate(const AccUniforms &acc, const Tile &tile, const float4 *input, float4 *accum,
-                       int store_f16, hipStream_t s)
-{
-    const size_t n = (size_t)tile.local_rows * tile.tex_w;
-    if (n == 0) return;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(256), 0, s, acc, tile, input, accum, store_f16);
-}
-
-// ---------------------------------------------------------------------------------
-// The moments image (include/mi3pt.h: mi3pt_set_moments): the two accumulate kernels above, keeping (M2.rgb, n) beside the mean in
-// the same pass.  Welford's update written around the mean as it is STORED: c the frame's radiance, p the mean before the step,
-// pn the mean after it (after store_round); a step of weight 1 (accumulate_texel) restarts the sums.  The mean's own arithmetic is
-// that of the kernels above, operation for operation.
-// ---------------------------------------------------------------------------------
+// The moments image (include/mi3pt.h: mi3pt_set_moments): (M2.rgb, n) kept beside the mean in the same pass.  Welford's update written
+// around the mean as it is STORED: c the frame's radiance, p the mean before the step, pn the mean after it (after store_round); a step
+// of weight 1 (accumulate_texel) restarts the sums.
 PT_DEV float4 moments_step(const AccUniforms &acc, f3 c, f3 p, f3 pn, float4 m)
 {
     if (acc.frame <= 1u || acc.enabled != 1u) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
     return make_float4(m.x + (c.x - p.x) * (c.x - pn.x), m.y + (c.y - p.y) * (c.y - pn.y), m.z + (c.z - p.z) * (c.z - pn.z), m.w + 1.0f);
 }
 
-__global__ void __launch_bounds__(256) k_accumulate_moments(const AccUniforms acc, const Tile tile, const float4 *__restrict__ input,
-                                                            float4 *__restrict__ accum, float4 *__restrict__ moments, int store_f16)
-{
-    const size_t n = (size_t)tile.local_rows * tile.tex_w;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int ly = (int)(i / tile.tex_w);
-        const int gx = (int)(i - (size_t)ly * tile.tex_w);
-        const int gy = local_to_global_row(ly, tile);
-        if ((uint32_t)gx >= acc.res_w || (uint32_t)gy >= acc.res_h) continue;
-        const f3 c = xyz(input[i]), p = xyz(accum[i]);
-        const f3 nc = accumulate_texel(acc, c, p);
-        const f3 pn = F3(store_round(nc.x, store_f16), store_round(nc.y, store_f16), store_round(nc.z, store_f16));
-        accum[i] = make_float4(pn.x, pn.y, pn.z, 1.0f);
-        moments[i] = moments_step(acc, c, p, pn, moments[i]);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_accumulate_batch_moments(const AccUniforms acc0, const Tile tile, const float4 *__restrict__ slots,
-                                                                  size_t slot_pixels, int nframes, float4 *__restrict__ accum,
-                                                                  float4 *__restrict__ moments, int store_f16)
+// The running mean over `nframes` consecutive frames' radiance slots, applied per pixel in
+// frame order (frame, frame+1, ...) -- the same sequence of accumulate.wgsl passes, with the
+// accumulator (MOMENTS: and the moments image; otherwise `moments` is never touched) read and
+// written once.  One frame is nframes == 1: the mean's arithmetic does not depend on either parameter.
+template <bool MOMENTS>
+__global__ void __launch_bounds__(256) k_accumulate_frames(const AccUniforms acc0, const Tile tile, const float4 *__restrict__ slots,
+                                                           size_t slot_pixels, int nframes, float4 *__restrict__ accum,
+                                                           float4 *__restrict__ moments, int store_f16)
 {
     const size_t n = (size_t)tile.local_rows * tile.tex_w;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -2881,41 +2803,34 @@ __global__ void __launch_bounds__(256) k_accumulate_batch_moments(const AccUnifo
         const int gy = local_to_global_row(ly, tile);
         if ((uint32_t)gx >= acc0.res_w || (uint32_t)gy >= acc0.res_h) continue;
         f3 p = xyz(accum[i]);
-        float4 m = moments[i];
+        float4 m;
+        if (MOMENTS) m = moments[i];
         for (int k = 0; k < nframes; k++) {
             AccUniforms a = acc0;
             a.frame = acc0.frame + (uint32_t)k;
             const f3 c = xyz(slots[(size_t)k * slot_pixels + i]);
             const f3 nc = accumulate_texel(a, c, p);
             const f3 pn = F3(store_round(nc.x, store_f16), store_round(nc.y, store_f16), store_round(nc.z, store_f16));
-            m = moments_step(a, c, p, pn, m);
+            if (MOMENTS) m = moments_step(a, c, p, pn, m);
             p = pn;
         }
         accum[i] = make_float4(p.x, p.y, p.z, 1.0f);
-        moments[i] = m;
+        if (MOMENTS) moments[i] = m;
     }
 }
 
-// (the grids of launch_accumulate_batch / launch_accumulate: capped, the kernels stride beyond)
-void launch_accumulate_batch_moments(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels,
-                                     int nframes, float4 *accum, float4 *moments, int store_f16, hipStream_t s)
+// (the grid is capped, the kernel strides beyond)
+void launch_accumulate_frames(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels, int nframes,
+                              float4 *accum, float4 *moments, int store_f16, int max_blocks, hipStream_t s)
 {
     const size_t n = (size_t)tile.local_rows * tile.tex_w;
     if (n == 0 || nframes <= 0) return;
     int blocks = (int)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_accumulate_batch_moments, dim3(blocks), dim3(256), 0, s, acc0, tile, slots, slot_pixels, nframes,
-                       accum, moments, store_f16);
-}
-
-void launch_accumulate_moments(const AccUniforms &acc, const Tile &tile, const float4 *input, float4 *accum, float4 *moments,
-                               int store_f16, hipStream_t s)
-{
-    const size_t n = (size_t)tile.local_rows * tile.tex_w;
-    if (n == 0) return;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_accumulate_moments, dim3(blocks), dim3(256), 0, s, acc, tile, input, accum, moments, store_f16);
+    if (blocks > max_blocks) blocks = max_blocks;
+    if (moments)
+        hipLaunchKernelGGL(k_accumulate_frames<true>, dim3(blocks), dim3(256), 0, s, acc0, tile, slots, slot_pixels, nframes, accum, moments, store_f16);
+    else
+        hipLaunchKernelGGL(k_accumulate_frames<false>, dim3(blocks), dim3(256), 0, s, acc0, tile, slots, slot_pixels, nframes, accum, moments, store_f16);
 }
 
 // ---------------------------------------------------------------------------------
