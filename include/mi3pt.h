@@ -62,7 +62,7 @@ extern "C" {
  * MI3PT_OPT_PACKET_ORDER, MI3PT_OPT_SIX_WAVES (22 .. 27); MI3PT_OPT_WAVES_PER_CU reads up to 24 (six waves per SIMD). */
 /* 4 (round 6): mi3pt_set_rows and mi3pt_measure_tile_cost are GONE (contiguous cost-balanced bands: measured 7 % slower than the dealt
  * 8-row blocks in round 4 and kept since as dead surface); mi3pt_set_kernel_variant accepts 14 (the eight-wide walk: an option).
- * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31); mi3pt_host_scene_compile;
+ * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31); mi3pt_host_scene_compile; mi3pt_host_walk_buffer;
  * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3); mi3pt_denoise_guided, mi3pt_read_guided,
  * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4). */
 #define MI3PT_ABI_VERSION 4
@@ -678,6 +678,14 @@ int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes, const voi
 #define MI3PT_SCENE_COMPILE_WORDS 32
 int mi3pt_host_scene_compile(const void *nodes, size_t nodes_bytes, const void *triangles, size_t triangles_bytes, int collapse, int packet_order,
                              int want_eight_wide, uint64_t *out, size_t out_capacity);
+/* Host-only: the BYTES of one buffer of that compile's walk stage, for the same arguments and by the same code -- they hash (64-bit FNV-1a)
+ * to the digest mi3pt_host_scene_compile reports for it.  kind: 0 the cull words (one uint32 per node packet), 1 wide packets (128 bytes
+ * each, digest word 27), 2 compressed 4-ary packets (64 bytes, word 28), 3 64-byte triangle records (word 29), 4 8-wide packets (80 bytes,
+ * word 30), 5 8-wide records (64 bytes, word 31); 4 and 5 build the packets of kernel variant 14 (want_eight_wide = 1).  *bytes_out = the
+ * buffer's size, 0 when the compile does not build it for this tree; `out` may be NULL to ask for the size only, otherwise `capacity` bytes
+ * must hold it.  The layouts are the kernels' own (csrc/pt_kernels.h) and no part of the ABI: for tests that decode what a context uploads. */
+int mi3pt_host_walk_buffer(const void *nodes, size_t nodes_bytes, const void *triangles, size_t triangles_bytes, int collapse, int packet_order,
+                           int kind, void *out, size_t capacity, size_t *bytes_out);
 /* The EMPTY TILES of a view (no device): the 8x8 tiles of rank `rank`'s share of a width x height image (tiles_x = ceil(width / 8), rows of
  * tiles over the rank's LOCAL rows, row-major) in which no pixel's camera ray, for any frame's jitter, can pass the reference's slab
  * test on any box of a cut of the tree `nodes` (48-byte records) -- such a ray reaches no leaf, the path is one miss.  A context

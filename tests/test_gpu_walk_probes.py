@@ -10,6 +10,7 @@ comparison is bit for bit or one-sided."""
 import numpy as np
 import pytest
 
+import micro_geometry as mg
 import ptcommon as pc
 import walk_probe_inputs as wpi
 from mi3pt_host import capi
@@ -90,7 +91,7 @@ def scene_cases():
 
 
 SCENE_NAMES = ("demo", "slivers", "tiny next to huge", "sphere", wpi.TIE_SCENE, "comb 40", "demo x 2^-6", "demo x 2^6",
-               "demo + (1000, 1000, 1000)", "demo, broken boxes")
+               "demo + (1000, 1000, 1000)", "demo, broken boxes") + mg.SCENES
 
 
 def _upload(ctx, nodes, tris, mats, env):
@@ -107,7 +108,7 @@ def test_every_walk_equals_the_oracle_ray_for_ray(gpu_ctx, orc, env, scene_cases
     nodes, tris, mats = scene_cases[scene]
     ctx = gpu_ctx
     _upload(ctx, nodes, tris, mats, env)
-    fam = wpi.scene_rays(nodes, tris)
+    fam = wpi.scene_rays_of(scene, nodes, tris)
     names = list(fam)
     rays = np.concatenate([fam[k] for k in names])
     owner = np.concatenate([np.full(len(fam[k]), i) for i, k in enumerate(names)])

@@ -414,7 +414,7 @@ def test_eight_wide_packets_pass_their_host_side_check(built):
         for greedy in (False, True):
             r = capi.host_eight_wide_check(sc.nodes, sc.triangles, greedy)
             assert r["leaves"] == n and r["offered"] and r["packets"] >= 1, (n, r)
-            assert r["packets"] <= max(1, n - 1) and r["records"] <= 8 * r["packets"] + 8
+            assert r["packets"] <= max(1, n - 1) and r["records"] <= 8 * r["packets"] + 16      # (eight inert records at the head, eight at the tail)
     spec = importlib.util.spec_from_file_location("culling_scenes", os.path.join(ROOT, "tests", "test_gpu_culling.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)

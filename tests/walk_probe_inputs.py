@@ -735,4 +735,17 @@ def scenes():
     n2, t2 = _scaled(demo.nodes, demo.triangles, 1.0, (1000.0, 1000.0, 1000.0))
     out["demo + (1000, 1000, 1000)"] = (n2, t2, demo.material_bytes)
     out["demo, broken boxes"] = (broken_boxes(demo.nodes), demo.triangles, demo.material_bytes)
+    import micro_geometry as mg                      # packets that are tiny AND close to the origin: empty slots pass the box test there
+    for name in mg.SCENES:
+        sc = mg.scene(name)
+        out[name] = (sc.nodes, sc.triangles, sc.material_bytes)
     return out
+
+
+def scene_rays_of(name, nodes, triangles):
+    """scene_rays, and for a micro-geometry scene its rays aimed into the clusters from 0.5, 5 and 500 units as one more family"""
+    import micro_geometry as mg
+    fam = scene_rays(nodes, triangles)
+    if name in mg.SCENES:
+        fam["aimed into the clusters"] = mg.aimed_rays(mg.scene(name))
+    return fam

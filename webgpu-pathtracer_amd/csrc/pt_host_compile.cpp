@@ -5,6 +5,7 @@
 //   compile_walk               culling weights, 4-ary packets (exact + compressed), 64-byte records, 8-wide packets, what `auto` means
 //                              (the context's lazy analysis, prepare_cull); buffers leave through a sink as each becomes ready
 //   mi3pt_host_scene_compile   all three with a hashing sink
+//   mi3pt_host_walk_buffer     the tree and walk compiles with a sink that copies ONE of the walk's buffers out (what the CPU tests decode)
 #include "../../include/mi3pt.h"
 #include "pt_internal.h"
 
@@ -512,11 +513,14 @@ int compile_walk(const uint8_t *src, size_t n, const TriVerts *tris, size_t nt, 
                         meta |= (uint32_t)(e + 127) << (8 * ax);
                         uint32_t qlo = 0, qhi = 0;
                         for (int k = 0; k < 4; k++) {
-                            uint32_t a = 255u, z = 0u;                                   // empty slot: an inverted box, never entered
+                            uint32_t a = 255u, z = 0u;                                   // empty slot: an inverted box; the box test may pass it (PROOFS.md 4a): its ref, REF_NONE, is what makes the pushed entry empty
                             if (p.ref[k] != REF_NONE) {
                                 const float *b = box_at(k);
-                                const double x0 = ((double)b[ax] - (double)o) / cell, x1 = ((double)b[3 + ax] - (double)o) / cell;     // exact: fp32 values, a power-of-two cell
-                                const double f0 = std::floor(x0) - 1.0, f1 = std::ceil(x1) + 1.0;
+                                const double x0 = ((double)b[ax] - (double)o) / cell, x1 = ((double)b[3 + ax] - (double)o) / cell;     // (the difference is rounded once; the division by a power of two is exact)
+                                double f0 = std::floor(x0) - 1.0, f1 = std::ceil(x1) + 1.0;
+                                // (x0 / x1 are rounded quotients: a whole cell of margin is decided exactly, see plane_cells_from_origin)
+                                if (!plane_cells_from_origin(b[ax], o, (f0 + 1.0) * cell, true)) f0 -= 1.0;
+                                if (!plane_cells_from_origin(b[3 + ax], o, (f1 - 1.0) * cell, false)) f1 += 1.0;
                                 if (!(f0 >= 0.0 && f1 <= 254.0 && f0 < f1)) { ok = false; break; }
                                 a = (uint32_t)f0; z = (uint32_t)f1;
                                 // ... and checked the way the kernel's plain-division path DECODES a plane, one fp32 fma: RN(o + cell q) is not
@@ -684,5 +688,40 @@ extern "C" int mi3pt_host_scene_compile(const void *nodes, size_t nodes_bytes, c
     out[24] = fnv(tree.packets.data(), tree.packets.size() * sizeof(pt::NodePacket));
     out[25] = fnv(tree.leaf_rank.data(), tree.leaf_rank.size() * sizeof(uint32_t));
     out[26] = fnv(tripk.data(), tripk.size() * sizeof(pt::TriPacket));
+    return MI3PT_OK;
+}
+
+// Host-only: the bytes of one of the buffers compile_walk emits (kind: pt::WalkBuffer -- 0 cull words, 1 wide packets, 2 compressed packets,
+// 3 64-byte records, 4 8-wide packets, 5 8-wide records), for the same arguments and by the same calls as mi3pt_host_scene_compile: they
+// hash to its words 27 .. 31.  *bytes_out = the buffer's size (0: not built for this tree); copied to `out` when it is given.
+extern "C" int mi3pt_host_walk_buffer(const void *nodes, size_t nodes_bytes, const void *triangles, size_t triangles_bytes, int collapse,
+                                      int packet_order, int kind, void *out, size_t capacity, size_t *bytes_out)
+{
+    if (!nodes || !triangles || !bytes_out || nodes_bytes == 0 || nodes_bytes % MI3PT_BVHNODE_STRIDE || triangles_bytes == 0 ||
+        triangles_bytes % MI3PT_TRIANGLE_STRIDE || collapse < -1 || collapse > 1 || packet_order < 0 || packet_order > 2 ||
+        kind < (int)pt::WALK_CULL || kind > (int)pt::WALK_TRI8)
+        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_host_walk_buffer: bad argument");
+    const size_t n = nodes_bytes / MI3PT_BVHNODE_STRIDE, nt = triangles_bytes / MI3PT_TRIANGLE_STRIDE;
+    if (n > 0x7fffffffu || nt > 0x7fffffffu) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_host_walk_buffer: too many nodes or triangles");
+    const uint8_t *src = static_cast<const uint8_t *>(nodes), *tsrc = static_cast<const uint8_t *>(triangles);
+    *bytes_out = 0;
+    pt::TreeCompile tree;
+    if (const char *e = pt::compile_tree(src, n, tree)) return pt_set_error(MI3PT_ERR_INVALID, e);
+    if (!(tree.cull_stack_ok && tree.npackets != 0)) return MI3PT_OK;
+    pt::WalkOptions opt;
+    opt.collapse = collapse; opt.packet_order = packet_order; opt.eight_wide = kind >= (int)pt::WALK_CW8;
+    const std::vector<pt::TriVerts> verts = pt::triangle_verts(tsrc, nt);
+    std::vector<uint8_t> kept;
+    auto sink = [&](pt::WalkBuffer k, const void *p, size_t bytes) {
+        if ((int)k == kind) kept.assign(static_cast<const uint8_t *>(p), static_cast<const uint8_t *>(p) + bytes);
+        return MI3PT_OK;
+    };
+    pt::WalkCompile walk;
+    if (int rc = pt::compile_walk(src, n, verts.data(), nt, tree.npackets, opt, sink, walk)) return rc;
+    *bytes_out = kept.size();
+    if (out) {
+        if (capacity < kept.size()) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_host_walk_buffer: the buffer is larger than `capacity`");
+        if (!kept.empty()) std::memcpy(out, kept.data(), kept.size());
+    }
     return MI3PT_OK;
 }

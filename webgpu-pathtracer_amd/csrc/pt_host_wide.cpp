@@ -86,6 +86,10 @@ bool collapse_optimal(const uint8_t *src, size_t n, int W, const std::vector<uin
 // Internal children are numbered consecutively in ascending slot order (breadth-first queue); a node's leaf children get the
 // records base + slot of a record array of their own (slots between its first and last leaf slot are allocated; a slot in
 // between that holds no leaf stays an inert record).  Weights: 8 bits against a per-node power of two, rounded up.
+// An EMPTY slot carries an inverted box (255, 0), which the walk's box test does NOT reject in general (PROOFS.md 4a: a tiny packet
+// close to the origin, seen from far away, passes it): what keeps a walk out of an empty slot is the packet's OCCUPANCY MASK
+// (CW8Packet::tri bits 24-31), which the kernel ANDs onto its hit mask; and whatever slot of whatever packet an index is formed
+// from, base + 0 .. 7 stays inside the records: eight inert ones at the head (base = next - first >= 8 - 7) and eight at the tail.
 bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per triangle: a, pad, b, pad, c, pad */, size_t nt,
                       const std::vector<float> &wmax, Cw8Build &out, bool greedy)
 {
@@ -182,7 +186,7 @@ bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per
         if (first >= 0) { rec_base[w] = (uint32_t)(next_rec - (size_t)first); next_rec += (size_t)(last - first + 1); }
     }
     if (next_rec + 8 >= (1u << 24)) return false;
-    out.records.assign(next_rec, pt::TriPacket64());
+    out.records.assign(next_rec + 8, pt::TriPacket64());      // (+ 8: base + 7 of the last packet with leaves stays inside)
     for (auto &q : out.records) {      // inert: an empty box, a degenerate triangle
         for (int k = 0; k < 3; k++) { q.a[k] = q.e1[k] = q.e2[k] = 0.0f; q.bmin[k] = 1.0f; q.bmax[k] = -1.0f; }
         q.unsafe = 0;
@@ -190,9 +194,9 @@ bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per
     for (size_t w = 0; w < np; w++) {
         pt::CW8Packet &c = out.packets[w];
         const auto &ks = kids[w];
-        uint32_t imask = 0, nchild = 0;
+        uint32_t imask = 0, occupied = 0;
         for (int sl = 0; sl < 8; sl++)
-            if (ks[(size_t)sl] >= 0) { nchild++; if (!is_leaf((size_t)ks[(size_t)sl])) imask |= 1u << sl; }
+            if (ks[(size_t)sl] >= 0) { occupied |= 1u << sl; if (!is_leaf((size_t)ks[(size_t)sl])) imask |= 1u << sl; }
         uint32_t meta = imask << 24;
         for (int ax = 0; ax < 3; ax++) {
             double lo = 1e300, hi = -1e300, maxabs = 0.0;
@@ -220,12 +224,15 @@ bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per
             meta |= (uint32_t)(e + 127) << (8 * ax);
             const float cf = (float)cell;
             for (int sl = 0; sl < 8; sl++) {
-                uint32_t a = 255u, z = 0u;
+                uint32_t a = 255u, z = 0u;                           // empty slot: an inverted box; kept out of the walk by the occupancy mask, not by this
                 if (ks[(size_t)sl] >= 0) {
                     const size_t ci = (size_t)ks[(size_t)sl];
                     const float b0 = box(ci, ax), b1 = box(ci, 3 + ax);
                     const double x0 = ((double)b0 - (double)o) / cell, x1 = ((double)b1 - (double)o) / cell;
-                    const double f0 = std::floor(x0) - 1.0, f1 = std::ceil(x1) + 1.0;
+                    double f0 = std::floor(x0) - 1.0, f1 = std::ceil(x1) + 1.0;
+                    // (x0 / x1 are rounded quotients: a whole cell of margin is decided exactly, see plane_cells_from_origin)
+                    if (!plane_cells_from_origin(b0, o, (f0 + 1.0) * cell, true)) f0 -= 1.0;
+                    if (!plane_cells_from_origin(b1, o, (f1 - 1.0) * cell, false)) f1 += 1.0;
                     if (!(f0 >= 0.0 && f1 <= 254.0 && f0 < f1)) return false;
                     a = (uint32_t)f0; z = (uint32_t)f1;
                     if (!(std::fma((float)a, cf, o) <= b0 && std::fma((float)z, cf, o) >= b1)) return false;      // (the plain-division path's decode: see CWidePacket's builder, compile_walk)
@@ -266,7 +273,7 @@ bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per
             c.wq[sl >> 2] |= q << (8 * (sl & 3));
         }
         c.child = (child_base[w] & 0xffffffu) | (wexp << 24);
-        c.tri = (rec_base[w] & 0xffffffu) | (nchild << 24);
+        c.tri = (rec_base[w] & 0xffffffu) | (occupied << 24);
         for (int sl = 0; sl < 8; sl++) {
             if (ks[(size_t)sl] < 0 || !is_leaf((size_t)ks[(size_t)sl])) continue;
             const size_t li = (size_t)ks[(size_t)sl];
@@ -291,7 +298,9 @@ bool build_cw8(const uint8_t *src, size_t n, const float *verts /* 12 floats per
 // Host-only check of the 8-wide packets (no device: `-m "not gpu"` tests call it): obtains them for a tree + triangles in the reference's
 // layouts from the scene compile a context runs (pt_host_compile.cpp: compile_walk, real culling weights) and walks the result INDEPENDENTLY
 // of the builder's bookkeeping -- every leaf triangle of the tree reachable exactly once, every packet referenced exactly once, a leaf slot's record carrying that triangle's index
-// and its leaf's box bit for bit, every decoded child box (the fma the kernel's plain-division path uses) containing everything below it.
+// and its leaf's box bit for bit, every decoded child box (the fma the kernel's plain-division path uses) containing everything below it,
+// every packet's occupancy mask equal to "the slot's box is not (255, 0) on every axis", and record base + 7 inside the records for EVERY
+// packet (no index the triangle step can form from any hit mask leaves the array).
 // out[0..5] = packets, records, packet levels, children per packet x 1000, leaves reached, 1 if the kernel would be offered these packets.
 extern "C" int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes, const void *triangles, size_t triangles_bytes, int greedy, uint64_t out[6])
 {
@@ -355,7 +364,8 @@ extern "C" int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes
         float cell[3];
         for (int ax = 0; ax < 3; ax++) { const uint32_t e = (c.meta >> (8 * ax)) & 0xffu; const uint32_t bits = e << 23; std::memcpy(&cell[ax], &bits, 4); }
         std::array<float, 6> u = { 1e30f, 1e30f, 1e30f, -1e30f, -1e30f, -1e30f };
-        uint32_t rank = 0, children = 0;
+        uint32_t rank = 0, children = 0, occupied = 0;
+        if ((size_t)rbase + 7 >= b.records.size()) return fail("a record base whose slots leave the records");
         for (int sl = 0; sl < 8; sl++) {
             uint32_t qa[3], qz[3];
             bool empty = true;
@@ -366,6 +376,7 @@ extern "C" int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes
             const bool internal = (imask >> sl) & 1u;
             if (empty) { if (internal) return fail("an empty slot marked internal"); continue; }
             children++;
+            occupied |= 1u << sl;
             std::array<float, 6> cb;                   // what lies below this slot
             if (internal) cb = below[(size_t)base + rank++];
             else {
@@ -387,7 +398,8 @@ extern "C" int mi3pt_host_eight_wide_check(const void *nodes, size_t nodes_bytes
                 u[(size_t)ax] = std::min(u[(size_t)ax], cb[(size_t)ax]); u[3 + (size_t)ax] = std::max(u[3 + (size_t)ax], cb[3 + (size_t)ax]);
             }
         }
-        if (children != ((c.tri >> 24) & 15u) || children < 2) return fail("a packet's child count");
+        if (occupied != (c.tri >> 24)) return fail("a packet's occupancy mask is not its non-empty slots");
+        if (children < 2) return fail("a packet's child count");
         below[w] = u;
     }
     if (reached != nleaves) return fail("not every leaf is reachable");

@@ -24,6 +24,17 @@ static inline int32_t ldi(const uint8_t *p, size_t off) { int32_t v; std::memcpy
 static inline uint32_t ldu(const uint8_t *p, size_t off) { uint32_t v; std::memcpy(&v, p + off, 4); return v; }
 // precondition of the exact fast slab test (pt_kernels.hip, RayPre): per box, every coordinate is 0 or within [2^-70, 2^60]
 bool node_box_safe(const uint8_t *src, size_t node);
+// the compressed packets' outward rounding, decided EXACTLY: is the plane b at least / at most k cells above the grid origin o, i.e.
+// b - o >= kc (at_least) or b - o <= kc (!at_least), with kc = k x cell exact in double?  b - o as an error-free pair (TwoSum): the rounded
+// difference alone calls a plane 3e-15 cells short of an index line "on" it (a sphere's 1e-17 residue beside an origin at -0.5), and the
+// decoded box then misses its whole cell of margin by that much
+static inline bool plane_cells_from_origin(float b, float o, double kc, bool at_least)
+{
+    const double x = (double)b, y = -(double)o;
+    const double s = x + y, bb = s - x, e = (x - (s - bb)) + (y - bb);
+    if (s != kc) return at_least ? s > kc : s < kc;
+    return at_least ? e >= 0.0 : e <= 0.0;
+}
 // the SAH-optimal grouping of a binary tree's nodes into W-wide packets, and the eight-wide packets of kernel variant 14 (pt_host_wide.cpp)
 struct WideCollapse {
     int W = 4;

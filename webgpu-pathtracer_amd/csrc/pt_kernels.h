@@ -121,7 +121,7 @@ struct CWidePacket {
     float o[3];              // grid origin: at least two cells below the smallest child coordinate on each axis
     uint32_t meta;           // bits 0-7 / 8-15 / 16-23: biased exponents of the cell size per axis (cell = 2^(e - 127)); bits 24-26: children
     uint32_t qlo[3];         // per axis: the four children's lower cell indices, one byte each (child k = byte k); empty slot: 255
-    uint32_t qhi[3];         // ... upper cell indices; empty slot: 0
+    uint32_t qhi[3];         // ... upper cell indices; empty slot: 0 (the box test may PASS such a slot, PROOFS.md 4a: its ref, REF_NONE, makes the entry empty)
     uint32_t cull01, cull23; // culling weights, 16 bits each (as WidePacket)
     uint32_t ref[4];         // child references (as WidePacket)
 };
@@ -151,10 +151,13 @@ struct CW8Packet {
     float o[3];              // grid origin (as CWidePacket)
     uint32_t meta;           // bits 0-7 / 8-15 / 16-23: biased cell exponents per axis; bits 24-31: mask of the slots that hold INTERNAL children
     uint32_t qlo[3][2];      // per axis: lower cell indices of slots 0-3, 4-7 (one byte each); empty slot: 255
-    uint32_t qhi[3][2];      // ... upper cell indices; empty slot: 0
+    uint32_t qhi[3][2];      // ... upper cell indices; empty slot: 0 (a marker the host-side check reads, NOT what keeps a walk out: `tri`)
     uint32_t wq[2];          // culling weights of slots 0-3, 4-7: W_k <= wq_k * 2^(wexp - 127), rounded up (empty / leafless: 0)
     uint32_t child;          // bits 0-23: packet index of the first internal child; bits 24-31: wexp (255: never skip below this node)
-    uint32_t tri;            // bits 0-23: record base (slot s -> record base + s); bits 24-27: number of children (the box-test count)
+    uint32_t tri;            // bits 0-23: record base (slot s -> record base + s; base + 0 .. 7 lie inside the records for EVERY packet: eight
+                             // inert records at either end); bits 24-31: OCCUPANCY mask of the slots -- bit s set: slot s holds a child.  The walk
+                             // ANDs its hit mask with it: an empty slot's inverted box is not rejected by the box test in general (PROOFS.md 4a).
+                             // Its popcount is the number of children (the box-test count)
 };
 static_assert(sizeof(CW8Packet) == 80, "five 16-B vectors");
 #ifndef PT_W8_LEAF_CAP_VALUE

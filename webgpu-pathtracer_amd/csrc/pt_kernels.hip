@@ -1782,7 +1782,11 @@ __global__ void __launch_bounds__(64, DIAG ? SM_OTHER_WAVES_PER_SIMD : WAVES) k_
                             mask |= h_ ? (1u << k) : 0u;
                         }
                     }
-                    cnt.box += (tb >> 24) & 15u;         // the packet's number of children
+                    // the box test does NOT keep a ray out of an EMPTY slot (its inverted box passes cwide_hit when the packet is tiny, near the
+                    // origin and far away: PROOFS.md 4a; the plain-division test passes it for a NaN): the packet's occupancy mask does
+                    const uint32_t occ = tb >> 24;
+                    mask &= occ;
+                    cnt.box += (uint32_t)__popc(occ);    // the packet's number of children
                     // the leaves that were hit: ONE entry {record base, hit slots} in the lane's leaf list (nl <= LCAP - 1 before the step: the slot is free)
                     // both hit masks -- internal children in bits 0-7, leaves in bits 8-15 -- moved from slot order into visiting order
                     // (bit s -> bit s ^ octant: three conditional swaps, on both bytes at once)

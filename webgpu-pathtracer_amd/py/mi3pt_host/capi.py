@@ -49,7 +49,7 @@ SYMBOLS = (
     "mi3pt_set_env_sampling", "mi3pt_device_build_bvh",
     "mi3pt_set_pipelining", "mi3pt_flush", "mi3pt_set_present_mode", "mi3pt_raytrace_launch_span", "mi3pt_batch_capacity", "mi3pt_debug_active_variant", "mi3pt_debug_last_launch", "mi3pt_submit_frames", "mi3pt_debug_set_packet_layout",
     "mi3pt_debug_intersect", "mi3pt_debug_intersect_shipped", "mi3pt_debug_pairs", "mi3pt_debug_math", "mi3pt_debug_wave_times", "mi3pt_host_build_bvh", "mi3pt_host_build_bvh_f64",
-    "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_host_scene_compile", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
+    "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_host_scene_compile", "mi3pt_host_walk_buffer", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
     "mi3pt_create_group", "mi3pt_group_size", "mi3pt_group_member",
     "mi3pt_tile_global_row", "mi3pt_tile_owner",
     "mi3pt_render_aovs", "mi3pt_read_aov", "mi3pt_aov_device_ptr",
@@ -149,6 +149,7 @@ def load_library(path=None):
     lib.mi3pt_host_env_cdf.argtypes = [c_void_p, c_int, c_int, c_void_p]
     lib.mi3pt_host_eight_wide_check.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p]
     lib.mi3pt_host_scene_compile.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_size_t]
+    lib.mi3pt_host_walk_buffer.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
     lib.mi3pt_host_sky_tiles.argtypes = [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
     lib.mi3pt_device_count.argtypes = [ctypes.POINTER(c_int)]
     lib.mi3pt_device_name.argtypes = [c_int, ctypes.c_char_p, c_size_t]
@@ -270,6 +271,25 @@ def host_scene_compile(nodes, triangles, collapse=-1, packet_order=0, want_eight
     _check(lib, lib.mi3pt_host_scene_compile(_ptr(nd), nd.nbytes, _ptr(tr), tr.nbytes, int(collapse), int(packet_order),
                                              1 if want_eight_wide else 0, _ptr(out), len(out)))
     return dict(zip(SCENE_COMPILE_FIELDS, (int(x) for x in out)))
+
+
+# mi3pt_host_walk_buffer's kinds, and the record size of each (csrc/pt_kernels.h: uint32, WidePacket, CWidePacket, TriPacket64, CW8Packet, TriPacket64)
+WALK_CULL, WALK_WIDE, WALK_CWIDE, WALK_TRI64, WALK_CW8, WALK_TRI8 = range(6)
+WALK_RECORD_BYTES = (4, 128, 64, 64, 80, 64)
+WALK_DIGEST_FIELD = (None, "digest_wide_packets", "digest_cwide_packets", "digest_tri_records", "digest_cw8_packets", "digest_cw8_records")
+
+
+def host_walk_buffer(nodes, triangles, kind, collapse=-1, packet_order=0):
+    """mi3pt_host_walk_buffer: the bytes of one buffer of the scene compile's walk stage as (records, WALK_RECORD_BYTES[kind]) uint8;
+    zero records when the compile does not build it for this tree."""
+    lib = load_library()
+    nd, tr = np.ascontiguousarray(nodes), np.ascontiguousarray(triangles)
+    n = ctypes.c_size_t(0)
+    args = (_ptr(nd), nd.nbytes, _ptr(tr), tr.nbytes, int(collapse), int(packet_order), int(kind))
+    _check(lib, lib.mi3pt_host_walk_buffer(*args, None, 0, ctypes.byref(n)))
+    out = np.zeros(max(n.value, 1), np.uint8)
+    _check(lib, lib.mi3pt_host_walk_buffer(*args, _ptr(out), out.nbytes, ctypes.byref(n)))
+    return out[:n.value].reshape(-1, WALK_RECORD_BYTES[kind])
 
 
 def host_env_cdf(rgba):
