@@ -229,7 +229,13 @@ int mi3pt_tile_owner(int y, int nranks, int block_rows);
  * raytrace.ts:104-121 (triangles), :138-160 (materials), :177-193 (BVH nodes).
  * nbytes must be a non-zero multiple of the stride.  Buffer handles are resolved at
  * dispatch time, so a new scene is picked up by the next submit (the reference needs
- * a reset() for that: raytrace.ts:403 vs :508-522). */
+ * a reset() for that: raytrace.ts:403 vs :508-522).
+ * mi3pt_upload_bvh checks EVERY record of the buffer, the nodes the root never reaches included: a child index of a non-leaf
+ * node that is not negative must be greater than its parent's and inside the buffer, and a leaf's triangleIndex must not be
+ * negative -- MI3PT_ERR_INVALID otherwise, and the scene uploaded before stays (the reference's walk would not care about
+ * records it never visits; this is what bounds every walk on the device).  Anything else is rendered as the reference's walk
+ * defines it: a leaf as root, absent children, shared subtrees, triangles with several leaves, isLeaf values other than 0 and 1
+ * (internal nodes), boxes that are NaN, infinite, inverted or empty. */
 int mi3pt_upload_triangles(mi3pt_ctx *ctx, const void *bytes, size_t nbytes);
 int mi3pt_upload_materials(mi3pt_ctx *ctx, const void *bytes, size_t nbytes);
 int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes);

@@ -24,12 +24,17 @@ PT_DEV float pow2i(int n) { return __uint_as_float((uint32_t)(n + 127) << 23); }
 // compiler's IEEE expansions (11 / 11 / 14).  Each identity was checked by exhaustion on
 // gfx950 (profiles/div_proof.hip; logs under profiles/r01_g_*_proof_exhaustive.log) and is
 // only applied where no intermediate can leave the normal range; outside, the plain
-// operation runs.  Results are bit-identical to '/', 1.0f / x and sqrtf.
+// operation runs.  Results are bit-identical to '/', 1.0f / x and sqrtf -- with one exception,
+// the sign of a zero quotient of div_pre (below).
 // ---------------------------------------------------------------------------------
 
 // RN(n/d) given y = RN(1/d): all 2^23 x 2^23 significand pairs checked; the caller guarantees
 // that n is 0 or large enough for the residual to be exact (|n| >= 2^-103) and that n/d stays
 // within the normal range.
+// n = -0 gives +0 where '/' gives -0 (for d > 0): q0 = -0, the residual fma rounds d * 0 + -0 to +0, and
+// +0 * y + -0 is +0.  The callers: normalize() copies the component's sign back onto the quotient (the
+// length is positive); the slab tests only order and compare their quotients, and -0 == +0 in every
+// comparison and in min / max of unequal values; the uv numerators (pixel indices) are never negative.
 PT_DEV float div_pre(float n, float d, float y)
 {
     const float q0 = n * y;

@@ -168,7 +168,7 @@ const char *compile_tree(const uint8_t *src, size_t n, TreeCompile &out)
         }
     }
     // The 64-entry abort (raytrace.wgsl:167-171) counts leaves too: it cannot fire while the
-    // worst case stays below 64.  LDS holds 32 entries per lane: the node stack (internal
+    // worst case stays below 64.  LDS holds SM_LDS_DEPTH (24) entries per lane: the node stack (internal
     // nodes only in the deferred walk) from the bottom, parked leaves from the top.
     out.tree_proper = proper && worst < 64;
     out.leaf_cap = out.tree_proper && (int)worst_internal <= SM_LDS_DEPTH - 4 ? SM_LDS_DEPTH - (int)worst_internal : 0;
@@ -252,12 +252,23 @@ int compile_walk(const uint8_t *src, size_t n, const TriVerts *tris, size_t nt, 
         e1 = std::sqrt(e1); e2 = std::sqrt(e2);
         E = e1 * e2; Lsum = e1 + e2;
     };
+    // The nodes the root reaches (children come after their parent: one forward pass).  No walk visits any other node, so no other node
+    // enters the statistics, denies the compressed packets or writes a triangle's record -- a buffer may carry records nobody walks,
+    // with any box and any (uploaded) triangle.  What the UPLOAD checks it checks on every record, and so does the line below.
+    std::vector<uint8_t> reached(n, 0);
+    reached[0] = 1;
+    for (size_t i = 0; i < n; i++) {
+        if (!reached[i] || is_leaf(src, i)) continue;
+        for (int32_t c : { ldi(rec_of(src, i), 32), ldi(rec_of(src, i), 36) })
+            if (c >= 0 && (size_t)c < n) reached[(size_t)c] = 1;
+    }
     double mean_l = 0.0;
     size_t counted = 0;
     for (size_t i = 0; i < n; i++) {
         if (!is_leaf(src, i)) continue;
         const int32_t ti = ldi(rec_of(src, i), 40);
-        if (ti < 0 || (size_t)ti >= nt) return MI3PT_OK;      // (the context's check_scene reports it; no analysis)
+        if (ti < 0 || (size_t)ti >= nt) return MI3PT_OK;      // (the context's check_scene reports it, reachable or not; no analysis)
+        if (!reached[i]) continue;
         double E, Ls;
         tri_el((size_t)ti, E, Ls);
         if (Ls == Ls && Ls < 1e30) { mean_l += Ls; counted++; }
@@ -281,6 +292,7 @@ int compile_walk(const uint8_t *src, size_t n, const TriVerts *tris, size_t nt, 
     std::vector<uint8_t> nested(n, 0);
     bool compressible = true;
     for (size_t i = 0; i < n; i++) {
+        if (!reached[i]) continue;          // (nested stays 0: never absorbed, never opened)
         const Box b = box_of(src, i);
         for (int k = 0; k < 3; k++)
             if (!(std::fabs(b.mn[k]) < 1e30f && std::fabs(b.mx[k]) < 1e30f)) compressible = false;
@@ -539,8 +551,10 @@ int compile_walk(const uint8_t *src, size_t n, const TriVerts *tris, size_t nt, 
                 std::vector<TriPacket64> t64(ok ? nt : 0);
                 if (ok) {
                     std::vector<uint8_t> seen(nt, 0);
+                    // (only the leaves the root reaches: a node nobody walks may name a reachable leaf's triangle with another box, and
+                    // the record's box is the exact test of the REACHABLE leaf)
                     for (size_t i = 0; i < n; i++) {
-                        if (!is_leaf(src, i)) continue;
+                        if (!is_leaf(src, i) || !reached[i]) continue;
                         const size_t ti = (size_t)ldi(rec_of(src, i), 40);
                         const TriVerts &v = tris[ti];
                         TriPacket64 &q = t64[ti];
@@ -610,7 +624,7 @@ int compile_walk(const uint8_t *src, size_t n, const TriVerts *tris, size_t nt, 
         std::vector<float> ws;
         ws.reserve(nt);
         for (size_t i = 0; i < n; i++) {
-            if (!is_leaf(src, i)) continue;
+            if (!is_leaf(src, i) || !reached[i]) continue;
             const Box b = box_of(src, i);
             const double x = (double)b.mx[0] - b.mn[0], y = (double)b.mx[1] - b.mn[1], z = (double)b.mx[2] - b.mn[2];
             if ((x <= thin || y <= thin || z <= thin) && area0 > 0.0) {

@@ -97,7 +97,9 @@ PT_DEV f3 normalize(f3 a)
     if (comps && l >= 9.094947017729282e-13f && l <= 1.099511627776e12f) {
         const float y0 = __builtin_amdgcn_rcpf(l);
         const float y = fmaf(fmaf(-l, y0, 1.0f), y0, y0);          // RN(1/l), see ptm::rcp_exact
-        return F3(div_pre(a.x, l, y), div_pre(a.y, l, y), div_pre(a.z, l, y));
+        // (div_pre turns a numerator of -0 into +0 -- its residual fma rounds -0 + +0 to +0 -- where the division keeps the sign; l > 0,
+        // so the quotient's sign is the component's: one bit-field insert each)
+        return F3(__builtin_copysignf(div_pre(a.x, l, y), a.x), __builtin_copysignf(div_pre(a.y, l, y), a.y), __builtin_copysignf(div_pre(a.z, l, y), a.z));
     }
     return F3(a.x / l, a.y / l, a.z / l);
 }
