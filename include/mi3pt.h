@@ -62,7 +62,7 @@ extern "C" {
  * MI3PT_OPT_PACKET_ORDER, MI3PT_OPT_SIX_WAVES (22 .. 27); MI3PT_OPT_WAVES_PER_CU reads up to 24 (six waves per SIMD). */
 /* 4 (round 6): mi3pt_set_rows and mi3pt_measure_tile_cost are GONE (contiguous cost-balanced bands: measured 7 % slower than the dealt
  * 8-row blocks in round 4 and kept since as dead surface); mi3pt_set_kernel_variant accepts 14 (the eight-wide walk: an option).
- * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31); mi3pt_host_scene_compile; mi3pt_host_walk_buffer;
+ * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31); mi3pt_host_scene_compile; mi3pt_host_walk_buffer; mi3pt_host_route;
  * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3); mi3pt_denoise_guided, mi3pt_read_guided,
  * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4). */
 #define MI3PT_ABI_VERSION 4
@@ -701,6 +701,19 @@ int mi3pt_host_walk_buffer(const void *nodes, size_t nodes_bytes, const void *tr
  * every cut box and every box of the tree contains its children's. */
 int mi3pt_host_sky_tiles(const void *nodes, size_t nodes_bytes, const void *raytrace_uniforms, int width, int height,
                          int rank, int nranks, int block_rows, uint8_t *empty_out, size_t capacity, size_t *ntiles_out);
+/* Host-only (no device, no context): WHICH KERNEL a raytrace launch runs and on how many workgroups, by the function a context's launches
+ * go through, for `rows` launches described by MI3PT_HOST_ROUTE_INPUTS int64 each: 0 the requested variant (what
+ * mi3pt_debug_active_variant names); 1 / 2 the rank's tile, width and local rows; 3 frames of the launch, 4 compute units, 5
+ * MI3PT_OPT_WAVES_PER_CU, 6 tiles on the launch's active list (0: all), 7 MI3PT_OPT_SIX_WAVES; 8 walk_min, 9 leaf_min, 10 shade_split,
+ * 11 tail_policy, 12 job_chunk, 13 tri_pair; 14 / 15 / 16 whether the wave-times buffer, the tile-cost buffer and the service block are bound,
+ * 17 diag_lite; 18 maxBounces, 19 samplesPerFrame, 20 / 21 the bits of the resolution's two floats; 22 nodes, 23 scene flags, 24 root
+ * reference, 25 leaf_cap; 26 / 27 whether the compressed 4-ary / the 8-wide packets and their records are built.  Per row
+ * MI3PT_HOST_ROUTE_OUTPUTS int64: 0 kind, 1 variant, 2 lean, 3 workgroups (as mi3pt_debug_last_launch), 4 waves per SIMD, 5 one-axis
+ * culling condition, 6 walk threshold (as MI3PT_OPT_LAST_BUILD); 7 .. 18 the state-machine kernel's twelve template arguments (kind 1;
+ * 0 otherwise); 19 the library carries that instantiation; 20 the service-setup kernel runs in front.  For tests; no part of the ABI. */
+#define MI3PT_HOST_ROUTE_INPUTS 28
+#define MI3PT_HOST_ROUTE_OUTPUTS 21
+int mi3pt_host_route(const int64_t *in, size_t rows, int64_t *out);
 
 #ifdef __cplusplus
 }

@@ -112,7 +112,7 @@ struct mi3pt_ctx {
     int wide_leaf_cap = 0;
     uint32_t wide_root = 0;
     int num_cus = 256;              // hipDeviceProp_t::multiProcessorCount
-    pt::RtRoute last_route = { 0, 0, false, 0, 0, false, 0 };      // the kernel the most recent raytrace launch ran (mi3pt_debug_last_launch)
+    pt::RtRoute last_route;      // the kernel the most recent raytrace launch ran (mi3pt_debug_last_launch)
     // Debug: packet / triangle numbering (mi3pt_debug_set_packet_layout).  0 = breadth-first packets,
     // triangles as uploaded (shipped).  1 = packets in the reference's visiting order (node, right
     // subtree, left subtree) and triangles in leaf-visiting order: a pure relabelling.
@@ -1887,6 +1887,7 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     const mi3pt_ctx::PendingFrame &first = frames[0];
     const pt::AccUniforms acc = acc_from(first.u_acc);
     pt::RtLaunch L = build_launch(ctx, first.u_rt, acc);
+    const int variant = pick_variant(ctx);
     const bool f16 = ctx->storage == MI3PT_STORAGE_F16;
     const int par = (int)(ctx->seq & 1u);                        // stream, counters, queue head
     const int set = (int)(ctx->seq % (uint64_t)ctx->slot_sets);   // radiance slots
@@ -1914,7 +1915,7 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     L.park = ctx->d_park + (size_t)par * pt::PT_MAX_RESIDENT_WAVES * 6 * 64;
     L.service = reinterpret_cast<pt::RtService *>(ctx->d_service + (size_t)((ctx->seq - 1) % SERVICE_SLOTS) * service_slot_bytes());
     bool cost_measuring = false, cost_ordered = false;
-    if (int rc = cost_order_prepare(ctx, L, first.u_rt, pick_variant(ctx), rs, &cost_measuring, &cost_ordered)) return rc;
+    if (int rc = cost_order_prepare(ctx, L, first.u_rt, variant, rs, &cost_measuring, &cost_ordered)) return rc;
     if (ctx->timing)
         if (int rc = collect_rt_time(ctx, par)) return rc;      // the launch of two batches ago
     // Hold this launch until the previous one (on the other stream) has handed out its last job:
@@ -1926,7 +1927,7 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     // Only the state-machine kernel publishes a drain mark (pt_kernels.hip, the ticket draw).  A batch routed to the per-pixel
     // kernels -- launches beyond the packing limits, maxBounces >= 65536 -- gets its mark from the host side of its stream after
     // its last frame: left to a kernel that never stores it, the NEXT batch would wait for ever (round-4 advice).
-    ctx->last_route = pt::raytrace_route(L, pick_variant(ctx));          // (does not depend on the two fields set below)
+    ctx->last_route = pt::raytrace_route(L, variant);          // (does not depend on the two fields set below)
     uint32_t publish_after = 0;
     if (ctx->gate_enabled && launches) {
         if (ctx->launch_seq != 0 &&
@@ -1978,11 +1979,11 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     // (>= 250 k jobs: a short launch -- an interactive host's single frames -- is all ramp and drain, and keeps the ordinary build.  Counted in
     // tiles of the FRAME, empty ones included: which of the two builds a view gets does not depend on how much sky it shows --
     // tests/test_gpu_configs.py::test_walk_threshold_follows_the_view pins the sequence; the grid and the six-wave choice count the real jobs)
-    if (ctx->deep_by_view && ctx->walk_min == 0 && L.walk_min == PT_DEFAULT_WALK_MIN && pick_variant(ctx) == 13 &&
+    if (ctx->deep_by_view && ctx->walk_min == 0 && L.walk_min == PT_DEFAULT_WALK_MIN && variant == 13 &&
         (long long)pt::raytrace_grid_blocks(L.tile) * n >= 250000)
         L.walk_min = PT_DEEP_WALK_MIN;
-    ctx->last_route = pt::raytrace_route(L, pick_variant(ctx));          // (the grid and the build follow the number of jobs)
-    pt::launch_raytrace_setup(L, false, pick_variant(ctx), rs);
+    ctx->last_route = pt::raytrace_route(L, variant);          // (the grid and the build follow the number of jobs)
+    pt::launch_raytrace_setup(L, ctx->last_route, rs);
     if (ctx->timing) {
         HIP_TRY(hipEventRecord(ctx->ev_rt[par][0], rs));
         if (!ctx->span_started) { HIP_TRY(hipEventRecord(ctx->ev_span_start, rs)); ctx->span_started = true; }
@@ -1990,7 +1991,7 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     // (in front of the persistent kernel: it runs while the predecessor's last paths drain -- +0.4 % over behind it, where it would follow this
     // launch's own drain: profiles/sky_tiles_ab.log)
     if (sky_count && ctx->sky_tiles != 2) pt::launch_sky_samples(L, sky_list, sky_count, sky_samples, rs);
-    pt::launch_raytrace(L, false, pick_variant(ctx), rs);
+    pt::launch_raytrace(L, ctx->last_route, false, rs);
     if (sky_count && ctx->sky_tiles == 2) pt::launch_sky_samples(L, sky_list, sky_count, sky_samples, rs);
     if (publish_after && !ctx->debug_suppress_drain && hipStreamWriteValue32(rs, ctx->d_drain_flag, publish_after, 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -2160,9 +2161,9 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
             L.service = reinterpret_cast<pt::RtService *>(ctx->d_service + (size_t)SERVICE_SLOTS * service_slot_bytes());
             L.block_counters = ctx->d_block_counters;
             ctx->last_route = pt::raytrace_route(L, variant);
-            pt::launch_raytrace_setup(L, fused, variant, ctx->stream);
+            pt::launch_raytrace_setup(L, ctx->last_route, ctx->stream);
             if (ctx->timing) HIP_TRY(ctx->pass_timer[0].begin(ctx->stream));
-            pt::launch_raytrace(L, fused, variant, ctx->stream);
+            pt::launch_raytrace(L, ctx->last_route, fused, ctx->stream);
             HIP_TRY(hipGetLastError());
             if (ctx->timing) HIP_TRY(ctx->pass_timer[0].end(ctx->stream));
             ctx->last_radiance = ctx->d_radiance;

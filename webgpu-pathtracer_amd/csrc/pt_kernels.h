@@ -294,7 +294,7 @@ struct RtLaunch {
     const float4 *cam_base;      // state-machine kernel, or null: per texel of this rank's image, cam_pos + dir0 * focalDistance -- the part of
                                  // cameraToRay (raytrace.wgsl:219-238, 446) that depends on the PIXEL only, formed once per camera by
                                  // launch_camera_base instead of once per frame of a batch in the service step (same operations, same bits)
-    int32_t six_waves;           // the compressed-wide walk's build: 1 = six waves per SIMD, 0 = five, -1 = by the size of the launch (route_waves_per_simd)
+    int32_t six_waves;           // the compressed-wide walk's build: 1 = six waves per SIMD, 0 = five, -1 = by the size of the launch (raytrace_route)
     float *park;                 // state-machine kernel builds that park a path's throughput and collected light in MEMORY instead of LDS (the
                                  // six-wave build for very large trees: its whole LDS share is stack): [grid][6][64] floats, or null
     RtService *service;          // device memory for one RtService block (service_block_bytes()), or null: the tuned twin of the
@@ -302,14 +302,79 @@ struct RtLaunch {
 };
 size_t service_block_bytes();
 
-// The kernel launch_raytrace runs for a requested variant.  kind: 0 = per-pixel kernel (variant 1 / 2), 1 = state-machine kernel
-// (variant 4, 7, 9 .. 12; experiment builds: 5, 6, 8), 2 = k_raytrace_persistent (variant 3, experiment builds); lean: the build
-// without diagnostics (DIAG = false); blocks: its grid.
-struct RtRoute { int kind, variant; bool lean; int blocks; int waves; bool ymax; int walk_min; };      // (waves per SIMD the build is compiled for; the one-axis culling condition; the walk threshold: what names the instantiation)
+// One instantiation of k_raytrace_sm: its twelve template arguments, in their order (pt_kernels.hip says what each one does)
+struct SmBuild { bool defer, cull, wide, filt, ymax, diag, toplds, lite, cw; int wmin, waves; bool w8; };
+inline bool operator==(const SmBuild &a, const SmBuild &b)
+{
+    return a.defer == b.defer && a.cull == b.cull && a.wide == b.wide && a.filt == b.filt && a.ymax == b.ymax && a.diag == b.diag &&
+           a.toplds == b.toplds && a.lite == b.lite && a.cw == b.cw && a.wmin == b.wmin && a.waves == b.waves && a.w8 == b.w8;
+}
+#ifndef PT_X_TOP_CW
+#define PT_TOP_CW false
+#else
+#define PT_TOP_CW true          // (A/B build: the first PT_X_TOP_CW compressed packets staged in LDS per wave)
+#endif
+// Every instantiation of k_raytrace_sm the library carries, one row each: launch_raytrace launches the row a route's build equals
+// (and nothing for a build that has no row), raytrace_route says whether there is one (RtRoute::has_kernel).  The compiler lays the
+// kernels out in the order of the rows, and a kernel descriptor holds the distance to its code: the rows stand in the order that keeps
+// the code object what it was byte for byte, which puts the experiment build's extra rows (PT_SM_EXPERIMENTS: none in a release build) in between.
+//    DEFER  CULL   WIDE   FILT   YMAX   DIAG   TOPLDS LITE   CW     WMIN                 WAVES                    W8
+#define PT_SM_BUILDS_CW(X, TOPLDS, W8)      /* a compressed-packet walk: walk threshold x waves per SIMD x one-axis culling condition */ \
+    X(true,  true,  true,  true,  true,  false, TOPLDS, false, true, PT_DEEP_WALK_MIN,    SM_SIX_WAVES_PER_SIMD,   W8) \
+    X(true,  true,  true,  true,  false, false, TOPLDS, false, true, PT_DEEP_WALK_MIN,    SM_SIX_WAVES_PER_SIMD,   W8) \
+    X(true,  true,  true,  true,  true,  false, TOPLDS, false, true, PT_DEEP_WALK_MIN,    SM_TUNED_WAVES_PER_SIMD, W8) \
+    X(true,  true,  true,  true,  false, false, TOPLDS, false, true, PT_DEEP_WALK_MIN,    SM_TUNED_WAVES_PER_SIMD, W8) \
+    X(true,  true,  true,  true,  true,  false, TOPLDS, false, true, PT_DEFAULT_WALK_MIN, SM_SIX_WAVES_PER_SIMD,   W8) \
+    X(true,  true,  true,  true,  false, false, TOPLDS, false, true, PT_DEFAULT_WALK_MIN, SM_SIX_WAVES_PER_SIMD,   W8) \
+    X(true,  true,  true,  true,  true,  false, TOPLDS, false, true, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, W8) \
+    X(true,  true,  true,  true,  false, false, TOPLDS, false, true, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, W8)
+#ifdef MI3PT_EXPERIMENTS
+#define PT_SM_EXPERIMENTS(...) __VA_ARGS__
+#else
+#define PT_SM_EXPERIMENTS(...)
+#endif
+#define PT_SM_BUILDS(X) \
+    PT_SM_EXPERIMENTS(                       /* the lean builds of 14, 13, 12, 11, 10 + lane counts */ \
+    X(true,  true,  true,  true,  true,  false, false, true,  true,  PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, true) \
+    X(true,  true,  true,  true,  false, false, false, true,  true,  PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, true) \
+    X(true,  true,  true,  true,  true,  false, false, true,  true,  PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false) \
+    X(true,  true,  true,  true,  false, false, false, true,  true,  PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false) \
+    X(true,  true,  true,  true,  true,  false, false, true,  false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false) \
+    X(true,  true,  true,  true,  false, false, false, true,  false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false) \
+    X(true,  true,  true,  false, false, false, false, true,  false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)) \
+    PT_SM_BUILDS_CW(X, false, true)                                                                                             /* 14 */ \
+    PT_SM_BUILDS_CW(X, PT_TOP_CW, false)                                                                                        /* 13 */ \
+    PT_SM_EXPERIMENTS( \
+    X(true,  true,  true,  true,  true,  false, false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* lean 12 */ \
+    X(true,  true,  true,  true,  false, false, false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false))     /* lean 11 */ \
+    X(true,  true,  true,  false, false, false, false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* lean 10 */ \
+    X(true,  true,  false, false, false, false, false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* lean 9 */ \
+    X(true,  false, false, false, false, false, false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* lean 7 */ \
+    X(false, false, false, false, false, false, false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* lean 4 */ \
+    X(true,  true,  true,  false, false, true,  false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* twin 10 */ \
+    X(true,  true,  false, false, false, true,  false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* twin 9 */ \
+    PT_SM_EXPERIMENTS( \
+    X(true,  false, false, false, false, true,  true,  false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* twin 8 */ \
+    X(true,  false, false, false, false, true,  false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* twin 7 */ \
+    X(false, false, false, false, false, true,  true,  false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false)      /* twin 6 */ \
+    X(false, false, false, false, false, true,  false, false, false, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, false))     /* twin 4, 5 */
+
+// The kernel launch_raytrace runs for a requested variant (raytrace_route, pt_host_route.cpp: the one place that decides it).  kind: 0 =
+// per-pixel kernel (variant 1 / 2), 1 = state-machine kernel (variant 4, 7, 9 .. 14; experiment builds: 5, 6, 8), 2 = k_raytrace_persistent
+// (variant 3, experiment builds); lean: the build without diagnostics (DIAG = false); blocks: its grid; build (kind 1): the instantiation,
+// has_kernel: it is a row of PT_SM_BUILDS; setup: k_rt_service_setup runs in front.  waves, ymax, walk_min: what the build is compiled for,
+// as mi3pt_debug_last_launch / MI3PT_OPT_LAST_BUILD report it -- waves per SIMD (a diagnostic twin: SM_OTHER_WAVES_PER_SIMD), YMAX of a lean
+// build, WMIN (a twin: the launch's own walk_min)
+struct RtRoute {
+    int kind = 0, variant = 0; bool lean = false; int blocks = 0;
+    int waves = 0; bool ymax = false; int walk_min = 0;
+    SmBuild build = {}; bool has_kernel = true, setup = false;
+};
 RtRoute raytrace_route(const RtLaunch &L, int variant);
 bool raytrace_variant_fuses(int variant);      // can launch_raytrace fold the accumulate pass into this variant's kernel?  (the per-pixel kernels)
-void launch_raytrace_setup(const RtLaunch &L, bool fuse_accumulate, int variant, hipStream_t s);    // before launch_raytrace, same stream
-void launch_raytrace(const RtLaunch &L, bool fuse_accumulate, int variant, hipStream_t s);
+// both take the route raytrace_route gave for L; `fuse_accumulate` only where raytrace_variant_fuses(variant)
+void launch_raytrace_setup(const RtLaunch &L, const RtRoute &r, hipStream_t s);    // before launch_raytrace, same stream
+void launch_raytrace(const RtLaunch &L, const RtRoute &r, bool fuse_accumulate, hipStream_t s);
 // fills `out` (tile.local_rows x tile.tex_w float4) for RtLaunch::cam_base from L.un / L.tile
 void launch_camera_base(const RtLaunch &L, float4 *out, hipStream_t s);
 // the running mean over nframes consecutive radiance slots (one frame: nframes 1, slot_pixels unused), at most max_blocks blocks of 256;

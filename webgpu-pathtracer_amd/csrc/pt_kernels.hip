@@ -2527,233 +2527,27 @@ __global__ void __launch_bounds__(64, DIAG ? SM_OTHER_WAVES_PER_SIMD : WAVES) k_
     }
 }
 
-int raytrace_persistent_blocks(const Tile &tile, int nframes, int waves_per_cu, int num_cus, bool tuned, int waves_per_simd, int job_tiles)
-{
-    const int ntiles = job_tiles > 0 ? job_tiles : raytrace_grid_blocks(tile);
-    if (num_cus <= 0) num_cus = 256;
-    if (waves_per_simd <= 0) waves_per_simd = tuned ? SM_TUNED_WAVES_PER_SIMD : SM_OTHER_WAVES_PER_SIMD;
-    if (waves_per_cu > 4 * waves_per_simd) waves_per_cu = 0;          // (more than the build can keep resident: its own width)
-    if (waves_per_cu <= 0 || waves_per_cu > PT_MAX_WAVES_PER_CU) {
-        waves_per_cu = 4 * waves_per_simd;
-        // A small launch (an interactive host: one or two frames, or a small image) gets fewer waves: at least 8 jobs each,
-        // at least 4 per CU.  With a handful of jobs per wave a launch is all ramp and drain, and a launch that fills every
-        // wave slot keeps its successor out until its own waves exit; narrower launches overlap.  One 1080p frame per
-        // launch: 16 waves per CU, -6 % time; 640 x 360: 4, -20 % (profiles/r03_k_small_launches.log; fewer still is
-        // faster on the default scene and slower on every other one tried: MI3PT_OPT_WAVES_PER_CU)
-        // Up to ~3 frames of 1080p per launch, 16 per CU beats 20 on every scene tried (-5 ... -12 %: the successor finds
-        // four wave slots per CU free from the start); from 4 frames on the full width wins.
-        const long long jobs = (long long)ntiles * (nframes > 0 ? nframes : 1);
-        const long long want = (jobs + (long long)num_cus * 8 - 1) / ((long long)num_cus * 8);
-        if (want < 16) waves_per_cu = want < 4 ? 4 : (int)want;
-        else if (want < 48 && waves_per_cu > 16) waves_per_cu = 16;
-    }
-    int resident = num_cus * waves_per_cu;                            // the device's own CU count (hipDeviceProp_t)
-    if (resident > PT_MAX_RESIDENT_WAVES) resident = PT_MAX_RESIDENT_WAVES;
-    // One wave per JOB at most -- (frame slot, tile) pairs, not tiles of one frame.  Until round 4 this read `ntiles`: a rank of an
-    // 8-way split of 1080p has 17 x 240 = 4 080 tiles per frame, so its 512-frame launches ran 4 080 of the 5 120 wave slots
-    // (16 instead of 20 per CU) -- the "unexplained +14 % per pixel" of a rank of eight (profiles/r04_a_rank_penalty.log:
-    // fewer wave cycles per ray than the whole image, yet more time per ray).
-    const long long jobs = (long long)ntiles * (nframes > 0 ? nframes : 1);
-    return jobs < (long long)resident ? (int)jobs : resident;
-}
-
-int raytrace_grid_blocks(const Tile &tile)
-{
-    const int tiles_x = (tile.tex_w + 7) / 8;
-    const int tiles_y = (tile.local_rows + 7) / 8;
-    return tiles_x * tiles_y;
-}
-
-// Tiles of a frame that the state-machine kernel is given as jobs: all of them, or the launch's active list
-int raytrace_job_tiles(const RtLaunch &L)
-{
-    return L.ntiles_active > 0 ? L.ntiles_active : raytrace_grid_blocks(L.tile);
-}
-
-// Frame slot and bounce share a word in the state-machine kernel, and the sample count of a multi-sample frame is a float in the
-// pixel's texel: launches beyond these (absurd) limits run the per-pixel kernel, frame by frame.
-static bool launch_packs(const RtLaunch &L)
-{
-    return L.un.max_bounces < 65536 && L.nframes <= 65535 && L.un.samples_per_frame <= 16777216;
-}
-// The lean build (DIAG = false: no step statistics, the step-voting options as constants, the service step's scalars in
-// memory) runs unless a diagnostic buffer is bound or a step-voting option was changed (mi3pt_debug_set_option).
-static bool launch_is_lean(const RtLaunch &L)
-{
-    return (!L.wave_times || L.diag_lite) && !L.tile_cost && (L.walk_min == PT_DEFAULT_WALK_MIN || L.walk_min == PT_DEEP_WALK_MIN) && L.leaf_min == PT_DEFAULT_LEAF_MIN && L.shade_split == PT_DEFAULT_SHADE_SPLIT &&
-           L.tail_policy == PT_DEFAULT_TAIL_POLICY && L.job_chunk == PT_DEFAULT_JOB_CHUNK && L.tri_pair == 1 && L.service != nullptr;
-}
-// What the lean builds of the culling walks have as constants (ASSUME in the kernel): a scene with nodes whose root is an
-// internal node with a guard-range box, and a resolution of ordinary magnitude.  Every tree the culling walks are offered for
-// has nodes and an internal root; the rest fails for scenes ~1e18 across or images ~1e12 wide.
-static bool launch_assumptions_hold(const RtLaunch &L)
-{
-    return L.scene.nnodes != 0 && (L.scene.flags & 1u) != 0u && (L.scene.root_ref & PT_REF_LEAF) == 0u &&
-           L.un.res_x >= 9.5367431640625e-07f && L.un.res_x <= 1.099511627776e12f &&
-           L.un.res_y >= 9.5367431640625e-07f && L.un.res_y <= 1.099511627776e12f;
-}
-
-// The kernel a launch runs for a requested variant.  kind: 0 = per-pixel kernel (variant 1 / 2), 1 = state-machine kernel
-// (variant 4, 7, 9 .. 12; experiment builds: 5, 6, 8), 2 = k_raytrace_persistent (variant 3, experiment builds).
-static RtRoute route_launch(const RtLaunch &L, int variant)
-{
-    RtRoute r = { 0, variant <= 1 ? 1 : 2, false, 0 };
-    if (variant < 3) return r;
-#ifdef MI3PT_EXPERIMENTS
-    if (variant == 3) { r.kind = 2; r.variant = 3; return r; }
-#else
-    if (variant == 3) variant = 4;                       // (release builds: the experiment variants resolve to their nearest walk)
-    if (variant == 5 || variant == 6) variant = 4;
-    if (variant == 8) variant = 7;
-#endif
-    if (!launch_packs(L)) return r;                      // per-pixel kernel 2, frame by frame
-    r.kind = 1;
-    r.lean = launch_is_lean(L);
-    if (variant == 14 && !(L.scene.cw8 && L.scene.tripk8 && (L.scene.flags & 2u))) variant = 13;      // (the 8-wide walk never tests the root's own box)
-    if (variant == 13 && !(L.scene.cwide && L.scene.tripk64)) variant = 10;
-    if (L.walk_min == PT_DEEP_WALK_MIN && variant != 13 && variant != 14) r.lean = false;        // (the deep-walk threshold is instantiated for the compressed-wide walk only)
-#ifndef MI3PT_EXPERIMENTS
-    if (variant == 11 || variant == 12) variant = 10;       // (release builds: superseded by 13; the exact-packet walk with the exact slab test stands in -- same bits)
-#endif
-    if (variant >= 9 && variant <= 14 && r.lean && !launch_assumptions_hold(L)) variant = L.scene.leaf_cap >= 4 ? 7 : 4;
-    if (variant >= 10 && variant <= 14 && !r.lean) variant = 10;      // the diagnostic twin of the wide walks runs the exact slab test: same bits
-#ifndef MI3PT_EXPERIMENTS
-    if (variant < 9 && !r.lean) {
-        // release builds carry diagnostic twins for the culling walks only: the lean build runs (options and the diagnostic buffer
-        // are ignored) -- or, without a service block, the per-pixel kernel
-        if (!L.service) { r.kind = 0; r.variant = 2; return r; }
-        r.lean = true;
-    }
-#endif
-    r.variant = variant;
-    return r;
-}
-bool raytrace_variant_fuses(int variant)
-{
-#ifdef MI3PT_EXPERIMENTS
-    return variant <= 3;
-#else
-    return variant <= 2;
-#endif
-}
-// Waves per SIMD of the build a route runs.  The compressed-wide walk has two lean builds per instantiation: FIVE waves (96 registers, a
-// 24-entry LDS stack) and SIX (80 registers with a handful spilled around the walk loop; 19 entries -- or 25 with the parked path state in
-// memory, for very large trees).  Six waves overlap more of the per-step round trips: +2 .. +5 % on launches that run for tens of
-// milliseconds.  But a sixth more paths are in flight when the job queue runs empty, and that drain is paid once per launch: a rank of an
-// 8-way split (a 10 ms launch) is 2 .. 3 % SLOWER with six (profiles/r05_i_six_waves_by_launch_size.log).  So the choice goes by the size of
-// the launch: jobs (tiles x frames) per resident wave.  L.six_waves forces it (MI3PT_OPT_SIX_WAVES).  Other lean builds: five; twins: four.
-#ifndef PT_SIX_WAVES_MIN_JOBS
-#define PT_SIX_WAVES_MIN_JOBS 1500000      // (round 6, re-swept on the cheaper node step: six waves win from ~1.3 M jobs on -- profiles/r06_i_six_waves_threshold.log; was 2.5 M)
-#endif
-static int route_waves_per_simd(const RtLaunch &L, const RtRoute &r)
-{
-    if (!(r.kind == 1 && r.lean)) return SM_OTHER_WAVES_PER_SIMD;
-    if (r.variant == 13 || r.variant == 14) {
-#ifdef MI3PT_EXPERIMENTS
-        if (L.wave_times && L.diag_lite) return SM_TUNED_WAVES_PER_SIMD;      // (the lean build + lane counts: five)
-#endif
-        if (L.six_waves >= 0) return L.six_waves ? SM_SIX_WAVES_PER_SIMD : SM_TUNED_WAVES_PER_SIMD;
-        const long long jobs = (long long)raytrace_job_tiles(L) * (L.nframes > 0 ? L.nframes : 1);
-        // (a job of a very large tree -- the walk_min-44 builds -- is an order of magnitude longer)
-        return jobs >= (L.walk_min == PT_DEEP_WALK_MIN ? PT_SIX_WAVES_MIN_JOBS / 10 : PT_SIX_WAVES_MIN_JOBS) ? SM_SIX_WAVES_PER_SIMD : SM_TUNED_WAVES_PER_SIMD;
-    }
-    return SM_TUNED_WAVES_PER_SIMD;
-}
-static int persistent_blocks_for(const RtLaunch &L, const RtRoute &r)
-{
-    return raytrace_persistent_blocks(L.tile, L.nframes, L.waves_per_cu, L.num_cus, r.kind == 1 && r.lean, route_waves_per_simd(L, r), L.ntiles_active);
-}
-RtRoute raytrace_route(const RtLaunch &L, int variant)
-{
-    RtRoute r = route_launch(L, variant);
-    r.blocks = r.kind == 1 ? persistent_blocks_for(L, r) : raytrace_grid_blocks(L.tile);
-    r.waves = r.kind == 1 ? route_waves_per_simd(L, r) : 0;
-    r.ymax = r.kind == 1 && r.lean && r.variant >= 12 && (L.scene.flags & 4u) != 0u;
-    r.walk_min = r.kind == 1 ? (r.lean ? ((r.variant == 13 || r.variant == 14) && L.walk_min == PT_DEEP_WALK_MIN ? PT_DEEP_WALK_MIN : PT_DEFAULT_WALK_MIN) : L.walk_min) : 0;
-    return r;
-}
-
 // The lean builds read their service step's scalars from L.service: filled here, in stream order, by one wave.  Its own
 // call so that the caller can put its timing event between this and the raytrace kernel (the little kernel waits for the
 // first wave slot a draining predecessor frees; that wait is not the raytrace kernel's time).
-void launch_raytrace_setup(const RtLaunch &L, bool fuse, int variant, hipStream_t s)
+void launch_raytrace_setup(const RtLaunch &L, const RtRoute &r, hipStream_t s)
 {
-    (void)fuse;
-    const RtRoute r = route_launch(L, variant);
-    if (raytrace_grid_blocks(L.tile) > 0 && r.kind == 1 && r.lean)
-        hipLaunchKernelGGL(k_rt_service_setup, dim3(1), dim3(64), 0, s, L, L.service);
+    if (r.setup) hipLaunchKernelGGL(k_rt_service_setup, dim3(1), dim3(64), 0, s, L, L.service);
 }
 
-// (the caller has called launch_raytrace_setup with the same arguments on the same stream; `fuse` only where
-// raytrace_variant_fuses(variant))
-void launch_raytrace(const RtLaunch &L, bool fuse, int variant, hipStream_t s)
+// The kernel of a route (raytrace_route(L, variant), pt_host_route.cpp: every decision is taken there).  The caller has called
+// launch_raytrace_setup with the same arguments on the same stream; `fuse` only where raytrace_variant_fuses(variant).
+void launch_raytrace(const RtLaunch &L, const RtRoute &r, bool fuse, hipStream_t s)
 {
     const int blocks = raytrace_grid_blocks(L.tile);
     if (blocks <= 0) return;
     const dim3 block(64);
-    const RtRoute r = route_launch(L, variant);
     if (r.kind == 1) {
-        const dim3 grid(persistent_blocks_for(L, r));
-#define PT_SM(...) hipLaunchKernelGGL((k_raytrace_sm<__VA_ARGS__>), grid, block, 0, s, L)
-        //                               DEFER  CULL   WIDE   FILT   YMAX   DIAG
-#ifdef MI3PT_EXPERIMENTS
-        if (r.lean && L.wave_times && L.diag_lite && r.variant >= 10) switch (r.variant) {      // the lean build + lane counts
-            case 14: if (L.scene.flags & 4u) PT_SM(true, true, true, true, true, false, false, true, true, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, true);
-                     else PT_SM(true, true, true, true, false, false, false, true, true, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, true); break;
-            case 13: if (L.scene.flags & 4u) PT_SM(true, true, true, true, true, false, false, true, true); else PT_SM(true, true, true, true, false, false, false, true, true); break;
-            case 12: PT_SM(true,  true,  true,  true,  true,  false, false, true); break;
-            case 11: PT_SM(true,  true,  true,  true,  false, false, false, true); break;
-            default: PT_SM(true,  true,  true,  false, false, false, false, true); break;
-        } else
-#endif
-#ifndef PT_X_TOP_CW
-#define PT_TOP_CW false
-#else
-#define PT_TOP_CW true          // (A/B build: the first PT_X_TOP_CW compressed packets staged in LDS per wave)
-#endif
-        if (r.lean && r.variant == 14) {        // eight-wide compressed packets
-            const bool six = route_waves_per_simd(L, r) == SM_SIX_WAVES_PER_SIMD, ymax = (L.scene.flags & 4u) != 0u;
-            if (L.walk_min == PT_DEEP_WALK_MIN) {
-                if (six) { if (ymax) PT_SM(true, true, true, true, true, false, false, false, true, PT_DEEP_WALK_MIN, SM_SIX_WAVES_PER_SIMD, true); else PT_SM(true, true, true, true, false, false, false, false, true, PT_DEEP_WALK_MIN, SM_SIX_WAVES_PER_SIMD, true); }
-                else { if (ymax) PT_SM(true, true, true, true, true, false, false, false, true, PT_DEEP_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, true); else PT_SM(true, true, true, true, false, false, false, false, true, PT_DEEP_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, true); }
-            } else {
-                if (six) { if (ymax) PT_SM(true, true, true, true, true, false, false, false, true, PT_DEFAULT_WALK_MIN, SM_SIX_WAVES_PER_SIMD, true); else PT_SM(true, true, true, true, false, false, false, false, true, PT_DEFAULT_WALK_MIN, SM_SIX_WAVES_PER_SIMD, true); }
-                else { if (ymax) PT_SM(true, true, true, true, true, false, false, false, true, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, true); else PT_SM(true, true, true, true, false, false, false, false, true, PT_DEFAULT_WALK_MIN, SM_TUNED_WAVES_PER_SIMD, true); }
-            }
-        } else
-        if (r.lean && r.variant == 13) {        // compressed wide packets (SceneRefs::flags bit 2: the one-axis culling condition suits this scene)
-            const bool six = route_waves_per_simd(L, r) == SM_SIX_WAVES_PER_SIMD, ymax = (L.scene.flags & 4u) != 0u;
-            if (L.walk_min == PT_DEEP_WALK_MIN) {
-                if (six) { if (ymax) PT_SM(true, true, true, true, true, false, PT_TOP_CW, false, true, PT_DEEP_WALK_MIN, SM_SIX_WAVES_PER_SIMD); else PT_SM(true, true, true, true, false, false, PT_TOP_CW, false, true, PT_DEEP_WALK_MIN, SM_SIX_WAVES_PER_SIMD); }
-                else { if (ymax) PT_SM(true, true, true, true, true, false, PT_TOP_CW, false, true, PT_DEEP_WALK_MIN); else PT_SM(true, true, true, true, false, false, PT_TOP_CW, false, true, PT_DEEP_WALK_MIN); }
-            } else {
-                if (six) { if (ymax) PT_SM(true, true, true, true, true, false, PT_TOP_CW, false, true, PT_DEFAULT_WALK_MIN, SM_SIX_WAVES_PER_SIMD); else PT_SM(true, true, true, true, false, false, PT_TOP_CW, false, true, PT_DEFAULT_WALK_MIN, SM_SIX_WAVES_PER_SIMD); }
-                else { if (ymax) PT_SM(true, true, true, true, true, false, PT_TOP_CW, false, true); else PT_SM(true, true, true, true, false, false, PT_TOP_CW, false, true); }
-            }
-        } else
-        if (r.lean) switch (r.variant) {
-#ifdef MI3PT_EXPERIMENTS
-            case 12: PT_SM(true,  true,  true,  true,  true,  false); break;
-            case 11: PT_SM(true,  true,  true,  true,  false, false); break;
-#endif
-            case 10: PT_SM(true,  true,  true,  false, false, false); break;
-            case 9:  PT_SM(true,  true,  false, false, false, false); break;
-            case 7:  PT_SM(true,  false, false, false, false, false); break;
-            default: PT_SM(false, false, false, false, false, false); break;
-        } else switch (r.variant) {
-            case 10: PT_SM(true,  true,  true,  false, false, true); break;
-            case 9:  PT_SM(true,  true,  false, false, false, true); break;
-#ifdef MI3PT_EXPERIMENTS
-            case 8:  PT_SM(true,  false, false, false, false, true, true); break;
-            case 7:  PT_SM(true,  false, false, false, false, true); break;
-            case 6:  PT_SM(false, false, false, false, false, true, true); break;
-            default: PT_SM(false, false, false, false, false, true); break;
-#else
-            default: break;          // (not reached: route_launch)
-#endif
-        }
-#undef PT_SM
-        return;
+        const dim3 grid(r.blocks);
+#define PT_SM_ROW(...) if (r.build == SmBuild{ __VA_ARGS__ }) { hipLaunchKernelGGL((k_raytrace_sm<__VA_ARGS__>), grid, block, 0, s, L); return; }
+        PT_SM_BUILDS(PT_SM_ROW)
+#undef PT_SM_ROW
+        return;          // (a build without a row: RtRoute::has_kernel is false)
     }
 #ifdef MI3PT_EXPERIMENTS
     if (r.kind == 2) {

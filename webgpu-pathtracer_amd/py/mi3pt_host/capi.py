@@ -49,7 +49,7 @@ SYMBOLS = (
     "mi3pt_set_env_sampling", "mi3pt_device_build_bvh",
     "mi3pt_set_pipelining", "mi3pt_flush", "mi3pt_set_present_mode", "mi3pt_raytrace_launch_span", "mi3pt_batch_capacity", "mi3pt_debug_active_variant", "mi3pt_debug_last_launch", "mi3pt_submit_frames", "mi3pt_debug_set_packet_layout",
     "mi3pt_debug_intersect", "mi3pt_debug_intersect_shipped", "mi3pt_debug_pairs", "mi3pt_debug_math", "mi3pt_debug_wave_times", "mi3pt_host_build_bvh", "mi3pt_host_build_bvh_f64",
-    "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_host_scene_compile", "mi3pt_host_walk_buffer", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
+    "mi3pt_host_env_cdf", "mi3pt_host_eight_wide_check", "mi3pt_host_sky_tiles", "mi3pt_host_scene_compile", "mi3pt_host_walk_buffer", "mi3pt_host_route", "mi3pt_debug_set_option", "mi3pt_debug_get_option",
     "mi3pt_create_group", "mi3pt_group_size", "mi3pt_group_member",
     "mi3pt_tile_global_row", "mi3pt_tile_owner",
     "mi3pt_render_aovs", "mi3pt_read_aov", "mi3pt_aov_device_ptr",
@@ -151,6 +151,7 @@ def load_library(path=None):
     lib.mi3pt_host_scene_compile.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_size_t]
     lib.mi3pt_host_walk_buffer.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
     lib.mi3pt_host_sky_tiles.argtypes = [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
+    lib.mi3pt_host_route.argtypes = [c_void_p, c_size_t, c_void_p]
     lib.mi3pt_device_count.argtypes = [ctypes.POINTER(c_int)]
     lib.mi3pt_device_name.argtypes = [c_int, ctypes.c_char_p, c_size_t]
     lib.mi3pt_tile_local_rows.argtypes = [c_int, c_int, c_int, c_int]
@@ -290,6 +291,24 @@ def host_walk_buffer(nodes, triangles, kind, collapse=-1, packet_order=0):
     out = np.zeros(max(n.value, 1), np.uint8)
     _check(lib, lib.mi3pt_host_walk_buffer(*args, _ptr(out), out.nbytes, ctypes.byref(n)))
     return out[:n.value].reshape(-1, WALK_RECORD_BYTES[kind])
+
+
+# mi3pt_host_route's inputs and outputs, in order (include/mi3pt.h)
+ROUTE_INPUTS = (
+    "variant", "tex_w", "local_rows", "nframes", "num_cus", "waves_per_cu", "ntiles_active", "six_waves",
+    "walk_min", "leaf_min", "shade_split", "tail_policy", "job_chunk", "tri_pair", "wave_times", "tile_cost", "service", "diag_lite",
+    "max_bounces", "samples_per_frame", "res_x_bits", "res_y_bits", "nnodes", "flags", "root_ref", "leaf_cap", "cwide", "cw8")
+ROUTE_BUILD = ("defer", "cull", "wide", "filt", "ymax", "diag", "toplds", "lite", "cw", "wmin", "waves", "w8")      # k_raytrace_sm's template arguments
+ROUTE_OUTPUTS = ("kind", "variant", "lean", "blocks", "waves", "ymax", "walk_min") + tuple("build_" + b for b in ROUTE_BUILD) + ("has_kernel", "setup")
+
+
+def host_route(rows):
+    """mi3pt_host_route: the kernel each of `rows` (n x len(ROUTE_INPUTS) integers) would launch, as n x len(ROUTE_OUTPUTS) int64."""
+    lib = load_library()
+    rows = np.ascontiguousarray(rows, np.int64).reshape(-1, len(ROUTE_INPUTS))
+    out = np.zeros((len(rows), len(ROUTE_OUTPUTS)), np.int64)
+    _check(lib, lib.mi3pt_host_route(_ptr(rows), len(rows), _ptr(out)))
+    return out
 
 
 def host_env_cdf(rgba):
