@@ -27,7 +27,7 @@
  *     caller's (mi3pt_set_stream) -- and everything that can be observed happens in that stream's order; the raytrace
  *     kernels run on internal streams tied to it by events in both directions, which no caller can see.
  *     STREAM ORDERED, returning before the device has run anything: mi3pt_submit, mi3pt_submit_frames, mi3pt_flush,
- *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided.  mi3pt_set_uniforms, the setters of
+ *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided, mi3pt_estimate_convergence.  mi3pt_set_uniforms, the setters of
  *     modes and options and the *_device_ptr getters start no device work of their own (those that observe state launch
  *     the frame queue first).  A host that has set its own stream may therefore enqueue its work in front of and behind
  *     these calls on that stream -- fill a bound accumulation tensor, copy out of a *_device_ptr image -- and wait once.
@@ -35,6 +35,8 @@
  *     mi3pt_resize (the internal streams too), mi3pt_set_stream (the stream it leaves), mi3pt_bind_accumulation,
  *     mi3pt_set_moments when it changes the state, every mi3pt_read_*, mi3pt_sync, mi3pt_get_counters, mi3pt_pass_time_us,
  *     mi3pt_raytrace_launch_stats / _span, the mi3pt_debug_* probes, mi3pt_device_build_bvh, mi3pt_destroy.
+ *     BLOCKING, but for ONE EVENT only and without launching the frame queue: mi3pt_read_convergence and
+ *     mi3pt_read_convergence_tiles wait for the most recent mi3pt_estimate_convergence, not for what was enqueued behind it.
  *     Three things make a stream-ordered call wait ONCE: the first raytrace submit or mi3pt_render_aovs after a scene
  *     upload (or a change of kernel variant) compiles the scene and reads it back; the first call that needs an image
  *     allocates it, and a launch deeper than any before on this context replaces its radiance slots (freeing waits for
@@ -64,7 +66,8 @@ extern "C" {
  * 8-row blocks in round 4 and kept since as dead surface); mi3pt_set_kernel_variant accepts 14 (the eight-wide walk: an option).
  * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31); mi3pt_host_scene_compile; mi3pt_host_walk_buffer; mi3pt_host_route;
  * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3); mi3pt_denoise_guided, mi3pt_read_guided,
- * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4). */
+ * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4); mi3pt_estimate_convergence,
+ * mi3pt_read_convergence, mi3pt_read_convergence_tiles, struct mi3pt_convergence, MI3PT_PASS_CONVERGENCE (5). */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -92,8 +95,10 @@ typedef enum mi3pt_pass {
     MI3PT_PASS_FULLSCREEN = 2,
     MI3PT_PASS_AOV = 3,          /* -- no counterpart: the first-hit feature images (mi3pt_render_aovs).  Known to
                                     mi3pt_pass_time_us only; it has no uniform block (mi3pt_set_uniforms refuses it) */
-    MI3PT_PASS_GUIDED = 4        /* -- no counterpart: the feature-guided de-noise (mi3pt_denoise_guided), pack kernel and every level.
+    MI3PT_PASS_GUIDED = 4,       /* -- no counterpart: the feature-guided de-noise (mi3pt_denoise_guided), pack kernel and every level.
                                     Known to mi3pt_pass_time_us only */
+    MI3PT_PASS_CONVERGENCE = 5   /* -- no counterpart: the per-tile error estimate (mi3pt_estimate_convergence), its tile kernel and the
+                                    kernel that folds the summary.  Known to mi3pt_pass_time_us only */
 } mi3pt_pass;
 
 #define MI3PT_SUBMIT_RAYTRACE 1u
@@ -417,6 +422,62 @@ int mi3pt_moments_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes);
 #define MI3PT_GUIDED_VARIANCE 2u
 #define MI3PT_GUIDED_VARIANCE_EPS 1e-8f
 int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfloats);
+
+/* ---- the per-tile error estimate of the running mean: when to stop sampling -- no counterpart in the reference, which renders a fixed
+ * number of frames.  mi3pt_estimate_convergence reduces (accumulation image, moments image) on the device to one record per 8 x 8 tile
+ * and a 40-byte summary; a host reads those instead of two whole images.  Pinned arithmetic as everywhere: fp32, round to nearest even,
+ * nothing contracted, correctly rounded division.
+ * Tile grid: 8 x 8 texels over the context's compact image, as mi3pt_host_sky_tiles lays them out: tiles_x = ceil(width / 8),
+ * tiles_y = ceil(rows / 8), row-major; rows = this rank's local rows.
+ * Per texel q, with c = the accumulation image as mi3pt_read_texture(MI3PT_TEX_ACCUMULATION) would return it (a bound image included)
+ * and (M2, n) = its moments texel:
+ *   counts(q) = q lies inside [0, width) x [0, rows) and n >= 1 (a NaN n does not count: texels the accumulate rectangle never touched)
+ *   v(q) = the v of MI3PT_GUIDED_VARIANCE: fmax(((M2.r + M2.g) + M2.b) / (n * (n - 1)), 0) for n >= 2, else 0
+ *   s = ((c.r + c.g) + c.b) * (1.0f / 3.0f);   m = s < 0 ? 0 : s   (fmax(s, 0) for every number s; a NaN s STAYS a NaN: a mean that is
+ *   not a number must show in the verdict, not pass for black);   d = 1 + m;   d2 = d * d;   d4 = d2 * d2;   r(q) = v(q) / d4
+ * -- the variance of the tone-mapped mean x / (1 + x) summed over rgb, to first order: the derivative of x / (1 + x) is 1 / (1 + x)^2,
+ * taken at the texel's mean brightness.
+ * Per tile: the 64 lanes are j = 8 * (row in tile) + (column in tile); a lane that counts holds sum r, count 1, n_min n, a lane that does
+ * not holds sum 0, count 0, n_min +inf.
+ *   sum_r: six halving rounds, a[j] = a[j] + a[j + s] for j < s, s = 32, 16, 8, 4, 2, 1 (a fixed tree: the sum is reproducible)
+ *   max_r: fmaxf over 0 and the counting lanes' r (fmaxf drops a NaN: never a NaN, never below 0)
+ *   n_min: fminf over the lanes;   count: an integer
+ *   record: 4 x fp32 = (sum_r, max_r, (float)count, n_min); a tile with count 0 is (0, 0, 0, 0)
+ * Verdict, for threshold (a target RMSE of the tone-mapped mean; finite, >= 0) and min_frames (0 .. 2^24), t2 = (threshold * threshold)
+ * * 3.0f.  A tile with count > 0 is
+ *   young      iff n_min < (float)min_frames  (a texel that has only seen black has zero variance: min_frames is the guard against that)
+ *   above      iff young or !(sum_r <= t2 * (float)count)     (a NaN sum is above)
+ *   nonfinite  iff sum_r is NaN or +-inf
+ * Summary: every field is independent of the order in which the tiles are combined (integer sums, maxima of the bit patterns of
+ * non-negative floats), so it is bitwise reproducible.  "Converged" is tiles > 0 && tiles_above == 0.  The image-wide RMSE estimate,
+ * sqrt(sum over tiles of sum_r / (3 * texels)), is left to hosts, in double, from the tile map.
+ * mi3pt_estimate_convergence launches the frame queue first, as mi3pt_denoise_guided does -- the estimate is of every frame submitted so
+ * far -- and is asynchronous and stream ordered after that: two kernels, the summary's copy into pinned host memory, one event.  It
+ * changes no image, no counter and nothing mi3pt_debug_last_launch / MI3PT_OPT_LAST_BUILD report; frames submitted afterwards accumulate
+ * as if it had not been called.  The tile map and the summary are allocated by the first call and freed by mi3pt_resize / mi3pt_destroy
+ * (a context that never calls it allocates nothing and launches exactly what it launched before).
+ *   MI3PT_ERR_INVALID for a negative or non-finite threshold or min_frames outside 0 .. 2^24; MI3PT_ERR_STATE before mi3pt_resize or
+ *   while mi3pt_set_moments is off.
+ * mi3pt_read_convergence and mi3pt_read_convergence_tiles (nfloats = tiles_y x tiles_x x 4) block, but for THAT ESTIMATE'S EVENT only:
+ * they do not launch the queue and do not wait for the stream, so frames submitted and flushed after the estimate keep running while
+ * the host reads, and the values are those as of the estimate.
+ *   MI3PT_ERR_STATE before the first estimate since the last resize; MI3PT_ERR_INVALID for a null pointer or a wrong nfloats.
+ * With timing enabled, mi3pt_pass_time_us(MI3PT_PASS_CONVERGENCE) is the device time of the most recent estimate.
+ * Tile split: the tiles of this rank's compact rows.  Device group: the estimate goes to every member; mi3pt_read_convergence combines the
+ * members' summaries (counts add, max of max, min of min).  mi3pt_read_convergence_tiles returns the whole image's map, ceil(height / 8)
+ * x tiles_x, when the group's block_rows is a multiple of 8 -- assembled on the host, member `rank`'s local tile row t at tile row
+ * mi3pt_tile_global_row(t, rank, n, block_rows / 8) -- and is MI3PT_ERR_STATE otherwise. ---- */
+typedef struct mi3pt_convergence {
+    uint32_t tiles, tiles_above, tiles_young, tiles_nonfinite;  /* tiles: those with count > 0 */
+    uint64_t texels;                                            /* sum of counts */
+    float worst_tile;    /* fmaxf over counted tiles of sum_r / (float)count; 0 when none */
+    float worst_texel;   /* fmaxf over tiles of max_r */
+    float n_min;         /* fminf over counted tiles; 0 when none */
+    float threshold;     /* as given */
+} mi3pt_convergence;     /* 40 bytes */
+int mi3pt_estimate_convergence(mi3pt_ctx *ctx, float threshold, int min_frames);
+int mi3pt_read_convergence(mi3pt_ctx *ctx, mi3pt_convergence *out);
+int mi3pt_read_convergence_tiles(mi3pt_ctx *ctx, float *dst, size_t nfloats);  /* tiles_y x tiles_x x 4 */
 
 /* ---- read-back (the capability a headless drop-in needs; the reference only has
  * canvas.toDataURL, main.ts:351-356).  Blocking.  dst holds rows x width x 4 floats

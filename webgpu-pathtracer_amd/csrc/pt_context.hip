@@ -316,6 +316,17 @@ struct mi3pt_ctx {
     bool moments = false;
     bool moments_opted = false;          // mi3pt_set_moments(1) has been called: until then MI3PT_GUIDED_VARIANCE is an unknown flag bit, as it was before the image existed
     float4 *d_moments = nullptr;
+    // The per-tile error estimate (mi3pt_estimate_convergence; pt_converge.hip): the tile map ceil(local_rows / 8) x ceil(width / 8) x 16 B,
+    // the tile kernel's per-block records and the summary on the device, the summary's copy in pinned host memory, all allocated by the
+    // first call and freed with the textures; conv_done: recorded behind the copy of the most recent estimate -- what the two reads wait for, and nothing else.
+    float4 *d_conv_tiles = nullptr;
+    pt::ConvergePart *d_conv_parts = nullptr;
+    pt::ConvergeSummary *d_conv_summary = nullptr, *h_conv_summary = nullptr;
+    hipEvent_t conv_done = nullptr;
+    hipStream_t conv_read_stream = nullptr;      // the tile map's read-back, beside the context's stream (created by the first read)
+    bool conv_valid = false;             // an estimate has been enqueued since the last resize
+    float conv_threshold = 0.0f;         // ... with this threshold
+    PassTimer conv_timer;
     int walk_stack_worst = 64;           // mi3pt_upload_bvh: entries the reference walk's stack can hold at most on this tree (64: unknown, or the abort can fire)
     int wide_stack_worst = 64;           // prepare_cull: the wide walks' node stack, order-independent worst case (internal packets only; <= SM_CULL_STACK_MAX where wide_ok)
 };
@@ -367,6 +378,8 @@ static int group_aov_ptr(mi3pt_ctx *g, int which, void **dev_ptr, size_t *nbytes
 static int group_set_moments(mi3pt_ctx *g, int enabled);
 static int group_read_moments(mi3pt_ctx *g, void *dst, size_t nbytes);
 static int group_moments_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes);
+static int group_read_convergence(mi3pt_ctx *g, mi3pt_convergence *out);
+static int group_read_convergence_tiles(mi3pt_ctx *g, float *dst, size_t nfloats);
 static int group_unsupported(const char *what);
 static int group_set_option(mi3pt_ctx *g, int option, int value);
 // one call applied to every member (and, where marked, to the presenting context too)
@@ -750,6 +763,15 @@ static void free_textures(mi3pt_ctx *ctx)
     ctx->d_guided_var[0] = ctx->d_guided_var[1] = nullptr;
     ctx->guided_var_result = nullptr;
     ctx->d_moments = nullptr;
+    if (ctx->d_conv_tiles) (void)hipFree(ctx->d_conv_tiles);
+    if (ctx->d_conv_parts) (void)hipFree(ctx->d_conv_parts);
+    if (ctx->d_conv_summary) (void)hipFree(ctx->d_conv_summary);
+    if (ctx->h_conv_summary) (void)hipHostFree(ctx->h_conv_summary);
+    ctx->d_conv_tiles = nullptr;
+    ctx->d_conv_parts = nullptr;
+    ctx->d_conv_summary = ctx->h_conv_summary = nullptr;
+    ctx->conv_valid = false;
+    ctx->conv_timer.forget();
 }
 
 extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
@@ -778,7 +800,12 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     for (void *p : { ctx->d_cw8, ctx->d_tripk8, ctx->d_cwide, ctx->d_tripk64, ctx->d_wide, ctx->d_tris, ctx->d_tris_perm, ctx->d_nodes, ctx->d_mats, ctx->d_env, ctx->d_cdf, ctx->d_packets, ctx->d_tripk, ctx->d_leaf_rank,
                      (void *)ctx->d_tile_counter, (void *)ctx->d_drain_flag, (void *)ctx->d_wave_times, (void *)ctx->d_stack_overflow, (void *)ctx->d_park, (void *)ctx->d_service, ctx->d_fs_taps })
         if (p) (void)hipFree(p);
-    for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer }) t->destroy();
+    for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer, &ctx->conv_timer }) t->destroy();
+    if (ctx->conv_read_stream) {
+        (void)hipStreamSynchronize(ctx->conv_read_stream);
+        (void)hipStreamDestroy(ctx->conv_read_stream);
+    }
+    if (ctx->conv_done) (void)hipEventDestroy(ctx->conv_done);
     for (int k = 0; k < 2; k++) {
         if (ctx->rt_stream[k]) (void)hipStreamDestroy(ctx->rt_stream[k]);
         if (ctx->rt_done[k]) (void)hipEventDestroy(ctx->rt_done[k]);
@@ -2636,6 +2663,85 @@ extern "C" int mi3pt_moments_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *
     return hand_out_plane(ctx, ctx->d_moments, dev_ptr, nbytes);
 }
 
+// ---- the per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip) ----
+static size_t conv_tiles_x(const mi3pt_ctx *ctx) { return ((size_t)ctx->width + 7) / 8; }
+static size_t conv_tiles_y(const mi3pt_ctx *ctx) { return ((size_t)ctx->local_rows + 7) / 8; }
+
+extern "C" int mi3pt_estimate_convergence(mi3pt_ctx *ctx, float threshold, int min_frames)
+{
+    PT_GROUP_ALL(ctx, false, mi3pt_estimate_convergence(m, threshold, min_frames));
+    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
+    if (!(threshold >= 0.0f) || std::isinf(threshold)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_estimate_convergence: the threshold must be finite and >= 0");
+    if (min_frames < 0 || min_frames > (1 << 24)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_estimate_convergence: min_frames must be 0 .. 2^24");
+    if (int rc = require_ctx(ctx)) return rc;
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_estimate_convergence before resize");
+    if (!ctx->moments || !ctx->d_moments)
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_estimate_convergence needs the moments image (mi3pt_set_moments(ctx, 1) before the frames are accumulated)");
+    if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far: the accumulate passes run on this stream
+    const size_t ntiles = conv_tiles_x(ctx) * conv_tiles_y(ctx);
+    if (!ctx->d_conv_tiles) HIP_TRY(alloc_plane(&ctx->d_conv_tiles, ntiles * 16));
+    if (!ctx->d_conv_parts) HIP_TRY(alloc_plane(&ctx->d_conv_parts, (size_t)pt::converge_blocks(ctx->width, ctx->local_rows) * sizeof(pt::ConvergePart)));
+    if (!ctx->d_conv_summary) HIP_TRY(hipMalloc((void **)&ctx->d_conv_summary, sizeof(pt::ConvergeSummary)));
+    if (!ctx->h_conv_summary) HIP_TRY(hipHostMalloc((void **)&ctx->h_conv_summary, sizeof(pt::ConvergeSummary), hipHostMallocDefault));
+    if (!ctx->conv_done) HIP_TRY(hipEventCreateWithFlags(&ctx->conv_done, hipEventDisableTiming));
+    const float t2 = (threshold * threshold) * 3.0f;
+    if (ctx->timing) HIP_TRY(ctx->conv_timer.begin(ctx->stream));
+    pt::launch_converge(ctx->d_accum, ctx->d_moments, ctx->d_conv_tiles, ctx->d_conv_parts, ctx->d_conv_summary, ctx->width, ctx->local_rows, t2,
+                        (float)min_frames, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) HIP_TRY(ctx->conv_timer.end(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_conv_summary, ctx->d_conv_summary, sizeof(pt::ConvergeSummary), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->conv_done, ctx->stream));
+    ctx->conv_valid = true;
+    ctx->conv_threshold = threshold;
+    return MI3PT_OK;
+}
+
+// what both reads start with: the state, then the wait for the estimate's event -- not for the stream, and the queue is not launched
+static int conv_wait(mi3pt_ctx *ctx, const char *what)
+{
+    if (int rc = require_ctx(ctx)) return rc;
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
+    if (!ctx->conv_valid) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": nothing has been estimated since the last resize (mi3pt_estimate_convergence)");
+    HIP_TRY(ctx_event_sync(ctx, ctx->conv_done, "convergence estimate"));
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_read_convergence(mi3pt_ctx *ctx, mi3pt_convergence *out)
+{
+    PT_GROUP(ctx, group_read_convergence(ctx, out));
+    if (!ctx || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = conv_wait(ctx, "mi3pt_read_convergence")) return rc;
+    const pt::ConvergeSummary s = *ctx->h_conv_summary;
+    auto as_float = [](uint32_t bits) { float f; std::memcpy(&f, &bits, 4); return f; };
+    out->tiles = s.tiles;
+    out->tiles_above = s.above;
+    out->tiles_young = s.young;
+    out->tiles_nonfinite = s.nonfinite;
+    out->texels = s.texels;
+    out->worst_tile = as_float(s.worst_tile);
+    out->worst_texel = as_float(s.worst_texel);
+    out->n_min = out->tiles ? as_float(~s.n_min_inv) : 0.0f;
+    out->threshold = ctx->conv_threshold;
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_read_convergence_tiles(mi3pt_ctx *ctx, float *dst, size_t nfloats)
+{
+    PT_GROUP(ctx, group_read_convergence_tiles(ctx, dst, nfloats));
+    if (!ctx || !dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = require_ctx(ctx)) return rc;
+    if (ctx->width != 0 && ctx->conv_valid && nfloats != conv_tiles_x(ctx) * conv_tiles_y(ctx) * 4)
+        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the tile map (ceil(rows / 8) x ceil(width / 8) x 4 floats)");
+    if (int rc = conv_wait(ctx, "mi3pt_read_convergence_tiles")) return rc;
+    if (nfloats == 0) return MI3PT_OK;
+    // the map is the estimate's until the next estimate: copied beside the context's stream, which may be busy with later frames
+    if (!ctx->conv_read_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->conv_read_stream, hipStreamNonBlocking));
+    HIP_TRY(hipMemcpyAsync(dst, ctx->d_conv_tiles, nfloats * 4, hipMemcpyDeviceToHost, ctx->conv_read_stream));
+    HIP_TRY(hipStreamSynchronize(ctx->conv_read_stream));
+    return MI3PT_OK;
+}
+
 extern "C" int mi3pt_enable_timing(mi3pt_ctx *ctx, int enabled)
 {
     PT_GROUP_ALL(ctx, true, mi3pt_enable_timing(m, enabled));
@@ -2650,6 +2756,7 @@ extern "C" int mi3pt_pass_time_us(mi3pt_ctx *ctx, int pass, float *microseconds)
     if (int rc = require_idle(ctx)) return rc;
     if (microseconds && pass == MI3PT_PASS_AOV) return ctx->aov_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_render_aovs since the last resize");
     if (microseconds && pass == MI3PT_PASS_GUIDED) return ctx->guided_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_denoise_guided since the last resize");
+    if (microseconds && pass == MI3PT_PASS_CONVERGENCE) return ctx->conv_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_estimate_convergence since the last resize");
     if (!microseconds || pass < 0 || pass > 2) return pt_set_error(MI3PT_ERR_INVALID, "bad argument");
     if (pass == MI3PT_PASS_RAYTRACE && !ctx->pass_timer[0].recorded && (ctx->ev_rt_pending[0] || ctx->ev_rt_pending[1] || ctx->rt_launches)) {
         // batched launch: the most recent batch's kernel time divided by its frames (the older
@@ -3332,6 +3439,59 @@ static int group_moments_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes)
     if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = group_gather_moments(g, "mi3pt_moments_device_ptr")) return rc;
     return mi3pt_moments_device_ptr(g->group->present, dev_ptr, nbytes);
+}
+
+// ---- the error estimate: mi3pt_estimate_convergence goes to every member (PT_GROUP_ALL); the summaries combine on the host -- counts add,
+// max of max, min of min -- and so do the tile maps, which are kilobytes: no peer copies ----
+static int group_read_convergence(mi3pt_ctx *g, mi3pt_convergence *out)
+{
+    if (!out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    mi3pt_convergence all = {};
+    bool first = true;
+    for (mi3pt_ctx *m : g->group->members) {
+        mi3pt_convergence c;
+        if (int rc = mi3pt_read_convergence(m, &c)) return rc;
+        all.tiles += c.tiles; all.tiles_above += c.tiles_above; all.tiles_young += c.tiles_young; all.tiles_nonfinite += c.tiles_nonfinite;
+        all.texels += c.texels;
+        all.worst_tile = fmaxf(all.worst_tile, c.worst_tile);
+        all.worst_texel = fmaxf(all.worst_texel, c.worst_texel);
+        if (c.tiles) {
+            all.n_min = first ? c.n_min : fminf(all.n_min, c.n_min);
+            first = false;
+        }
+        all.threshold = c.threshold;
+    }
+    *out = all;
+    return MI3PT_OK;
+}
+
+static int group_read_convergence_tiles(mi3pt_ctx *g, float *dst, size_t nfloats)
+{
+    GroupState *gs = g->group;
+    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_convergence_tiles before resize");
+    if (gs->block_rows % 8)
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_convergence_tiles: the members' tiles only form the image's tile map when the group's block_rows is a multiple of 8 (read each member's map: mi3pt_group_member)");
+    for (mi3pt_ctx *m : gs->members)
+        if (!m->conv_valid) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_convergence_tiles: nothing has been estimated since the last resize (mi3pt_estimate_convergence)");
+    const size_t tiles_x = ((size_t)gs->width + 7) / 8, tiles_y = ((size_t)gs->height + 7) / 8;
+    if (nfloats != tiles_x * tiles_y * 4)
+        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the tile map (a group reads the whole map: ceil(height / 8) x ceil(width / 8) x 4 floats)");
+    const int n = (int)gs->members.size();
+    std::vector<float> part;
+    for (int i = 0; i < n; i++) {
+        mi3pt_ctx *m = gs->members[(size_t)i];
+        const size_t rows = conv_tiles_y(m);
+        part.resize(rows * tiles_x * 4);
+        if (rows == 0) continue;
+        if (int rc = mi3pt_read_convergence_tiles(m, part.data(), part.size())) return rc;
+        for (size_t t = 0; t < rows; t++) {
+            const size_t gt = (size_t)mi3pt_tile_global_row((int)t, i, n, gs->block_rows / 8);
+            if (gt >= tiles_y) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_convergence_tiles: a member's tile row lies outside the image");
+            std::memcpy(dst + gt * tiles_x * 4, part.data() + t * tiles_x * 4, tiles_x * 16);
+        }
+    }
+    return MI3PT_OK;
 }
 
 static int group_draw_canvas(mi3pt_ctx *g)

@@ -12,6 +12,7 @@
 #include "../../include/mi3pt.h"
 #include "pt_kernels.h"
 #include "pt_devmath.h"
+#include "pt_moments.h"
 
 namespace pt {
 
@@ -101,14 +102,7 @@ __global__ void __launch_bounds__(256) k_guided_level(const GuidedLaunch G, cons
 // ---- MI3PT_GUIDED_VARIANCE: the colour term steered by the per-pixel variance of the mean (SVGF's spatial filter: Schied et al.,
 // HPG 2017), from the moments image, carried from level to level: the variance kernel and guided_level's second instantiation. ----
 
-// v of one moments texel: the variance of the mean summed over rgb, 0 with fewer than two samples; fmaxf drops a NaN
-PT_DEV float moments_variance(const float4 m)
-{
-    const float sum = (m.x + m.y) + m.z;
-    return m.w >= 2.0f ? fmaxf(sum / (m.w * (m.w - 1.0f)), 0.0f) : 0.0f;
-}
-
-// var_0: v averaged over the 3 x 3 neighbours of the centre's hit class, g = [1/4, 1/2, 1/4]
+// var_0: v (moments_variance, pt_moments.h) averaged over the 3 x 3 neighbours of the centre's hit class, g = [1/4, 1/2, 1/4]
 __global__ void __launch_bounds__(256) k_guided_variance(const float4 *__restrict__ moments, const float4 *__restrict__ normal_hit,
                                                          float *__restrict__ var, const int width, const int rows)
 {

@@ -429,6 +429,24 @@ void launch_guided_level(const GuidedLaunch &G, const float4 *src, float4 *dst, 
 void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, int width, int rows, hipStream_t s);
 void launch_guided_level_variance(const GuidedLaunch &G, const float4 *src, float4 *dst, const float *var_src, float *var_dst, int level,
                                   float sigma_color, hipStream_t s);
+// The per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip).  ConvergePart: what
+// one block of the tile kernel adds to the summary (texels: at most 16 tiles x 64); ConvergeSummary: the records folded by the second
+// kernel, which writes every word.  worst_*: bit patterns of non-negative floats; n_min_inv: ~(bit pattern of the smallest n_min), 0
+// while no tile counted.
+struct ConvergePart {
+    uint32_t tiles, above, young, nonfinite, texels, worst_tile, worst_texel, n_min_inv;
+};
+struct ConvergeSummary {
+    uint32_t tiles, above, young, nonfinite;
+    unsigned long long texels;
+    uint32_t worst_tile, worst_texel, n_min_inv, pad;
+};
+static_assert(sizeof(ConvergePart) == 32 && sizeof(ConvergeSummary) == 40, "eight words; four words, a 64-bit count and four words");
+// records the tile kernel writes for a width x rows image (`parts` holds that many)
+uint32_t converge_blocks(int width, int rows);
+// tiles: ceil(rows / 8) x ceil(width / 8) records (sum_r, max_r, count, n_min); t2 = (threshold * threshold) * 3 and min_frames as fp32
+void launch_converge(const float4 *accum, const float4 *moments, float4 *tiles, ConvergePart *parts, ConvergeSummary *summary, int width,
+                     int rows, float t2, float min_frames, hipStream_t s);
 // packs the three position vectors of `ntris` 112-byte triangle records into 48-byte rows (the context's cull analysis)
 void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipStream_t s);
 // writes NodePacket::cull of `npackets` packets from a dense array (the context's cull analysis)

@@ -476,6 +476,72 @@ napi_value ReadMoments(napi_env env, napi_callback_info info)
     return ta;
 }
 
+// estimateConvergence(ctx, threshold, minFrames): mi3pt_estimate_convergence; asynchronous
+napi_value EstimateConvergence(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t min_frames;
+    double threshold;
+    if (!get_args(env, info, a, 3) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[2], &min_frames)) return nullptr;
+    if (napi_get_value_double(env, a.v[1], &threshold) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "expected a number");
+        return nullptr;
+    }
+    MI3PT_TRY(mi3pt_estimate_convergence(ctx, (float)threshold, min_frames));
+    return undefined(env);
+}
+
+// readConvergence(ctx) -> the nine fields of mi3pt_convergence; waits for the last estimateConvergence only
+napi_value ReadConvergence(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    if (!get_args(env, info, a, 1) || !get_ctx(env, a.v[0], &ctx)) return nullptr;
+    mi3pt_convergence c;
+    MI3PT_TRY(mi3pt_read_convergence(ctx, &c));
+    napi_value obj, v;
+    NAPI_OK(napi_create_object(env, &obj));
+    const struct { const char *name; double value; } fields[] = {
+        { "tiles", (double)c.tiles }, { "tilesAbove", (double)c.tiles_above }, { "tilesYoung", (double)c.tiles_young },
+        { "tilesNonfinite", (double)c.tiles_nonfinite }, { "texels", (double)c.texels }, { "worstTile", (double)c.worst_tile },
+        { "worstTexel", (double)c.worst_texel }, { "nMin", (double)c.n_min }, { "threshold", (double)c.threshold },
+    };
+    for (const auto &f : fields) {
+        NAPI_OK(napi_create_double(env, f.value, &v));
+        NAPI_OK(napi_set_named_property(env, obj, f.name, v));
+    }
+    return obj;
+}
+
+// readConvergenceTiles(ctx, ntiles) -> Float32Array of ntiles x 4: (sum_r, max_r, count, n_min) per 8 x 8 tile
+napi_value ReadConvergenceTiles(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t ntiles;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &ntiles) || ntiles < 0) return nullptr;
+    void *data = nullptr;
+    napi_value ab, ta;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)ntiles * 16, &data, &ab));
+    MI3PT_TRY(mi3pt_read_convergence_tiles(ctx, static_cast<float *>(data), (size_t)ntiles * 4));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, (size_t)ntiles * 4, ab, 0, &ta));
+    return ta;
+}
+
+// batchCapacity(ctx) -> frames one launch covers at the current size (mi3pt_batch_capacity)
+napi_value BatchCapacity(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    if (!get_args(env, info, a, 1) || !get_ctx(env, a.v[0], &ctx)) return nullptr;
+    int frames = 0;
+    MI3PT_TRY(mi3pt_batch_capacity(ctx, &frames));
+    napi_value v;
+    NAPI_OK(napi_create_int32(env, frames, &v));
+    return v;
+}
+
 // writeTexture(ctx, which, Float32Array) : GPUQueue.writeTexture for the HDR images
 napi_value WriteTexture(napi_env env, napi_callback_info info)
 {
@@ -672,6 +738,8 @@ napi_value Init(napi_env env, napi_value exports)
         { "raytraceLaunchStats", RaytraceLaunchStats }, { "renderAovs", RenderAovs }, { "readAov", ReadAov },
         { "denoiseGuided", DenoiseGuided }, { "readGuided", ReadGuided }, { "readGuidedVariance", ReadGuidedVariance },
         { "setMoments", SetMoments }, { "readMoments", ReadMoments },
+        { "estimateConvergence", EstimateConvergence }, { "readConvergence", ReadConvergence }, { "readConvergenceTiles", ReadConvergenceTiles },
+        { "batchCapacity", BatchCapacity },
     };
     for (const auto &f : fns) {
         napi_value v;

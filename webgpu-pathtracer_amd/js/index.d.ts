@@ -72,7 +72,7 @@ export class RaytracePass extends Pass {
 export class AccumulatePass extends Pass { setUniforms(value: object): void; update(): void; render(e: { passes: number }): void; }
 export class FullscreenPass extends Pass { setUniforms(value: object): void; update(): void; render(e: { passes: number }): void; }
 
-export type RendererEventType = 'start' | 'pause' | 'reset' | 'progress' | 'complete' | 'resize';
+export type RendererEventType = 'start' | 'pause' | 'reset' | 'progress' | 'complete' | 'resize' | 'converged';
 export interface RendererOptions {
   device?: number;
   enableTimestampQuery?: boolean;
@@ -134,6 +134,19 @@ export class Renderer {
   setMoments(enabled: boolean): void;
   /** localRows x width x 4, row 0 = bottom */
   readMoments(): Float32Array;
+  /** enqueue the per-tile error estimate of the mean of every frame rendered so far (include/mi3pt.h: mi3pt_estimate_convergence);
+   *  needs setMoments(true).  minFrames defaults to 16 */
+  estimateConvergence(threshold: number, minFrames?: number): void;
+  /** the summary of the last estimateConvergence; waits for that estimate only.  Converged: tiles > 0 && tilesAbove === 0 */
+  readConvergence(): ConvergenceSummary;
+  /** tilesY x tilesX x 4: (sum_r, max_r, count, n_min) per 8 x 8 tile, row 0 = bottom */
+  readConvergenceTiles(): Float32Array;
+  static isConverged(summary: ConvergenceSummary): boolean;
+  /** render() until every tile's estimated RMSE of the tone-mapped mean is at most `threshold` or maxFrames (default: frames) are in the
+   *  mean; checked every checkEvery frames (default: the batch capacity).  lookahead (default true): the estimate is read one chunk late,
+   *  so the device never idles.  Emits 'converged' with the summary, then 'complete' */
+  renderUntil(scene: RaytracingScene, camera: RaytracingCamera, threshold: number,
+    options?: { minFrames?: number; maxFrames?: number; checkEvery?: number; lookahead?: boolean }): { converged: boolean; frames: number; summary: ConvergenceSummary };
   counters(): { rays: number; boxTests: number; triTests: number; hits: number; misses: number; stackOverflows: number; pixels: number };
   /** src/main.ts:351-356: the presented canvas as PNG bytes (written to `file` when given) */
   screenshot(file?: string): Buffer;
@@ -144,6 +157,12 @@ export class Renderer {
   raytraceLaunchStats(reset?: boolean): { totalMs: number; launches: number; frames: number };
   /** the reference's dormant environment importance sampling (raytrace.wgsl:398-404 un-commented); default off */
   setEnvironmentSampling(enabled: boolean): void;
+}
+
+/** mi3pt_convergence */
+export interface ConvergenceSummary {
+  tiles: number; tilesAbove: number; tilesYoung: number; tilesNonfinite: number; texels: number;
+  worstTile: number; worstTexel: number; nMin: number; threshold: number;
 }
 
 /** src/main.ts:251-266 -- .glb / .gltf (no Draco) to a node hierarchy of indexed meshes */

@@ -253,6 +253,64 @@ class Renderer {
   setMoments(enabled) { this.native.setMoments(this.handle, enabled ? 1 : 0); this._moments = !!enabled; }
   // localRows x width x 4 floats; row 0 = bottom of the picture
   readMoments() { return this.native.readMoments(this.handle, this.localRows * this._width); }
+  // ---- sample until converged (no counterpart in the reference): the per-tile error estimate of the running mean, include/mi3pt.h:
+  // mi3pt_estimate_convergence.  estimateConvergence enqueues the estimate of the mean of every frame rendered so far; readConvergence
+  // returns its summary { tiles, tilesAbove, tilesYoung, tilesNonfinite, texels, worstTile, worstTexel, nMin, threshold } and waits for
+  // that estimate only; readConvergenceTiles the map, tilesY x tilesX x 4 floats (sum_r, max_r, count, n_min).
+  estimateConvergence(threshold, minFrames) { this.native.estimateConvergence(this.handle, threshold, minFrames === undefined ? 16 : minFrames); }
+  readConvergence() { return this.native.readConvergence(this.handle); }
+  readConvergenceTiles() {
+    return this.native.readConvergenceTiles(this.handle, Math.ceil(this.localRows / 8) * Math.ceil(this._width / 8));
+  }
+  static isConverged(summary) { return summary.tiles > 0 && summary.tilesAbove === 0; }
+  // render() until every 8 x 8 tile's estimated RMSE of the tone-mapped mean is at most `threshold` and has seen minFrames frames, or
+  // until maxFrames (undefined: this.frames, otherwise it becomes this.frames) are in the mean.  The mean is checked every checkEvery
+  // frames (undefined: the context's batch capacity, so launches keep one shape).  lookahead (default true): the estimate of a chunk is
+  // read after the NEXT chunk has been flushed, so the device never idles while the host decides; the run then stops one chunk after the
+  // estimate that said converged, and those frames stay in the mean.  Without it the run stops at once.  The frame count at which it stops
+  // is a function of the images alone.  Returns { converged, frames, summary }; the summary is the estimate that stopped the run, or, at
+  // the end of the budget, that of the final mean.
+  renderUntil(scene, camera, threshold, options) {
+    const o = Object.assign({ minFrames: 16, maxFrames: undefined, checkEvery: undefined, lookahead: true }, options || {});
+    if (!this._moments) throw new Error('renderUntil needs the moments image: setMoments(true) before sampling starts');
+    if (o.maxFrames !== undefined && o.maxFrames !== null) this.frames = o.maxFrames;
+    const checkEvery = Math.max(1, o.checkEvery === undefined || o.checkEvery === null ? this.native.batchCapacity(this.handle) : o.checkEvery);
+    let pending = false;         // an estimate has been enqueued and not read
+    let current = false;         // `summary` is of the mean as it stands
+    let summary = null;
+    while (this.status === 'sampling' && this.hasFramesToSample) {
+      const n = Math.min(checkEvery, this.frames - (this._frame - 1));
+      for (let i = 0; i < n; i++) this.render(scene, camera);
+      this.native.flush(this.handle);
+      if (o.lookahead) {
+        if (pending) {
+          summary = this.native.readConvergence(this.handle);      // (the chunk just flushed runs while the host waits)
+          if (Renderer.isConverged(summary)) return this._converged(summary);
+        }
+        this.native.estimateConvergence(this.handle, threshold, o.minFrames);
+        pending = true;
+      } else {
+        this.native.estimateConvergence(this.handle, threshold, o.minFrames);
+        summary = this.native.readConvergence(this.handle);
+        current = true;
+        if (Renderer.isConverged(summary)) return this._converged(summary);
+      }
+    }
+    if (!current) {              // the end of the budget: the result describes the final mean
+      if (!pending) this.native.estimateConvergence(this.handle, threshold, o.minFrames);
+      summary = this.native.readConvergence(this.handle);
+    }
+    if (Renderer.isConverged(summary)) return this._converged(summary);
+    return { converged: false, frames: this._frame - 1, summary };
+  }
+  _converged(summary) {
+    this.emit('converged', summary);
+    if (this.status !== 'idle') {
+      this.status = 'idle';
+      this.emit('complete');
+    }
+    return { converged: true, frames: this._frame - 1, summary };
+  }
   // localRows x width x 4 floats: the filtered image of the last denoiseGuided; row 0 = bottom of the picture
   readGuided() { return this.native.readGuided(this.handle, this.localRows * this._width); }
   // localRows x width x 4: Float32Array, Int32Array for 'ids' (triangle, material, hit, 0); row 0 = bottom of the picture

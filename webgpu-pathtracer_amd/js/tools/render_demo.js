@@ -12,6 +12,9 @@
 //   --guided-variance  the moments image on from the start, then renderer.denoiseGuided({ variance: true, present: true }): the outputs of
 //                      --guided from the variance-guided filter, <prefix>_guided_variance.f32 (raw float, one per texel) and
 //                      <prefix>_moments.f32 (raw RGBA float: M2.rgb, n).  Not together with --guided: both write <prefix>_guided.*
+//   --until <rmse>     sample until converged instead of a fixed count: renderer.renderUntil(scene, camera, rmse, { maxFrames: --frames })
+//                      with the moments image on; --min-frames N (16), --check-every N (the batch capacity), --no-lookahead.  Prints the
+//                      frames taken and the summary of the estimate under "until"
 //   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
 //   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
 //                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
@@ -62,10 +65,20 @@ async function main() {
   renderer.setUniforms('raytrace', { maxBounces: bounces, envMapIntensity: PARAMS.envMapIntensity });
   renderer.setUniforms('accumulate', { enabled: PARAMS.accumulate ? 1 : 0 });
   renderer.setUniforms('fullscreen', { denoise: PARAMS.denoise ? 1 : 0, tonemapping: PARAMS.tonemapping });
-  if (guidedVariance) renderer.setMoments(true);
+  const untilArg = arg('until', null);
+  if (guidedVariance || untilArg !== null) renderer.setMoments(true);
   renderer.resize(width, height);
   const t0 = Date.now();
-  for (let i = 0; i < frames + 1; i++) renderer.render(scene, camera);     // the last call only presents
+  let until = null;
+  if (untilArg !== null) {
+    const checkEvery = arg('check-every', null);
+    until = renderer.renderUntil(scene, camera, parseFloat(untilArg), { maxFrames: frames, minFrames: parseInt(arg('min-frames', '16'), 10),
+      checkEvery: checkEvery === null ? undefined : parseInt(checkEvery, 10), lookahead: !process.argv.includes('--no-lookahead') });
+    renderer.render(scene, camera);                                        // only presents
+    console.error('--until ' + untilArg + ': ' + (until.converged ? 'converged' : 'not converged') + ' after ' + until.frames + ' of ' + frames + ' frames');
+  } else {
+    for (let i = 0; i < frames + 1; i++) renderer.render(scene, camera);   // the last call only presents
+  }
   const firstStats = renderer.passes.raytrace.stats;
   if (process.argv.includes('--second-scene')) {
     scene.remove(scene.children[scene.children.length - 1]);
@@ -110,7 +123,7 @@ async function main() {
     renderer.screenshot(out + '_guided.png');
   }
   const summary = {
-    width, height, frames, status: renderer.status, frame: renderer.frame, events,
+    width, height, frames, until, status: renderer.status, frame: renderer.frame, events,
     counters: renderer.counters(), stats: renderer.passes.raytrace.stats, first_stats: firstStats, wall_ms: ms,
     timings_us: { raytrace: renderer.timings.raytrace.value, accumulate: renderer.timings.accumulate.value,
       fullscreen: renderer.timings.fullscreen.value },

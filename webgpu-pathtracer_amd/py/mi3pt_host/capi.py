@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MI3PT_LIBRARY") or os.path.join(PKG_ROOT, "libmi3pt.s
 PASS_RAYTRACE, PASS_ACCUMULATE, PASS_FULLSCREEN = 0, 1, 2
 PASS_AOV = 3          # mi3pt_pass_time_us only: the first-hit feature images have no uniform block
 PASS_GUIDED = 4       # mi3pt_pass_time_us only: the feature-guided de-noise (denoise_guided)
+PASS_CONVERGENCE = 5  # mi3pt_pass_time_us only: the per-tile error estimate (estimate_convergence)
 GUIDED_PRESENT = 1    # mi3pt_guided_params.flags: draw the canvas from the filtered image
 GUIDED_VARIANCE = 2   # ... the colour weight steered by the per-pixel variance of the mean (needs set_moments(True))
 # mi3pt_aov: the first-hit feature images (render_aovs takes an OR of 1 << AOV_*)
@@ -55,6 +56,7 @@ SYMBOLS = (
     "mi3pt_render_aovs", "mi3pt_read_aov", "mi3pt_aov_device_ptr",
     "mi3pt_denoise_guided", "mi3pt_read_guided", "mi3pt_guided_device_ptr",
     "mi3pt_set_moments", "mi3pt_read_moments", "mi3pt_write_moments", "mi3pt_moments_device_ptr", "mi3pt_read_guided_variance",
+    "mi3pt_estimate_convergence", "mi3pt_read_convergence", "mi3pt_read_convergence_tiles",
 )
 
 
@@ -62,6 +64,13 @@ class GuidedParams(ctypes.Structure):
     """mi3pt_guided_params"""
     _fields_ = [("levels", ctypes.c_int), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
                 ("sigma_albedo", ctypes.c_float), ("sigma_plane", ctypes.c_float), ("flags", ctypes.c_uint)]
+
+
+class Convergence(ctypes.Structure):
+    """mi3pt_convergence"""
+    _fields_ = [("tiles", ctypes.c_uint32), ("tiles_above", ctypes.c_uint32), ("tiles_young", ctypes.c_uint32),
+                ("tiles_nonfinite", ctypes.c_uint32), ("texels", ctypes.c_uint64), ("worst_tile", ctypes.c_float),
+                ("worst_texel", ctypes.c_float), ("n_min", ctypes.c_float), ("threshold", ctypes.c_float)]
 
 
 class Mi3ptError(RuntimeError):
@@ -122,6 +131,9 @@ def load_library(path=None):
     lib.mi3pt_write_moments.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.mi3pt_moments_device_ptr.argtypes = [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]
     lib.mi3pt_read_guided_variance.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_estimate_convergence.argtypes = [c_void_p, ctypes.c_float, c_int]
+    lib.mi3pt_read_convergence.argtypes = [c_void_p, ctypes.POINTER(Convergence)]
+    lib.mi3pt_read_convergence_tiles.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.mi3pt_enable_timing.argtypes = [c_void_p, c_int]
     lib.mi3pt_pass_time_us.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]
     lib.mi3pt_raytrace_launch_stats.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
@@ -532,6 +544,25 @@ class Context:
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         self._c(self.lib.mi3pt_moments_device_ptr(self.handle, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
+
+    def estimate_convergence(self, threshold, min_frames=16):
+        """Reduce the running mean and its moments image to one error record per 8 x 8 tile and a summary (include/mi3pt.h:
+        mi3pt_estimate_convergence), of every frame submitted so far.  Asynchronous; needs set_moments(True)."""
+        self._c(self.lib.mi3pt_estimate_convergence(self.handle, threshold, int(min_frames)))
+
+    def read_convergence(self):
+        """The summary of the last estimate_convergence as a dict of the nine fields of mi3pt_convergence.  Waits for that estimate
+        only: frames flushed after it keep running.  Converged: tiles > 0 and tiles_above == 0."""
+        c = Convergence()
+        self._c(self.lib.mi3pt_read_convergence(self.handle, ctypes.byref(c)))
+        return {name: getattr(c, name) for name, _ in Convergence._fields_}
+
+    def read_convergence_tiles(self):
+        """The tile map of the last estimate_convergence as (tiles_y, tiles_x, 4) float32: sum_r, max_r, count, n_min per 8 x 8
+        tile of this rank's compact rows; a device group whose block_rows is a multiple of 8 returns the whole image's."""
+        out = np.empty(((self.local_rows + 7) // 8, (self.width + 7) // 8, 4), np.float32)
+        self._c(self.lib.mi3pt_read_convergence_tiles(self.handle, _ptr(out), out.size))
+        return out
 
     def bind_accumulation(self, dev_ptr, nbytes):
         self._c(self.lib.mi3pt_bind_accumulation(self.handle, dev_ptr, nbytes))

@@ -419,6 +419,73 @@ class Renderer:
         """(rows, width, 4) float32: M2.r, M2.g, M2.b, n."""
         return self.ctx.read_moments()
 
+    # ---- sample until converged: the per-tile error estimate of the running mean (no counterpart in the reference) ----
+    def estimateConvergence(self, threshold, minFrames=16):
+        """Enqueue the error estimate of the mean of every frame rendered so far (include/mi3pt.h: mi3pt_estimate_convergence)."""
+        self.ctx.estimate_convergence(threshold, minFrames)
+
+    def readConvergence(self):
+        """The summary of the last estimateConvergence: a dict of the nine fields of mi3pt_convergence."""
+        return self.ctx.read_convergence()
+
+    def readConvergenceTiles(self):
+        """(tiles_y, tiles_x, 4) float32: sum_r, max_r, count, n_min per 8 x 8 tile."""
+        return self.ctx.read_convergence_tiles()
+
+    @staticmethod
+    def isConverged(summary):
+        return summary["tiles"] > 0 and summary["tiles_above"] == 0
+
+    def renderUntil(self, scene, camera, threshold, minFrames=16, maxFrames=None, checkEvery=None, lookahead=True):
+        """render() until every 8 x 8 tile's estimated RMSE of the tone-mapped mean is at most `threshold` and has seen minFrames
+        frames, or until maxFrames (None: self.frames, otherwise it becomes self.frames) are in the mean.  The mean is checked every
+        checkEvery frames (None: the context's batch capacity, so launches keep one shape).  lookahead: the estimate of a chunk is
+        read after the NEXT chunk has been flushed, so the device never idles while the host decides; the run then stops one chunk
+        after the estimate that said converged, and those frames stay in the mean.  Without it the run stops at once.  The frame
+        count at which it stops is a function of the images alone.  Returns {"converged", "frames", "summary"}; the summary is the
+        estimate that stopped the run, or, at the end of the budget, that of the final mean."""
+        if not self._moments:
+            raise ValueError("renderUntil needs the moments image: setMoments(True) before sampling starts")
+        if maxFrames is not None:
+            self.frames = int(maxFrames)
+        if checkEvery is None:
+            checkEvery = self.ctx.batch_capacity()
+        checkEvery = max(1, int(checkEvery))
+        pending = False          # an estimate has been enqueued and not read
+        current = False          # `summary` is of the mean as it stands
+        summary = None
+        while self.status == "sampling" and self.hasFramesToSample:
+            for _ in range(min(checkEvery, self.frames - (self._frame - 1))):
+                self.render(scene, camera)
+            self.ctx.flush()
+            if lookahead:
+                if pending:
+                    summary = self.ctx.read_convergence()      # (the chunk just flushed runs while the host waits)
+                    if self.isConverged(summary):
+                        return self._converged(summary)
+                self.ctx.estimate_convergence(threshold, minFrames)
+                pending = True
+            else:
+                self.ctx.estimate_convergence(threshold, minFrames)
+                summary = self.ctx.read_convergence()
+                current = True
+                if self.isConverged(summary):
+                    return self._converged(summary)
+        if not current:          # the end of the budget: the result describes the final mean
+            if not pending:
+                self.ctx.estimate_convergence(threshold, minFrames)
+            summary = self.ctx.read_convergence()
+        if self.isConverged(summary):
+            return self._converged(summary)
+        return {"converged": False, "frames": self._frame - 1, "summary": summary}
+
+    def _converged(self, summary):
+        self.emit("converged", summary)
+        if self.status != "idle":
+            self.status = "idle"
+            self.emit("complete")
+        return {"converged": True, "frames": self._frame - 1, "summary": summary}
+
     def readGuided(self):
         """(rows, width, 4) float32: the filtered image of the last denoiseGuided."""
         return self.ctx.read_guided()
