@@ -27,7 +27,8 @@
  *     caller's (mi3pt_set_stream) -- and everything that can be observed happens in that stream's order; the raytrace
  *     kernels run on internal streams tied to it by events in both directions, which no caller can see.
  *     STREAM ORDERED, returning before the device has run anything: mi3pt_submit, mi3pt_submit_frames, mi3pt_flush,
- *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided, mi3pt_estimate_convergence.  mi3pt_set_uniforms, the setters of
+ *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided, mi3pt_estimate_convergence, mi3pt_set_sample_mask (it
+ *     launches the frame queue, under the old mask, and waits for nothing).  mi3pt_set_uniforms, the setters of
  *     modes and options and the *_device_ptr getters start no device work of their own (those that observe state launch
  *     the frame queue first).  A host that has set its own stream may therefore enqueue its work in front of and behind
  *     these calls on that stream -- fill a bound accumulation tensor, copy out of a *_device_ptr image -- and wait once.
@@ -36,7 +37,8 @@
  *     mi3pt_set_moments when it changes the state, every mi3pt_read_*, mi3pt_sync, mi3pt_get_counters, mi3pt_pass_time_us,
  *     mi3pt_raytrace_launch_stats / _span, the mi3pt_debug_* probes, mi3pt_device_build_bvh, mi3pt_destroy.
  *     BLOCKING, but for ONE EVENT only and without launching the frame queue: mi3pt_read_convergence and
- *     mi3pt_read_convergence_tiles wait for the most recent mi3pt_estimate_convergence, not for what was enqueued behind it.
+ *     mi3pt_read_convergence_tiles wait for the most recent mi3pt_estimate_convergence, not for what was enqueued behind it;
+ *     mi3pt_freeze_converged waits for the same event, then acts as mi3pt_set_sample_mask.  mi3pt_read_sample_mask reads host state.
  *     Three things make a stream-ordered call wait ONCE: the first raytrace submit or mi3pt_render_aovs after a scene
  *     upload (or a change of kernel variant) compiles the scene and reads it back; the first call that needs an image
  *     allocates it, and a launch deeper than any before on this context replaces its radiance slots (freeing waits for
@@ -67,7 +69,8 @@ extern "C" {
  * Added since under the same number (nothing existing changed): mi3pt_host_sky_tiles, MI3PT_OPT_SKY_TILES (31); mi3pt_host_scene_compile; mi3pt_host_walk_buffer; mi3pt_host_route;
  * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3); mi3pt_denoise_guided, mi3pt_read_guided,
  * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4); mi3pt_estimate_convergence,
- * mi3pt_read_convergence, mi3pt_read_convergence_tiles, struct mi3pt_convergence, MI3PT_PASS_CONVERGENCE (5). */
+ * mi3pt_read_convergence, mi3pt_read_convergence_tiles, struct mi3pt_convergence, MI3PT_PASS_CONVERGENCE (5); mi3pt_set_sample_mask,
+ * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles. */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -109,7 +112,10 @@ typedef enum mi3pt_pass {
 typedef enum mi3pt_texture {
     MI3PT_TEX_OUTPUT = 0,        /* renderer.outputTexture (renderer.ts:94-109): the frame's radiance
                                     after a raytrace pass, the running mean after an accumulate pass
-                                    (accumulate.ts:171-175 copies it back) */
+                                    (accumulate.ts:171-175 copies it back).  Under a sample mask
+                                    (mi3pt_set_sample_mask) a queued frame's radiance is written for the
+                                    SAMPLED tiles only where the launch takes a tile list: the radiance
+                                    texels of frozen tiles are not written and hold whatever they held */
     MI3PT_TEX_ACCUMULATION = 1,  /* accumulate.ts:45-59 accumulationTexture == outputTexturePrev */
     MI3PT_TEX_CANVAS = 2         /* the fullscreen pass's colour attachment, as float RGBA
                                     (canvas_w x canvas_h, row 0 = top) */
@@ -478,6 +484,57 @@ typedef struct mi3pt_convergence {
 int mi3pt_estimate_convergence(mi3pt_ctx *ctx, float threshold, int min_frames);
 int mi3pt_read_convergence(mi3pt_ctx *ctx, mi3pt_convergence *out);
 int mi3pt_read_convergence_tiles(mi3pt_ctx *ctx, float *dst, size_t nfloats);  /* tiles_y x tiles_x x 4 */
+
+/* ---- adaptive sampling: stop sampling the tiles that have converged -- no counterpart in the reference.  The error estimate above says
+ * which tiles are done; the sample mask stops them from being traced and accumulated.
+ * The sample mask: one byte per 8 x 8 tile of the context's compact image, on the grid of mi3pt_estimate_convergence (tiles_x =
+ * ceil(width / 8), tiles_y = ceil(rows / 8), row-major, rows = local rows).  Non-zero = sampled, zero = frozen.  Default: no mask,
+ * every tile sampled; a context that never sets one allocates nothing new and launches exactly what it launched before (same kernels,
+ * grids, counters, mi3pt_debug_last_launch, MI3PT_OPT_LAST_BUILD).
+ * What the mask changes: while one is set, an accumulate step touches the texels of sampled tiles only -- queued sample frames, the
+ * immediate path of mi3pt_submit and an ACCUMULATE-only submit alike.  A frozen tile's accumulation texels and moments texels keep
+ * their bits.  The arithmetic of a sampled texel is unchanged: the same operations in frame order, the weight taken from the accumulate
+ * block's `frame` as always.  Hence, if tiles are only ever frozen between resets, every texel equals, bit for bit, the unmasked run's
+ * texel after the last frame its tile was sampled in -- mean and moments, F32 and F16 storage, a bound image.  A tile that is thawed
+ * again continues with the uniform's weight 1 / frame although it has seen fewer samples: the result is then the law's weighted mean,
+ * NOT the sample mean.  The hosts only ever freeze.
+ * What the mask saves: queued RAYTRACE | ACCUMULATE frames trace only the sampled tiles wherever the launch can take a tile list (the
+ * state-machine kernel's lean build of variants 9 - 14, without a cost order); the view's empty tiles among them are shaded by the
+ * streaming sky kernel as without a mask.  There MI3PT_CNT pixels, rays and misses count the sampled tiles' in-bounds pixels only and
+ * the radiance slots of frozen tiles are not written.  On every other route (variants 1 - 8, the per-pixel kernels, RAYTRACE without
+ * ACCUMULATE) every tile is traced as before and the accumulate step alone applies the mask; the per-pixel variants 1 / 2 run their two
+ * passes unfused while a mask is set, as they do for moments.  The image is the same on every route.  With no tile sampled a queued
+ * launch enqueues no raytrace, sky or accumulate kernel.  The ordered mean's work falls with the sampled tiles on every route.
+ * Life time: mi3pt_resize and mi3pt_reset drop the mask -- a new accumulation starts whole.  mi3pt_write_texture,
+ * mi3pt_bind_accumulation and mi3pt_set_moments leave it.  Setting or changing the mask launches the frame queue first, under the old
+ * mask, and does not wait for the stream.
+ *   mi3pt_set_sample_mask(tiles, ntiles): ntiles = tiles_y x tiles_x; (NULL, 0) removes the mask.
+ *   mi3pt_read_sample_mask: the mask as 0 / 1 bytes (no mask: all 1) and the number of sampled tiles.  Host state: no wait.
+ *   mi3pt_freeze_converged(guard): waits for the last estimate's event only, exactly as mi3pt_read_convergence_tiles does; applies
+ *     mi3pt_host_freeze_tiles to that estimate's tile records, with that estimate's threshold and min_frames, and to the current mask
+ *     (all ones if none); installs the result as by mi3pt_set_sample_mask; *sampled_out = the tiles still sampled.
+ *   mi3pt_host_freeze_tiles: the rule, plain host code, no device.  records = tiles_y x tiles_x x (sum_r, max_r, count, n_min).  With
+ *     above(t) exactly the verdict above (young or !(sum_r <= t2 * (float)count), t2 = (threshold * threshold) * 3.0f):
+ *       under(t) = count(t) > 0 && !above(t)
+ *       a tile with count == 0 is frozen at once: it has nothing to sample
+ *       a sampled tile with count > 0 is frozen iff under(t) and, for guard == 1, under(u) || count(u) == 0 for each of its up to eight
+ *       neighbours u inside the map -- the ring keeps a converged tile sampling while a neighbour is still noisy, which hides tile borders
+ *       an already frozen tile stays frozen: the function never thaws.  guard is 0 or 1.
+ *     The ring reads the verdicts of ALL neighbours, frozen ones included: a tile that was frozen on an older estimate and reads above in this
+ *     one (a host that applies a decision one chunk late, renderUntil's lookahead) keeps its neighbours sampling for as long as it does.
+ *   MI3PT_ERR_INVALID for a wrong ntiles, a null pointer where one is needed, or guard outside 0 / 1; MI3PT_ERR_STATE before
+ *   mi3pt_resize, and for mi3pt_freeze_converged before the first estimate since the last resize.
+ * Tile split: the mask is over this rank's compact rows, and the guard ring is taken over that compact map: across a block boundary
+ * these are NOT the image's neighbours.  A host that wants the image's ring gathers the ranks' maps, applies mi3pt_host_freeze_tiles
+ * to the whole map and hands each rank its rows with mi3pt_set_sample_mask.
+ * Device group: the three context calls take and return the WHOLE image's map, ceil(height / 8) x tiles_x, when the group's block_rows
+ * is a multiple of 8 -- assembled and scattered on the host by the row rule of mi3pt_read_convergence_tiles -- and are MI3PT_ERR_STATE
+ * otherwise; the group's mi3pt_freeze_converged applies the rule to the whole map, so its ring is the image's. ---- */
+int mi3pt_set_sample_mask(mi3pt_ctx *ctx, const uint8_t *tiles, size_t ntiles);   /* NULL, 0: no mask */
+int mi3pt_read_sample_mask(mi3pt_ctx *ctx, uint8_t *dst, size_t ntiles, uint32_t *sampled_out);  /* no mask: all 1 */
+int mi3pt_freeze_converged(mi3pt_ctx *ctx, int guard, uint32_t *sampled_out);
+int mi3pt_host_freeze_tiles(const float *records, int tiles_x, int tiles_y, float threshold, int min_frames,
+                            int guard, uint8_t *mask_inout, uint32_t *sampled_out);   /* plain host C++, no device */
 
 /* ---- read-back (the capability a headless drop-in needs; the reference only has
  * canvas.toDataURL, main.ts:351-356).  Blocking.  dst holds rows x width x 4 floats

@@ -176,16 +176,29 @@ struct mi3pt_ctx {
     bool sky_cut_ok = false;
     uint8_t sky_key[104] = {}, sky_seen_key[104] = {};
     bool sky_host_valid = false;
-    std::vector<uint32_t> sky_host;      // the list for sky_key
-    int sky_host_active = 0;
-    uint64_t sky_host_pixels = 0;        // in-bounds pixels of the empty tiles
-    uint32_t *d_sky_list[2] = { nullptr, nullptr };
-    size_t sky_list_cap[2] = { 0, 0 };
-    uint8_t sky_dev_key[2][104] = {};
-    bool sky_dev_valid[2] = { false, false };
-    std::vector<uint32_t> sky_staged[2]; // what the last copy into d_sky_list[par] reads (kept until sky_copied[par])
-    hipEvent_t sky_copied[2] = {};
-    bool sky_copied_valid[2] = { false, false };
+    std::vector<uint8_t> sky_empty;      // the classification for sky_key: 1 per empty tile
+    std::vector<uint32_t> sky_host;      // the list for sky_list_key: [sampled and not empty | sampled and empty] (pt_host_adapt.cpp)
+    uint8_t sky_list_key[104] = {};      // the view's key (zero but for the tile where the list is of the mask alone) + the mask's epoch
+    bool sky_list_valid = false;
+    int sky_host_active = 0, sky_host_sky = 0;
+    uint64_t sky_host_pixels = 0;        // in-bounds pixels of the listed empty tiles
+    // (slot 2: the list of the launches mi3pt_submit runs at once on the context's stream -- written and read on that stream only)
+    uint32_t *d_sky_list[3] = { nullptr, nullptr, nullptr };
+    size_t sky_list_cap[3] = { 0, 0, 0 };
+    uint8_t sky_dev_key[3][104] = {};
+    bool sky_dev_valid[3] = { false, false, false };
+    std::vector<uint32_t> sky_staged[3]; // what the last copy into d_sky_list[par] reads (kept until sky_copied[par])
+    hipEvent_t sky_copied[3] = {};
+    bool sky_copied_valid[3] = { false, false, false };
+    // The sample mask (mi3pt_set_sample_mask): one byte per 8 x 8 tile of the compact image, empty = no mask.  Every mask that is set
+    // gets a new epoch, which is part of the lists' keys (0: no mask), so a list a launch in flight reads is never taken for the new
+    // mask's.  list_read[slot]: behind the last ordered mean that read d_sky_list[slot] -- the copy of a new list waits for it (the mean
+    // runs on the context's stream, the copy on the launch's).  The events are created by the first mask.
+    std::vector<uint8_t> mask;
+    uint64_t mask_epoch = 0, mask_epochs = 0;
+    uint32_t mask_sampled = 0;
+    hipEvent_t list_read[3] = {};
+    bool list_read_valid[3] = { false, false, false };
     int collapse = -1;                   // MI3PT_OPT_COLLAPSE: 1 = the SAH-optimal grouping of the tree's nodes into wide packets, 0 = the greedy one of rounds 2 - 5, -1 = greedy for the 4-ary packets, optimal for the 8-ary ones (what each measured best with)
     int six_waves = -1;                  // MI3PT_OPT_SIX_WAVES: the compressed-wide walk's build, -1 = by the size of the launch (pt::RtLaunch::six_waves)
     int packet_order = 0;                // MI3PT_OPT_PACKET_ORDER: numbering of the wide packets in memory (prepare_cull): 0 breadth-first, 1 depth-first, 2 treelets
@@ -326,6 +339,7 @@ struct mi3pt_ctx {
     hipStream_t conv_read_stream = nullptr;      // the tile map's read-back, beside the context's stream (created by the first read)
     bool conv_valid = false;             // an estimate has been enqueued since the last resize
     float conv_threshold = 0.0f;         // ... with this threshold
+    int conv_min_frames = 0;             // ... and these min_frames (mi3pt_freeze_converged applies the rule with both)
     PassTimer conv_timer;
     int walk_stack_worst = 64;           // mi3pt_upload_bvh: entries the reference walk's stack can hold at most on this tree (64: unknown, or the abort can fire)
     int wide_stack_worst = 64;           // prepare_cull: the wide walks' node stack, order-independent worst case (internal packets only; <= SM_CULL_STACK_MAX where wide_ok)
@@ -380,6 +394,10 @@ static int group_read_moments(mi3pt_ctx *g, void *dst, size_t nbytes);
 static int group_moments_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes);
 static int group_read_convergence(mi3pt_ctx *g, mi3pt_convergence *out);
 static int group_read_convergence_tiles(mi3pt_ctx *g, float *dst, size_t nfloats);
+static int group_set_sample_mask(mi3pt_ctx *g, const uint8_t *tiles, size_t ntiles);
+static int group_read_sample_mask(mi3pt_ctx *g, uint8_t *dst, size_t ntiles, uint32_t *sampled_out);
+static int group_freeze_converged(mi3pt_ctx *g, int guard, uint32_t *sampled_out);
+static void drop_sample_mask(mi3pt_ctx *ctx);
 static int group_unsupported(const char *what);
 static int group_set_option(mi3pt_ctx *g, int option, int value);
 // one call applied to every member (and, where marked, to the presenting context too)
@@ -809,7 +827,10 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     for (int k = 0; k < 2; k++) {
         if (ctx->rt_stream[k]) (void)hipStreamDestroy(ctx->rt_stream[k]);
         if (ctx->rt_done[k]) (void)hipEventDestroy(ctx->rt_done[k]);
+    }
+    for (int k = 0; k < 3; k++) {
         if (ctx->sky_copied[k]) (void)hipEventDestroy(ctx->sky_copied[k]);
+        if (ctx->list_read[k]) (void)hipEventDestroy(ctx->list_read[k]);
         if (ctx->d_sky_list[k]) (void)hipFree(ctx->d_sky_list[k]);
         ctx->d_sky_list[k] = nullptr;
     }
@@ -1220,6 +1241,14 @@ static int zero_textures(mi3pt_ctx *ctx)
     return MI3PT_OK;
 }
 
+// mi3pt_resize / mi3pt_reset: no mask, every tile sampled (the queue has been launched under the old one)
+static void drop_sample_mask(mi3pt_ctx *ctx)
+{
+    ctx->mask.clear();
+    ctx->mask_epoch = 0;
+    ctx->mask_sampled = 0;
+}
+
 // Frames one launch may cover for this context's tile (before the memory cap of mi3pt_resize).
 static int batch_limit(const mi3pt_ctx *ctx, int nranks)
 {
@@ -1234,6 +1263,7 @@ extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
     if (int rc = require_idle(ctx)) return rc;
     if (width <= 0 || height <= 0 || width > 32768 || height > 32768)
         return pt_set_error(MI3PT_ERR_INVALID, "width/height must be in [1, 32768]");
+    drop_sample_mask(ctx);
     HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
     for (int k = 0; k < 2; k++) HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[k]));
     // Transactional: the new images are allocated into locals and the context only changes once
@@ -1286,6 +1316,7 @@ extern "C" int mi3pt_reset(mi3pt_ctx *ctx)
     PT_GROUP(ctx, group_reset(ctx));
     if (int rc = require_idle(ctx)) return rc;
     if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "reset before resize");
+    drop_sample_mask(ctx);          // a new accumulation starts whole
     return zero_textures(ctx);
 }
 
@@ -1830,81 +1861,158 @@ static void adapt_walk(mi3pt_ctx *ctx)
 // check), with the camera base at hand, without a cost order.  The host's classification (a millisecond or two at 1080p) runs at
 // once for a launch of SKY_MIN_FRAMES frames or more, which hides it; a shallower launch -- an interactive host -- gets it once its camera
 // has stood still for a launch, so that a host that moves the camera every frame never pays for it.
+// With a sample mask (mi3pt_set_sample_mask) the same list carries the mask: [A: sampled and not empty | S: sampled and empty], composed by
+// pt::compose_tile_lists -- the persistent kernel gets A wherever the launch can take a list (the conditions above but for the ones the
+// empty tiles alone need: the cut, the camera base, two tiles or more), k_sky_samples gets S, and the ordered mean (k_accumulate_tiles)
+// gets all of it through *acc_list / *acc_count on EVERY route.  Without a classification S is empty; with A empty S is the job list.
 #define SKY_MIN_FRAMES 8
+static void tile_key_of(const pt::Tile &tile, uint64_t mask_epoch, uint8_t key[104])
+{
+    const int32_t tl[6] = { tile.tex_w, tile.tex_h, tile.local_rows, tile.rank, tile.nranks, tile.block_rows };
+    std::memcpy(key + 60, tl, sizeof tl);
+    std::memcpy(key + 96, &mask_epoch, 8);
+}
+
+// ctx->sky_host = the lists for `key` (the mask as it stands; the classification in ctx->sky_empty if `classified`)
+static void tile_lists_compose(mi3pt_ctx *ctx, const pt::Tile &tile, const uint8_t *u_rt, const uint8_t *key, bool classified)
+{
+    if (ctx->sky_list_valid && std::memcmp(key, ctx->sky_list_key, sizeof ctx->sky_list_key) == 0) return;
+    // the in-bounds pixels of the empty tiles (the refill's test, raytrace.wgsl:425-427): each is one ray, one miss, one pixel per frame
+    const double rx = u_rt ? ldf(u_rt, 0) : 0.0, ry = u_rt ? ldf(u_rt, 4) : 0.0;
+    pt::TileListInput in;
+    in.tex_w = tile.tex_w; in.tex_h = tile.tex_h; in.local_rows = tile.local_rows;
+    in.rank = tile.rank; in.nranks = tile.nranks; in.block_rows = tile.block_rows;
+    in.res_w = rx >= 1.0 ? (long long)std::min(rx, 4294967295.0) : 0;
+    in.res_h = ry >= 1.0 ? (long long)std::min(ry, 4294967295.0) : 0;
+    pt::TileLists out;
+    pt::compose_tile_lists(in, ctx->mask.empty() ? nullptr : ctx->mask.data(), classified ? ctx->sky_empty.data() : nullptr, out);
+    ctx->sky_host.swap(out.list);
+    ctx->sky_host_active = out.active;
+    ctx->sky_host_sky = out.sky;
+    ctx->sky_host_pixels = out.sky_pixels;
+    std::memcpy(ctx->sky_list_key, key, sizeof ctx->sky_list_key);
+    ctx->sky_list_valid = true;
+}
+
+// d_sky_list[slot] = ctx->sky_host (composed for `key`), copied on `s` unless the slot holds that list already.  *staged = false: no
+// memory for it (an unmasked launch then stays whole; under a mask the ordered mean cannot do without: `required`)
+static int tile_lists_stage(mi3pt_ctx *ctx, int slot, const uint8_t *key, size_t ntiles, hipStream_t s, bool required, bool *staged)
+{
+    *staged = true;
+    if (ctx->sky_dev_valid[slot] && std::memcmp(key, ctx->sky_dev_key[slot], sizeof ctx->sky_dev_key[slot]) == 0) return MI3PT_OK;
+    if (!ctx->sky_copied[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->sky_copied[slot], hipEventDisableTiming));
+    if (ctx->sky_copied_valid[slot]) HIP_TRY(hipEventSynchronize(ctx->sky_copied[slot]));      // (long done: this slot's previous list)
+    if (ctx->sky_list_cap[slot] < ntiles) {
+        uint32_t *fresh = nullptr;
+        if (hipMalloc((void **)&fresh, ntiles * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            *staged = false;
+            return required ? pt_set_error(MI3PT_ERR_HIP, "no device memory for the sample mask's tile list") : MI3PT_OK;
+        }
+        if (ctx->d_sky_list[slot]) (void)hipFree(ctx->d_sky_list[slot]);          // (hipFree waits for the device: nothing still reads it)
+        ctx->d_sky_list[slot] = fresh;
+        ctx->sky_list_cap[slot] = ntiles;
+    }
+    ctx->sky_dev_valid[slot] = false;
+    ctx->sky_staged[slot] = ctx->sky_host;
+    // (an ordered mean of an earlier launch may still read the slot's list from the context's stream)
+    if (ctx->list_read_valid[slot]) HIP_TRY(hipStreamWaitEvent(s, ctx->list_read[slot], 0));
+    if (!ctx->sky_staged[slot].empty())
+        HIP_TRY(hipMemcpyAsync(ctx->d_sky_list[slot], ctx->sky_staged[slot].data(), ctx->sky_staged[slot].size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ctx->sky_copied[slot], s));
+    ctx->sky_copied_valid[slot] = true;
+    std::memcpy(ctx->sky_dev_key[slot], key, sizeof ctx->sky_dev_key[slot]);
+    ctx->sky_dev_valid[slot] = true;
+    return MI3PT_OK;
+}
+
 static int sky_prepare(mi3pt_ctx *ctx, pt::RtLaunch &L, const uint8_t *u_rt, int par, int n, hipStream_t rs,
-                       const uint32_t **sky_list, int *sky_count, uint64_t *sky_samples)
+                       const uint32_t **sky_list, int *sky_count, uint64_t *sky_samples, const uint32_t **acc_list, int *acc_count)
 {
     *sky_list = nullptr; *sky_count = 0; *sky_samples = 0;
+    *acc_list = nullptr; *acc_count = 0;
+    const bool masked = !ctx->mask.empty();
     const pt::RtRoute &r = ctx->last_route;
-    if (!ctx->sky_tiles || !ctx->sky_cut_ok || ctx->env_sampling || !L.cam_base || L.tile_perm || L.tile_cost ||
-        !(r.kind == 1 && r.lean && r.variant >= 9 && r.variant <= 14))
-        return MI3PT_OK;
     const int ntiles = pt::raytrace_grid_blocks(L.tile);
-    if (ntiles < 2) return MI3PT_OK;
+    const bool takes_list = !L.tile_perm && !L.tile_cost && r.kind == 1 && r.lean && r.variant >= 9 && r.variant <= 14;
+    const bool sky_ok = takes_list && ctx->sky_tiles && ctx->sky_cut_ok && !ctx->env_sampling && L.cam_base && ntiles >= 2;
+    if (!masked && !sky_ok) return MI3PT_OK;
     uint8_t key[104];
     std::memset(key, 0, sizeof key);
-    std::memcpy(key, u_rt, 12);                       // resolution, aspect
-    std::memcpy(key + 12, u_rt + 32, 40);             // camera position, direction, fov, focal distance, aperture (32 .. 72)
-    std::memcpy(key + 52, u_rt + 16, 8);              // maxBounces, samplesPerFrame
-    const int32_t tl[6] = { L.tile.tex_w, L.tile.tex_h, L.tile.local_rows, L.tile.rank, L.tile.nranks, L.tile.block_rows };
-    std::memcpy(key + 60, tl, sizeof tl);
-    std::memcpy(key + 88, &ctx->scene_epoch, 8);
-    if (!ctx->sky_host_valid || std::memcmp(key, ctx->sky_key, sizeof key) != 0) {
-        const bool stood_still = std::memcmp(key, ctx->sky_seen_key, sizeof key) == 0;
-        std::memcpy(ctx->sky_seen_key, key, sizeof key);
-        if (n < SKY_MIN_FRAMES && !stood_still) return MI3PT_OK;
-        std::vector<uint8_t> empty;
-        (void)pt::sky_classify(ctx->sky_cut, true, u_rt, L.tile.tex_w, L.tile.local_rows, L.tile.tex_h,
-                               L.tile.rank, L.tile.nranks, L.tile.block_rows, empty);
-        ctx->sky_host.assign((size_t)ntiles, 0u);
-        size_t at = 0;
-        for (int t = 0; t < ntiles; t++) if (!empty[(size_t)t]) ctx->sky_host[at++] = (uint32_t)t;
-        ctx->sky_host_active = (int)at;
-        // the in-bounds pixels of the empty tiles (the refill's test, raytrace.wgsl:425-427): each is one ray, one miss, one pixel per frame
-        const double rx = ldf(u_rt, 0), ry = ldf(u_rt, 4);
-        const long long res_w = rx >= 1.0 ? (long long)std::min(rx, 4294967295.0) : 0, res_h = ry >= 1.0 ? (long long)std::min(ry, 4294967295.0) : 0;
-        const int tiles_x = (L.tile.tex_w + 7) / 8;
-        uint64_t pixels = 0;
-        for (int t = 0; t < ntiles; t++) {
-            if (!empty[(size_t)t]) continue;
-            ctx->sky_host[at++] = (uint32_t)t;
-            const int trow = t / tiles_x, tcol = t - trow * tiles_x;
-            int cols = 0;
-            for (int px = tcol * 8; px < tcol * 8 + 8; px++) cols += px < L.tile.tex_w && (long long)px < res_w ? 1 : 0;
-            for (int ply = trow * 8; ply < trow * 8 + 8; ply++) {
-                if (ply >= L.tile.local_rows) continue;
-                const int pgy = L.tile.nranks <= 1 ? ply : mi3pt_tile_global_row(ply, L.tile.rank, L.tile.nranks, L.tile.block_rows);
-                if (pgy >= 0 && pgy < L.tile.tex_h && (long long)pgy < res_h) pixels += (uint64_t)cols;
+    bool classified = false;
+    if (sky_ok) {
+        std::memcpy(key, u_rt, 12);                       // resolution, aspect
+        std::memcpy(key + 12, u_rt + 32, 40);             // camera position, direction, fov, focal distance, aperture (32 .. 72)
+        std::memcpy(key + 52, u_rt + 16, 8);              // maxBounces, samplesPerFrame
+        tile_key_of(L.tile, 0, key);
+        std::memcpy(key + 88, &ctx->scene_epoch, 8);
+        classified = true;
+        if (!ctx->sky_host_valid || std::memcmp(key, ctx->sky_key, sizeof key) != 0) {
+            const bool stood_still = std::memcmp(key, ctx->sky_seen_key, sizeof key) == 0;
+            std::memcpy(ctx->sky_seen_key, key, sizeof key);
+            if (n < SKY_MIN_FRAMES && !stood_still) {
+                classified = false;
+            } else {
+                (void)pt::sky_classify(ctx->sky_cut, true, u_rt, L.tile.tex_w, L.tile.local_rows, L.tile.tex_h,
+                                       L.tile.rank, L.tile.nranks, L.tile.block_rows, ctx->sky_empty);
+                std::memcpy(ctx->sky_key, key, sizeof key);
+                ctx->sky_host_valid = true;
             }
         }
-        ctx->sky_host_pixels = pixels;
-        std::memcpy(ctx->sky_key, key, sizeof key);
-        ctx->sky_host_valid = true;
-    }
-    const int active = ctx->sky_host_active, nempty = ntiles - active;
-    if (nempty <= 0 || active <= 0) return MI3PT_OK;          // (nothing to take out -- or nothing left: such a launch stays whole)
-    if (!ctx->sky_dev_valid[par] || std::memcmp(key, ctx->sky_dev_key[par], sizeof key) != 0) {
-        if (ctx->sky_copied_valid[par]) HIP_TRY(hipEventSynchronize(ctx->sky_copied[par]));      // (long done: this parity's previous view)
-        if (ctx->sky_list_cap[par] < (size_t)ntiles) {
-            uint32_t *fresh = nullptr;
-            if (hipMalloc((void **)&fresh, (size_t)ntiles * 4) != hipSuccess) { (void)hipGetLastError(); return MI3PT_OK; }      // no memory: no split
-            if (ctx->d_sky_list[par]) (void)hipFree(ctx->d_sky_list[par]);          // (hipFree waits for the device: nothing still reads it)
-            ctx->d_sky_list[par] = fresh;
-            ctx->sky_list_cap[par] = (size_t)ntiles;
+        if (!classified) {
+            if (!masked) return MI3PT_OK;
+            std::memset(key, 0, sizeof key);              // (the list of the mask alone)
         }
-        ctx->sky_dev_valid[par] = false;
-        ctx->sky_staged[par] = ctx->sky_host;
-        HIP_TRY(hipMemcpyAsync(ctx->d_sky_list[par], ctx->sky_staged[par].data(), (size_t)ntiles * 4, hipMemcpyHostToDevice, rs));
-        HIP_TRY(hipEventRecord(ctx->sky_copied[par], rs));
-        ctx->sky_copied_valid[par] = true;
-        std::memcpy(ctx->sky_dev_key[par], key, sizeof key);
-        ctx->sky_dev_valid[par] = true;
     }
-    L.tile_perm = ctx->d_sky_list[par];
-    L.ntiles_active = active;
-    *sky_list = ctx->d_sky_list[par] + active;
-    *sky_count = nempty;
-    *sky_samples = ctx->sky_host_pixels * (uint64_t)n;
+    tile_key_of(L.tile, ctx->mask_epoch, key);
+    tile_lists_compose(ctx, L.tile, u_rt, key, classified);
+    const int active = ctx->sky_host_active, nsky = ctx->sky_host_sky;
+    if (!masked && (nsky <= 0 || active <= 0)) return MI3PT_OK;          // (nothing to take out -- or nothing left: such a launch stays whole)
+    if (active + nsky == 0) return MI3PT_OK;                             // (no tile is sampled: launch_batch launches nothing)
+    bool staged = false;
+    if (int rc = tile_lists_stage(ctx, par, key, (size_t)ntiles, rs, masked, &staged)) return rc;
+    if (!staged) return MI3PT_OK;                                        // no memory: no split
+    if (takes_list && active == 0) {                  // only empty tiles are sampled: they are the job list, no sky kernel
+        L.tile_perm = ctx->d_sky_list[par];
+        L.ntiles_active = nsky;
+    } else if (takes_list && (nsky > 0 || active < ntiles)) {
+        L.tile_perm = ctx->d_sky_list[par];
+        L.ntiles_active = active;
+        if (nsky > 0) {
+            *sky_list = ctx->d_sky_list[par] + active;
+            *sky_count = nsky;
+            *sky_samples = ctx->sky_host_pixels * (uint64_t)n;
+        }
+    }
+    if (masked) {
+        *acc_list = ctx->d_sky_list[par];
+        *acc_count = active + nsky;
+    }
+    return MI3PT_OK;
+}
+
+// The list of the sampled tiles for an ordered mean that runs at once on the context's stream (mi3pt_submit's immediate path): slot 2
+static int mask_list_main(mi3pt_ctx *ctx, const pt::Tile &tile, const uint32_t **list, int *count)
+{
+    *list = nullptr; *count = 0;
+    uint8_t key[104];
+    std::memset(key, 0, sizeof key);
+    tile_key_of(tile, ctx->mask_epoch, key);
+    tile_lists_compose(ctx, tile, nullptr, key, false);
+    if (ctx->sky_host_active == 0) return MI3PT_OK;
+    bool staged = false;
+    if (int rc = tile_lists_stage(ctx, 2, key, (size_t)pt::raytrace_grid_blocks(tile), ctx->stream, true, &staged)) return rc;
+    *list = ctx->d_sky_list[2];
+    *count = ctx->sky_host_active;
+    return MI3PT_OK;
+}
+
+// behind an ordered mean that read d_sky_list[slot]
+static int mask_list_used(mi3pt_ctx *ctx, int slot)
+{
+    if (!ctx->list_read[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->list_read[slot], hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ctx->list_read[slot], ctx->stream));
+    ctx->list_read_valid[slot] = true;
     return MI3PT_OK;
 }
 
@@ -1950,7 +2058,10 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     // free.  Enqueued earlier, the kernel would sit in the dispatcher for the previous launch's
     // whole run -- same throughput, but event / profiler durations twice the execution time.
     const uint32_t seq_before = ctx->launch_seq;
-    const bool launches = pt::raytrace_grid_blocks(L.tile) > 0;       // (an empty tile launches nothing)
+    // (under a sample mask with no sampled tile -- mi3pt_set_sample_mask -- nothing is launched either: no raytrace, sky or accumulate kernel,
+    // and, like the empty tile, no sequence number is taken at the gate, so no later launch waits for a mark nobody publishes)
+    const bool masked = !ctx->mask.empty(), none_sampled = masked && ctx->mask_sampled == 0;
+    const bool launches = pt::raytrace_grid_blocks(L.tile) > 0 && !none_sampled;       // (an empty tile launches nothing)
     // Only the state-machine kernel publishes a drain mark (pt_kernels.hip, the ticket draw).  A batch routed to the per-pixel
     // kernels -- launches beyond the packing limits, maxBounces >= 65536 -- gets its mark from the host side of its stream after
     // its last frame: left to a kernel that never stores it, the NEXT batch would wait for ever (round-4 advice).
@@ -2000,8 +2111,10 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     const uint32_t *sky_list = nullptr;
     int sky_count = 0;
     uint64_t sky_samples = 0;
+    const uint32_t *acc_list = nullptr;      // under a sample mask: the sampled tiles, for the ordered mean
+    int acc_count = 0;
     if (launches)
-        if (int rc = sky_prepare(ctx, L, first.u_rt, par, n, rs, &sky_list, &sky_count, &sky_samples)) return rc;
+        if (int rc = sky_prepare(ctx, L, first.u_rt, par, n, rs, &sky_list, &sky_count, &sky_samples, &acc_list, &acc_count)) return rc;
     // the walk threshold by the view (adapt_walk): the deep-walk build for a launch of the shipped walk long enough to run its six-wave form
     // (>= 250 k jobs: a short launch -- an interactive host's single frames -- is all ramp and drain, and keeps the ordinary build.  Counted in
     // tiles of the FRAME, empty ones included: which of the two builds a view gets does not depend on how much sky it shows --
@@ -2010,7 +2123,7 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
         (long long)pt::raytrace_grid_blocks(L.tile) * n >= 250000)
         L.walk_min = PT_DEEP_WALK_MIN;
     ctx->last_route = pt::raytrace_route(L, variant);          // (the grid and the build follow the number of jobs)
-    pt::launch_raytrace_setup(L, ctx->last_route, rs);
+    if (!none_sampled) pt::launch_raytrace_setup(L, ctx->last_route, rs);
     if (ctx->timing) {
         HIP_TRY(hipEventRecord(ctx->ev_rt[par][0], rs));
         if (!ctx->span_started) { HIP_TRY(hipEventRecord(ctx->ev_span_start, rs)); ctx->span_started = true; }
@@ -2018,7 +2131,7 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
     // (in front of the persistent kernel: it runs while the predecessor's last paths drain -- +0.4 % over behind it, where it would follow this
     // launch's own drain: profiles/sky_tiles_ab.log)
     if (sky_count && ctx->sky_tiles != 2) pt::launch_sky_samples(L, sky_list, sky_count, sky_samples, rs);
-    pt::launch_raytrace(L, ctx->last_route, false, rs);
+    if (!none_sampled) pt::launch_raytrace(L, ctx->last_route, false, rs);
     if (sky_count && ctx->sky_tiles == 2) pt::launch_sky_samples(L, sky_list, sky_count, sky_samples, rs);
     if (publish_after && !ctx->debug_suppress_drain && hipStreamWriteValue32(rs, ctx->d_drain_flag, publish_after, 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -2061,7 +2174,12 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
         pt::AccUniforms a = acc;
         a.frame = acc.frame + (uint32_t)k;
         if (ctx->timing && last_run) HIP_TRY(ctx->pass_timer[1].begin(ctx->stream));
-        pt::launch_accumulate_frames(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, ctx->d_moments, f16, 4096, ctx->stream);
+        if (masked) {        // the sampled tiles only: a frozen tile's mean and moments keep their bits
+            pt::launch_accumulate_tiles(a, L.tile, acc_list, acc_count, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum,
+                                        ctx->d_moments, f16, ctx->stream);
+        } else {
+            pt::launch_accumulate_frames(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, ctx->d_moments, f16, 4096, ctx->stream);
+        }
         HIP_TRY(hipGetLastError());
         if (ctx->timing && last_run) HIP_TRY(ctx->pass_timer[1].end(ctx->stream));
         ctx->accum_version++;
@@ -2069,6 +2187,8 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
             if (int rc = run_fullscreen(ctx, frames[e].u_fs)) return rc;
         k = e + 1;
     }
+    if (masked && acc_count)
+        if (int rc = mask_list_used(ctx, par)) return rc;
     HIP_TRY(hipEventRecord(ctx->acc_done[set], ctx->stream));
     ctx->acc_done_valid[set] = true;
     return MI3PT_OK;
@@ -2182,7 +2302,8 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
             // Fuse when the accumulate pass covers exactly the pixels the raytrace pass writes (the per-pixel kernels; the
             // state-machine kernel writes the frame's radiance and the accumulate pass follows as a kernel of its own: same bits).
             // (not with the moments image: the per-pixel kernels do not keep it, the two passes run separately -- same bits)
-            const bool fused = do_acc && same_region && pt::raytrace_variant_fuses(variant) && !ctx->d_moments;
+            // (nor under a sample mask: the fused kernels step every texel)
+            const bool fused = do_acc && same_region && pt::raytrace_variant_fuses(variant) && !ctx->d_moments && ctx->mask.empty();
             // (the service block of a launch that runs at once: its own slot -- launches on the main stream follow each other,
             // and the batches launched before it are waited for by this stream)
             L.service = reinterpret_cast<pt::RtService *>(ctx->d_service + (size_t)SERVICE_SLOTS * service_slot_bytes());
@@ -2202,7 +2323,16 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
     }
     if (do_acc && !acc_done) {
         if (ctx->timing) HIP_TRY(ctx->pass_timer[1].begin(ctx->stream));
-        pt::launch_accumulate_frames(acc, tile, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, 2048, ctx->stream);
+        if (!ctx->mask.empty()) {
+            const uint32_t *list = nullptr;
+            int count = 0;
+            if (int rc = mask_list_main(ctx, tile, &list, &count)) return rc;
+            pt::launch_accumulate_tiles(acc, tile, list, count, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, ctx->stream);
+            if (count)
+                if (int rc = mask_list_used(ctx, 2)) return rc;
+        } else {
+            pt::launch_accumulate_frames(acc, tile, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, 2048, ctx->stream);
+        }
         HIP_TRY(hipGetLastError());
         if (ctx->timing) HIP_TRY(ctx->pass_timer[1].end(ctx->stream));
         ctx->output_is_accum = true;   // accumulate.ts:171-175 copies the mean into outputTexture
@@ -2694,6 +2824,7 @@ extern "C" int mi3pt_estimate_convergence(mi3pt_ctx *ctx, float threshold, int m
     HIP_TRY(hipEventRecord(ctx->conv_done, ctx->stream));
     ctx->conv_valid = true;
     ctx->conv_threshold = threshold;
+    ctx->conv_min_frames = min_frames;
     return MI3PT_OK;
 }
 
@@ -2739,6 +2870,70 @@ extern "C" int mi3pt_read_convergence_tiles(mi3pt_ctx *ctx, float *dst, size_t n
     if (!ctx->conv_read_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->conv_read_stream, hipStreamNonBlocking));
     HIP_TRY(hipMemcpyAsync(dst, ctx->d_conv_tiles, nfloats * 4, hipMemcpyDeviceToHost, ctx->conv_read_stream));
     HIP_TRY(hipStreamSynchronize(ctx->conv_read_stream));
+    return MI3PT_OK;
+}
+
+// ---- adaptive sampling: the per-tile sample mask (include/mi3pt.h: mi3pt_set_sample_mask; pt_host_adapt.cpp, pt_accumulate_tiles.hip) ----
+extern "C" int mi3pt_set_sample_mask(mi3pt_ctx *ctx, const uint8_t *tiles, size_t ntiles)
+{
+    PT_GROUP(ctx, group_set_sample_mask(ctx, tiles, ntiles));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_set_sample_mask before resize");
+    const bool clear = !tiles && ntiles == 0;
+    if (!clear && !tiles) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (!clear && ntiles != conv_tiles_x(ctx) * conv_tiles_y(ctx))
+        return pt_set_error(MI3PT_ERR_INVALID, "the mask's size does not match the tile map (ceil(rows / 8) x ceil(width / 8) bytes)");
+    if (int rc = flush_pending(ctx)) return rc;      // the frames queued so far were submitted under the old mask
+    if (clear || ntiles == 0) {                       // (a rank without rows has nothing to mask)
+        drop_sample_mask(ctx);
+        return MI3PT_OK;
+    }
+    ctx->mask.resize(ntiles);
+    uint32_t sampled = 0;
+    for (size_t t = 0; t < ntiles; t++) {
+        ctx->mask[t] = tiles[t] ? 1 : 0;
+        sampled += tiles[t] ? 1u : 0u;
+    }
+    ctx->mask_sampled = sampled;
+    ctx->mask_epoch = ++ctx->mask_epochs;
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_read_sample_mask(mi3pt_ctx *ctx, uint8_t *dst, size_t ntiles, uint32_t *sampled_out)
+{
+    PT_GROUP(ctx, group_read_sample_mask(ctx, dst, ntiles, sampled_out));
+    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_sample_mask before resize");
+    const size_t need = conv_tiles_x(ctx) * conv_tiles_y(ctx);
+    if (ntiles != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the tile map (ceil(rows / 8) x ceil(width / 8) bytes)");
+    if (!dst && need) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (ctx->mask.empty()) {
+        if (need) std::memset(dst, 1, need);
+        if (sampled_out) *sampled_out = (uint32_t)need;
+        return MI3PT_OK;
+    }
+    std::memcpy(dst, ctx->mask.data(), need);
+    if (sampled_out) *sampled_out = ctx->mask_sampled;
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_freeze_converged(mi3pt_ctx *ctx, int guard, uint32_t *sampled_out)
+{
+    PT_GROUP(ctx, group_freeze_converged(ctx, guard, sampled_out));
+    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
+    if (guard != 0 && guard != 1) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_freeze_converged: guard must be 0 or 1");
+    if (int rc = conv_wait(ctx, "mi3pt_freeze_converged")) return rc;
+    const size_t tiles_x = conv_tiles_x(ctx), tiles_y = conv_tiles_y(ctx), n = tiles_x * tiles_y;
+    std::vector<float> records(n * 4);
+    if (n)
+        if (int rc = mi3pt_read_convergence_tiles(ctx, records.data(), records.size())) return rc;
+    std::vector<uint8_t> mask(n, 1);
+    if (!ctx->mask.empty()) mask = ctx->mask;
+    uint32_t sampled = 0;
+    if (int rc = mi3pt_host_freeze_tiles(records.data(), (int)tiles_x, (int)tiles_y, ctx->conv_threshold, ctx->conv_min_frames, guard, mask.data(), &sampled)) return rc;
+    if (n)
+        if (int rc = mi3pt_set_sample_mask(ctx, mask.data(), n)) return rc;
+    if (sampled_out) *sampled_out = sampled;
     return MI3PT_OK;
 }
 
@@ -3491,6 +3686,93 @@ static int group_read_convergence_tiles(mi3pt_ctx *g, float *dst, size_t nfloats
             std::memcpy(dst + gt * tiles_x * 4, part.data() + t * tiles_x * 4, tiles_x * 16);
         }
     }
+    return MI3PT_OK;
+}
+
+// ---- the sample mask: the whole image's map in and out, scattered to / assembled from the members' maps on the host by the row rule of
+// group_read_convergence_tiles; the freeze rule runs on the WHOLE map, so its guard ring is the image's ----
+static int group_mask_shape(mi3pt_ctx *g, const char *what, size_t *tiles_x, size_t *tiles_y)
+{
+    GroupState *gs = g->group;
+    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
+    if (gs->block_rows % 8)
+        return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": the members' tiles only form the image's tile map when the group's block_rows is a multiple of 8 (use each member's mask: mi3pt_group_member)");
+    *tiles_x = ((size_t)gs->width + 7) / 8;
+    *tiles_y = ((size_t)gs->height + 7) / 8;
+    return MI3PT_OK;
+}
+
+static int group_set_sample_mask(mi3pt_ctx *g, const uint8_t *tiles, size_t ntiles)
+{
+    GroupState *gs = g->group;
+    size_t tiles_x = 0, tiles_y = 0;
+    if (int rc = group_mask_shape(g, "mi3pt_set_sample_mask", &tiles_x, &tiles_y)) return rc;
+    if (!tiles && ntiles == 0) return group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_set_sample_mask(m, nullptr, 0); });
+    if (!tiles) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (ntiles != tiles_x * tiles_y)
+        return pt_set_error(MI3PT_ERR_INVALID, "the mask's size does not match the tile map (a group takes the whole map: ceil(height / 8) x ceil(width / 8) bytes)");
+    const int n = (int)gs->members.size();
+    std::vector<uint8_t> part;
+    for (int i = 0; i < n; i++) {
+        mi3pt_ctx *m = gs->members[(size_t)i];
+        const size_t rows = conv_tiles_y(m);
+        part.assign(rows * tiles_x, 0);
+        for (size_t t = 0; t < rows; t++) {
+            const size_t gt = (size_t)mi3pt_tile_global_row((int)t, i, n, gs->block_rows / 8);
+            if (gt >= tiles_y) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_set_sample_mask: a member's tile row lies outside the image");
+            std::memcpy(part.data() + t * tiles_x, tiles + gt * tiles_x, tiles_x);
+        }
+        if (rows == 0) continue;
+        if (int rc = mi3pt_set_sample_mask(m, part.data(), part.size())) return rc;
+    }
+    return MI3PT_OK;
+}
+
+static int group_read_sample_mask(mi3pt_ctx *g, uint8_t *dst, size_t ntiles, uint32_t *sampled_out)
+{
+    GroupState *gs = g->group;
+    size_t tiles_x = 0, tiles_y = 0;
+    if (int rc = group_mask_shape(g, "mi3pt_read_sample_mask", &tiles_x, &tiles_y)) return rc;
+    if (ntiles != tiles_x * tiles_y)
+        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the tile map (a group reads the whole map: ceil(height / 8) x ceil(width / 8) bytes)");
+    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    const int n = (int)gs->members.size();
+    std::vector<uint8_t> part;
+    uint32_t sampled = 0;
+    for (int i = 0; i < n; i++) {
+        mi3pt_ctx *m = gs->members[(size_t)i];
+        const size_t rows = conv_tiles_y(m);
+        if (rows == 0) continue;
+        part.resize(rows * tiles_x);
+        uint32_t mine = 0;
+        if (int rc = mi3pt_read_sample_mask(m, part.data(), part.size(), &mine)) return rc;
+        sampled += mine;
+        for (size_t t = 0; t < rows; t++) {
+            const size_t gt = (size_t)mi3pt_tile_global_row((int)t, i, n, gs->block_rows / 8);
+            if (gt >= tiles_y) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_sample_mask: a member's tile row lies outside the image");
+            std::memcpy(dst + gt * tiles_x, part.data() + t * tiles_x, tiles_x);
+        }
+    }
+    if (sampled_out) *sampled_out = sampled;
+    return MI3PT_OK;
+}
+
+static int group_freeze_converged(mi3pt_ctx *g, int guard, uint32_t *sampled_out)
+{
+    GroupState *gs = g->group;
+    if (guard != 0 && guard != 1) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_freeze_converged: guard must be 0 or 1");
+    size_t tiles_x = 0, tiles_y = 0;
+    if (int rc = group_mask_shape(g, "mi3pt_freeze_converged", &tiles_x, &tiles_y)) return rc;
+    const size_t n = tiles_x * tiles_y;
+    std::vector<float> records(n * 4);
+    if (int rc = group_read_convergence_tiles(g, records.data(), records.size())) return rc;
+    std::vector<uint8_t> mask(n);
+    if (int rc = group_read_sample_mask(g, mask.data(), n, nullptr)) return rc;
+    const mi3pt_ctx *m0 = gs->members[0];
+    uint32_t sampled = 0;
+    if (int rc = mi3pt_host_freeze_tiles(records.data(), (int)tiles_x, (int)tiles_y, m0->conv_threshold, m0->conv_min_frames, guard, mask.data(), &sampled)) return rc;
+    if (int rc = group_set_sample_mask(g, mask.data(), n)) return rc;
+    if (sampled_out) *sampled_out = sampled;
     return MI3PT_OK;
 }
 

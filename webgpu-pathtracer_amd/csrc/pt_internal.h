@@ -133,3 +133,11 @@ bool sky_cut_of(const uint8_t *src, size_t n, std::vector<float> &boxes);
 size_t sky_classify(const std::vector<float> &boxes, bool have_cut, const uint8_t *u, int width, int local_rows, int height,
                     int rank, int nranks, int block_rows, std::vector<uint8_t> &empty);
 }
+// pt_host_adapt.cpp: a launch's tile lists from the sample mask (mi3pt_set_sample_mask; null: every tile) and the view's empty tiles
+// (sky_classify's map; null: none) -- list = [A: sampled, not empty | S: sampled, empty], both ascending; active = |A|, sky = |S|,
+// sky_pixels = the in-bounds pixels of S for the raytrace uniforms' resolution res_w x res_h
+namespace pt {
+struct TileListInput { int tex_w, tex_h, local_rows, rank, nranks, block_rows; long long res_w, res_h; };
+struct TileLists { std::vector<uint32_t> list; int active = 0, sky = 0; uint64_t sky_pixels = 0; };
+void compose_tile_lists(const TileListInput &in, const uint8_t *mask, const uint8_t *empty, TileLists &out);
+}

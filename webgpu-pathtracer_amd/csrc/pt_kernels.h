@@ -381,6 +381,10 @@ void launch_camera_base(const RtLaunch &L, float4 *out, hipStream_t s);
 // moments: null, or the moments image (local_rows x width float4: M2.rgb, n; include/mi3pt.h: mi3pt_set_moments) kept beside the mean
 void launch_accumulate_frames(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels, int nframes,
                               float4 *accum, float4 *moments, int store_f16, int max_blocks, hipStream_t s);
+// the same mean for the texels of the `ntiles` listed 8 x 8 tiles only (device array of tile indices of the rank's compact image, each listed
+// once; pt_accumulate_tiles.hip): what a context with a sample mask runs instead (include/mi3pt.h: mi3pt_set_sample_mask)
+void launch_accumulate_tiles(const AccUniforms &acc0, const Tile &tile, const uint32_t *list, int ntiles, const float4 *slots,
+                             size_t slot_pixels, int nframes, float4 *accum, float4 *moments, int store_f16, hipStream_t s);
 // `taps`: fullscreen_taps_bytes() of device memory (the de-noise pass's tap table); `taps_current`: an earlier call on
 // this stream has filled it from the same fs.res_x / fs.res_y
 size_t fullscreen_taps_bytes();

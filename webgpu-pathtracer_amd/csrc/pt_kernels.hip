@@ -33,6 +33,7 @@
 //   k_debug_intersect/_math    component probes for the parity tests
 #include "pt_kernels.h"
 #include "pt_devmath.h"
+#include "pt_accum.h"      // f3, mix, the tile split's row rule, the running mean's device functions
 #include <hip/hip_fp16.h>
 
 namespace pt {
@@ -48,8 +49,6 @@ namespace pt {
 
 #define PT_REF_LEAF pt::REF_LEAF
 #define PT_REF_NONE pt::REF_NONE
-
-struct f3 { float x, y, z; };
 
 using ptm::div_pre;
 using ptm::rcp_exact;
@@ -70,8 +69,6 @@ PT_DEV void keep16(float4 &v)
         asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
     }
 }
-PT_DEV f3 F3(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
-PT_DEV f3 xyz(const float4 &v) { return F3(v.x, v.y, v.z); }
 PT_DEV f3 operator+(f3 a, f3 b) { return F3(a.x + b.x, a.y + b.y, a.z + b.z); }
 PT_DEV f3 operator-(f3 a, f3 b) { return F3(a.x - b.x, a.y - b.y, a.z - b.z); }
 PT_DEV f3 operator*(f3 a, f3 b) { return F3(a.x * b.x, a.y * b.y, a.z * b.z); }
@@ -103,9 +100,6 @@ PT_DEV f3 normalize(f3 a)
     }
     return F3(a.x / l, a.y / l, a.z / l);
 }
-// pinned: mix(a, b, t) = a * (1 - t) + b * t
-PT_DEV float mix1(float a, float b, float t) { return a * (1.0f - t) + b * t; }
-PT_DEV f3 mix(f3 a, f3 b, float t) { return F3(mix1(a.x, b.x, t), mix1(a.y, b.y, t), mix1(a.z, b.z, t)); }
 // pinned: reflect(i, n) = i - (2 * dot(n, i)) * n
 PT_DEV f3 reflect(f3 i, f3 n)
 {
@@ -745,20 +739,6 @@ PT_DEV FastDiv fast_div_of(uint32_t d)
 }
 PT_DEV int fast_div(int t, const FastDiv &f) { return (int)(uint32_t)(((uint64_t)(uint32_t)t * f.m) >> f.sh); }
 
-PT_DEV int local_to_global_row(int ly, const Tile &t)
-{
-    // The tile split (pt_kernels.h, Tile): local block b of rank r is block b * nranks + pos of the image, pos = r in even rounds of the
-    // deal and nranks - 1 - r in odd ones -- back and forth, so that a cost that rises or falls down the image (floor, model, sky)
-    // is shared out evenly (dealt one way only, rank 0 of eight got 5 % more work than rank 6: profiles/r04_rejected_and_adopted.log)
-    if (t.nranks == 1) return ly;                     // (wave-uniform fast paths: no division for the whole image ...
-    if (t.block_rows == 8) {                          // ... nor for the usual 8-row blocks)
-        const int b = ly >> 3;
-        return (((b * t.nranks + ((b & 1) ? t.nranks - 1 - t.rank : t.rank)) << 3) | (ly & 7));
-    }
-    const int b = ly / t.block_rows;
-    return (b * t.nranks + ((b & 1) ? t.nranks - 1 - t.rank : t.rank)) * t.block_rows + (ly - b * t.block_rows);
-}
-
 PT_DEV uint32_t wave_sum(uint32_t v)
 {
 #pragma unroll
@@ -838,17 +818,6 @@ PT_DEV f3 shade_pixel(const RtLaunch &L, uint32_t gx, uint32_t gy, uint32_t *sta
     }
     const float n = (float)un.samples_per_frame;
     return F3(incoming.x / n, incoming.y / n, incoming.z / n);
-}
-
-PT_DEV float store_round(float v, int store_f16) { return store_f16 ? ptm::round_f16(v) : v; }
-
-// accumulate.wgsl:18-28 for one texel
-PT_DEV f3 accumulate_texel(const AccUniforms &acc, f3 color, f3 prev)
-{
-    float weight = 1.0f;
-    if (acc.frame > 0u) weight = 1.0f / (float)acc.frame;
-    weight = (acc.enabled == 1u) ? weight : 1.0f;
-    return mix(prev, color, weight);
 }
 
 template <bool FUSE, int VARIANT>
@@ -2578,15 +2547,6 @@ void launch_raytrace(const RtLaunch &L, const RtRoute &r, bool fuse, hipStream_t
 // ---------------------------------------------------------------------------------
 // accumulate.wgsl:12-29 as its own pass
 // ---------------------------------------------------------------------------------
-// The moments image (include/mi3pt.h: mi3pt_set_moments): (M2.rgb, n) kept beside the mean in the same pass.  Welford's update written
-// around the mean as it is STORED: c the frame's radiance, p the mean before the step, pn the mean after it (after store_round); a step
-// of weight 1 (accumulate_texel) restarts the sums.
-PT_DEV float4 moments_step(const AccUniforms &acc, f3 c, f3 p, f3 pn, float4 m)
-{
-    if (acc.frame <= 1u || acc.enabled != 1u) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-    return make_float4(m.x + (c.x - p.x) * (c.x - pn.x), m.y + (c.y - p.y) * (c.y - pn.y), m.z + (c.z - p.z) * (c.z - pn.z), m.w + 1.0f);
-}
-
 // The running mean over `nframes` consecutive frames' radiance slots, applied per pixel in
 // frame order (frame, frame+1, ...) -- the same sequence of accumulate.wgsl passes, with the
 // accumulator (MOMENTS: and the moments image; otherwise `moments` is never touched) read and

@@ -529,6 +529,55 @@ napi_value ReadConvergenceTiles(napi_env env, napi_callback_info info)
     return ta;
 }
 
+// setSampleMask(ctx, Uint8Array | null): mi3pt_set_sample_mask -- one byte per 8 x 8 tile, non-zero = sampled; null removes the mask
+napi_value SetSampleMask(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx)) return nullptr;
+    napi_valuetype type;
+    NAPI_OK(napi_typeof(env, a.v[1], &type));
+    if (type == napi_null || type == napi_undefined) {
+        MI3PT_TRY(mi3pt_set_sample_mask(ctx, nullptr, 0));
+        return undefined(env);
+    }
+    void *data;
+    size_t n;
+    if (!get_bytes(env, a.v[1], &data, &n)) return nullptr;
+    MI3PT_TRY(mi3pt_set_sample_mask(ctx, static_cast<const uint8_t *>(data), n));
+    return undefined(env);
+}
+
+// readSampleMask(ctx, ntiles) -> Uint8Array of ntiles 0 / 1 bytes (no mask: all 1)
+napi_value ReadSampleMask(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t ntiles;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &ntiles) || ntiles < 0) return nullptr;
+    void *data = nullptr;
+    napi_value ab, ta;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)ntiles, &data, &ab));
+    uint32_t sampled = 0;
+    MI3PT_TRY(mi3pt_read_sample_mask(ctx, static_cast<uint8_t *>(data), (size_t)ntiles, &sampled));
+    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, (size_t)ntiles, ab, 0, &ta));
+    return ta;
+}
+
+// freezeConverged(ctx, guard) -> tiles still sampled (mi3pt_freeze_converged); waits for the last estimateConvergence only
+napi_value FreezeConverged(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t guard;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &guard)) return nullptr;
+    uint32_t sampled = 0;
+    MI3PT_TRY(mi3pt_freeze_converged(ctx, guard, &sampled));
+    napi_value v;
+    NAPI_OK(napi_create_uint32(env, sampled, &v));
+    return v;
+}
+
 // batchCapacity(ctx) -> frames one launch covers at the current size (mi3pt_batch_capacity)
 napi_value BatchCapacity(napi_env env, napi_callback_info info)
 {
@@ -740,6 +789,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "setMoments", SetMoments }, { "readMoments", ReadMoments },
         { "estimateConvergence", EstimateConvergence }, { "readConvergence", ReadConvergence }, { "readConvergenceTiles", ReadConvergenceTiles },
         { "batchCapacity", BatchCapacity },
+        { "setSampleMask", SetSampleMask }, { "readSampleMask", ReadSampleMask }, { "freezeConverged", FreezeConverged },
     };
     for (const auto &f : fns) {
         napi_value v;

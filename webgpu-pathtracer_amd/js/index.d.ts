@@ -146,7 +146,12 @@ export class Renderer {
    *  mean; checked every checkEvery frames (default: the batch capacity).  lookahead (default true): the estimate is read one chunk late,
    *  so the device never idles.  Emits 'converged' with the summary, then 'complete' */
   renderUntil(scene: RaytracingScene, camera: RaytracingCamera, threshold: number,
-    options?: { minFrames?: number; maxFrames?: number; checkEvery?: number; lookahead?: boolean }): { converged: boolean; frames: number; summary: ConvergenceSummary };
+    options?: { minFrames?: number; maxFrames?: number; checkEvery?: number; lookahead?: boolean; adaptive?: boolean; guard?: 0 | 1 }): { converged: boolean; frames: number; summary: ConvergenceSummary; sampled?: number };
+  /** adaptive sampling: one byte per 8 x 8 tile (tilesY x tilesX), non-zero = sampled, zero = frozen; null removes the mask (include/mi3pt.h: mi3pt_set_sample_mask) */
+  setSampleMask(mask: ArrayLike<number> | null): void;
+  readSampleMask(): Uint8Array;
+  /** freeze the tiles the last estimateConvergence found under its threshold; returns the tiles still sampled */
+  freezeConverged(guard?: 0 | 1): number;
   counters(): { rays: number; boxTests: number; triTests: number; hits: number; misses: number; stackOverflows: number; pixels: number };
   /** src/main.ts:351-356: the presented canvas as PNG bytes (written to `file` when given) */
   screenshot(file?: string): Buffer;

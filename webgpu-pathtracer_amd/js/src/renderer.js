@@ -263,6 +263,15 @@ class Renderer {
     return this.native.readConvergenceTiles(this.handle, Math.ceil(this.localRows / 8) * Math.ceil(this._width / 8));
   }
   static isConverged(summary) { return summary.tiles > 0 && summary.tilesAbove === 0; }
+  // ---- adaptive sampling (no counterpart in the reference; include/mi3pt.h: mi3pt_set_sample_mask): one byte per 8 x 8 tile, tilesY x tilesX,
+  // non-zero = sampled, zero = frozen -- a frozen tile is neither traced nor accumulated, its mean and moments keep their bits.
+  // setSampleMask(null) removes the mask; reset() and resize() drop it.  freezeConverged(guard = 1) freezes the tiles the last
+  // estimateConvergence found under its threshold (guard 1: and whose up to eight neighbours are, too) and returns the tiles still sampled.
+  setSampleMask(mask) {
+    this.native.setSampleMask(this.handle, mask === null || mask === undefined ? null : Uint8Array.from(mask, (v) => (v ? 1 : 0)));
+  }
+  readSampleMask() { return this.native.readSampleMask(this.handle, Math.ceil(this.localRows / 8) * Math.ceil(this._width / 8)); }
+  freezeConverged(guard) { return this.native.freezeConverged(this.handle, guard === undefined ? 1 : guard); }
   // render() until every 8 x 8 tile's estimated RMSE of the tone-mapped mean is at most `threshold` and has seen minFrames frames, or
   // until maxFrames (undefined: this.frames, otherwise it becomes this.frames) are in the mean.  The mean is checked every checkEvery
   // frames (undefined: the context's batch capacity, so launches keep one shape).  lookahead (default true): the estimate of a chunk is
@@ -270,11 +279,19 @@ class Renderer {
   // estimate that said converged, and those frames stay in the mean.  Without it the run stops at once.  The frame count at which it stops
   // is a function of the images alone.  Returns { converged, frames, summary }; the summary is the estimate that stopped the run, or, at
   // the end of the budget, that of the final mean.
+  // { adaptive: true, guard: 0 | 1 }: after every estimate that is read, freezeConverged(guard) stops sampling the tiles that are done; the
+  // run is converged when no tile is sampled any more, i.e. every tile was under the threshold at the check that froze it.  With lookahead
+  // the decision from estimate k is applied after chunk k + 1 has been flushed, so a tile is sampled one chunk longer.  The summary is then
+  // always that of an estimate of the FINAL image, and may show a tile above the threshold although the run converged: with lookahead a
+  // tile is sampled one chunk beyond the estimate that found it under, and the estimate is not monotone in the frames.  Such a tile stays
+  // frozen, and with guard 1 it keeps its neighbours sampling (the ring reads frozen neighbours too): a run with lookahead and guard 1 can
+  // then last to maxFrames -- { lookahead: false } or { guard: 0 } end it.  The result gains `sampled`: the tile-frames actually sampled.
   renderUntil(scene, camera, threshold, options) {
-    const o = Object.assign({ minFrames: 16, maxFrames: undefined, checkEvery: undefined, lookahead: true }, options || {});
+    const o = Object.assign({ minFrames: 16, maxFrames: undefined, checkEvery: undefined, lookahead: true, adaptive: false, guard: 1 }, options || {});
     if (!this._moments) throw new Error('renderUntil needs the moments image: setMoments(true) before sampling starts');
     if (o.maxFrames !== undefined && o.maxFrames !== null) this.frames = o.maxFrames;
     const checkEvery = Math.max(1, o.checkEvery === undefined || o.checkEvery === null ? this.native.batchCapacity(this.handle) : o.checkEvery);
+    if (o.adaptive) return this._renderUntilAdaptive(scene, camera, threshold, o, checkEvery);
     let pending = false;         // an estimate has been enqueued and not read
     let current = false;         // `summary` is of the mean as it stands
     let summary = null;
@@ -302,6 +319,44 @@ class Renderer {
     }
     if (Renderer.isConverged(summary)) return this._converged(summary);
     return { converged: false, frames: this._frame - 1, summary };
+  }
+  _renderUntilAdaptive(scene, camera, threshold, o, checkEvery) {
+    let sampling = this.readSampleMask().reduce((n, v) => n + (v ? 1 : 0), 0);      // tiles the next chunk samples
+    let sampled = 0;             // tile-frames sampled so far
+    let pending = false;         // an estimate has been enqueued and not read
+    let summary = null;          // the summary of the mean as it stands, once read
+    let done = false;
+    while (this.status === 'sampling' && this.hasFramesToSample && !done) {
+      const n = Math.min(checkEvery, this.frames - (this._frame - 1));
+      for (let i = 0; i < n; i++) this.render(scene, camera);
+      this.native.flush(this.handle);
+      sampled += n * sampling;
+      summary = null;
+      if (o.lookahead) {
+        if (pending) {
+          this.native.readConvergence(this.handle);      // (the chunk just flushed runs while the host waits)
+          pending = false;
+          sampling = this.native.freezeConverged(this.handle, o.guard);
+          done = sampling === 0;
+        }
+        if (!done) {
+          this.native.estimateConvergence(this.handle, threshold, o.minFrames);
+          pending = true;
+        }
+      } else {
+        this.native.estimateConvergence(this.handle, threshold, o.minFrames);
+        summary = this.native.readConvergence(this.handle);
+        sampling = this.native.freezeConverged(this.handle, o.guard);
+        done = sampling === 0;
+      }
+    }
+    if (summary === null) {      // the result describes the final mean
+      if (!pending) this.native.estimateConvergence(this.handle, threshold, o.minFrames);
+      summary = this.native.readConvergence(this.handle);
+    }
+    const out = done ? this._converged(summary) : { converged: false, frames: this._frame - 1, summary };
+    out.sampled = sampled;
+    return out;
   }
   _converged(summary) {
     this.emit('converged', summary);

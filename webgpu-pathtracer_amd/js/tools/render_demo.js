@@ -15,6 +15,9 @@
 //   --until <rmse>     sample until converged instead of a fixed count: renderer.renderUntil(scene, camera, rmse, { maxFrames: --frames })
 //                      with the moments image on; --min-frames N (16), --check-every N (the batch capacity), --no-lookahead.  Prints the
 //                      frames taken and the summary of the estimate under "until"
+//   --adaptive         with --until: renderUntil(..., { adaptive: true }) -- converged tiles stop being sampled (renderer.freezeConverged after every
+//                      check); --guard 0|1 (1): keep a converged tile sampling while one of its eight neighbours is not.  "until" gains `sampled`;
+//                      also writes <prefix>_mask.u8 (the final sample mask, one byte per 8 x 8 tile) and <prefix>_moments.f32
 //   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
 //   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
 //                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
@@ -73,7 +76,8 @@ async function main() {
   if (untilArg !== null) {
     const checkEvery = arg('check-every', null);
     until = renderer.renderUntil(scene, camera, parseFloat(untilArg), { maxFrames: frames, minFrames: parseInt(arg('min-frames', '16'), 10),
-      checkEvery: checkEvery === null ? undefined : parseInt(checkEvery, 10), lookahead: !process.argv.includes('--no-lookahead') });
+      checkEvery: checkEvery === null ? undefined : parseInt(checkEvery, 10), lookahead: !process.argv.includes('--no-lookahead'),
+      adaptive: process.argv.includes('--adaptive'), guard: parseInt(arg('guard', '1'), 10) });
     renderer.render(scene, camera);                                        // only presents
     console.error('--until ' + untilArg + ': ' + (until.converged ? 'converged' : 'not converged') + ' after ' + until.frames + ' of ' + frames + ' frames');
   } else {
@@ -121,6 +125,10 @@ async function main() {
     fs.writeFileSync(out + '_guided_variance.f32', Buffer.from(renderer.readGuidedVariance().buffer));
     fs.writeFileSync(out + '_moments.f32', Buffer.from(renderer.readMoments().buffer));
     renderer.screenshot(out + '_guided.png');
+  }
+  if (untilArg !== null && process.argv.includes('--adaptive')) {
+    fs.writeFileSync(out + '_mask.u8', Buffer.from(renderer.readSampleMask()));
+    fs.writeFileSync(out + '_moments.f32', Buffer.from(renderer.readMoments().buffer));
   }
   const summary = {
     width, height, frames, until, status: renderer.status, frame: renderer.frame, events,

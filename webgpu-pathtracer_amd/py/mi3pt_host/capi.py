@@ -57,6 +57,7 @@ SYMBOLS = (
     "mi3pt_denoise_guided", "mi3pt_read_guided", "mi3pt_guided_device_ptr",
     "mi3pt_set_moments", "mi3pt_read_moments", "mi3pt_write_moments", "mi3pt_moments_device_ptr", "mi3pt_read_guided_variance",
     "mi3pt_estimate_convergence", "mi3pt_read_convergence", "mi3pt_read_convergence_tiles",
+    "mi3pt_set_sample_mask", "mi3pt_read_sample_mask", "mi3pt_freeze_converged", "mi3pt_host_freeze_tiles",
 )
 
 
@@ -134,6 +135,10 @@ def load_library(path=None):
     lib.mi3pt_estimate_convergence.argtypes = [c_void_p, ctypes.c_float, c_int]
     lib.mi3pt_read_convergence.argtypes = [c_void_p, ctypes.POINTER(Convergence)]
     lib.mi3pt_read_convergence_tiles.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_set_sample_mask.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_read_sample_mask.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.POINTER(ctypes.c_uint32)]
+    lib.mi3pt_freeze_converged.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_uint32)]
+    lib.mi3pt_host_freeze_tiles.argtypes = [c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_void_p, ctypes.POINTER(ctypes.c_uint32)]
     lib.mi3pt_enable_timing.argtypes = [c_void_p, c_int]
     lib.mi3pt_pass_time_us.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]
     lib.mi3pt_raytrace_launch_stats.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
@@ -321,6 +326,22 @@ def host_route(rows):
     out = np.zeros((len(rows), len(ROUTE_OUTPUTS)), np.int64)
     _check(lib, lib.mi3pt_host_route(_ptr(rows), len(rows), _ptr(out)))
     return out
+
+
+def host_freeze_tiles(records, threshold, min_frames, guard=1, mask=None):
+    """The rule of adaptive sampling (include/mi3pt.h: mi3pt_host_freeze_tiles) on a (tiles_y, tiles_x, 4) tile map as
+    read_convergence_tiles returns it and a (tiles_y, tiles_x) mask (None: every tile sampled): (new mask as uint8, sampled tiles).
+    Plain host code, no device."""
+    lib = load_library()
+    rec = np.ascontiguousarray(records, np.float32)
+    if rec.ndim != 3 or rec.shape[2] != 4:
+        raise ValueError("records must be (tiles_y, tiles_x, 4)")
+    ty, tx = rec.shape[:2]
+    out = np.ones((ty, tx), np.uint8) if mask is None else (np.asarray(mask).reshape(ty, tx) != 0).astype(np.uint8)
+    out = np.ascontiguousarray(out)
+    n = ctypes.c_uint32()
+    _check(lib, lib.mi3pt_host_freeze_tiles(_ptr(rec), tx, ty, threshold, int(min_frames), int(guard), _ptr(out), ctypes.byref(n)))
+    return out, n.value
 
 
 def host_env_cdf(rgba):
@@ -563,6 +584,33 @@ class Context:
         out = np.empty(((self.local_rows + 7) // 8, (self.width + 7) // 8, 4), np.float32)
         self._c(self.lib.mi3pt_read_convergence_tiles(self.handle, _ptr(out), out.size))
         return out
+
+    def _mask_shape(self):
+        return ((self.local_rows + 7) // 8, (self.width + 7) // 8)
+
+    def set_sample_mask(self, mask):
+        """Adaptive sampling (include/mi3pt.h: mi3pt_set_sample_mask): one value per 8 x 8 tile of this rank's compact rows (a device
+        group: of the whole image), non-zero = sampled, zero = frozen; None removes the mask.  Frames queued so far run under the
+        old mask.  reset() and resize() drop it."""
+        if mask is None:
+            self._c(self.lib.mi3pt_set_sample_mask(self.handle, None, 0))
+            return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        self._c(self.lib.mi3pt_set_sample_mask(self.handle, _ptr(m), m.size))
+
+    def read_sample_mask(self):
+        """The sample mask as (tiles_y, tiles_x) uint8 of 0 / 1 (no mask: all 1)."""
+        out = np.empty(self._mask_shape(), np.uint8)
+        n = ctypes.c_uint32()
+        self._c(self.lib.mi3pt_read_sample_mask(self.handle, _ptr(out), out.size, ctypes.byref(n)))
+        return out
+
+    def freeze_converged(self, guard=1):
+        """Freeze the tiles the last estimate_convergence found under its threshold (guard 1: and whose eight neighbours are, too);
+        returns the number of tiles still sampled.  Waits for that estimate only."""
+        n = ctypes.c_uint32()
+        self._c(self.lib.mi3pt_freeze_converged(self.handle, int(guard), ctypes.byref(n)))
+        return n.value
 
     def bind_accumulation(self, dev_ptr, nbytes):
         self._c(self.lib.mi3pt_bind_accumulation(self.handle, dev_ptr, nbytes))

@@ -436,14 +436,38 @@ class Renderer:
     def isConverged(summary):
         return summary["tiles"] > 0 and summary["tiles_above"] == 0
 
-    def renderUntil(self, scene, camera, threshold, minFrames=16, maxFrames=None, checkEvery=None, lookahead=True):
+    # ---- adaptive sampling: stop sampling the tiles that have converged (include/mi3pt.h: mi3pt_set_sample_mask) ----
+    def setSampleMask(self, mask):
+        """One value per 8 x 8 tile (tiles_y, tiles_x), non-zero = sampled, zero = frozen: a frozen tile is neither traced nor
+        accumulated, its mean and moments keep their bits.  None removes the mask; reset() and resize() drop it."""
+        self.ctx.set_sample_mask(mask)
+
+    def readSampleMask(self):
+        """(tiles_y, tiles_x) uint8 of 0 / 1; without a mask all 1."""
+        return self.ctx.read_sample_mask()
+
+    def freezeConverged(self, guard=1):
+        """Freeze the tiles the last estimateConvergence found under its threshold -- with guard 1 only those whose up to eight
+        neighbours are under it too, which hides tile borders.  Never thaws.  Returns the number of tiles still sampled."""
+        return self.ctx.freeze_converged(guard)
+
+    def renderUntil(self, scene, camera, threshold, minFrames=16, maxFrames=None, checkEvery=None, lookahead=True, adaptive=False,
+                    guard=1):
         """render() until every 8 x 8 tile's estimated RMSE of the tone-mapped mean is at most `threshold` and has seen minFrames
         frames, or until maxFrames (None: self.frames, otherwise it becomes self.frames) are in the mean.  The mean is checked every
         checkEvery frames (None: the context's batch capacity, so launches keep one shape).  lookahead: the estimate of a chunk is
         read after the NEXT chunk has been flushed, so the device never idles while the host decides; the run then stops one chunk
         after the estimate that said converged, and those frames stay in the mean.  Without it the run stops at once.  The frame
         count at which it stops is a function of the images alone.  Returns {"converged", "frames", "summary"}; the summary is the
-        estimate that stopped the run, or, at the end of the budget, that of the final mean."""
+        estimate that stopped the run, or, at the end of the budget, that of the final mean.
+        adaptive: after every estimate that is read, freezeConverged(guard) stops sampling the tiles that are done; the run is
+        converged when no tile is sampled any more, i.e. every tile was under the threshold at the check that froze it.  With
+        lookahead the decision from estimate k is applied after chunk k + 1 has been flushed, so a tile is sampled one chunk longer.
+        The summary is then always that of an estimate of the FINAL image, and may show a tile above the threshold although the run
+        converged: with lookahead a tile is sampled one chunk beyond the estimate that found it under, and the estimate is not
+        monotone in the frames.  Such a tile stays frozen, and with guard 1 it keeps its neighbours sampling (the ring reads frozen
+        neighbours too): a run with lookahead and guard 1 can then last to maxFrames -- lookahead=False or guard=0 end it.  The result
+        gains "sampled": the tile-frames actually sampled."""
         if not self._moments:
             raise ValueError("renderUntil needs the moments image: setMoments(True) before sampling starts")
         if maxFrames is not None:
@@ -451,6 +475,8 @@ class Renderer:
         if checkEvery is None:
             checkEvery = self.ctx.batch_capacity()
         checkEvery = max(1, int(checkEvery))
+        if adaptive:
+            return self._renderUntilAdaptive(scene, camera, threshold, minFrames, checkEvery, lookahead, guard)
         pending = False          # an estimate has been enqueued and not read
         current = False          # `summary` is of the mean as it stands
         summary = None
@@ -478,6 +504,41 @@ class Renderer:
         if self.isConverged(summary):
             return self._converged(summary)
         return {"converged": False, "frames": self._frame - 1, "summary": summary}
+
+    def _renderUntilAdaptive(self, scene, camera, threshold, minFrames, checkEvery, lookahead, guard):
+        sampling = int(np.count_nonzero(self.ctx.read_sample_mask()))      # tiles the next chunk samples
+        sampled = 0              # tile-frames sampled so far
+        pending = False          # an estimate has been enqueued and not read
+        summary = None           # the summary of the mean as it stands, once read
+        done = False
+        while self.status == "sampling" and self.hasFramesToSample and not done:
+            n = min(checkEvery, self.frames - (self._frame - 1))
+            for _ in range(n):
+                self.render(scene, camera)
+            self.ctx.flush()
+            sampled += n * sampling
+            summary = None
+            if lookahead:
+                if pending:
+                    self.ctx.read_convergence()                # (the chunk just flushed runs while the host waits)
+                    pending = False
+                    sampling = self.ctx.freeze_converged(guard)
+                    done = sampling == 0
+                if not done:
+                    self.ctx.estimate_convergence(threshold, minFrames)
+                    pending = True
+            else:
+                self.ctx.estimate_convergence(threshold, minFrames)
+                summary = self.ctx.read_convergence()
+                sampling = self.ctx.freeze_converged(guard)
+                done = sampling == 0
+        if summary is None:      # the result describes the final mean
+            if not pending:
+                self.ctx.estimate_convergence(threshold, minFrames)
+            summary = self.ctx.read_convergence()
+        out = self._converged(summary) if done else {"converged": False, "frames": self._frame - 1, "summary": summary}
+        out["sampled"] = sampled
+        return out
 
     def _converged(self, summary):
         self.emit("converged", summary)
