@@ -27,8 +27,8 @@
  *     caller's (mi3pt_set_stream) -- and everything that can be observed happens in that stream's order; the raytrace
  *     kernels run on internal streams tied to it by events in both directions, which no caller can see.
  *     STREAM ORDERED, returning before the device has run anything: mi3pt_submit, mi3pt_submit_frames, mi3pt_flush,
- *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided, mi3pt_estimate_convergence, mi3pt_set_sample_mask (it
- *     launches the frame queue, under the old mask, and waits for nothing).  mi3pt_set_uniforms, the setters of
+ *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided, mi3pt_estimate_convergence, mi3pt_reproject,
+ *     mi3pt_set_mean_by_count, mi3pt_set_sample_mask (it launches the frame queue, under the old mask, and waits for nothing).  mi3pt_set_uniforms, the setters of
  *     modes and options and the *_device_ptr getters start no device work of their own (those that observe state launch
  *     the frame queue first).  A host that has set its own stream may therefore enqueue its work in front of and behind
  *     these calls on that stream -- fill a bound accumulation tensor, copy out of a *_device_ptr image -- and wait once.
@@ -70,7 +70,8 @@ extern "C" {
  * mi3pt_render_aovs, mi3pt_read_aov, mi3pt_aov_device_ptr, enum mi3pt_aov, MI3PT_PASS_AOV (3); mi3pt_denoise_guided, mi3pt_read_guided,
  * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4); mi3pt_estimate_convergence,
  * mi3pt_read_convergence, mi3pt_read_convergence_tiles, struct mi3pt_convergence, MI3PT_PASS_CONVERGENCE (5); mi3pt_set_sample_mask,
- * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles. */
+ * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles; mi3pt_set_mean_by_count, mi3pt_host_view_frame, mi3pt_reproject,
+ * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6). */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -100,8 +101,10 @@ typedef enum mi3pt_pass {
                                     mi3pt_pass_time_us only; it has no uniform block (mi3pt_set_uniforms refuses it) */
     MI3PT_PASS_GUIDED = 4,       /* -- no counterpart: the feature-guided de-noise (mi3pt_denoise_guided), pack kernel and every level.
                                     Known to mi3pt_pass_time_us only */
-    MI3PT_PASS_CONVERGENCE = 5   /* -- no counterpart: the per-tile error estimate (mi3pt_estimate_convergence), its tile kernel and the
+    MI3PT_PASS_CONVERGENCE = 5,  /* -- no counterpart: the per-tile error estimate (mi3pt_estimate_convergence), its tile kernel and the
                                     kernel that folds the summary.  Known to mi3pt_pass_time_us only */
+    MI3PT_PASS_REPROJECT = 6     /* -- no counterpart: the gather kernel of mi3pt_reproject and the copy into a bound accumulation image (the
+                                    feature render inside that call is MI3PT_PASS_AOV's).  Known to mi3pt_pass_time_us only */
 } mi3pt_pass;
 
 #define MI3PT_SUBMIT_RAYTRACE 1u
@@ -497,7 +500,7 @@ int mi3pt_read_convergence_tiles(mi3pt_ctx *ctx, float *dst, size_t nfloats);  /
  * block's `frame` as always.  Hence, if tiles are only ever frozen between resets, every texel equals, bit for bit, the unmasked run's
  * texel after the last frame its tile was sampled in -- mean and moments, F32 and F16 storage, a bound image.  A tile that is thawed
  * again continues with the uniform's weight 1 / frame although it has seen fewer samples: the result is then the law's weighted mean,
- * NOT the sample mean.  The hosts only ever freeze.
+ * NOT the sample mean (under mi3pt_set_mean_by_count it continues as a sample mean).  The hosts only ever freeze.
  * What the mask saves: queued RAYTRACE | ACCUMULATE frames trace only the sampled tiles wherever the launch can take a tile list (the
  * state-machine kernel's lean build of variants 9 - 14, without a cost order); the view's empty tiles among them are shaded by the
  * streaming sky kernel as without a mask.  There MI3PT_CNT pixels, rays and misses count the sampled tiles' in-bounds pixels only and
@@ -535,6 +538,100 @@ int mi3pt_read_sample_mask(mi3pt_ctx *ctx, uint8_t *dst, size_t ntiles, uint32_t
 int mi3pt_freeze_converged(mi3pt_ctx *ctx, int guard, uint32_t *sampled_out);
 int mi3pt_host_freeze_tiles(const float *records, int tiles_x, int tiles_y, float threshold, int min_frames,
                             int guard, uint8_t *mask_inout, uint32_t *sampled_out);   /* plain host C++, no device */
+
+/* ---- the mean by count: a running mean whose weight comes from the texel's OWN sample count -- no counterpart in the reference, whose
+ * weight is 1 / frame for every texel (accumulate.wgsl:18-28).  Off by default; a context that never enables it launches exactly what it
+ * launched before (the two existing instantiations of each accumulate kernel are untouched; the mode runs a third).  Needs the moments
+ * image, whose n IS the count: MI3PT_ERR_STATE while mi3pt_set_moments is off, and mi3pt_set_moments(ctx, 0) switches the mode off too.
+ * Both calls launch the frame queue first (queued frames accumulate under the law they were submitted under).
+ * While the mode is on, EVERY accumulate step of a texel inside the accumulate block's rectangle -- queued frames, the immediate path of
+ * mi3pt_submit, an ACCUMULATE-only submit, with and without a sample mask -- is, with p the mean, (M2, n) the moments texel, c the
+ * radiance, fp32, nothing contracted, the division correctly rounded:
+ *   restart = (enabled != 1) || !(n >= 1.0f)              a NaN, zero or negative n restarts
+ *   weight  = restart ? 1.0f : 1.0f / (n + 1.0f)
+ *   p'      = the stored mix(p, c, weight) = p * (1 - weight) + c * weight, rounded to binary16 under MI3PT_STORAGE_F16 -- as always
+ *   restart:   M2.k = 0;   n = 1
+ *   otherwise: M2.k = M2.k + (c.k - p.k) * (c.k - p'.k);   n = n + 1
+ * The accumulate block's `frame` does not enter the step (the raytrace block's `frame` still seeds the samples).  Hence:
+ *   - after mi3pt_reset (n = 0 everywhere) N steps give the SAMPLE MEAN, bit-identical -- mean and moments, F32 and F16 storage -- to
+ *     the default law run with the accumulate `frame` = 1, 2, ..., N;
+ *   - a tile that is frozen by a sample mask and thawed again continues as a sample mean (the default law does not, see above);
+ *   - mi3pt_write_texture and mi3pt_bind_accumulation zero the moments, so the next step RESTARTS every texel from the frame's radiance:
+ *     follow them with mi3pt_write_moments to resume a checkpoint;
+ *   - both hosts start their accumulate `frame` at 2 (renderer.ts:369-377), so their default mean after N frames is N / (N + 1) of the
+ *     sample mean (the first step mixes with the zeroed image at weight 1 / 2); a by-count image is BRIGHTER by (N + 1) / N.
+ * The per-pixel kernel variants (1 / 2) run their two passes unfused, as they do whenever moments are on.  Tile split: the step is
+ * pointwise.  Device group: the call goes to every member. ---- */
+int mi3pt_set_mean_by_count(mi3pt_ctx *ctx, int enabled);                  /* default 0 */
+
+/* ---- reprojection: carry the running mean and its moments across a camera move -- no counterpart in the reference, whose hosts reset
+ * on every camera change (renderer.ts:397-416).  The temporal half of SVGF (Schied et al. 2017): every texel of the NEW view looks its
+ * first hit's world point up in the OLD view's images and takes over mean, variance and sample count where the old view saw the same
+ * surface.  The scene is taken as STATIC between the two views; uploads in between are not detected (taps are then rejected or carry
+ * stale radiance; nothing faults).
+ * mi3pt_host_view_frame (plain host C++, no device): the camera frame the reprojection projects with, from a 96-byte raytrace block,
+ * computed in double from the block's fp32 fields, each output rounded to fp32 once:
+ *   w = normalize(-direction);  up = (0,1,0), or (0,0,1) when |w.y| > 0.99999;  u = normalize(cross(up, w));  v = cross(w, u)
+ *   t = tan(fov * pi / 360);  r = aspect * t;  fwd = -w
+ *   out = position.xyz, aspect,  fwd.xyz, t,  u.xyz, r,  v.xyz, 0
+ * (cameraToRay's frame, raytrace.wgsl:217-236; it need not equal the ray generator's fp32 frame bit for bit -- an ulp of t moves a
+ * reprojected coordinate by 1e-6 texels -- it is an INPUT of the pinned arithmetic below.)  MI3PT_ERR_INVALID for a wrong nbytes, a
+ * null pointer, a zero or non-finite direction, a fov outside (0, 180), a non-finite position.
+ * State: the context remembers the raytrace block each feature image was rendered from.  The OLD view U0 is the block of POSITION,
+ * NORMAL and IDS as they stand -- the caller rendered them in the view the mean was sampled in; the NEW view U1 is the raytrace block
+ * at the call.  mi3pt_reproject, in order:
+ *   1 launches the frame queue;  2 F0 = mi3pt_host_view_frame(U0);  3 makes the three old feature images the "previous set" (a swap of
+ *   pointers with a second set of three images, allocated by the first call and freed by mi3pt_resize / mi3pt_destroy);  4 renders all
+ *   four feature images from U1 exactly as mi3pt_render_aovs(ctx, 15) -- the de-noiser finds them current;  5 runs the kernel below from
+ *   (A, M) = (accumulation image, moments image) into a scratch pair;  6 makes the scratch pair the accumulation and moments images: a
+ *   swap of pointers where the image is the context's own, a copy on the stream into memory bound by mi3pt_bind_accumulation;  7 drops
+ *   the sample mask, as mi3pt_reset does.
+ * Asynchronous and stream ordered.  It changes no counter and nothing mi3pt_debug_last_launch / MI3PT_OPT_LAST_BUILD report.  Because
+ * of the swaps, pointers handed out earlier by mi3pt_accumulation_device_ptr (of the context's own image), mi3pt_moments_device_ptr and
+ * mi3pt_aov_device_ptr name other images afterwards: ask again.
+ * The kernel.  Pinned fp32: dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, correctly rounded division, nothing contracted.  Index 1: the new
+ * features, index 0: the previous set; hit = word 2 of IDS, mat = word 1.  For every texel p = (x, y) of the image inside the
+ * accumulate block's rectangle:
+ *   carry needs hit1(p) == 1;   P = POSITION1(p).xyz;  t1 = POSITION1(p).w;  N = NORMAL1(p).xyz
+ *   d = P - F0.position;  a = dot(d, F0.u);  b = dot(d, F0.v);  cz = dot(d, F0.fwd);      needs cz > 0
+ *   k = F0.aspect / cz;   uvx = (a * k + F0.r) / (F0.r + F0.r);   uvy = (b * k + F0.t) / (F0.t + F0.t)
+ *   fx = uvx * U0.resolution.x;  fy = uvy * U0.resolution.y;   needs fx > -1 && fx < width && fy > -1 && fy < rows   (a NaN fails)
+ *   x0 = floorf(fx);  tx = fx - x0;  wx = [1 - tx, tx];   y0, ty, wy likewise
+ *   taps q = (x0 + i, y0 + j), j = 0, 1 outer, i = 0, 1 inner, bw = wx[i] * wy[j].  A tap COUNTS iff
+ *       q lies inside the rectangle and the image,  bw > 0,  hit0(q) == 1,  mat0(q) == mat1(p),
+ *       n0 = M(q).w >= 1                       (a NaN does not count)
+ *       dot(N, NORMAL0(q).xyz) >= normal_cos_min
+ *       fabsf(dot(N, POSITION0(q).xyz - P)) <= plane_tolerance * t1
+ *     for each that counts, in that order:
+ *       ws = ws + bw;   col.k = col.k + bw * A(q).k;   nmin = fminf(nmin, n0)       (ws, col, var start at 0, nmin at +inf)
+ *       var.k = var.k + bw * (n0 >= 2 ? fmaxf(M2(q).k / (n0 - 1), 0) : 0)
+ *   carried (ws > 0):   n' = fminf(nmin, (float)max_history)
+ *                       A'(p) = (stored col.k / ws, 1)                 (rounded to binary16 under MI3PT_STORAGE_F16)
+ *                       M'(p) = ((var.k / ws) * (n' - 1), n')
+ *   restarted (a "needs" failed, or no tap counted):   A'(p) = (0, 0, 0, 1);   M'(p) = (0, 0, 0, 0)
+ * Texels outside the rectangle keep their bits.  The cap by max_history keeps the per-sample variance and shortens the history: new
+ * samples then take over from reprojected ones, which are exact for diffuse surfaces and biased for glossy ones (their radiance
+ * depends on the direction they are seen from).  Misses restart: a texel that sees the environment directly has next to no variance.
+ * Non-finite inputs give unspecified values; every index is range-checked before it is used, so they neither hang nor fault.  The
+ * un-jittered pinhole ray defines the features: with aperture > 0 the carried mean is that of the in-focus surface.
+ * Afterwards everything works in the new view unchanged: under mi3pt_set_mean_by_count sampling continues per texel -- a restarted texel
+ * (n = 0) takes its first frame at weight 1 --, mi3pt_estimate_convergence sees disoccluded tiles as young, MI3PT_GUIDED_VARIANCE filters
+ * with the carried variance.
+ *   MI3PT_ERR_STATE before mi3pt_resize; while moments or the mean by count are off; unless POSITION, NORMAL and IDS have all been
+ *   rendered since the last resize, from blocks whose resolution, aspect and camera fields are bitwise equal; unless U1's resolution
+ *   equals U0's bitwise; for a rank of a tile split with more than one rank and for a device group (taps cross rows; the halo exchange
+ *   is NOT BUILT).  MI3PT_ERR_INVALID for a null pointer, a plane_tolerance that is negative or not finite, normal_cos_min outside
+ *   [-1, 1], max_history outside 1 .. 2^24, non-zero flags.
+ * With timing enabled, mi3pt_pass_time_us(MI3PT_PASS_REPROJECT) is the device time of the kernel and the copy of the most recent call;
+ * the feature render inside it is timed as MI3PT_PASS_AOV. ---- */
+typedef struct mi3pt_reproject_params {
+    float plane_tolerance;   /* finite, >= 0; relative to the new texel's hit distance */
+    float normal_cos_min;    /* in [-1, 1] */
+    int   max_history;       /* 1 .. 2^24 */
+    unsigned flags;          /* 0 */
+} mi3pt_reproject_params;
+int mi3pt_host_view_frame(const void *raytrace_uniforms, size_t nbytes, float out[16]);   /* plain host C++, no device */
+int mi3pt_reproject(mi3pt_ctx *ctx, const mi3pt_reproject_params *params);
 
 /* ---- read-back (the capability a headless drop-in needs; the reference only has
  * canvas.toDataURL, main.ts:351-356).  Blocking.  dst holds rows x width x 4 floats

@@ -50,4 +50,32 @@ PT_DEV float4 moments_step(const AccUniforms &acc, f3 c, f3 p, f3 pn, float4 m)
     return make_float4(m.x + (c.x - p.x) * (c.x - pn.x), m.y + (c.y - p.y) * (c.y - pn.y), m.z + (c.z - p.z) * (c.z - pn.z), m.w + 1.0f);
 }
 
+// The mean BY COUNT (include/mi3pt.h: mi3pt_set_mean_by_count): the twins of the two functions above whose weight comes from the
+// texel's own sample count n (the moments texel's w) instead of the block's `frame`.  A texel without history -- n NaN, zero or
+// negative -- restarts like a step of weight 1; for n = frame - 1 the quotient and the restart are the default law's, bit for bit.
+PT_DEV bool count_restarts(const AccUniforms &acc, float n) { return acc.enabled != 1u || !(n >= 1.0f); }
+
+PT_DEV f3 accumulate_texel_by_count(const AccUniforms &acc, f3 color, f3 prev, float n)
+{
+    const float weight = count_restarts(acc, n) ? 1.0f : 1.0f / (n + 1.0f);
+    return mix(prev, color, weight);
+}
+
+PT_DEV float4 moments_step_by_count(const AccUniforms &acc, f3 c, f3 p, f3 pn, float4 m)
+{
+    if (count_restarts(acc, m.w)) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    return make_float4(m.x + (c.x - p.x) * (c.x - pn.x), m.y + (c.y - p.y) * (c.y - pn.y), m.z + (c.z - p.z) * (c.z - pn.z), m.w + 1.0f);
+}
+
+// one accumulate step of a texel: the mean p and, with MOMENTS, its moments texel m; BY_COUNT (needs MOMENTS) takes the weight from m.w
+template <bool MOMENTS, bool BY_COUNT>
+PT_DEV void mean_step(const AccUniforms &a, f3 c, f3 &p, float4 &m, int store_f16)
+{
+    static_assert(MOMENTS || !BY_COUNT, "the count is the moments texel's");
+    const f3 nc = BY_COUNT ? accumulate_texel_by_count(a, c, p, m.w) : accumulate_texel(a, c, p);
+    const f3 pn = F3(store_round(nc.x, store_f16), store_round(nc.y, store_f16), store_round(nc.z, store_f16));
+    if (MOMENTS) m = BY_COUNT ? moments_step_by_count(a, c, p, pn, m) : moments_step(a, c, p, pn, m);
+    p = pn;
+}
+
 }  // namespace pt

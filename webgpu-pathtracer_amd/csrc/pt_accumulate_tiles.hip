@@ -2,7 +2,7 @@
 //
 // k_accumulate_frames (pt_kernels.hip) walks the whole image; under a sample mask the mean of a frozen tile must keep its bits and the
 // pass's work must fall with the sampled tiles, so this kernel steps the listed tiles only.  The arithmetic of a texel is that kernel's,
-// function for function (pt_accum.h: accumulate_texel, store_round, moments_step; frame order, the weight from the block's `frame`), and
+// function for function (pt_accum.h: mean_step; frame order, the weight from the block's `frame` -- or, <true, true>, from the texel's count), and
 // so are its tests, in its order: inside the image, the image row of the local row, the accumulate block's rectangle.
 //
 // pt_converge.hip's shape: one wave per listed tile, lane j = 8 * (row in tile) + (column in tile), so a lane's loads and stores are 16 B
@@ -18,19 +18,15 @@ namespace pt {
 
 constexpr int AT_WAVES = 4, AT_UNROLL = 4;
 
-template <bool MOMENTS>
-PT_DEV void mean_step(const AccUniforms &acc0, int k, const float4 &slot, f3 &p, float4 &m, int store_f16)
+template <bool MOMENTS, bool BY_COUNT>
+PT_DEV void mean_step_k(const AccUniforms &acc0, int k, const float4 &slot, f3 &p, float4 &m, int store_f16)
 {
     AccUniforms a = acc0;
     a.frame = acc0.frame + (uint32_t)k;
-    const f3 c = xyz(slot);
-    const f3 nc = accumulate_texel(a, c, p);
-    const f3 pn = F3(store_round(nc.x, store_f16), store_round(nc.y, store_f16), store_round(nc.z, store_f16));
-    if (MOMENTS) m = moments_step(a, c, p, pn, m);
-    p = pn;
+    mean_step<MOMENTS, BY_COUNT>(a, xyz(slot), p, m, store_f16);
 }
 
-template <bool MOMENTS>
+template <bool MOMENTS, bool BY_COUNT = false>
 __global__ void __launch_bounds__(256) k_accumulate_tiles(const AccUniforms acc0, const Tile tile, const uint32_t *__restrict__ list,
                                                           const uint32_t ntiles, const float4 *__restrict__ slots, const size_t slot_pixels,
                                                           const int nframes, float4 *__restrict__ accum, float4 *__restrict__ moments,
@@ -58,19 +54,22 @@ __global__ void __launch_bounds__(256) k_accumulate_tiles(const AccUniforms acc0
 #pragma unroll
         for (int j = 0; j < AT_UNROLL; j++) c[j] = s[(size_t)(k + j) * slot_pixels];
 #pragma unroll
-        for (int j = 0; j < AT_UNROLL; j++) mean_step<MOMENTS>(acc0, k + j, c[j], p, m, store_f16);
+        for (int j = 0; j < AT_UNROLL; j++) mean_step_k<MOMENTS, BY_COUNT>(acc0, k + j, c[j], p, m, store_f16);
     }
-    for (; k < nframes; k++) mean_step<MOMENTS>(acc0, k, s[(size_t)k * slot_pixels], p, m, store_f16);
+    for (; k < nframes; k++) mean_step_k<MOMENTS, BY_COUNT>(acc0, k, s[(size_t)k * slot_pixels], p, m, store_f16);
     accum[i] = make_float4(p.x, p.y, p.z, 1.0f);
     if (MOMENTS) moments[i] = m;
 }
 
 void launch_accumulate_tiles(const AccUniforms &acc0, const Tile &tile, const uint32_t *list, int ntiles, const float4 *slots,
-                             size_t slot_pixels, int nframes, float4 *accum, float4 *moments, int store_f16, hipStream_t s)
+                             size_t slot_pixels, int nframes, float4 *accum, float4 *moments, int store_f16, bool by_count, hipStream_t s)
 {
     if (ntiles <= 0 || nframes <= 0 || !list || tile.local_rows <= 0 || tile.tex_w <= 0) return;
     const unsigned blocks = ((unsigned)ntiles + AT_WAVES - 1) / AT_WAVES;      // (at most 4096 x 4096 / 4 tiles: the grid is never capped)
-    if (moments)
+    if (moments && by_count)      // (the mean by count: mi3pt_set_mean_by_count)
+        hipLaunchKernelGGL((k_accumulate_tiles<true, true>), dim3(blocks), dim3(256), 0, s, acc0, tile, list, (uint32_t)ntiles, slots, slot_pixels, nframes,
+                           accum, moments, store_f16);
+    else if (moments)
         hipLaunchKernelGGL(k_accumulate_tiles<true>, dim3(blocks), dim3(256), 0, s, acc0, tile, list, (uint32_t)ntiles, slots, slot_pixels, nframes,
                            accum, moments, store_f16);
     else

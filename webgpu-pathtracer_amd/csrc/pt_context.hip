@@ -329,6 +329,15 @@ struct mi3pt_ctx {
     bool moments = false;
     bool moments_opted = false;          // mi3pt_set_moments(1) has been called: until then MI3PT_GUIDED_VARIANCE is an unknown flag bit, as it was before the image existed
     float4 *d_moments = nullptr;
+    // The mean by count (mi3pt_set_mean_by_count): the accumulate kernels' by-count twins take a step's weight from the moments texel's n
+    bool by_count = false;
+    // The reprojection (mi3pt_reproject; pt_reproject.hip).  aov_u: the raytrace block each feature image was rendered from; d_aov_prev:
+    // the old view's NORMAL / POSITION / IDS (indexed by mi3pt_aov; pointers swapped with d_aov), d_reproject: the scratch (mean, moments)
+    // the kernel writes -- all allocated by the first call and freed with the textures.
+    uint8_t aov_u[MI3PT_AOV_COUNT][MI3PT_RAYTRACE_UNIFORMS_SIZE] = {};
+    float4 *d_aov_prev[MI3PT_AOV_COUNT] = {};
+    float4 *d_reproject[2] = {};
+    PassTimer reproject_timer;
     // The per-tile error estimate (mi3pt_estimate_convergence; pt_converge.hip): the tile map ceil(local_rows / 8) x ceil(width / 8) x 16 B,
     // the tile kernel's per-block records and the summary on the device, the summary's copy in pinned host memory, all allocated by the
     // first call and freed with the textures; conv_done: recorded behind the copy of the most recent estimate -- what the two reads wait for, and nothing else.
@@ -781,6 +790,9 @@ static void free_textures(mi3pt_ctx *ctx)
     ctx->d_guided_var[0] = ctx->d_guided_var[1] = nullptr;
     ctx->guided_var_result = nullptr;
     ctx->d_moments = nullptr;
+    for (float4 *&p : ctx->d_aov_prev) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float4 *&p : ctx->d_reproject) { if (p) (void)hipFree(p); p = nullptr; }
+    ctx->reproject_timer.forget();
     if (ctx->d_conv_tiles) (void)hipFree(ctx->d_conv_tiles);
     if (ctx->d_conv_parts) (void)hipFree(ctx->d_conv_parts);
     if (ctx->d_conv_summary) (void)hipFree(ctx->d_conv_summary);
@@ -818,7 +830,7 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     for (void *p : { ctx->d_cw8, ctx->d_tripk8, ctx->d_cwide, ctx->d_tripk64, ctx->d_wide, ctx->d_tris, ctx->d_tris_perm, ctx->d_nodes, ctx->d_mats, ctx->d_env, ctx->d_cdf, ctx->d_packets, ctx->d_tripk, ctx->d_leaf_rank,
                      (void *)ctx->d_tile_counter, (void *)ctx->d_drain_flag, (void *)ctx->d_wave_times, (void *)ctx->d_stack_overflow, (void *)ctx->d_park, (void *)ctx->d_service, ctx->d_fs_taps })
         if (p) (void)hipFree(p);
-    for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer, &ctx->conv_timer }) t->destroy();
+    for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer, &ctx->conv_timer, &ctx->reproject_timer }) t->destroy();
     if (ctx->conv_read_stream) {
         (void)hipStreamSynchronize(ctx->conv_read_stream);
         (void)hipStreamDestroy(ctx->conv_read_stream);
@@ -2176,9 +2188,9 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
         if (ctx->timing && last_run) HIP_TRY(ctx->pass_timer[1].begin(ctx->stream));
         if (masked) {        // the sampled tiles only: a frozen tile's mean and moments keep their bits
             pt::launch_accumulate_tiles(a, L.tile, acc_list, acc_count, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum,
-                                        ctx->d_moments, f16, ctx->stream);
+                                        ctx->d_moments, f16, ctx->by_count, ctx->stream);
         } else {
-            pt::launch_accumulate_frames(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, ctx->d_moments, f16, 4096, ctx->stream);
+            pt::launch_accumulate_frames(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, ctx->d_moments, f16, ctx->by_count, 4096, ctx->stream);
         }
         HIP_TRY(hipGetLastError());
         if (ctx->timing && last_run) HIP_TRY(ctx->pass_timer[1].end(ctx->stream));
@@ -2327,11 +2339,11 @@ extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
             const uint32_t *list = nullptr;
             int count = 0;
             if (int rc = mask_list_main(ctx, tile, &list, &count)) return rc;
-            pt::launch_accumulate_tiles(acc, tile, list, count, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, ctx->stream);
+            pt::launch_accumulate_tiles(acc, tile, list, count, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, ctx->by_count, ctx->stream);
             if (count)
                 if (int rc = mask_list_used(ctx, 2)) return rc;
         } else {
-            pt::launch_accumulate_frames(acc, tile, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, 2048, ctx->stream);
+            pt::launch_accumulate_frames(acc, tile, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, ctx->by_count, 2048, ctx->stream);
         }
         HIP_TRY(hipGetLastError());
         if (ctx->timing) HIP_TRY(ctx->pass_timer[1].end(ctx->stream));
@@ -2572,7 +2584,10 @@ extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
         if (ctx->timing) HIP_TRY(ctx->aov_timer.end(ctx->stream));
     }
     for (int k = 0; k < MI3PT_AOV_COUNT; k++)
-        if ((aov_mask >> k) & 1u) ctx->aov_valid[k] = true;
+        if ((aov_mask >> k) & 1u) {
+            ctx->aov_valid[k] = true;
+            std::memcpy(ctx->aov_u[k], ctx->u_rt, sizeof ctx->u_rt);      // (the view this image belongs to: mi3pt_reproject's old view)
+        }
     return MI3PT_OK;
 }
 
@@ -2732,6 +2747,7 @@ extern "C" int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled)
         if (ctx->d_moments) (void)hipFree(ctx->d_moments);
         ctx->d_moments = nullptr;
         ctx->moments = false;
+        ctx->by_count = false;      // (the count is the image's n: the mode goes with it)
         return MI3PT_OK;
     }
     if (ctx->width != 0) {
@@ -2791,6 +2807,86 @@ extern "C" int mi3pt_moments_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *
     if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = moments_image(ctx, "mi3pt_moments_device_ptr")) return rc;
     return hand_out_plane(ctx, ctx->d_moments, dev_ptr, nbytes);
+}
+
+// ---- the mean by count and the reprojection (include/mi3pt.h: mi3pt_set_mean_by_count, mi3pt_reproject; pt_accum.h, pt_reproject.hip) ----
+extern "C" int mi3pt_set_mean_by_count(mi3pt_ctx *ctx, int enabled)
+{
+    PT_GROUP_ALL(ctx, false, mi3pt_set_mean_by_count(m, enabled));
+    if (int rc = require_idle(ctx)) return rc;      // the frames queued so far were submitted under the old law
+    if (enabled && !ctx->moments)
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_set_mean_by_count needs the moments image: the count is its n (mi3pt_set_moments(ctx, 1) first)");
+    ctx->by_count = enabled != 0;
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_reproject(mi3pt_ctx *ctx, const mi3pt_reproject_params *params)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_reproject: not built for a device group (a tap crosses the members' rows; no halo exchange)"));
+    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (!(params->plane_tolerance >= 0.0f) || std::isinf(params->plane_tolerance))
+        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_reproject: plane_tolerance must be finite and >= 0");
+    if (!(params->normal_cos_min >= -1.0f && params->normal_cos_min <= 1.0f))
+        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_reproject: normal_cos_min must lie in [-1, 1]");
+    if (params->max_history < 1 || params->max_history > (1 << 24)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_reproject: max_history must be 1 .. 2^24");
+    if (params->flags) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_reproject: unknown flag bits");
+    if (int rc = require_ctx(ctx)) return rc;
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject before resize");
+    if (!ctx->moments || !ctx->d_moments || !ctx->by_count)
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject needs the moments image and the mean by count (mi3pt_set_moments, mi3pt_set_mean_by_count)");
+    if (ctx->partial())
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject: not built for a rank of a tile split (a tap crosses the ranks' rows; no halo exchange)");
+    static const int old_set[3] = { MI3PT_AOV_POSITION, MI3PT_AOV_NORMAL, MI3PT_AOV_IDS };
+    const uint8_t *u0 = ctx->aov_u[MI3PT_AOV_POSITION];
+    for (int k : old_set) {
+        if (!ctx->aov_valid[k] || !ctx->d_aov[k])
+            return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject: the POSITION, NORMAL and IDS images of the old view have not been rendered since the last resize (mi3pt_render_aovs)");
+        // (resolution and aspect; camera position, direction and fov: what the first hit depends on)
+        if (std::memcmp(ctx->aov_u[k], u0, 12) || std::memcmp(ctx->aov_u[k] + 32, u0 + 32, 32))
+            return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject: the POSITION, NORMAL and IDS images were rendered from different views");
+    }
+    if (std::memcmp(ctx->u_rt, u0, 8))
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject: the new view's resolution differs from the old view's");
+    if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far belongs to the old view's mean
+    pt::ReprojectLaunch R;
+    if (int rc = mi3pt_host_view_frame(u0, MI3PT_RAYTRACE_UNIFORMS_SIZE, R.f0)) return rc;
+    R.res0_x = ldf(u0, 0); R.res0_y = ldf(u0, 4);
+    const size_t tex_bytes = plane_bytes(ctx);
+    for (int k : old_set)
+        if (!ctx->d_aov_prev[k]) HIP_TRY(alloc_plane(&ctx->d_aov_prev[k], tex_bytes));
+    for (float4 *&p : ctx->d_reproject)
+        if (!p) HIP_TRY(alloc_plane(&p, tex_bytes));
+    // the old features become the previous set; the new view's are rendered into the images the set before it held
+    for (int k : old_set) std::swap(ctx->d_aov[k], ctx->d_aov_prev[k]);
+    if (int rc = mi3pt_render_aovs(ctx, (1u << MI3PT_AOV_COUNT) - 1u)) {
+        for (int k : old_set) std::swap(ctx->d_aov[k], ctx->d_aov_prev[k]);      // (nothing was rendered: the old view's images stand)
+        return rc;
+    }
+    const pt::AccUniforms acc = acc_uniforms(ctx);
+    R.accum = ctx->d_accum; R.moments = ctx->d_moments;
+    R.accum_out = ctx->d_reproject[0]; R.moments_out = ctx->d_reproject[1];
+    R.pos1 = ctx->d_aov[MI3PT_AOV_POSITION]; R.nrm1 = ctx->d_aov[MI3PT_AOV_NORMAL]; R.ids1 = ctx->d_aov[MI3PT_AOV_IDS];
+    R.pos0 = ctx->d_aov_prev[MI3PT_AOV_POSITION]; R.nrm0 = ctx->d_aov_prev[MI3PT_AOV_NORMAL]; R.ids0 = ctx->d_aov_prev[MI3PT_AOV_IDS];
+    R.width = ctx->width; R.rows = ctx->local_rows;
+    R.res_w = acc.res_w; R.res_h = acc.res_h;
+    R.plane_tolerance = params->plane_tolerance; R.normal_cos_min = params->normal_cos_min; R.max_history = (float)params->max_history;
+    R.store_f16 = ctx->storage == MI3PT_STORAGE_F16;
+    if (ctx->timing) HIP_TRY(ctx->reproject_timer.begin(ctx->stream));
+    pt::launch_reproject(R, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    // the scratch pair takes the images' place: the context's own by a swap of pointers, a bound accumulation image by a copy on the stream
+    std::swap(ctx->d_moments, ctx->d_reproject[1]);
+    if (ctx->d_accum == ctx->d_accum_own) {
+        std::swap(ctx->d_accum_own, ctx->d_reproject[0]);
+        ctx->d_accum = ctx->d_accum_own;
+    } else if (tex_bytes) {
+        HIP_TRY(hipMemcpyAsync(ctx->d_accum, ctx->d_reproject[0], tex_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (ctx->timing) HIP_TRY(ctx->reproject_timer.end(ctx->stream));
+    drop_sample_mask(ctx);          // a new view starts whole
+    ctx->main_dirty = true;
+    ctx->accum_version++;
+    return MI3PT_OK;
 }
 
 // ---- the per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip) ----
@@ -2951,6 +3047,7 @@ extern "C" int mi3pt_pass_time_us(mi3pt_ctx *ctx, int pass, float *microseconds)
     if (int rc = require_idle(ctx)) return rc;
     if (microseconds && pass == MI3PT_PASS_AOV) return ctx->aov_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_render_aovs since the last resize");
     if (microseconds && pass == MI3PT_PASS_GUIDED) return ctx->guided_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_denoise_guided since the last resize");
+    if (microseconds && pass == MI3PT_PASS_REPROJECT) return ctx->reproject_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_reproject since the last resize");
     if (microseconds && pass == MI3PT_PASS_CONVERGENCE) return ctx->conv_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_estimate_convergence since the last resize");
     if (!microseconds || pass < 0 || pass > 2) return pt_set_error(MI3PT_ERR_INVALID, "bad argument");
     if (pass == MI3PT_PASS_RAYTRACE && !ctx->pass_timer[0].recorded && (ctx->ev_rt_pending[0] || ctx->ev_rt_pending[1] || ctx->rt_launches)) {

@@ -378,13 +378,14 @@ void launch_raytrace(const RtLaunch &L, const RtRoute &r, bool fuse_accumulate, 
 // fills `out` (tile.local_rows x tile.tex_w float4) for RtLaunch::cam_base from L.un / L.tile
 void launch_camera_base(const RtLaunch &L, float4 *out, hipStream_t s);
 // the running mean over nframes consecutive radiance slots (one frame: nframes 1, slot_pixels unused), at most max_blocks blocks of 256;
-// moments: null, or the moments image (local_rows x width float4: M2.rgb, n; include/mi3pt.h: mi3pt_set_moments) kept beside the mean
+// moments: null, or the moments image (local_rows x width float4: M2.rgb, n; include/mi3pt.h: mi3pt_set_moments) kept beside the mean;
+// by_count (with moments only): the weight of a step from the texel's n instead of the block's `frame` (mi3pt_set_mean_by_count)
 void launch_accumulate_frames(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels, int nframes,
-                              float4 *accum, float4 *moments, int store_f16, int max_blocks, hipStream_t s);
+                              float4 *accum, float4 *moments, int store_f16, bool by_count, int max_blocks, hipStream_t s);
 // the same mean for the texels of the `ntiles` listed 8 x 8 tiles only (device array of tile indices of the rank's compact image, each listed
 // once; pt_accumulate_tiles.hip): what a context with a sample mask runs instead (include/mi3pt.h: mi3pt_set_sample_mask)
 void launch_accumulate_tiles(const AccUniforms &acc0, const Tile &tile, const uint32_t *list, int ntiles, const float4 *slots,
-                             size_t slot_pixels, int nframes, float4 *accum, float4 *moments, int store_f16, hipStream_t s);
+                             size_t slot_pixels, int nframes, float4 *accum, float4 *moments, int store_f16, bool by_count, hipStream_t s);
 // `taps`: fullscreen_taps_bytes() of device memory (the de-noise pass's tap table); `taps_current`: an earlier call on
 // this stream has filled it from the same fs.res_x / fs.res_y
 size_t fullscreen_taps_bytes();
@@ -451,6 +452,21 @@ uint32_t converge_blocks(int width, int rows);
 // tiles: ceil(rows / 8) x ceil(width / 8) records (sum_r, max_r, count, n_min); t2 = (threshold * threshold) * 3 and min_frames as fp32
 void launch_converge(const float4 *accum, const float4 *moments, float4 *tiles, ConvergePart *parts, ConvergeSummary *summary, int width,
                      int rows, float t2, float min_frames, hipStream_t s);
+// The reprojection of (mean, moments) from an old view into a new one (include/mi3pt.h: mi3pt_reproject; pt_reproject.hip), all images
+// rows x width float4.  *1: the new view's feature images, *0: the old view's; f0: mi3pt_host_view_frame of the old view's block, res0_*
+// its resolution floats; res_w / res_h: the accumulate block's rectangle; max_history as fp32.  The outputs must not alias the inputs.
+struct ReprojectLaunch {
+    const float4 *accum, *moments;
+    float4 *accum_out, *moments_out;
+    const float4 *pos1, *nrm1, *ids1, *pos0, *nrm0, *ids0;
+    int32_t width, rows;
+    uint32_t res_w, res_h;
+    float f0[16];
+    float res0_x, res0_y;
+    float plane_tolerance, normal_cos_min, max_history;
+    int32_t store_f16;
+};
+void launch_reproject(const ReprojectLaunch &R, hipStream_t s);
 // packs the three position vectors of `ntris` 112-byte triangle records into 48-byte rows (the context's cull analysis)
 void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipStream_t s);
 // writes NodePacket::cull of `npackets` packets from a dense array (the context's cull analysis)

@@ -27,7 +27,7 @@
 //       true: the diagnostic twin (step statistics, clock stamps, step-voting options at run time);
 //       TOPLDS / LITE and k_raytrace_persistent (variant 3): experiment builds only
 //   k_rt_service_setup         the launch-invariant scalars of the service step, one block per launch
-//   k_accumulate_frames        accumulate.wgsl computeMain (one frame / an ordered batch of frames; <true>: keeping the moments image)
+//   k_accumulate_frames        accumulate.wgsl computeMain (one frame / an ordered batch of frames; <true>: keeping the moments image; <true, true>: the mean by count)
 //   k_fullscreen[_setup]       fullscreen.wgsl fragmentMain (de-noise + tone-map) and its tap table
 //   k_pack_vertices, k_patch_cull   helpers of the context's cull analysis
 //   k_debug_intersect/_math    component probes for the parity tests
@@ -2551,7 +2551,7 @@ void launch_raytrace(const RtLaunch &L, const RtRoute &r, bool fuse, hipStream_t
 // frame order (frame, frame+1, ...) -- the same sequence of accumulate.wgsl passes, with the
 // accumulator (MOMENTS: and the moments image; otherwise `moments` is never touched) read and
 // written once.  One frame is nframes == 1: the mean's arithmetic does not depend on either parameter.
-template <bool MOMENTS>
+template <bool MOMENTS, bool BY_COUNT = false>
 __global__ void __launch_bounds__(256) k_accumulate_frames(const AccUniforms acc0, const Tile tile, const float4 *__restrict__ slots,
                                                            size_t slot_pixels, int nframes, float4 *__restrict__ accum,
                                                            float4 *__restrict__ moments, int store_f16)
@@ -2568,11 +2568,7 @@ __global__ void __launch_bounds__(256) k_accumulate_frames(const AccUniforms acc
         for (int k = 0; k < nframes; k++) {
             AccUniforms a = acc0;
             a.frame = acc0.frame + (uint32_t)k;
-            const f3 c = xyz(slots[(size_t)k * slot_pixels + i]);
-            const f3 nc = accumulate_texel(a, c, p);
-            const f3 pn = F3(store_round(nc.x, store_f16), store_round(nc.y, store_f16), store_round(nc.z, store_f16));
-            if (MOMENTS) m = moments_step(a, c, p, pn, m);
-            p = pn;
+            mean_step<MOMENTS, BY_COUNT>(a, xyz(slots[(size_t)k * slot_pixels + i]), p, m, store_f16);
         }
         accum[i] = make_float4(p.x, p.y, p.z, 1.0f);
         if (MOMENTS) moments[i] = m;
@@ -2581,13 +2577,15 @@ __global__ void __launch_bounds__(256) k_accumulate_frames(const AccUniforms acc
 
 // (the grid is capped, the kernel strides beyond)
 void launch_accumulate_frames(const AccUniforms &acc0, const Tile &tile, const float4 *slots, size_t slot_pixels, int nframes,
-                              float4 *accum, float4 *moments, int store_f16, int max_blocks, hipStream_t s)
+                              float4 *accum, float4 *moments, int store_f16, bool by_count, int max_blocks, hipStream_t s)
 {
     const size_t n = (size_t)tile.local_rows * tile.tex_w;
     if (n == 0 || nframes <= 0) return;
     int blocks = (int)((n + 255) / 256);
     if (blocks > max_blocks) blocks = max_blocks;
-    if (moments)
+    if (moments && by_count)      // (the mean by count: mi3pt_set_mean_by_count)
+        hipLaunchKernelGGL((k_accumulate_frames<true, true>), dim3(blocks), dim3(256), 0, s, acc0, tile, slots, slot_pixels, nframes, accum, moments, store_f16);
+    else if (moments)
         hipLaunchKernelGGL(k_accumulate_frames<true>, dim3(blocks), dim3(256), 0, s, acc0, tile, slots, slot_pixels, nframes, accum, moments, store_f16);
     else
         hipLaunchKernelGGL(k_accumulate_frames<false>, dim3(blocks), dim3(256), 0, s, acc0, tile, slots, slot_pixels, nframes, accum, moments, store_f16);

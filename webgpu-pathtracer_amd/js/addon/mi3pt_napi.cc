@@ -289,6 +289,7 @@ CTX_INT_FN(SetPipelining, mi3pt_set_pipelining)
 CTX_INT_FN(SetPresentMode, mi3pt_set_present_mode)
 CTX_INT_FN(SetEnvSampling, mi3pt_set_env_sampling)
 CTX_INT_FN(SetMoments, mi3pt_set_moments)
+CTX_INT_FN(SetMeanByCount, mi3pt_set_mean_by_count)
 CTX_VOID_FN(Reset, mi3pt_reset)
 CTX_VOID_FN(Sync, mi3pt_sync)
 CTX_VOID_FN(Flush, mi3pt_flush)
@@ -578,6 +579,43 @@ napi_value FreezeConverged(napi_env env, napi_callback_info info)
     return v;
 }
 
+// reproject(ctx, planeTolerance, normalCosMin, maxHistory): mi3pt_reproject -- the mean and its moments carried into the view of the
+// raytrace uniforms as they stand
+napi_value Reproject(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t max_history;
+    double plane_tolerance, normal_cos_min;
+    if (!get_args(env, info, a, 4) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[3], &max_history)) return nullptr;
+    if (napi_get_value_double(env, a.v[1], &plane_tolerance) != napi_ok || napi_get_value_double(env, a.v[2], &normal_cos_min) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "expected a number");
+        return nullptr;
+    }
+    mi3pt_reproject_params p;
+    p.plane_tolerance = (float)plane_tolerance;
+    p.normal_cos_min = (float)normal_cos_min;
+    p.max_history = max_history;
+    p.flags = 0;
+    MI3PT_TRY(mi3pt_reproject(ctx, &p));
+    return undefined(env);
+}
+
+// hostViewFrame(raytraceUniforms: 96 bytes) -> Float32Array of 16 (mi3pt_host_view_frame; no device)
+napi_value HostViewFrame(napi_env env, napi_callback_info info)
+{
+    Args a;
+    void *u;
+    size_t n;
+    if (!get_args(env, info, a, 1) || !get_bytes(env, a.v[0], &u, &n)) return nullptr;
+    void *data = nullptr;
+    napi_value ab, ta;
+    NAPI_OK(napi_create_arraybuffer(env, 64, &data, &ab));
+    MI3PT_TRY(mi3pt_host_view_frame(u, n, static_cast<float *>(data)));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, 16, ab, 0, &ta));
+    return ta;
+}
+
 // batchCapacity(ctx) -> frames one launch covers at the current size (mi3pt_batch_capacity)
 napi_value BatchCapacity(napi_env env, napi_callback_info info)
 {
@@ -790,6 +828,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "estimateConvergence", EstimateConvergence }, { "readConvergence", ReadConvergence }, { "readConvergenceTiles", ReadConvergenceTiles },
         { "batchCapacity", BatchCapacity },
         { "setSampleMask", SetSampleMask }, { "readSampleMask", ReadSampleMask }, { "freezeConverged", FreezeConverged },
+        { "setMeanByCount", SetMeanByCount }, { "reproject", Reproject }, { "hostViewFrame", HostViewFrame },
     };
     for (const auto &f : fns) {
         napi_value v;

@@ -72,7 +72,7 @@ export class RaytracePass extends Pass {
 export class AccumulatePass extends Pass { setUniforms(value: object): void; update(): void; render(e: { passes: number }): void; }
 export class FullscreenPass extends Pass { setUniforms(value: object): void; update(): void; render(e: { passes: number }): void; }
 
-export type RendererEventType = 'start' | 'pause' | 'reset' | 'progress' | 'complete' | 'resize' | 'converged';
+export type RendererEventType = 'start' | 'pause' | 'reset' | 'progress' | 'complete' | 'resize' | 'converged' | 'reproject';
 export interface RendererOptions {
   device?: number;
   enableTimestampQuery?: boolean;
@@ -152,6 +152,15 @@ export class Renderer {
   readSampleMask(): Uint8Array;
   /** freeze the tiles the last estimateConvergence found under its threshold; returns the tiles still sampled */
   freezeConverged(guard?: 0 | 1): number;
+  /** weight every accumulate step by the texel's own sample count instead of the frame counter (include/mi3pt.h: mi3pt_set_mean_by_count);
+   *  enables the moments image itself.  The mean is then the sample mean: brighter than the default law's by (N + 1) / N after N frames.
+   *  Default off; `on` defaults to true */
+  setMeanByCount(on?: boolean): void;
+  /** instead of reset() when only the camera changed: carries the running mean and its moments into the new view (include/mi3pt.h:
+   *  mi3pt_reproject), texels the old view did not see restart, the frame budget starts over; emits 'reproject'.  Returns true; falls back
+   *  to reset() and returns false when the scene needs an upload, setMeanByCount is off, nothing has been sampled yet, or the renderer is
+   *  a rank of a tile split or a device group.  Defaults: planeTolerance 0.02, normalCosMin 0.9, maxHistory 64 */
+  reproject(scene: RaytracingScene, camera: RaytracingCamera, options?: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number }): boolean;
   counters(): { rays: number; boxTests: number; triTests: number; hits: number; misses: number; stackOverflows: number; pixels: number };
   /** src/main.ts:351-356: the presented canvas as PNG bytes (written to `file` when given) */
   screenshot(file?: string): Buffer;

@@ -26,7 +26,8 @@ class RaytracePass extends Pass {
     this.setUniforms({
       resolution: [this.renderer.scaledWidth, this.renderer.scaledHeight],
       aspect: this.renderer.aspect,
-      frame: this.renderer.frame,
+      // (_seedOffset: 0 unless reproject() was ever called -- a new view's samples must not replay the old view's random sequences)
+      frame: (this.renderer.frame + (this.renderer._seedOffset || 0)) >>> 0,
       samplesPerFrame: this.renderer.samplesPerFrame,
     });
   }

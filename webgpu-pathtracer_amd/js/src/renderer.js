@@ -53,6 +53,8 @@ class Renderer {
     this._sceneVersion = 0;      // scene uploads so far; with the camera and the size: what the feature images depend on
     this._aovKey = null;         // ... as they were when all four feature images were last rendered (denoiseGuided)
     this._moments = false;       // setMoments: the moments image is kept beside the running mean
+    this._meanByCount = false;   // setMeanByCount: a step's weight comes from the texel's own sample count
+    this._seedOffset = 0;        // reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
     this.tile = args.tile || { rank: 0, nranks: 1, blockRows: 8 };
     if (this.options.enableTimestampQuery) this.native.enableTiming(this.handle, 1);
     this.passes = {
@@ -250,7 +252,44 @@ class Renderer {
   // ---- the moments image (no counterpart in the reference): (M2.r, M2.g, M2.b, n) -- Welford's sums around the running mean, include/mi3pt.h:
   // mi3pt_set_moments -- kept beside the accumulation image from now on (it starts at zero: enable it before sampling starts, or reset()).
   // The mean is bit-identical with and without.
-  setMoments(enabled) { this.native.setMoments(this.handle, enabled ? 1 : 0); this._moments = !!enabled; }
+  setMoments(enabled) {
+    this.native.setMoments(this.handle, enabled ? 1 : 0);
+    this._moments = !!enabled;
+    if (!enabled) this._meanByCount = false;     // (the count is the image's n: the context switches the mode off with it)
+  }
+  // ---- the mean by count and the reprojection of the mean across a camera move (no counterpart in the reference; include/mi3pt.h:
+  // mi3pt_set_mean_by_count, mi3pt_reproject).  setMeanByCount(on = true): every accumulate step takes its weight from the texel's own
+  // sample count instead of the frame counter; enables the moments image itself.  The mean is then the SAMPLE mean: brighter than the
+  // default law's by (N + 1) / N after N frames, because the accumulate `frame` starts at 2 like the reference's.
+  setMeanByCount(on) {
+    const enabled = on === undefined ? true : !!on;
+    if (enabled && !this._moments) this.setMoments(true);
+    this.native.setMeanByCount(this.handle, enabled ? 1 : 0);
+    this._meanByCount = enabled;
+  }
+  // reproject(scene, camera, { planeTolerance = 0.02, normalCosMin = 0.9, maxHistory = 64 }): what a host calls INSTEAD of reset() when
+  // only the camera changed -- the running mean and its moments are carried into the new view, texels the old view did not see restart,
+  // the frame budget starts over.  Returns true; falls back to reset() and returns false when the scene needs an upload, setMeanByCount
+  // is off, nothing has been sampled yet, or the context is a rank of a tile split or a device group.
+  reproject(scene, camera, options) {
+    const o = Object.assign({ planeTolerance: 0.02, normalCosMin: 0.9, maxHistory: 64 }, options || {});
+    const partial = this.tile.nranks !== 1 || Array.isArray(this.devices);
+    if (scene.needsUpdate || !this._meanByCount || this._frame <= 1 || !(this._width > 0) || partial) {
+      this.reset();
+      return false;
+    }
+    if (this._aovKey === null || this._aovKey !== this._aovKeyNow()) this.renderAovs();   // the old view's features, under the uniforms the mean was sampled with
+    this.update(scene, camera);
+    this.native.reproject(this.handle, o.planeTolerance, o.normalCosMin, o.maxHistory);
+    this._aovKey = this._aovKeyNow();            // (the call rendered all four images of the new view)
+    this.emit('reproject');
+    this._seedOffset = (this._seedOffset + this._frame - 1) >>> 0;
+    const prevStatus = this.status;
+    this._frame = 1;
+    this.status = prevStatus === 'idle' ? 'sampling' : prevStatus;
+    if (this.status === 'sampling') this.emit('start');
+    return true;
+  }
   // localRows x width x 4 floats; row 0 = bottom of the picture
   readMoments() { return this.native.readMoments(this.handle, this.localRows * this._width); }
   // ---- sample until converged (no counterpart in the reference): the per-tile error estimate of the running mean, include/mi3pt.h:

@@ -18,6 +18,12 @@
 //   --adaptive         with --until: renderUntil(..., { adaptive: true }) -- converged tiles stop being sampled (renderer.freezeConverged after every
 //                      check); --guard 0|1 (1): keep a converged tile sampling while one of its eight neighbours is not.  "until" gains `sampled`;
 //                      also writes <prefix>_mask.u8 (the final sample mask, one byte per 8 x 8 tile) and <prefix>_moments.f32
+//   --orbit N          N views around the scene instead of one: the camera turns about the vertical axis through its target by --step DEG (2)
+//                      per view and every view takes --spp K frames (4); writes <prefix>_view<i>.png, <prefix>_view<i>.acc.f32 and
+//                      <prefix>_view<i>.uniforms.bin (the view's 96-byte raytrace uniform block: its camera) per view.
+//                      Between views renderer.reset(), or with --reproject renderer.setMeanByCount(true) from the start and
+//                      renderer.reproject(scene, camera) (the mean is carried across the move); with --guided-variance every view's PNG
+//                      is drawn from renderer.denoiseGuided({ variance: true, present: true }).  The usual outputs are the last view's
 //   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
 //   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
 //                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
@@ -70,6 +76,8 @@ async function main() {
   renderer.setUniforms('fullscreen', { denoise: PARAMS.denoise ? 1 : 0, tonemapping: PARAMS.tonemapping });
   const untilArg = arg('until', null);
   if (guidedVariance || untilArg !== null) renderer.setMoments(true);
+  const orbit = parseInt(arg('orbit', '0'), 10), reproject = process.argv.includes('--reproject');
+  if (orbit > 0 && reproject) renderer.setMeanByCount(true);
   renderer.resize(width, height);
   const t0 = Date.now();
   let until = null;
@@ -80,6 +88,24 @@ async function main() {
       adaptive: process.argv.includes('--adaptive'), guard: parseInt(arg('guard', '1'), 10) });
     renderer.render(scene, camera);                                        // only presents
     console.error('--until ' + untilArg + ': ' + (until.converged ? 'converged' : 'not converged') + ' after ' + until.frames + ' of ' + frames + ' frames');
+  } else if (orbit > 0) {
+    const spp = parseInt(arg('spp', '4'), 10), step = parseFloat(arg('step', '2')) * Math.PI / 180;
+    const p0 = camera.position.clone();
+    renderer.frames = spp;
+    for (let view = 0; view < orbit; view++) {
+      const c = Math.cos(view * step), s = Math.sin(view * step);
+      camera.position.copy(new pt.Vector3(c * p0.x + s * p0.z, p0.y, -s * p0.x + c * p0.z));
+      camera.lookAt(0, 0, 0);
+      if (view > 0) {
+        if (reproject) renderer.reproject(scene, camera);
+        else renderer.reset();
+      }
+      for (let i = 0; i < spp + 1; i++) renderer.render(scene, camera);      // the last call only presents
+      fs.writeFileSync(out + '_view' + view + '.acc.f32', Buffer.from(renderer.readAccumulation().buffer));
+      fs.writeFileSync(out + '_view' + view + '.uniforms.bin', Buffer.from(renderer.passes.raytrace.uniforms.bytes));
+      if (guidedVariance) renderer.denoiseGuided({ variance: true, present: true });
+      renderer.screenshot(out + '_view' + view + '.png');
+    }
   } else {
     for (let i = 0; i < frames + 1; i++) renderer.render(scene, camera);   // the last call only presents
   }

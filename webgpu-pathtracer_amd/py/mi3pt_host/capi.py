@@ -19,6 +19,7 @@ PASS_RAYTRACE, PASS_ACCUMULATE, PASS_FULLSCREEN = 0, 1, 2
 PASS_AOV = 3          # mi3pt_pass_time_us only: the first-hit feature images have no uniform block
 PASS_GUIDED = 4       # mi3pt_pass_time_us only: the feature-guided de-noise (denoise_guided)
 PASS_CONVERGENCE = 5  # mi3pt_pass_time_us only: the per-tile error estimate (estimate_convergence)
+PASS_REPROJECT = 6    # mi3pt_pass_time_us only: the gather kernel of reproject (its feature render is PASS_AOV's)
 GUIDED_PRESENT = 1    # mi3pt_guided_params.flags: draw the canvas from the filtered image
 GUIDED_VARIANCE = 2   # ... the colour weight steered by the per-pixel variance of the mean (needs set_moments(True))
 # mi3pt_aov: the first-hit feature images (render_aovs takes an OR of 1 << AOV_*)
@@ -58,6 +59,7 @@ SYMBOLS = (
     "mi3pt_set_moments", "mi3pt_read_moments", "mi3pt_write_moments", "mi3pt_moments_device_ptr", "mi3pt_read_guided_variance",
     "mi3pt_estimate_convergence", "mi3pt_read_convergence", "mi3pt_read_convergence_tiles",
     "mi3pt_set_sample_mask", "mi3pt_read_sample_mask", "mi3pt_freeze_converged", "mi3pt_host_freeze_tiles",
+    "mi3pt_set_mean_by_count", "mi3pt_host_view_frame", "mi3pt_reproject",
 )
 
 
@@ -65,6 +67,12 @@ class GuidedParams(ctypes.Structure):
     """mi3pt_guided_params"""
     _fields_ = [("levels", ctypes.c_int), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
                 ("sigma_albedo", ctypes.c_float), ("sigma_plane", ctypes.c_float), ("flags", ctypes.c_uint)]
+
+
+class ReprojectParams(ctypes.Structure):
+    """mi3pt_reproject_params"""
+    _fields_ = [("plane_tolerance", ctypes.c_float), ("normal_cos_min", ctypes.c_float), ("max_history", ctypes.c_int),
+                ("flags", ctypes.c_uint)]
 
 
 class Convergence(ctypes.Structure):
@@ -139,6 +147,9 @@ def load_library(path=None):
     lib.mi3pt_read_sample_mask.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.POINTER(ctypes.c_uint32)]
     lib.mi3pt_freeze_converged.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_uint32)]
     lib.mi3pt_host_freeze_tiles.argtypes = [c_void_p, c_int, c_int, ctypes.c_float, c_int, c_int, c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+    lib.mi3pt_set_mean_by_count.argtypes = [c_void_p, c_int]
+    lib.mi3pt_host_view_frame.argtypes = [c_void_p, c_size_t, c_void_p]
+    lib.mi3pt_reproject.argtypes = [c_void_p, ctypes.POINTER(ReprojectParams)]
     lib.mi3pt_enable_timing.argtypes = [c_void_p, c_int]
     lib.mi3pt_pass_time_us.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]
     lib.mi3pt_raytrace_launch_stats.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
@@ -342,6 +353,16 @@ def host_freeze_tiles(records, threshold, min_frames, guard=1, mask=None):
     n = ctypes.c_uint32()
     _check(lib, lib.mi3pt_host_freeze_tiles(_ptr(rec), tx, ty, threshold, int(min_frames), int(guard), _ptr(out), ctypes.byref(n)))
     return out, n.value
+
+
+def host_view_frame(raytrace_uniforms):
+    """The camera frame of a 96-byte raytrace uniform block as 16 float32 (include/mi3pt.h: mi3pt_host_view_frame): position, aspect |
+    fwd, t | u, r | v, 0 -- what reproject projects the new view's first hits with.  Plain host code, no device."""
+    lib = load_library()
+    raw = bytes(raytrace_uniforms)
+    out = np.zeros(16, np.float32)
+    _check(lib, lib.mi3pt_host_view_frame(raw, len(raw), _ptr(out)))
+    return out
 
 
 def host_env_cdf(rgba):
@@ -611,6 +632,18 @@ class Context:
         n = ctypes.c_uint32()
         self._c(self.lib.mi3pt_freeze_converged(self.handle, int(guard), ctypes.byref(n)))
         return n.value
+
+    def set_mean_by_count(self, enabled=True):
+        """The mean by count (include/mi3pt.h: mi3pt_set_mean_by_count): every accumulate step takes its weight from the texel's own
+        sample count, the moments image's n, instead of the accumulate block's `frame`.  Needs set_moments(True)."""
+        self._c(self.lib.mi3pt_set_mean_by_count(self.handle, int(bool(enabled))))
+
+    def reproject(self, plane_tolerance=0.02, normal_cos_min=0.9, max_history=64, flags=0):
+        """Carry the running mean and its moments from the view the POSITION / NORMAL / IDS images were rendered in into the view of the
+        raytrace uniforms as they stand (include/mi3pt.h: mi3pt_reproject); renders all four feature images of the new view on the way
+        and drops the sample mask.  Asynchronous.  Needs set_moments(True) and set_mean_by_count(True)."""
+        p = ReprojectParams(plane_tolerance, normal_cos_min, int(max_history), int(flags))
+        self._c(self.lib.mi3pt_reproject(self.handle, ctypes.byref(p)))
 
     def bind_accumulation(self, dev_ptr, nbytes):
         self._c(self.lib.mi3pt_bind_accumulation(self.handle, dev_ptr, nbytes))

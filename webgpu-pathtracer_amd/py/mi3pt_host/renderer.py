@@ -104,8 +104,9 @@ class RaytracePass(Pass):
 
     def update(self):                             # raytrace.ts:371-378
         r = self.renderer
+        # (_seedOffset: 0 unless reproject() was ever called -- a new view's samples must not replay the old view's random sequences)
         self.setUniforms({"resolution": [r.scaledWidth, r.scaledHeight], "aspect": r.aspect,
-                          "frame": r.frame, "samplesPerFrame": r.samplesPerFrame})
+                          "frame": (r.frame + r._seedOffset) & 0xFFFFFFFF, "samplesPerFrame": r.samplesPerFrame})
 
     def updateScene(self, scene, camera):         # raytrace.ts:380-533
         self.setUniforms({"camera": {"position": camera.getWorldPosition(),
@@ -194,6 +195,8 @@ class Renderer:
         self._sceneVersion = 0             # scene uploads so far; with the camera and the size: what the feature images depend on
         self._aovKey = None                # ... as they were when all four feature images were last rendered (denoiseGuided)
         self._moments = False              # setMoments: the moments image is kept beside the running mean
+        self._meanByCount = False          # setMeanByCount: a step's weight comes from the texel's own sample count
+        self._seedOffset = 0               # reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
         self.passes = {"raytrace": RaytracePass(self), "accumulate": AccumulatePass(self),
                        "fullscreen": FullscreenPass(self)}
         if self.options["enableTimestampQuery"]:
@@ -414,6 +417,42 @@ class Renderer:
         image from now on (the image starts at zero: enable it before sampling starts, or reset()).  The mean is bit-identical."""
         self.ctx.set_moments(bool(enabled))
         self._moments = bool(enabled)
+        if not enabled:
+            self._meanByCount = False              # (the count is the image's n: the context switches the mode off with it)
+
+    # ---- the mean by count, and the reprojection of the mean across a camera move (no counterpart in the reference) ----
+    def setMeanByCount(self, on=True):
+        """Weight every accumulate step by the texel's own sample count (include/mi3pt.h: mi3pt_set_mean_by_count) instead of the
+        frame counter; enables the moments image itself.  The mean is then the SAMPLE mean: brighter than the default law's by
+        (N + 1) / N after N frames, because this host's accumulate `frame` starts at 2 like the reference's."""
+        if on and not self._moments:
+            self.setMoments(True)
+        self.ctx.set_mean_by_count(bool(on))
+        self._meanByCount = bool(on)
+
+    def reproject(self, scene, camera, planeTolerance=0.02, normalCosMin=0.9, maxHistory=64):
+        """What a host calls INSTEAD of reset() when only the camera changed: the running mean and its moments are carried into the
+        new view (include/mi3pt.h: mi3pt_reproject), texels the old view did not see restart, and the frame budget starts over.
+        Returns True; falls back to reset() and returns False when the scene needs an upload, setMeanByCount is off, nothing has
+        been sampled yet, or the context is a rank of a tile split or a device group."""
+        ctx = self.ctx
+        partial = ctx.group_size != 1 or ctx._tile[1] != 1          # (a device group, or a rank of a tile split as of the last resize)
+        if scene.needsUpdate or not self._meanByCount or self._frame <= 1 or not self._width or partial:
+            self.reset()
+            return False
+        if self._aovKey is None or self._aovKey != self._aovKeyNow():
+            self.renderAovs()                      # the old view's features, under the uniforms the mean was sampled with
+        self.update(scene, camera)
+        ctx.reproject(planeTolerance, normalCosMin, maxHistory)
+        self._aovKey = self._aovKeyNow()           # (the call rendered all four images of the new view)
+        self.emit("reproject")
+        self._seedOffset = (self._seedOffset + self._frame - 1) & 0xFFFFFFFF
+        prev = self.status
+        self._frame = 1
+        self.status = "sampling" if prev == "idle" else prev
+        if self.status == "sampling":
+            self.emit("start")
+        return True
 
     def readMoments(self):
         """(rows, width, 4) float32: M2.r, M2.g, M2.b, n."""
