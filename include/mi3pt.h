@@ -28,7 +28,7 @@
  *     kernels run on internal streams tied to it by events in both directions, which no caller can see.
  *     STREAM ORDERED, returning before the device has run anything: mi3pt_submit, mi3pt_submit_frames, mi3pt_flush,
  *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided, mi3pt_estimate_convergence, mi3pt_reproject,
- *     mi3pt_set_mean_by_count, mi3pt_set_sample_mask (it launches the frame queue, under the old mask, and waits for nothing).  mi3pt_set_uniforms, the setters of
+ *     mi3pt_reproject_scene, mi3pt_set_mean_by_count, mi3pt_set_sample_mask (it launches the frame queue, under the old mask, and waits for nothing).  mi3pt_set_uniforms, the setters of
  *     modes and options and the *_device_ptr getters start no device work of their own (those that observe state launch
  *     the frame queue first).  A host that has set its own stream may therefore enqueue its work in front of and behind
  *     these calls on that stream -- fill a bound accumulation tensor, copy out of a *_device_ptr image -- and wait once.
@@ -71,7 +71,7 @@ extern "C" {
  * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4); mi3pt_estimate_convergence,
  * mi3pt_read_convergence, mi3pt_read_convergence_tiles, struct mi3pt_convergence, MI3PT_PASS_CONVERGENCE (5); mi3pt_set_sample_mask,
  * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles; mi3pt_set_mean_by_count, mi3pt_host_view_frame, mi3pt_reproject,
- * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6). */
+ * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6); mi3pt_keep_geometry, mi3pt_reproject_scene, struct mi3pt_reproject_scene_params. */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -568,7 +568,7 @@ int mi3pt_set_mean_by_count(mi3pt_ctx *ctx, int enabled);                  /* de
  * on every camera change (renderer.ts:397-416).  The temporal half of SVGF (Schied et al. 2017): every texel of the NEW view looks its
  * first hit's world point up in the OLD view's images and takes over mean, variance and sample count where the old view saw the same
  * surface.  The scene is taken as STATIC between the two views; uploads in between are not detected (taps are then rejected or carry
- * stale radiance; nothing faults).
+ * stale radiance; nothing faults); mi3pt_reproject_scene below follows triangles that moved.
  * mi3pt_host_view_frame (plain host C++, no device): the camera frame the reprojection projects with, from a 96-byte raytrace block,
  * computed in double from the block's fp32 fields, each output rounded to fp32 once:
  *   w = normalize(-direction);  up = (0,1,0), or (0,0,1) when |w.y| > 0.99999;  u = normalize(cross(up, w));  v = cross(w, u)
@@ -632,6 +632,61 @@ typedef struct mi3pt_reproject_params {
 } mi3pt_reproject_params;
 int mi3pt_host_view_frame(const void *raytrace_uniforms, size_t nbytes, float out[16]);   /* plain host C++, no device */
 int mi3pt_reproject(mi3pt_ctx *ctx, const mi3pt_reproject_params *params);
+
+/* ---- reprojection across a scene change: the mean follows triangles that moved -- no counterpart in the reference.  mi3pt_reproject
+ * takes the scene as static; a host that nudges one object or plays an animation would lose every sample of every texel, the large
+ * majority whose surface did not move included.  The motion-vector half of SVGF: word 0 of IDS names the hit triangle, the context
+ * keeps the records in upload order, so a texel of the new view can find the point of the PREVIOUS geometry it shows now.
+ * Topology is the caller's contract: index i names the same surface element before and after the upload (both hosts flatten their
+ * scene in a fixed order: rigid motion and skinning satisfy this).
+ * mi3pt_keep_geometry(ctx, 1): the triangle records as they are uploaded NOW are the "previous geometry" from here on.  No second
+ * upload and no copy: until the next mi3pt_upload_triangles "previous" aliases "current"; that upload hands the current buffer over
+ * as the previous geometry instead of freeing it; later uploads replace the current records only.  The context records its upload
+ * count (every mi3pt_upload_triangles / _bvh / _materials counts) at the call and at every mi3pt_render_aovs, per image.  A later
+ * keep = 1 replaces what is kept; keep = 0, mi3pt_destroy or a second keep free a handed-over buffer, after a wait for the context's
+ * stream.  COST: 112 B per triangle of device memory from the hand-over until the release.  MI3PT_ERR_STATE without uploaded
+ * triangles (keep = 1) and for a device group.
+ * mi3pt_reproject_scene: steps 1 - 7 of mi3pt_reproject unchanged, with the kernel below in step 5; the feature images of step 4 are
+ * rendered from U1 and the CURRENT scene.  U1 may equal U0: a moved object under a fixed camera.  Asynchronous and stream ordered; it
+ * changes no counter and nothing mi3pt_debug_last_launch reports; timed as MI3PT_PASS_REPROJECT, its feature render as MI3PT_PASS_AOV.
+ * The kernel.  Pinned fp32: dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, correctly rounded division and sqrtf, nothing contracted.  For a
+ * texel p inside the rectangle with hit1(p) == 1:
+ *   T = word 0 of IDS1(p);   needs 0 <= T < ntris;   R1 = the current record T, R0 = the kept record T
+ *   P, t1, N as in mi3pt_reproject
+ *   static: the nine position floats of R0 and R1 are equal as 32-bit words.  Then  Q = P;  NQ = N;  len = 1;  tq = t1
+ *   moved, with a1, b1, c1 the positions of R1 and a0, b0, c0, na0, nb0, nc0 the positions and normals of R0:
+ *     e1 = b1 - a1;  e2 = c1 - a1;  w = P - a1
+ *     d11 = dot(e1,e1);  d12 = dot(e1,e2);  d22 = dot(e2,e2);  w1 = dot(w,e1);  w2 = dot(w,e2)
+ *     den = d11*d22 - d12*d12                                                                needs den > 0   (a NaN fails)
+ *     u = (d22*w1 - d12*w2) / den;   v = (d11*w2 - d12*w1) / den;   g = (1 - u) - v
+ *     f1 = b0 - a0;  f2 = c0 - a0;   Q.k = a0.k + (u*f1.k + v*f2.k)
+ *     NQ.k = (g*na0.k + u*nb0.k) + v*nc0.k;   len = sqrtf(dot(NQ,NQ))                          needs len > 0   (a NaN fails)
+ *     d = Q - F0.position;   tq = sqrtf(dot(d,d))
+ *   From there the law is mi3pt_reproject's with Q in P's place in d, a, b, cz, k, uvx, uvy, fx, fy and the taps, and the two surface
+ *   tests of a tap read
+ *       dot(NQ, NORMAL0(q).xyz) >= normal_cos_min * len
+ *       fabsf(dot(NQ, POSITION0(q).xyz - Q)) <= (plane_tolerance * tq) * len
+ *   hit0(q) == 1, mat0(q) == mat1(p), n0 >= 1, the tap order and the sums are unchanged.
+ *   carried:   n' = fminf(nmin, (float)(static ? max_history : max_history_moved));   A', M' as in mi3pt_reproject
+ *   restarted texels and texels outside the rectangle: as in mi3pt_reproject.
+ * With len = 1 both products are exact: a static texel is mi3pt_reproject's texel bit for bit, by construction.
+ * Known limits.  A needle triangle loses precision in den: its taps then fail the plane test or land a fraction of a texel off.
+ * Radiance that changed because a shadow or a reflection moved is carried stale: max_history and max_history_moved bound for how long.
+ *   MI3PT_ERR_STATE wherever mi3pt_reproject returns it (a rank of a tile split and a device group included); while no geometry is
+ *   kept; when the kept triangle count differs from the current one; unless POSITION, NORMAL and IDS were all rendered at exactly the
+ *   kept upload count -- any upload between rendering them and mi3pt_keep_geometry (in either order) refuses the call; "keep, then
+ *   render them, no upload in between" is accepted.  MI3PT_ERR_INVALID for mi3pt_reproject's argument faults and max_history_moved
+ *   outside 1 .. 2^24. ---- */
+int mi3pt_keep_geometry(mi3pt_ctx *ctx, int keep);          /* 1: remember the triangle records as they are uploaded NOW as the
+                                                               "previous geometry"; 0: release it */
+typedef struct mi3pt_reproject_scene_params {
+    float plane_tolerance;     /* finite, >= 0 */
+    float normal_cos_min;      /* [-1, 1] */
+    int   max_history;         /* 1 .. 2^24: cap for texels whose triangle did not move */
+    int   max_history_moved;   /* 1 .. 2^24: cap for texels whose triangle moved */
+    unsigned flags;            /* 0 */
+} mi3pt_reproject_scene_params;
+int mi3pt_reproject_scene(mi3pt_ctx *ctx, const mi3pt_reproject_scene_params *params);
 
 /* ---- read-back (the capability a headless drop-in needs; the reference only has
  * canvas.toDataURL, main.ts:351-356).  Blocking.  dst holds rows x width x 4 floats

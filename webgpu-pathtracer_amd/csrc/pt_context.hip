@@ -338,6 +338,15 @@ struct mi3pt_ctx {
     float4 *d_aov_prev[MI3PT_AOV_COUNT] = {};
     float4 *d_reproject[2] = {};
     PassTimer reproject_timer;
+    // The previous geometry (mi3pt_keep_geometry, mi3pt_reproject_scene).  upload_epoch counts the uploads of triangles, BVH and materials (scene_epoch also
+    // moves with the lazy analyses, which change no record); aov_epoch: its value when each feature image was rendered.  geometry_kept:
+    // d_tris as it stood at kept_epoch is the previous geometry -- d_tris itself while d_tris_kept is null (nothing uploaded since), else
+    // d_tris_kept, the buffer the first mi3pt_upload_triangles after the call handed over instead of freeing it.
+    uint64_t upload_epoch = 0, kept_epoch = 0;
+    uint64_t aov_epoch[MI3PT_AOV_COUNT] = {};
+    bool geometry_kept = false;
+    void *d_tris_kept = nullptr;
+    size_t ntris_kept = 0;
     // The per-tile error estimate (mi3pt_estimate_convergence; pt_converge.hip): the tile map ceil(local_rows / 8) x ceil(width / 8) x 16 B,
     // the tile kernel's per-block records and the summary on the device, the summary's copy in pinned host memory, all allocated by the
     // first call and freed with the textures; conv_done: recorded behind the copy of the most recent estimate -- what the two reads wait for, and nothing else.
@@ -827,7 +836,7 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     if (ctx->h_walk_stats) (void)hipHostFree(ctx->h_walk_stats);
     if (ctx->d_walk_prev) (void)hipFree(ctx->d_walk_prev);
     free_textures(ctx);
-    for (void *p : { ctx->d_cw8, ctx->d_tripk8, ctx->d_cwide, ctx->d_tripk64, ctx->d_wide, ctx->d_tris, ctx->d_tris_perm, ctx->d_nodes, ctx->d_mats, ctx->d_env, ctx->d_cdf, ctx->d_packets, ctx->d_tripk, ctx->d_leaf_rank,
+    for (void *p : { ctx->d_cw8, ctx->d_tripk8, ctx->d_cwide, ctx->d_tripk64, ctx->d_wide, ctx->d_tris, ctx->d_tris_kept, ctx->d_tris_perm, ctx->d_nodes, ctx->d_mats, ctx->d_env, ctx->d_cdf, ctx->d_packets, ctx->d_tripk, ctx->d_leaf_rank,
                      (void *)ctx->d_tile_counter, (void *)ctx->d_drain_flag, (void *)ctx->d_wave_times, (void *)ctx->d_stack_overflow, (void *)ctx->d_park, (void *)ctx->d_service, ctx->d_fs_taps })
         if (p) (void)hipFree(p);
     for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer, &ctx->conv_timer, &ctx->reproject_timer }) t->destroy();
@@ -1124,7 +1133,16 @@ extern "C" int mi3pt_upload_triangles(mi3pt_ctx *ctx, const void *bytes, size_t 
     std::vector<pt::TriPacket> pk;
     int64_t max_mat = -1;
     if (const char *e = pt::compile_triangles(static_cast<const uint8_t *>(bytes), n, pk, max_mat)) return pt_set_error(MI3PT_ERR_INVALID, e);
-    if (int rc = replace_buffer(ctx, &ctx->d_tris, bytes, nbytes)) return rc;
+    // (mi3pt_keep_geometry: the first upload after it hands the records over as the previous geometry instead of freeing them)
+    const bool hand_over = ctx->geometry_kept && !ctx->d_tris_kept;
+    void *tris = hand_over ? nullptr : ctx->d_tris;
+    if (int rc = replace_buffer(ctx, &tris, bytes, nbytes)) return rc;
+    if (hand_over) {
+        ctx->d_tris_kept = ctx->d_tris;
+        ctx->buf_bytes.erase(ctx->d_tris_kept);
+    }
+    ctx->d_tris = tris;
+    ctx->upload_epoch++;
     if (int rc = replace_buffer(ctx, &ctx->d_tripk, pk.data(), n * sizeof(pt::TriPacket))) return rc;
     ctx->ntris = n;
     ctx->host_analyses++;
@@ -1153,6 +1171,7 @@ extern "C" int mi3pt_upload_materials(mi3pt_ctx *ctx, const void *bytes, size_t 
     if (!bytes || nbytes == 0 || nbytes % MI3PT_MATERIAL_STRIDE)
         return pt_set_error(MI3PT_ERR_INVALID, "material bytes must be a non-zero multiple of 64");
     if (int rc = replace_buffer(ctx, &ctx->d_mats, bytes, nbytes)) return rc;
+    ctx->upload_epoch++;
     ctx->nmats = nbytes / MI3PT_MATERIAL_STRIDE;
     return MI3PT_OK;
 }
@@ -1170,6 +1189,7 @@ extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes
     pt::TreeCompile t;
     if (const char *e = pt::compile_tree(src, n, t)) return pt_set_error(MI3PT_ERR_INVALID, e);
     if (int rc = replace_buffer(ctx, &ctx->d_nodes, bytes, nbytes)) return rc;
+    ctx->upload_epoch++;
     if (int rc = replace_buffer(ctx, &ctx->d_packets, t.packets.data(), t.packets.size() * sizeof(pt::NodePacket))) return rc;
     if (int rc = replace_buffer(ctx, &ctx->d_leaf_rank, t.leaf_rank.data(), t.leaf_rank.size() * sizeof(uint32_t))) return rc;
     ctx->leaf_cap = t.leaf_cap;
@@ -2587,6 +2607,7 @@ extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
         if ((aov_mask >> k) & 1u) {
             ctx->aov_valid[k] = true;
             std::memcpy(ctx->aov_u[k], ctx->u_rt, sizeof ctx->u_rt);      // (the view this image belongs to: mi3pt_reproject's old view)
+            ctx->aov_epoch[k] = ctx->upload_epoch;                       // (and the geometry: mi3pt_reproject_scene's previous one)
         }
     return MI3PT_OK;
 }
@@ -2820,35 +2841,55 @@ extern "C" int mi3pt_set_mean_by_count(mi3pt_ctx *ctx, int enabled)
     return MI3PT_OK;
 }
 
-extern "C" int mi3pt_reproject(mi3pt_ctx *ctx, const mi3pt_reproject_params *params)
+// what mi3pt_reproject and mi3pt_reproject_scene share: the argument checks, the state checks and steps 1 - 7 of the header.  scene: the
+// kernel that follows a triangle back to the kept geometry (k_reproject_scene) takes k_reproject's place in step 5.
+struct ReprojectCall {
+    const char *who;
+    float plane_tolerance, normal_cos_min;
+    int max_history, max_history_moved;
+    unsigned flags;
+    bool scene;
+};
+
+static int reproject_run(mi3pt_ctx *ctx, const ReprojectCall &c)
 {
-    PT_GROUP(ctx, group_unsupported("mi3pt_reproject: not built for a device group (a tap crosses the members' rows; no halo exchange)"));
-    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (!(params->plane_tolerance >= 0.0f) || std::isinf(params->plane_tolerance))
-        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_reproject: plane_tolerance must be finite and >= 0");
-    if (!(params->normal_cos_min >= -1.0f && params->normal_cos_min <= 1.0f))
-        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_reproject: normal_cos_min must lie in [-1, 1]");
-    if (params->max_history < 1 || params->max_history > (1 << 24)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_reproject: max_history must be 1 .. 2^24");
-    if (params->flags) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_reproject: unknown flag bits");
+    const std::string who = c.who;
+    if (!(c.plane_tolerance >= 0.0f) || std::isinf(c.plane_tolerance))
+        return pt_set_error(MI3PT_ERR_INVALID, who + ": plane_tolerance must be finite and >= 0");
+    if (!(c.normal_cos_min >= -1.0f && c.normal_cos_min <= 1.0f))
+        return pt_set_error(MI3PT_ERR_INVALID, who + ": normal_cos_min must lie in [-1, 1]");
+    if (c.max_history < 1 || c.max_history > (1 << 24)) return pt_set_error(MI3PT_ERR_INVALID, who + ": max_history must be 1 .. 2^24");
+    if (c.scene && (c.max_history_moved < 1 || c.max_history_moved > (1 << 24)))
+        return pt_set_error(MI3PT_ERR_INVALID, who + ": max_history_moved must be 1 .. 2^24");
+    if (c.flags) return pt_set_error(MI3PT_ERR_INVALID, who + ": unknown flag bits");
     if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject before resize");
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, who + " before resize");
     if (!ctx->moments || !ctx->d_moments || !ctx->by_count)
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject needs the moments image and the mean by count (mi3pt_set_moments, mi3pt_set_mean_by_count)");
+        return pt_set_error(MI3PT_ERR_STATE, who + " needs the moments image and the mean by count (mi3pt_set_moments, mi3pt_set_mean_by_count)");
     if (ctx->partial())
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject: not built for a rank of a tile split (a tap crosses the ranks' rows; no halo exchange)");
+        return pt_set_error(MI3PT_ERR_STATE, who + ": not built for a rank of a tile split (a tap crosses the ranks' rows; no halo exchange)");
     static const int old_set[3] = { MI3PT_AOV_POSITION, MI3PT_AOV_NORMAL, MI3PT_AOV_IDS };
     const uint8_t *u0 = ctx->aov_u[MI3PT_AOV_POSITION];
     for (int k : old_set) {
         if (!ctx->aov_valid[k] || !ctx->d_aov[k])
-            return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject: the POSITION, NORMAL and IDS images of the old view have not been rendered since the last resize (mi3pt_render_aovs)");
+            return pt_set_error(MI3PT_ERR_STATE, who + ": the POSITION, NORMAL and IDS images of the old view have not been rendered since the last resize (mi3pt_render_aovs)");
         // (resolution and aspect; camera position, direction and fov: what the first hit depends on)
         if (std::memcmp(ctx->aov_u[k], u0, 12) || std::memcmp(ctx->aov_u[k] + 32, u0 + 32, 32))
-            return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject: the POSITION, NORMAL and IDS images were rendered from different views");
+            return pt_set_error(MI3PT_ERR_STATE, who + ": the POSITION, NORMAL and IDS images were rendered from different views");
     }
     if (std::memcmp(ctx->u_rt, u0, 8))
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_reproject: the new view's resolution differs from the old view's");
+        return pt_set_error(MI3PT_ERR_STATE, who + ": the new view's resolution differs from the old view's");
+    if (c.scene) {
+        if (!ctx->geometry_kept) return pt_set_error(MI3PT_ERR_STATE, who + ": no previous geometry is kept (mi3pt_keep_geometry)");
+        if (!ctx->d_tris || ctx->ntris != ctx->ntris_kept)
+            return pt_set_error(MI3PT_ERR_STATE, who + ": the kept geometry and the current one differ in their number of triangles");
+        for (int k : old_set)
+            if (ctx->aov_epoch[k] != ctx->kept_epoch)
+                return pt_set_error(MI3PT_ERR_STATE, who + ": the POSITION, NORMAL and IDS images were not rendered from the kept geometry (an upload lies between them and mi3pt_keep_geometry)");
+    }
     if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far belongs to the old view's mean
-    pt::ReprojectLaunch R;
+    pt::ReprojectSceneLaunch S;
+    pt::ReprojectLaunch &R = S.view;
     if (int rc = mi3pt_host_view_frame(u0, MI3PT_RAYTRACE_UNIFORMS_SIZE, R.f0)) return rc;
     R.res0_x = ldf(u0, 0); R.res0_y = ldf(u0, 4);
     const size_t tex_bytes = plane_bytes(ctx);
@@ -2869,10 +2910,19 @@ extern "C" int mi3pt_reproject(mi3pt_ctx *ctx, const mi3pt_reproject_params *par
     R.pos0 = ctx->d_aov_prev[MI3PT_AOV_POSITION]; R.nrm0 = ctx->d_aov_prev[MI3PT_AOV_NORMAL]; R.ids0 = ctx->d_aov_prev[MI3PT_AOV_IDS];
     R.width = ctx->width; R.rows = ctx->local_rows;
     R.res_w = acc.res_w; R.res_h = acc.res_h;
-    R.plane_tolerance = params->plane_tolerance; R.normal_cos_min = params->normal_cos_min; R.max_history = (float)params->max_history;
+    R.plane_tolerance = c.plane_tolerance; R.normal_cos_min = c.normal_cos_min; R.max_history = (float)c.max_history;
     R.store_f16 = ctx->storage == MI3PT_STORAGE_F16;
     if (ctx->timing) HIP_TRY(ctx->reproject_timer.begin(ctx->stream));
-    pt::launch_reproject(R, ctx->stream);
+    if (c.scene) {
+        // the records in upload order, which IDS indexes: the current ones, and the kept ones (the current ones until an upload handed them over)
+        S.tris1 = static_cast<const float4 *>(ctx->d_tris);
+        S.tris0 = static_cast<const float4 *>(ctx->d_tris_kept ? ctx->d_tris_kept : ctx->d_tris);
+        S.ntris = (int32_t)ctx->ntris;
+        S.max_history_moved = (float)c.max_history_moved;
+        pt::launch_reproject_scene(S, ctx->stream);
+    } else {
+        pt::launch_reproject(R, ctx->stream);
+    }
     HIP_TRY(hipGetLastError());
     // the scratch pair takes the images' place: the context's own by a swap of pointers, a bound accumulation image by a copy on the stream
     std::swap(ctx->d_moments, ctx->d_reproject[1]);
@@ -2887,6 +2937,39 @@ extern "C" int mi3pt_reproject(mi3pt_ctx *ctx, const mi3pt_reproject_params *par
     ctx->main_dirty = true;
     ctx->accum_version++;
     return MI3PT_OK;
+}
+
+extern "C" int mi3pt_reproject(mi3pt_ctx *ctx, const mi3pt_reproject_params *params)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_reproject: not built for a device group (a tap crosses the members' rows; no halo exchange)"));
+    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    return reproject_run(ctx, { "mi3pt_reproject", params->plane_tolerance, params->normal_cos_min, params->max_history, 1, params->flags, false });
+}
+
+// ---- the previous geometry and the reprojection across a scene change (include/mi3pt.h: mi3pt_keep_geometry, mi3pt_reproject_scene) ----
+extern "C" int mi3pt_keep_geometry(mi3pt_ctx *ctx, int keep)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_keep_geometry: not built for a device group (mi3pt_reproject_scene is not)"));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (keep && (!ctx->d_tris || ctx->ntris == 0))
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_keep_geometry: no triangles uploaded (mi3pt_upload_triangles)");
+    if (ctx->d_tris_kept) {        // (a second keep, or the release: behind whatever still reads the buffer)
+        HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "mi3pt_keep_geometry"));
+        (void)hipFree(ctx->d_tris_kept);
+        ctx->d_tris_kept = nullptr;
+    }
+    ctx->geometry_kept = keep != 0;
+    ctx->ntris_kept = keep ? ctx->ntris : 0;
+    ctx->kept_epoch = keep ? ctx->upload_epoch : 0;
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_reproject_scene(mi3pt_ctx *ctx, const mi3pt_reproject_scene_params *params)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_reproject_scene: not built for a device group (a tap crosses the members' rows; no halo exchange)"));
+    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    return reproject_run(ctx, { "mi3pt_reproject_scene", params->plane_tolerance, params->normal_cos_min, params->max_history,
+                                params->max_history_moved, params->flags, true });
 }
 
 // ---- the per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip) ----

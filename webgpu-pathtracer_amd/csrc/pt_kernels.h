@@ -467,6 +467,16 @@ struct ReprojectLaunch {
     int32_t store_f16;
 };
 void launch_reproject(const ReprojectLaunch &R, hipStream_t s);
+// The same across a scene change (include/mi3pt.h: mi3pt_reproject_scene; pt_reproject_scene.hip).  view: as above, its max_history the cap
+// of the texels whose triangle did not move; tris1 / tris0: the current and the kept 112-byte records in upload order, ntris of each (word 0
+// of IDS indexes both; they may be one buffer: nothing has moved); max_history_moved as fp32.
+struct ReprojectSceneLaunch {
+    ReprojectLaunch view;
+    const float4 *tris1, *tris0;
+    int32_t ntris;
+    float max_history_moved;
+};
+void launch_reproject_scene(const ReprojectSceneLaunch &S, hipStream_t s);
 // packs the three position vectors of `ntris` 112-byte triangle records into 48-byte rows (the context's cull analysis)
 void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipStream_t s);
 // writes NodePacket::cull of `npackets` packets from a dense array (the context's cull analysis)

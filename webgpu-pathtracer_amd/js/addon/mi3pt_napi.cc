@@ -601,6 +601,41 @@ napi_value Reproject(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+// keepGeometry(ctx, keep): mi3pt_keep_geometry -- the triangle records as they are uploaded now become the previous geometry (1) / release it (0)
+napi_value KeepGeometry(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t keep;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &keep)) return nullptr;
+    MI3PT_TRY(mi3pt_keep_geometry(ctx, keep));
+    return undefined(env);
+}
+
+// reprojectScene(ctx, planeTolerance, normalCosMin, maxHistory, maxHistoryMoved): mi3pt_reproject_scene -- reproject across a scene change,
+// texels whose triangle moved since keepGeometry follow it
+napi_value ReprojectScene(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t max_history, max_history_moved;
+    double plane_tolerance, normal_cos_min;
+    if (!get_args(env, info, a, 5) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[3], &max_history) || !get_i32(env, a.v[4], &max_history_moved))
+        return nullptr;
+    if (napi_get_value_double(env, a.v[1], &plane_tolerance) != napi_ok || napi_get_value_double(env, a.v[2], &normal_cos_min) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "expected a number");
+        return nullptr;
+    }
+    mi3pt_reproject_scene_params p;
+    p.plane_tolerance = (float)plane_tolerance;
+    p.normal_cos_min = (float)normal_cos_min;
+    p.max_history = max_history;
+    p.max_history_moved = max_history_moved;
+    p.flags = 0;
+    MI3PT_TRY(mi3pt_reproject_scene(ctx, &p));
+    return undefined(env);
+}
+
 // hostViewFrame(raytraceUniforms: 96 bytes) -> Float32Array of 16 (mi3pt_host_view_frame; no device)
 napi_value HostViewFrame(napi_env env, napi_callback_info info)
 {
@@ -829,6 +864,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "batchCapacity", BatchCapacity },
         { "setSampleMask", SetSampleMask }, { "readSampleMask", ReadSampleMask }, { "freezeConverged", FreezeConverged },
         { "setMeanByCount", SetMeanByCount }, { "reproject", Reproject }, { "hostViewFrame", HostViewFrame },
+        { "keepGeometry", KeepGeometry }, { "reprojectScene", ReprojectScene },
     };
     for (const auto &f : fns) {
         napi_value v;

@@ -161,6 +161,13 @@ export class Renderer {
    *  to reset() and returns false when the scene needs an upload, setMeanByCount is off, nothing has been sampled yet, or the renderer is
    *  a rank of a tile split or a device group.  Defaults: planeTolerance 0.02, normalCosMin 0.9, maxHistory 64 */
   reproject(scene: RaytracingScene, camera: RaytracingCamera, options?: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number }): boolean;
+  /** instead of reset() when scene.needsUpdate is set and the triangle count is unchanged (an object moved, an animation played; the camera
+   *  may have moved too): texels whose triangle did not move carry as in reproject(), texels whose triangle moved follow it back to its old
+   *  place and carry at most maxHistoryMoved samples (include/mi3pt.h: mi3pt_reproject_scene); emits 'reproject'.  Triangle i of the new
+   *  scene must be the surface element triangle i was.  Returns true; falls back to reset() and returns false under reproject()'s conditions,
+   *  when the scene has no triangles, nothing was uploaded yet or the triangle count differs from the last upload.  With scene.needsUpdate
+   *  clear it is reproject().  Defaults: planeTolerance 0.02, normalCosMin 0.9, maxHistory 64, maxHistoryMoved 8 */
+  reprojectScene(scene: RaytracingScene, camera: RaytracingCamera, options?: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number; maxHistoryMoved?: number }): boolean;
   counters(): { rays: number; boxTests: number; triTests: number; hits: number; misses: number; stackOverflows: number; pixels: number };
   /** src/main.ts:351-356: the presented canvas as PNG bytes (written to `file` when given) */
   screenshot(file?: string): Buffer;

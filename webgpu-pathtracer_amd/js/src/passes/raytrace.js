@@ -71,6 +71,18 @@ class RaytracePass extends Pass {
     return { triangles, materials };
   }
 
+  // how many triangles flattenScene would make of the scene, without making them (Renderer.reprojectScene compares it with the last upload's)
+  static countTriangles(scene) {
+    let count = 0;
+    scene.traverse((object) => {
+      if (object instanceof Mesh && object.visible && object.material instanceof RaytracingMaterial) {
+        const indices = object.geometry.getIndex();
+        if (indices) count += Math.ceil(indices.array.length / 3);
+      }
+    });
+    return count;
+  }
+
   // raytrace.ts:104-121 / :138-160: structured views -> bytes
   static packScene(flat) {
     const { triangles, materials } = flat;
@@ -134,6 +146,7 @@ class RaytracePass extends Pass {
     native.uploadMaterials(handle, packed.materialBytes);
     scene.needsUpdate = false;
     this.renderer._sceneVersion++;
+    this.renderer._trianglesUploaded = flat.triangles.length;      // (reprojectScene: the count the next scene must have)
     this.stats = { Triangles: flat.triangles.length, Materials: flat.materials.length, 'BVH Nodes': nodeBytes.length / 48 };
     if (this.renderer.options.verbose) console.table(this.stats);                     // raytrace.ts:528-532
   }

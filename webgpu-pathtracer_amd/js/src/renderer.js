@@ -54,6 +54,7 @@ class Renderer {
     this._aovKey = null;         // ... as they were when all four feature images were last rendered (denoiseGuided)
     this._moments = false;       // setMoments: the moments image is kept beside the running mean
     this._meanByCount = false;   // setMeanByCount: a step's weight comes from the texel's own sample count
+    this._trianglesUploaded = 0; // reprojectScene: the triangle count of the last upload (RaytracePass.updateScene)
     this._seedOffset = 0;        // reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
     this.tile = args.tile || { rank: 0, nranks: 1, blockRows: 8 };
     if (this.options.enableTimestampQuery) this.native.enableTiming(this.handle, 1);
@@ -282,6 +283,39 @@ class Renderer {
     this.update(scene, camera);
     this.native.reproject(this.handle, o.planeTolerance, o.normalCosMin, o.maxHistory);
     this._aovKey = this._aovKeyNow();            // (the call rendered all four images of the new view)
+    this.emit('reproject');
+    this._seedOffset = (this._seedOffset + this._frame - 1) >>> 0;
+    const prevStatus = this.status;
+    this._frame = 1;
+    this.status = prevStatus === 'idle' ? 'sampling' : prevStatus;
+    if (this.status === 'sampling') this.emit('start');
+    return true;
+  }
+  // reprojectScene(scene, camera, { planeTolerance = 0.02, normalCosMin = 0.9, maxHistory = 64, maxHistoryMoved = 8 }): what a host calls
+  // INSTEAD of reset() when scene.needsUpdate is set and the triangle count is unchanged -- an object moved, an animation played; the camera
+  // may have moved too.  Texels whose triangle did not move carry as in reproject(), texels whose triangle moved follow it back to its old
+  // place and carry at most maxHistoryMoved samples (include/mi3pt.h: mi3pt_reproject_scene).  Triangle i of the new scene must be the
+  // surface element triangle i was: flattenScene's order is fixed, so moving, turning or deforming meshes keeps it.  Returns true; falls
+  // back to reset() and returns false under reproject()'s conditions, when the scene has no triangles, nothing was uploaded yet or the
+  // triangle count differs from the last upload.  With scene.needsUpdate clear it is reproject().
+  reprojectScene(scene, camera, options) {
+    if (!scene.needsUpdate) return this.reproject(scene, camera, options);
+    const o = Object.assign({ planeTolerance: 0.02, normalCosMin: 0.9, maxHistory: 64, maxHistoryMoved: 8 }, options || {});
+    const partial = this.tile.nranks !== 1 || Array.isArray(this.devices);
+    const count = RaytracePass.countTriangles(scene);
+    if (!this._meanByCount || this._frame <= 1 || !(this._width > 0) || partial || count === 0 || count !== this._trianglesUploaded) {
+      this.reset();
+      return false;
+    }
+    if (this._aovKey === null || this._aovKey !== this._aovKeyNow()) this.renderAovs();   // the old view's features of the old scene
+    this.native.keepGeometry(this.handle, 1);
+    try {
+      this.update(scene, camera);                // (uploads: the context hands the old records over instead of freeing them)
+      this.native.reprojectScene(this.handle, o.planeTolerance, o.normalCosMin, o.maxHistory, o.maxHistoryMoved);
+    } finally {
+      this.native.keepGeometry(this.handle, 0);
+    }
+    this._aovKey = this._aovKeyNow();            // (the call rendered all four images of the new scene and view)
     this.emit('reproject');
     this._seedOffset = (this._seedOffset + this._frame - 1) >>> 0;
     const prevStatus = this.status;

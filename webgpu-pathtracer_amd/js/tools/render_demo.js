@@ -24,6 +24,10 @@
 //                      Between views renderer.reset(), or with --reproject renderer.setMeanByCount(true) from the start and
 //                      renderer.reproject(scene, camera) (the mean is carried across the move); with --guided-variance every view's PNG
 //                      is drawn from renderer.denoiseGuided({ variance: true, present: true }).  The usual outputs are the last view's
+//   --slide N          N steps of a moving object under a fixed camera: the demo's box slides by --step D (0.1) along x per step and every
+//                      step takes --spp K frames (4); writes <prefix>_step<i>.png, <prefix>_step<i>.acc.f32 and <prefix>_step<i>.uniforms.bin per step.  Between steps
+//                      scene.needsUpdate = true and renderer.reset(), or with --reproject renderer.setMeanByCount(true) from the start and
+//                      renderer.reprojectScene(scene, camera) (the mean follows the box).  Not together with --orbit
 //   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
 //   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
 //                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
@@ -77,7 +81,9 @@ async function main() {
   const untilArg = arg('until', null);
   if (guidedVariance || untilArg !== null) renderer.setMoments(true);
   const orbit = parseInt(arg('orbit', '0'), 10), reproject = process.argv.includes('--reproject');
-  if (orbit > 0 && reproject) renderer.setMeanByCount(true);
+  const slide = parseInt(arg('slide', '0'), 10);
+  if (orbit > 0 && slide > 0) throw new Error('--orbit and --slide both read --step: give one of them');
+  if ((orbit > 0 || slide > 0) && reproject) renderer.setMeanByCount(true);
   renderer.resize(width, height);
   const t0 = Date.now();
   let until = null;
@@ -105,6 +111,24 @@ async function main() {
       fs.writeFileSync(out + '_view' + view + '.uniforms.bin', Buffer.from(renderer.passes.raytrace.uniforms.bytes));
       if (guidedVariance) renderer.denoiseGuided({ variance: true, present: true });
       renderer.screenshot(out + '_view' + view + '.png');
+    }
+  } else if (slide > 0) {
+    const spp = parseInt(arg('spp', '4'), 10), step = parseFloat(arg('step', '0.1'));
+    const box = scene.children.find((c) => c instanceof pt.Mesh && c.geometry instanceof pt.BoxGeometry);
+    if (!box) throw new Error('--slide moves the box of the default scene');
+    const x0 = box.position.x;
+    renderer.frames = spp;
+    for (let k = 0; k < slide; k++) {
+      if (k > 0) {
+        box.position.x = x0 + k * step;
+        scene.needsUpdate = true;
+        if (reproject) renderer.reprojectScene(scene, camera);
+        else renderer.reset();
+      }
+      for (let i = 0; i < spp + 1; i++) renderer.render(scene, camera);      // the last call only presents
+      fs.writeFileSync(out + '_step' + k + '.acc.f32', Buffer.from(renderer.readAccumulation().buffer));
+      fs.writeFileSync(out + '_step' + k + '.uniforms.bin', Buffer.from(renderer.passes.raytrace.uniforms.bytes));
+      renderer.screenshot(out + '_step' + k + '.png');
     }
   } else {
     for (let i = 0; i < frames + 1; i++) renderer.render(scene, camera);   // the last call only presents

@@ -60,6 +60,7 @@ SYMBOLS = (
     "mi3pt_estimate_convergence", "mi3pt_read_convergence", "mi3pt_read_convergence_tiles",
     "mi3pt_set_sample_mask", "mi3pt_read_sample_mask", "mi3pt_freeze_converged", "mi3pt_host_freeze_tiles",
     "mi3pt_set_mean_by_count", "mi3pt_host_view_frame", "mi3pt_reproject",
+    "mi3pt_keep_geometry", "mi3pt_reproject_scene",
 )
 
 
@@ -73,6 +74,12 @@ class ReprojectParams(ctypes.Structure):
     """mi3pt_reproject_params"""
     _fields_ = [("plane_tolerance", ctypes.c_float), ("normal_cos_min", ctypes.c_float), ("max_history", ctypes.c_int),
                 ("flags", ctypes.c_uint)]
+
+
+class ReprojectSceneParams(ctypes.Structure):
+    """mi3pt_reproject_scene_params"""
+    _fields_ = [("plane_tolerance", ctypes.c_float), ("normal_cos_min", ctypes.c_float), ("max_history", ctypes.c_int),
+                ("max_history_moved", ctypes.c_int), ("flags", ctypes.c_uint)]
 
 
 class Convergence(ctypes.Structure):
@@ -150,6 +157,8 @@ def load_library(path=None):
     lib.mi3pt_set_mean_by_count.argtypes = [c_void_p, c_int]
     lib.mi3pt_host_view_frame.argtypes = [c_void_p, c_size_t, c_void_p]
     lib.mi3pt_reproject.argtypes = [c_void_p, ctypes.POINTER(ReprojectParams)]
+    lib.mi3pt_keep_geometry.argtypes = [c_void_p, c_int]
+    lib.mi3pt_reproject_scene.argtypes = [c_void_p, ctypes.POINTER(ReprojectSceneParams)]
     lib.mi3pt_enable_timing.argtypes = [c_void_p, c_int]
     lib.mi3pt_pass_time_us.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]
     lib.mi3pt_raytrace_launch_stats.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
@@ -644,6 +653,19 @@ class Context:
         and drops the sample mask.  Asynchronous.  Needs set_moments(True) and set_mean_by_count(True)."""
         p = ReprojectParams(plane_tolerance, normal_cos_min, int(max_history), int(flags))
         self._c(self.lib.mi3pt_reproject(self.handle, ctypes.byref(p)))
+
+    def keep_geometry(self, keep=True):
+        """Remember the triangle records as they are uploaded now as the previous geometry of reproject_scene (include/mi3pt.h:
+        mi3pt_keep_geometry); the next upload_triangles hands the buffer over instead of freeing it: 112 B per triangle until
+        keep_geometry(False)."""
+        self._c(self.lib.mi3pt_keep_geometry(self.handle, int(bool(keep))))
+
+    def reproject_scene(self, plane_tolerance=0.02, normal_cos_min=0.9, max_history=64, max_history_moved=8, flags=0):
+        """reproject across a scene change (include/mi3pt.h: mi3pt_reproject_scene): a texel whose triangle moved since keep_geometry
+        looks its point of the kept triangle up in the old view and carries at most max_history_moved samples; the others are
+        reproject's, bit for bit.  The POSITION / NORMAL / IDS images must be of the kept geometry.  Asynchronous."""
+        p = ReprojectSceneParams(plane_tolerance, normal_cos_min, int(max_history), int(max_history_moved), int(flags))
+        self._c(self.lib.mi3pt_reproject_scene(self.handle, ctypes.byref(p)))
 
     def bind_accumulation(self, dev_ptr, nbytes):
         self._c(self.lib.mi3pt_bind_accumulation(self.handle, dev_ptr, nbytes))

@@ -128,6 +128,7 @@ class RaytracePass(Pass):
         ctx.upload_materials(content.material_bytes)
         scene.needsUpdate = False
         self.renderer._sceneVersion += 1
+        self.renderer._trianglesUploaded = len(content.triangles)      # (reprojectScene: the count the next scene must have)
 
     def render(self, encoder):                    # raytrace.ts:696-708
         encoder.append(capi.SUBMIT_RAYTRACE)
@@ -196,6 +197,7 @@ class Renderer:
         self._aovKey = None                # ... as they were when all four feature images were last rendered (denoiseGuided)
         self._moments = False              # setMoments: the moments image is kept beside the running mean
         self._meanByCount = False          # setMeanByCount: a step's weight comes from the texel's own sample count
+        self._trianglesUploaded = 0        # reprojectScene: the triangle count of the last upload (updateScene)
         self._seedOffset = 0               # reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
         self.passes = {"raytrace": RaytracePass(self), "accumulate": AccumulatePass(self),
                        "fullscreen": FullscreenPass(self)}
@@ -445,6 +447,39 @@ class Renderer:
         self.update(scene, camera)
         ctx.reproject(planeTolerance, normalCosMin, maxHistory)
         self._aovKey = self._aovKeyNow()           # (the call rendered all four images of the new view)
+        self.emit("reproject")
+        self._seedOffset = (self._seedOffset + self._frame - 1) & 0xFFFFFFFF
+        prev = self.status
+        self._frame = 1
+        self.status = "sampling" if prev == "idle" else prev
+        if self.status == "sampling":
+            self.emit("start")
+        return True
+
+    def reprojectScene(self, scene, camera, planeTolerance=0.02, normalCosMin=0.9, maxHistory=64, maxHistoryMoved=8):
+        """What a host calls INSTEAD of reset() when scene.needsUpdate is set and the triangle count is unchanged -- an object moved,
+        an animation played; the camera may have moved too: texels whose triangle did not move carry as in reproject(), texels whose
+        triangle moved follow it back to its old place and carry at most maxHistoryMoved samples (include/mi3pt.h:
+        mi3pt_reproject_scene).  Triangle i of the new content must be the surface element triangle i was.  Returns True; falls back
+        to reset() and returns False under reproject()'s conditions, when the scene has no content, nothing was uploaded yet or the
+        triangle count differs from the last upload.  With scene.needsUpdate clear it is reproject()."""
+        if not scene.needsUpdate:
+            return self.reproject(scene, camera, planeTolerance, normalCosMin, maxHistory)
+        ctx = self.ctx
+        partial = ctx.group_size != 1 or ctx._tile[1] != 1          # (a device group, or a rank of a tile split as of the last resize)
+        count = 0 if scene.content is None else len(scene.content.triangles)
+        if not self._meanByCount or self._frame <= 1 or not self._width or partial or count == 0 or count != self._trianglesUploaded:
+            self.reset()
+            return False
+        if self._aovKey is None or self._aovKey != self._aovKeyNow():
+            self.renderAovs()                      # the old view's features of the old scene
+        ctx.keep_geometry(True)
+        try:
+            self.update(scene, camera)             # (uploads: the context hands the old records over instead of freeing them)
+            ctx.reproject_scene(planeTolerance, normalCosMin, maxHistory, maxHistoryMoved)
+        finally:
+            ctx.keep_geometry(False)
+        self._aovKey = self._aovKeyNow()           # (the call rendered all four images of the new scene and view)
         self.emit("reproject")
         self._seedOffset = (self._seedOffset + self._frame - 1) & 0xFFFFFFFF
         prev = self.status
