@@ -28,7 +28,7 @@
  *     kernels run on internal streams tied to it by events in both directions, which no caller can see.
  *     STREAM ORDERED, returning before the device has run anything: mi3pt_submit, mi3pt_submit_frames, mi3pt_flush,
  *     mi3pt_reset, mi3pt_reset_counters, mi3pt_render_aovs, mi3pt_denoise_guided, mi3pt_estimate_convergence, mi3pt_reproject,
- *     mi3pt_reproject_scene, mi3pt_set_mean_by_count, mi3pt_set_sample_mask (it launches the frame queue, under the old mask, and waits for nothing).  mi3pt_set_uniforms, the setters of
+ *     mi3pt_reproject_scene, mi3pt_hold_history, mi3pt_merge_history, mi3pt_set_mean_by_count, mi3pt_set_sample_mask (it launches the frame queue, under the old mask, and waits for nothing).  mi3pt_set_uniforms, the setters of
  *     modes and options and the *_device_ptr getters start no device work of their own (those that observe state launch
  *     the frame queue first).  A host that has set its own stream may therefore enqueue its work in front of and behind
  *     these calls on that stream -- fill a bound accumulation tensor, copy out of a *_device_ptr image -- and wait once.
@@ -71,7 +71,8 @@ extern "C" {
  * mi3pt_guided_device_ptr, struct mi3pt_guided_params, MI3PT_GUIDED_PRESENT, MI3PT_PASS_GUIDED (4); mi3pt_estimate_convergence,
  * mi3pt_read_convergence, mi3pt_read_convergence_tiles, struct mi3pt_convergence, MI3PT_PASS_CONVERGENCE (5); mi3pt_set_sample_mask,
  * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles; mi3pt_set_mean_by_count, mi3pt_host_view_frame, mi3pt_reproject,
- * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6); mi3pt_keep_geometry, mi3pt_reproject_scene, struct mi3pt_reproject_scene_params. */
+ * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6); mi3pt_keep_geometry, mi3pt_reproject_scene, struct mi3pt_reproject_scene_params;
+ * mi3pt_hold_history, mi3pt_merge_history, struct mi3pt_history_params, MI3PT_HISTORY_EPS, MI3PT_PASS_HISTORY (7). */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -103,8 +104,10 @@ typedef enum mi3pt_pass {
                                     Known to mi3pt_pass_time_us only */
     MI3PT_PASS_CONVERGENCE = 5,  /* -- no counterpart: the per-tile error estimate (mi3pt_estimate_convergence), its tile kernel and the
                                     kernel that folds the summary.  Known to mi3pt_pass_time_us only */
-    MI3PT_PASS_REPROJECT = 6     /* -- no counterpart: the gather kernel of mi3pt_reproject and the copy into a bound accumulation image (the
+    MI3PT_PASS_REPROJECT = 6,    /* -- no counterpart: the gather kernel of mi3pt_reproject and the copy into a bound accumulation image (the
                                     feature render inside that call is MI3PT_PASS_AOV's).  Known to mi3pt_pass_time_us only */
+    MI3PT_PASS_HISTORY = 7       /* -- no counterpart: the kernel of mi3pt_merge_history and the copy into a bound accumulation image.
+                                    Known to mi3pt_pass_time_us only */
 } mi3pt_pass;
 
 #define MI3PT_SUBMIT_RAYTRACE 1u
@@ -687,6 +690,65 @@ typedef struct mi3pt_reproject_scene_params {
     unsigned flags;            /* 0 */
 } mi3pt_reproject_scene_params;
 int mi3pt_reproject_scene(mi3pt_ctx *ctx, const mi3pt_reproject_scene_params *params);
+
+/* ---- a held history, validated against fresh samples before it is merged -- no counterpart in the reference.  Both reprojections merge
+ * what they carry into the live mean at once; radiance that changed although the surface did not (a repainted material, a dimmed
+ * environment, a shadow that moved) then stays in the picture until new samples outweigh the carried ones.  The temporal validation of
+ * an SVGF-style loop: set the carried mean ASIDE, sample a few frames of the scene as it is now, and merge per texel only as much of
+ * the carried history as a two-sample test of "fresh mean against carried mean" supports.  The moments image holds the per-sample
+ * variance of both sides, so the test needs no new input.
+ * mi3pt_hold_history, in order:  1 launches the frame queue;  2 makes the accumulation and moments images the HELD pair (a second pair
+ * of images, allocated by the first call and freed by mi3pt_resize / mi3pt_destroy): a swap of pointers where the image is the
+ * context's own, a copy on the stream out of memory bound by mi3pt_bind_accumulation;  3 leaves the live accumulation and moments
+ * images zero-filled, as mi3pt_reset leaves them.  Output, canvas, feature images, sample mask and counters are untouched; under the
+ * mean by count every texel restarts with its next frame.  Called after mi3pt_reproject / mi3pt_reproject_scene, or at any time; a
+ * second hold replaces the first.  mi3pt_reset, mi3pt_resize, mi3pt_reproject, mi3pt_reproject_scene, mi3pt_set_moments(ctx, 0) and
+ * mi3pt_destroy DROP a held history (the reprojections: when they pass their checks); nothing else about them changes.
+ * mi3pt_merge_history, in order:  1 launches the frame queue;  2 runs the kernel below from the live pair (A, M) and the held pair
+ * (Ah, Mh) into mi3pt_reproject's scratch pair;  3 makes the scratch pair the accumulation and moments images as step 6 of
+ * mi3pt_reproject does;  4 marks the history as no longer held.
+ * Both are asynchronous and stream ordered, change no counter and nothing mi3pt_debug_last_launch / MI3PT_OPT_LAST_BUILD report.
+ * Because of the swaps, pointers handed out earlier by mi3pt_accumulation_device_ptr (of the context's own image) and
+ * mi3pt_moments_device_ptr name other images after either call: ask again.
+ * The kernel.  Pinned fp32: correctly rounded division, nothing contracted, fmaxf / fminf return the other operand for a NaN;
+ * r = radius.  Live texel (a, .) = A(q), (m2, n) = M(q); held texel (ah, .) = Ah(q), (m2h, nh) = Mh(q).
+ *   pair(q) iff q lies inside the image and the accumulate block's rectangle, and n >= 1 && nh >= 1        (a NaN fails)
+ *   var(m2, n).k = n >= 2 ? fmaxf(m2.k / (n - 1), 0) : 0
+ * For every texel p = (x, y) inside the rectangle, D = V = 0, then for dy = -r .. r outer, dx = -r .. r inner, q = (x + dx, y + dy), the
+ * taps with pair(q) in that order:
+ *       sf = var(m2, n);   sh = var(m2h, nh);   w = 1 / n + 1 / nh
+ *       D.k = D.k + (a.k - ah.k);   V.k = V.k + fmaxf(sf.k, sh.k) * w
+ *   z.k = (D.k * D.k) / (V.k + MI3PT_HISTORY_EPS);   z2 = fmaxf(fmaxf(z.x, z.y), z.z)
+ *   drop2 = z_drop * z_drop;   keep2 = z_keep * z_keep;   lam = fminf(fmaxf((drop2 - z2) / (drop2 - keep2), 0), 1)
+ *   nk = floorf(nh(p) * lam)
+ *   dropped   (n(p) >= 1 and: !(nh(p) >= 1), or !(nk >= 1)):    A'(p) = A(p);   M'(p) = M(p)
+ *   only held (!(n(p) >= 1) and nh(p) >= 1):                     A'(p) = Ah(p);  M'(p) = Mh(p)
+ *   neither   (!(n(p) >= 1) and !(nh(p) >= 1)):                  A'(p) = A(p);   M'(p) = M(p)
+ *   merged, with d.k = ah.k - a.k and sh = var(m2h, nh) at p:
+ *       N = n + nk;   f = nk / N
+ *       A'(p) = (stored a.k + d.k * f, 1)                          (rounded to binary16 under MI3PT_STORAGE_F16)
+ *       M'(p) = ((m2.k + sh.k * (nk - 1)) + (d.k * d.k) * (n * f), N)
+ * Texels outside the rectangle keep their bits.  z2 is the largest squared z-score of the pooled difference among the channels;
+ * at or below z_keep the whole held history is kept, at or above z_drop none of it, a share linear in z2 in between.  The merge is
+ * Chan's pairwise combine of the live samples with nk samples of the held mean and the held per-sample variance: a shortened history
+ * keeps its variance, as max_history does, and counts stay whole numbers.  A z_drop whose square overflows, or squares that round to
+ * the same number, give lam = 0 (everything dropped).  Non-finite inputs give unspecified values; every index is range-checked before
+ * it is used, so they neither hang nor fault.
+ *   MI3PT_ERR_STATE before mi3pt_resize; while moments or the mean by count are off; for a rank of a tile split with more than one
+ *   rank and for a device group (a window crosses rows; the halo exchange is NOT BUILT); mi3pt_merge_history also while nothing is
+ *   held.  MI3PT_ERR_INVALID for a null pointer, a radius outside 0 .. 3, a z_keep that is negative or not finite, a z_drop that is
+ *   not finite or not above z_keep, non-zero flags.
+ * With timing enabled, mi3pt_pass_time_us(MI3PT_PASS_HISTORY) is the device time of the kernel and the copy of the most recent
+ * mi3pt_merge_history.  NOT BUILT: a host that reads the test's verdict without merging. ---- */
+#define MI3PT_HISTORY_EPS 1e-8f
+typedef struct mi3pt_history_params {
+    int   radius;     /* 0 .. 3: the test pools (2*radius+1)^2 texels */
+    float z_keep;     /* finite, >= 0: at or below it the whole carried history is kept */
+    float z_drop;     /* finite, > z_keep: at or above it none of it is */
+    unsigned flags;   /* 0 */
+} mi3pt_history_params;
+int mi3pt_hold_history(mi3pt_ctx *ctx);
+int mi3pt_merge_history(mi3pt_ctx *ctx, const mi3pt_history_params *params);
 
 /* ---- read-back (the capability a headless drop-in needs; the reference only has
  * canvas.toDataURL, main.ts:351-356).  Blocking.  dst holds rows x width x 4 floats

@@ -338,6 +338,11 @@ struct mi3pt_ctx {
     float4 *d_aov_prev[MI3PT_AOV_COUNT] = {};
     float4 *d_reproject[2] = {};
     PassTimer reproject_timer;
+    // The held history (mi3pt_hold_history, mi3pt_merge_history; pt_history.hip).  d_hold: the held (mean, moments), allocated by the first
+    // hold and freed with the textures (or with the moments image); history_held: they hold a history that nothing has dropped or merged.
+    float4 *d_hold[2] = {};
+    bool history_held = false;
+    PassTimer history_timer;
     // The previous geometry (mi3pt_keep_geometry, mi3pt_reproject_scene).  upload_epoch counts the uploads of triangles, BVH and materials (scene_epoch also
     // moves with the lazy analyses, which change no record); aov_epoch: its value when each feature image was rendered.  geometry_kept:
     // d_tris as it stood at kept_epoch is the previous geometry -- d_tris itself while d_tris_kept is null (nothing uploaded since), else
@@ -802,6 +807,9 @@ static void free_textures(mi3pt_ctx *ctx)
     for (float4 *&p : ctx->d_aov_prev) { if (p) (void)hipFree(p); p = nullptr; }
     for (float4 *&p : ctx->d_reproject) { if (p) (void)hipFree(p); p = nullptr; }
     ctx->reproject_timer.forget();
+    for (float4 *&p : ctx->d_hold) { if (p) (void)hipFree(p); p = nullptr; }
+    ctx->history_held = false;
+    ctx->history_timer.forget();
     if (ctx->d_conv_tiles) (void)hipFree(ctx->d_conv_tiles);
     if (ctx->d_conv_parts) (void)hipFree(ctx->d_conv_parts);
     if (ctx->d_conv_summary) (void)hipFree(ctx->d_conv_summary);
@@ -839,7 +847,7 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     for (void *p : { ctx->d_cw8, ctx->d_tripk8, ctx->d_cwide, ctx->d_tripk64, ctx->d_wide, ctx->d_tris, ctx->d_tris_kept, ctx->d_tris_perm, ctx->d_nodes, ctx->d_mats, ctx->d_env, ctx->d_cdf, ctx->d_packets, ctx->d_tripk, ctx->d_leaf_rank,
                      (void *)ctx->d_tile_counter, (void *)ctx->d_drain_flag, (void *)ctx->d_wave_times, (void *)ctx->d_stack_overflow, (void *)ctx->d_park, (void *)ctx->d_service, ctx->d_fs_taps })
         if (p) (void)hipFree(p);
-    for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer, &ctx->conv_timer, &ctx->reproject_timer }) t->destroy();
+    for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer, &ctx->conv_timer, &ctx->reproject_timer, &ctx->history_timer }) t->destroy();
     if (ctx->conv_read_stream) {
         (void)hipStreamSynchronize(ctx->conv_read_stream);
         (void)hipStreamDestroy(ctx->conv_read_stream);
@@ -1264,6 +1272,7 @@ static int zero_textures(mi3pt_ctx *ctx)
         HIP_TRY(hipMemsetAsync(ctx->d_canvas, 0, canvas_px * 16, ctx->stream));
         HIP_TRY(hipMemsetAsync(ctx->d_canvas8, 0, canvas_px * 4, ctx->stream));
     }
+    ctx->history_held = false;        // (mi3pt_reset, mi3pt_resize: a held history goes with the mean)
     ctx->output_is_accum = false;
     ctx->last_radiance = ctx->d_radiance;
     ctx->main_dirty = true;
@@ -2767,6 +2776,8 @@ extern "C" int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled)
     if (!on) {
         if (ctx->d_moments) (void)hipFree(ctx->d_moments);
         ctx->d_moments = nullptr;
+        for (float4 *&p : ctx->d_hold) { if (p) (void)hipFree(p); p = nullptr; }      // (a held history is a mean WITH its moments)
+        ctx->history_held = false;
         ctx->moments = false;
         ctx->by_count = false;      // (the count is the image's n: the mode goes with it)
         return MI3PT_OK;
@@ -2888,6 +2899,7 @@ static int reproject_run(mi3pt_ctx *ctx, const ReprojectCall &c)
                 return pt_set_error(MI3PT_ERR_STATE, who + ": the POSITION, NORMAL and IDS images were not rendered from the kept geometry (an upload lies between them and mi3pt_keep_geometry)");
     }
     if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far belongs to the old view's mean
+    ctx->history_held = false;                       // (what was held belongs to the view before this one)
     pt::ReprojectSceneLaunch S;
     pt::ReprojectLaunch &R = S.view;
     if (int rc = mi3pt_host_view_frame(u0, MI3PT_RAYTRACE_UNIFORMS_SIZE, R.f0)) return rc;
@@ -2970,6 +2982,90 @@ extern "C" int mi3pt_reproject_scene(mi3pt_ctx *ctx, const mi3pt_reproject_scene
     if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     return reproject_run(ctx, { "mi3pt_reproject_scene", params->plane_tolerance, params->normal_cos_min, params->max_history,
                                 params->max_history_moved, params->flags, true });
+}
+
+// ---- the held history and its validated merge (include/mi3pt.h: mi3pt_hold_history, mi3pt_merge_history; pt_history.hip) ----
+static int history_state(mi3pt_ctx *ctx, const std::string &who)
+{
+    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, who + " before resize");
+    if (!ctx->moments || !ctx->d_moments || !ctx->by_count)
+        return pt_set_error(MI3PT_ERR_STATE, who + " needs the moments image and the mean by count (mi3pt_set_moments, mi3pt_set_mean_by_count)");
+    if (ctx->partial())
+        return pt_set_error(MI3PT_ERR_STATE, who + ": not built for a rank of a tile split (a window crosses the ranks' rows; no halo exchange)");
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_hold_history(mi3pt_ctx *ctx)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_hold_history: not built for a device group (a window crosses the members' rows; no halo exchange)"));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (int rc = history_state(ctx, "mi3pt_hold_history")) return rc;
+    if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far belongs to the history that is held
+    const size_t tex_bytes = plane_bytes(ctx);
+    for (float4 *&p : ctx->d_hold)
+        if (!p) HIP_TRY(alloc_plane(&p, tex_bytes));
+    ctx->history_held = false;        // (a failure below leaves nothing half held)
+    // the images become the held pair: the context's own by a swap of pointers, a bound accumulation image by a copy on the stream
+    std::swap(ctx->d_moments, ctx->d_hold[1]);
+    if (ctx->d_accum == ctx->d_accum_own) {
+        std::swap(ctx->d_accum_own, ctx->d_hold[0]);
+        ctx->d_accum = ctx->d_accum_own;
+    } else if (tex_bytes) {
+        HIP_TRY(hipMemcpyAsync(ctx->d_hold[0], ctx->d_accum, tex_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    ctx->main_dirty = true;
+    ctx->accum_version++;
+    if (tex_bytes) {                  // the live pair as mi3pt_reset leaves it
+        HIP_TRY(hipMemsetAsync(ctx->d_accum, 0, tex_bytes, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, tex_bytes, ctx->stream));
+    }
+    ctx->history_held = true;
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_merge_history(mi3pt_ctx *ctx, const mi3pt_history_params *params)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_merge_history: not built for a device group (a window crosses the members' rows; no halo exchange)"));
+    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (params->radius < 0 || params->radius > 3) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_merge_history: radius must be 0 .. 3");
+    if (!(params->z_keep >= 0.0f) || std::isinf(params->z_keep))
+        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_merge_history: z_keep must be finite and >= 0");
+    if (!(params->z_drop > params->z_keep) || std::isinf(params->z_drop))
+        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_merge_history: z_drop must be finite and above z_keep");
+    if (params->flags) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_merge_history: unknown flag bits");
+    if (int rc = require_ctx(ctx)) return rc;
+    if (int rc = history_state(ctx, "mi3pt_merge_history")) return rc;
+    if (!ctx->history_held || !ctx->d_hold[0] || !ctx->d_hold[1])
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_merge_history: no history is held (mi3pt_hold_history; a reset, a resize and a reprojection drop it)");
+    if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far is a fresh sample of the test
+    const size_t tex_bytes = plane_bytes(ctx);
+    for (float4 *&p : ctx->d_reproject)
+        if (!p) HIP_TRY(alloc_plane(&p, tex_bytes));
+    const pt::AccUniforms acc = acc_uniforms(ctx);
+    pt::HistoryLaunch L;
+    L.accum = ctx->d_accum; L.moments = ctx->d_moments;
+    L.accum_held = ctx->d_hold[0]; L.moments_held = ctx->d_hold[1];
+    L.accum_out = ctx->d_reproject[0]; L.moments_out = ctx->d_reproject[1];
+    L.width = ctx->width; L.rows = ctx->local_rows;
+    L.res_w = acc.res_w; L.res_h = acc.res_h;
+    L.radius = params->radius; L.z_keep = params->z_keep; L.z_drop = params->z_drop;
+    L.store_f16 = ctx->storage == MI3PT_STORAGE_F16;
+    if (ctx->timing) HIP_TRY(ctx->history_timer.begin(ctx->stream));
+    pt::launch_history(L, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    // the scratch pair takes the images' place: the context's own by a swap of pointers, a bound accumulation image by a copy on the stream
+    std::swap(ctx->d_moments, ctx->d_reproject[1]);
+    if (ctx->d_accum == ctx->d_accum_own) {
+        std::swap(ctx->d_accum_own, ctx->d_reproject[0]);
+        ctx->d_accum = ctx->d_accum_own;
+    } else if (tex_bytes) {
+        HIP_TRY(hipMemcpyAsync(ctx->d_accum, ctx->d_reproject[0], tex_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (ctx->timing) HIP_TRY(ctx->history_timer.end(ctx->stream));
+    ctx->history_held = false;
+    ctx->main_dirty = true;
+    ctx->accum_version++;
+    return MI3PT_OK;
 }
 
 // ---- the per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip) ----
@@ -3131,6 +3227,7 @@ extern "C" int mi3pt_pass_time_us(mi3pt_ctx *ctx, int pass, float *microseconds)
     if (microseconds && pass == MI3PT_PASS_AOV) return ctx->aov_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_render_aovs since the last resize");
     if (microseconds && pass == MI3PT_PASS_GUIDED) return ctx->guided_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_denoise_guided since the last resize");
     if (microseconds && pass == MI3PT_PASS_REPROJECT) return ctx->reproject_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_reproject since the last resize");
+    if (microseconds && pass == MI3PT_PASS_HISTORY) return ctx->history_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_merge_history since the last resize");
     if (microseconds && pass == MI3PT_PASS_CONVERGENCE) return ctx->conv_timer.elapsed_us(ctx, microseconds, "no timed mi3pt_estimate_convergence since the last resize");
     if (!microseconds || pass < 0 || pass > 2) return pt_set_error(MI3PT_ERR_INVALID, "bad argument");
     if (pass == MI3PT_PASS_RAYTRACE && !ctx->pass_timer[0].recorded && (ctx->ev_rt_pending[0] || ctx->ev_rt_pending[1] || ctx->rt_launches)) {

@@ -477,6 +477,18 @@ struct ReprojectSceneLaunch {
     float max_history_moved;
 };
 void launch_reproject_scene(const ReprojectSceneLaunch &S, hipStream_t s);
+// The validated merge of a held (mean, moments) pair into the live one (include/mi3pt.h: mi3pt_merge_history; pt_history.hip), all images
+// rows x width float4.  res_w / res_h: the accumulate block's rectangle; radius 0 .. 3.  The outputs must not alias the inputs.
+struct HistoryLaunch {
+    const float4 *accum, *moments, *accum_held, *moments_held;
+    float4 *accum_out, *moments_out;
+    int32_t width, rows;
+    uint32_t res_w, res_h;
+    int32_t radius;
+    float z_keep, z_drop;
+    int32_t store_f16;
+};
+void launch_history(const HistoryLaunch &H, hipStream_t s);
 // packs the three position vectors of `ntris` 112-byte triangle records into 48-byte rows (the context's cull analysis)
 void launch_pack_vertices(const float4 *tris, float4 *out, uint32_t ntris, hipStream_t s);
 // writes NodePacket::cull of `npackets` packets from a dense array (the context's cull analysis)

@@ -636,6 +636,38 @@ napi_value ReprojectScene(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+// holdHistory(ctx): mi3pt_hold_history -- the mean and its moments are set aside, the live pair restarts
+napi_value HoldHistory(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    if (!get_args(env, info, a, 1) || !get_ctx(env, a.v[0], &ctx)) return nullptr;
+    MI3PT_TRY(mi3pt_hold_history(ctx));
+    return undefined(env);
+}
+
+// mergeHistory(ctx, radius, zKeep, zDrop): mi3pt_merge_history -- the held history merged into the mean sampled since, per texel as much
+// of it as the test over a (2 * radius + 1)^2 window supports
+napi_value MergeHistory(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t radius;
+    double z_keep, z_drop;
+    if (!get_args(env, info, a, 4) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &radius)) return nullptr;
+    if (napi_get_value_double(env, a.v[2], &z_keep) != napi_ok || napi_get_value_double(env, a.v[3], &z_drop) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "expected a number");
+        return nullptr;
+    }
+    mi3pt_history_params p;
+    p.radius = radius;
+    p.z_keep = (float)z_keep;
+    p.z_drop = (float)z_drop;
+    p.flags = 0;
+    MI3PT_TRY(mi3pt_merge_history(ctx, &p));
+    return undefined(env);
+}
+
 // hostViewFrame(raytraceUniforms: 96 bytes) -> Float32Array of 16 (mi3pt_host_view_frame; no device)
 napi_value HostViewFrame(napi_env env, napi_callback_info info)
 {
@@ -865,6 +897,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "setSampleMask", SetSampleMask }, { "readSampleMask", ReadSampleMask }, { "freezeConverged", FreezeConverged },
         { "setMeanByCount", SetMeanByCount }, { "reproject", Reproject }, { "hostViewFrame", HostViewFrame },
         { "keepGeometry", KeepGeometry }, { "reprojectScene", ReprojectScene },
+        { "holdHistory", HoldHistory }, { "mergeHistory", MergeHistory },
     };
     for (const auto &f : fns) {
         napi_value v;

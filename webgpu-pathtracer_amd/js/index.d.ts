@@ -161,6 +161,9 @@ export class Renderer {
    *  to reset() and returns false when the scene needs an upload, setMeanByCount is off, nothing has been sampled yet, or the renderer is
    *  a rank of a tile split or a device group.  Defaults: planeTolerance 0.02, normalCosMin 0.9, maxHistory 64 */
   reproject(scene: RaytracingScene, camera: RaytracingCamera, options?: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number }): boolean;
+  /** ... with validate: K > 0 the carried mean is held (holdHistory) and merged by mergeHistory() with its defaults once render() has
+   *  submitted K further sampled frames; 0, the default, merges at once as above */
+  reproject(scene: RaytracingScene, camera: RaytracingCamera, options: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number; validate?: number }): boolean;
   /** instead of reset() when scene.needsUpdate is set and the triangle count is unchanged (an object moved, an animation played; the camera
    *  may have moved too): texels whose triangle did not move carry as in reproject(), texels whose triangle moved follow it back to its old
    *  place and carry at most maxHistoryMoved samples (include/mi3pt.h: mi3pt_reproject_scene); emits 'reproject'.  Triangle i of the new
@@ -168,6 +171,15 @@ export class Renderer {
    *  when the scene has no triangles, nothing was uploaded yet or the triangle count differs from the last upload.  With scene.needsUpdate
    *  clear it is reproject().  Defaults: planeTolerance 0.02, normalCosMin 0.9, maxHistory 64, maxHistoryMoved 8 */
   reprojectScene(scene: RaytracingScene, camera: RaytracingCamera, options?: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number; maxHistoryMoved?: number }): boolean;
+  /** ... validate: as in reproject() */
+  reprojectScene(scene: RaytracingScene, camera: RaytracingCamera, options: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number; maxHistoryMoved?: number; validate?: number }): boolean;
+  /** set the running mean and its moments aside and restart the live pair as reset() would (include/mi3pt.h: mi3pt_hold_history); the frame
+   *  counter, the canvas and the feature images stay.  Needs setMeanByCount(true).  A reset(), a resize() and a reproject() drop what is held */
+  holdHistory(): void;
+  /** merge the held history into the mean sampled since holdHistory(): per texel as much of it as a two-sample test of the fresh mean against
+   *  the held one over a (2 * radius + 1)^2 window supports -- all of it up to a z-score of zKeep, none of it from zDrop (include/mi3pt.h:
+   *  mi3pt_merge_history).  Defaults: radius 1, zKeep 2, zDrop 4 */
+  mergeHistory(options?: { radius?: number; zKeep?: number; zDrop?: number }): void;
   counters(): { rays: number; boxTests: number; triTests: number; hits: number; misses: number; stackOverflows: number; pixels: number };
   /** src/main.ts:351-356: the presented canvas as PNG bytes (written to `file` when given) */
   screenshot(file?: string): Buffer;

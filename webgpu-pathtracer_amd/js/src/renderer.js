@@ -56,6 +56,7 @@ class Renderer {
     this._meanByCount = false;   // setMeanByCount: a step's weight comes from the texel's own sample count
     this._trianglesUploaded = 0; // reprojectScene: the triangle count of the last upload (RaytracePass.updateScene)
     this._seedOffset = 0;        // reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
+    this._validateLeft = 0;      // reproject({ validate: K }): sampled frames still to submit before the held history is merged
     this.tile = args.tile || { rank: 0, nranks: 1, blockRows: 8 };
     if (this.options.enableTimestampQuery) this.native.enableTiming(this.handle, 1);
     this.passes = {
@@ -164,6 +165,7 @@ class Renderer {
     if (shouldSample) this.passes.accumulate.render(commandEncoder);
     if (this.options.presentEveryFrame) this.passes.fullscreen.render(commandEncoder);
     if (commandEncoder.passes) this.native.submit(this.handle, commandEncoder.passes);   // queue.submit
+    if (shouldSample && this._validateLeft > 0 && --this._validateLeft === 0) this.mergeHistory();   // (reproject({ validate: K }): K fresh frames are in; the defaults)
     if (shouldSample) this.passes.raytrace.updateTimings();
     if (shouldSample) this.passes.accumulate.updateTimings();
     if (this.options.presentEveryFrame) this.passes.fullscreen.updateTimings();
@@ -172,6 +174,7 @@ class Renderer {
   reset() {                                                                  // renderer.ts:397-416
     const prevStatus = this.status;
     this.status = 'paused';
+    this._validateLeft = 0;                      // (the context drops a held history with the mean)
     if (this._width > 0) this.native.reset(this.handle);
     this.emit('reset');
     this._frame = 1;
@@ -256,7 +259,7 @@ class Renderer {
   setMoments(enabled) {
     this.native.setMoments(this.handle, enabled ? 1 : 0);
     this._moments = !!enabled;
-    if (!enabled) this._meanByCount = false;     // (the count is the image's n: the context switches the mode off with it)
+    if (!enabled) { this._meanByCount = false; this._validateLeft = 0; }   // (the count is the image's n: the context switches the mode off with it and drops a held history)
   }
   // ---- the mean by count and the reprojection of the mean across a camera move (no counterpart in the reference; include/mi3pt.h:
   // mi3pt_set_mean_by_count, mi3pt_reproject).  setMeanByCount(on = true): every accumulate step takes its weight from the texel's own
@@ -271,18 +274,22 @@ class Renderer {
   // reproject(scene, camera, { planeTolerance = 0.02, normalCosMin = 0.9, maxHistory = 64 }): what a host calls INSTEAD of reset() when
   // only the camera changed -- the running mean and its moments are carried into the new view, texels the old view did not see restart,
   // the frame budget starts over.  Returns true; falls back to reset() and returns false when the scene needs an upload, setMeanByCount
-  // is off, nothing has been sampled yet, or the context is a rank of a tile split or a device group.
+  // is off, nothing has been sampled yet, or the context is a rank of a tile split or a device group.  validate: K > 0 (default 0): the
+  // carried mean is held (holdHistory) and merged by mergeHistory() with its defaults once render() has submitted K further sampled frames.
   reproject(scene, camera, options) {
     const o = Object.assign({ planeTolerance: 0.02, normalCosMin: 0.9, maxHistory: 64 }, options || {});
+    o.validate = Renderer._validateFrames(o.validate);
     const partial = this.tile.nranks !== 1 || Array.isArray(this.devices);
     if (scene.needsUpdate || !this._meanByCount || this._frame <= 1 || !(this._width > 0) || partial) {
       this.reset();
       return false;
     }
+    this._settleValidation();
     if (this._aovKey === null || this._aovKey !== this._aovKeyNow()) this.renderAovs();   // the old view's features, under the uniforms the mean was sampled with
     this.update(scene, camera);
     this.native.reproject(this.handle, o.planeTolerance, o.normalCosMin, o.maxHistory);
     this._aovKey = this._aovKeyNow();            // (the call rendered all four images of the new view)
+    this._startValidation(o.validate);
     this.emit('reproject');
     this._seedOffset = (this._seedOffset + this._frame - 1) >>> 0;
     const prevStatus = this.status;
@@ -297,16 +304,18 @@ class Renderer {
   // place and carry at most maxHistoryMoved samples (include/mi3pt.h: mi3pt_reproject_scene).  Triangle i of the new scene must be the
   // surface element triangle i was: flattenScene's order is fixed, so moving, turning or deforming meshes keeps it.  Returns true; falls
   // back to reset() and returns false under reproject()'s conditions, when the scene has no triangles, nothing was uploaded yet or the
-  // triangle count differs from the last upload.  With scene.needsUpdate clear it is reproject().
+  // triangle count differs from the last upload.  With scene.needsUpdate clear it is reproject().  validate: as in reproject().
   reprojectScene(scene, camera, options) {
     if (!scene.needsUpdate) return this.reproject(scene, camera, options);
     const o = Object.assign({ planeTolerance: 0.02, normalCosMin: 0.9, maxHistory: 64, maxHistoryMoved: 8 }, options || {});
+    o.validate = Renderer._validateFrames(o.validate);
     const partial = this.tile.nranks !== 1 || Array.isArray(this.devices);
     const count = RaytracePass.countTriangles(scene);
     if (!this._meanByCount || this._frame <= 1 || !(this._width > 0) || partial || count === 0 || count !== this._trianglesUploaded) {
       this.reset();
       return false;
     }
+    this._settleValidation();
     if (this._aovKey === null || this._aovKey !== this._aovKeyNow()) this.renderAovs();   // the old view's features of the old scene
     this.native.keepGeometry(this.handle, 1);
     try {
@@ -316,6 +325,7 @@ class Renderer {
       this.native.keepGeometry(this.handle, 0);
     }
     this._aovKey = this._aovKeyNow();            // (the call rendered all four images of the new scene and view)
+    this._startValidation(o.validate);
     this.emit('reproject');
     this._seedOffset = (this._seedOffset + this._frame - 1) >>> 0;
     const prevStatus = this.status;
@@ -323,6 +333,34 @@ class Renderer {
     this.status = prevStatus === 'idle' ? 'sampling' : prevStatus;
     if (this.status === 'sampling') this.emit('start');
     return true;
+  }
+  // ---- a held history, validated against fresh samples before it is merged (no counterpart in the reference; include/mi3pt.h:
+  // mi3pt_hold_history, mi3pt_merge_history).  holdHistory(): the running mean and its moments are set aside and the live pair restarts,
+  // as reset() would restart it; the frame counter, the canvas and the feature images stay.  Needs setMeanByCount(true).  A reset(), a
+  // resize() and a reproject() drop what is held.  mergeHistory({ radius = 1, zKeep = 2, zDrop = 4 }): per texel as much of the held
+  // history as a two-sample test of the fresh mean against the held one over a (2 * radius + 1)^2 window supports is merged into the mean
+  // sampled since -- all of it up to a z-score of zKeep, none of it from zDrop.
+  holdHistory() {
+    this.native.holdHistory(this.handle);
+    this._validateLeft = 0;
+  }
+  mergeHistory(options) {
+    const o = Object.assign({ radius: 1, zKeep: 2, zDrop: 4 }, options || {});
+    this.native.mergeHistory(this.handle, o.radius, o.zKeep, o.zDrop);
+    this._validateLeft = 0;
+  }
+  // a move while a held history waits for its frames: it is merged on what has been sampled so far, not lost
+  _settleValidation() { if (this._validateLeft > 0) this.mergeHistory(); }
+  _startValidation(k) {
+    if (k > 0) {
+      this.holdHistory();
+      this._validateLeft = k;
+    }
+  }
+  static _validateFrames(validate) {
+    const k = validate === undefined ? 0 : Math.trunc(validate);
+    if (!(k >= 0)) throw new Error('validate must be >= 0');
+    return k;
   }
   // localRows x width x 4 floats; row 0 = bottom of the picture
   readMoments() { return this.native.readMoments(this.handle, this.localRows * this._width); }

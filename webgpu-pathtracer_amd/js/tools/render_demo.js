@@ -28,6 +28,10 @@
 //                      step takes --spp K frames (4); writes <prefix>_step<i>.png, <prefix>_step<i>.acc.f32 and <prefix>_step<i>.uniforms.bin per step.  Between steps
 //                      scene.needsUpdate = true and renderer.reset(), or with --reproject renderer.setMeanByCount(true) from the start and
 //                      renderer.reprojectScene(scene, camera) (the mean follows the box).  Not together with --orbit
+//   --validate K       with --reproject in the --orbit and --slide loops: the carried mean is not merged at once but held, validated against the
+//                      view's first K frames (K <= --spp) and then merged -- what reproject(scene, camera, { validate: K }) does, spelled out as
+//                      holdHistory() / mergeHistory() around two moments reads (the held counts nh; the counts n' after the merge, n = K before
+//                      it).  Prints the share of carried samples kept per view, sum(n' - n) / sum(nh), and lists it under "validate"
 //   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
 //   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
 //                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
@@ -82,6 +86,29 @@ async function main() {
   if (guidedVariance || untilArg !== null) renderer.setMoments(true);
   const orbit = parseInt(arg('orbit', '0'), 10), reproject = process.argv.includes('--reproject');
   const slide = parseInt(arg('slide', '0'), 10);
+  const validate = parseInt(arg('validate', '0'), 10), keptShares = [];
+  // after a reprojection that carried something: hold it and remember its counts
+  const hold = (carried) => {
+    if (!carried || !(validate > 0)) return null;
+    const held = renderer.readMoments();
+    renderer.holdHistory();
+    return held;
+  };
+  // a view's frames; the held history is merged once K of them are in
+  const sample = (spp, held, what) => {
+    const k = Math.min(validate, spp);
+    for (let i = 0; i < spp + 1; i++) {                                      // the last call only presents
+      renderer.render(scene, camera);
+      if (held && i + 1 === k) {
+        renderer.mergeHistory();
+        const now = renderer.readMoments();
+        let kept = 0, carried = 0;
+        for (let t = 3; t < now.length; t += 4) { kept += now[t] - k; carried += held[t]; }
+        keptShares.push(carried > 0 ? kept / carried : 0);
+        console.error('--validate ' + k + ': ' + what + ': ' + (100 * keptShares[keptShares.length - 1]).toFixed(1) + ' % of ' + carried + ' carried samples kept');
+      }
+    }
+  };
   if (orbit > 0 && slide > 0) throw new Error('--orbit and --slide both read --step: give one of them');
   if ((orbit > 0 || slide > 0) && reproject) renderer.setMeanByCount(true);
   renderer.resize(width, height);
@@ -102,11 +129,12 @@ async function main() {
       const c = Math.cos(view * step), s = Math.sin(view * step);
       camera.position.copy(new pt.Vector3(c * p0.x + s * p0.z, p0.y, -s * p0.x + c * p0.z));
       camera.lookAt(0, 0, 0);
+      let held = null;
       if (view > 0) {
-        if (reproject) renderer.reproject(scene, camera);
+        if (reproject) held = hold(renderer.reproject(scene, camera));
         else renderer.reset();
       }
-      for (let i = 0; i < spp + 1; i++) renderer.render(scene, camera);      // the last call only presents
+      sample(spp, held, 'view ' + view);
       fs.writeFileSync(out + '_view' + view + '.acc.f32', Buffer.from(renderer.readAccumulation().buffer));
       fs.writeFileSync(out + '_view' + view + '.uniforms.bin', Buffer.from(renderer.passes.raytrace.uniforms.bytes));
       if (guidedVariance) renderer.denoiseGuided({ variance: true, present: true });
@@ -119,13 +147,14 @@ async function main() {
     const x0 = box.position.x;
     renderer.frames = spp;
     for (let k = 0; k < slide; k++) {
+      let held = null;
       if (k > 0) {
         box.position.x = x0 + k * step;
         scene.needsUpdate = true;
-        if (reproject) renderer.reprojectScene(scene, camera);
+        if (reproject) held = hold(renderer.reprojectScene(scene, camera));
         else renderer.reset();
       }
-      for (let i = 0; i < spp + 1; i++) renderer.render(scene, camera);      // the last call only presents
+      sample(spp, held, 'step ' + k);
       fs.writeFileSync(out + '_step' + k + '.acc.f32', Buffer.from(renderer.readAccumulation().buffer));
       fs.writeFileSync(out + '_step' + k + '.uniforms.bin', Buffer.from(renderer.passes.raytrace.uniforms.bytes));
       renderer.screenshot(out + '_step' + k + '.png');
@@ -181,7 +210,7 @@ async function main() {
     fs.writeFileSync(out + '_moments.f32', Buffer.from(renderer.readMoments().buffer));
   }
   const summary = {
-    width, height, frames, until, status: renderer.status, frame: renderer.frame, events,
+    width, height, frames, until, validate: validate > 0 ? { frames: validate, kept: keptShares } : undefined, status: renderer.status, frame: renderer.frame, events,
     counters: renderer.counters(), stats: renderer.passes.raytrace.stats, first_stats: firstStats, wall_ms: ms,
     timings_us: { raytrace: renderer.timings.raytrace.value, accumulate: renderer.timings.accumulate.value,
       fullscreen: renderer.timings.fullscreen.value },

@@ -20,6 +20,7 @@ PASS_AOV = 3          # mi3pt_pass_time_us only: the first-hit feature images ha
 PASS_GUIDED = 4       # mi3pt_pass_time_us only: the feature-guided de-noise (denoise_guided)
 PASS_CONVERGENCE = 5  # mi3pt_pass_time_us only: the per-tile error estimate (estimate_convergence)
 PASS_REPROJECT = 6    # mi3pt_pass_time_us only: the gather kernel of reproject (its feature render is PASS_AOV's)
+PASS_HISTORY = 7      # mi3pt_pass_time_us only: the kernel of merge_history
 GUIDED_PRESENT = 1    # mi3pt_guided_params.flags: draw the canvas from the filtered image
 GUIDED_VARIANCE = 2   # ... the colour weight steered by the per-pixel variance of the mean (needs set_moments(True))
 # mi3pt_aov: the first-hit feature images (render_aovs takes an OR of 1 << AOV_*)
@@ -61,6 +62,7 @@ SYMBOLS = (
     "mi3pt_set_sample_mask", "mi3pt_read_sample_mask", "mi3pt_freeze_converged", "mi3pt_host_freeze_tiles",
     "mi3pt_set_mean_by_count", "mi3pt_host_view_frame", "mi3pt_reproject",
     "mi3pt_keep_geometry", "mi3pt_reproject_scene",
+    "mi3pt_hold_history", "mi3pt_merge_history",
 )
 
 
@@ -80,6 +82,11 @@ class ReprojectSceneParams(ctypes.Structure):
     """mi3pt_reproject_scene_params"""
     _fields_ = [("plane_tolerance", ctypes.c_float), ("normal_cos_min", ctypes.c_float), ("max_history", ctypes.c_int),
                 ("max_history_moved", ctypes.c_int), ("flags", ctypes.c_uint)]
+
+
+class HistoryParams(ctypes.Structure):
+    """mi3pt_history_params"""
+    _fields_ = [("radius", ctypes.c_int), ("z_keep", ctypes.c_float), ("z_drop", ctypes.c_float), ("flags", ctypes.c_uint)]
 
 
 class Convergence(ctypes.Structure):
@@ -159,6 +166,8 @@ def load_library(path=None):
     lib.mi3pt_reproject.argtypes = [c_void_p, ctypes.POINTER(ReprojectParams)]
     lib.mi3pt_keep_geometry.argtypes = [c_void_p, c_int]
     lib.mi3pt_reproject_scene.argtypes = [c_void_p, ctypes.POINTER(ReprojectSceneParams)]
+    lib.mi3pt_hold_history.argtypes = [c_void_p]
+    lib.mi3pt_merge_history.argtypes = [c_void_p, ctypes.POINTER(HistoryParams)]
     lib.mi3pt_enable_timing.argtypes = [c_void_p, c_int]
     lib.mi3pt_pass_time_us.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]
     lib.mi3pt_raytrace_launch_stats.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
@@ -666,6 +675,19 @@ class Context:
         reproject's, bit for bit.  The POSITION / NORMAL / IDS images must be of the kept geometry.  Asynchronous."""
         p = ReprojectSceneParams(plane_tolerance, normal_cos_min, int(max_history), int(max_history_moved), int(flags))
         self._c(self.lib.mi3pt_reproject_scene(self.handle, ctypes.byref(p)))
+
+    def hold_history(self):
+        """Set the running mean and its moments aside as the held history and leave the live pair zero-filled, as reset leaves it
+        (include/mi3pt.h: mi3pt_hold_history); output, canvas, feature images, sample mask and counters stay.  Asynchronous.  Needs
+        set_moments(True) and set_mean_by_count(True)."""
+        self._c(self.lib.mi3pt_hold_history(self.handle))
+
+    def merge_history(self, radius=1, z_keep=2.0, z_drop=4.0, flags=0):
+        """Merge the held history into the mean sampled since hold_history, per texel as much of it as a two-sample test over a
+        (2 * radius + 1)^2 window supports: all of it up to z_keep, none from z_drop (include/mi3pt.h: mi3pt_merge_history).
+        Asynchronous."""
+        p = HistoryParams(int(radius), z_keep, z_drop, int(flags))
+        self._c(self.lib.mi3pt_merge_history(self.handle, ctypes.byref(p)))
 
     def bind_accumulation(self, dev_ptr, nbytes):
         self._c(self.lib.mi3pt_bind_accumulation(self.handle, dev_ptr, nbytes))

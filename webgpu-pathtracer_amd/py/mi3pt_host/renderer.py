@@ -199,6 +199,7 @@ class Renderer:
         self._meanByCount = False          # setMeanByCount: a step's weight comes from the texel's own sample count
         self._trianglesUploaded = 0        # reprojectScene: the triangle count of the last upload (updateScene)
         self._seedOffset = 0               # reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
+        self._validateLeft = 0             # reproject(validate=K): sampled frames still to submit before the held history is merged
         self.passes = {"raytrace": RaytracePass(self), "accumulate": AccumulatePass(self),
                        "fullscreen": FullscreenPass(self)}
         if self.options["enableTimestampQuery"]:
@@ -305,6 +306,10 @@ class Renderer:
             mask |= bit
         if mask:
             self.ctx.submit(mask)                  # queue.submit, renderer.ts:389-390
+        if should_sample and self._validateLeft > 0:
+            self._validateLeft -= 1
+            if self._validateLeft == 0:
+                self.mergeHistory()                # (reproject(validate=K): K fresh frames are in; the defaults)
         if should_sample:
             self.passes["raytrace"].updateTimings()
             self.passes["accumulate"].updateTimings()
@@ -314,6 +319,7 @@ class Renderer:
     def reset(self):                               # renderer.ts:397-416
         prev = self.status
         self.status = "paused"
+        self._validateLeft = 0                     # (the context drops a held history with the mean)
         if self._width:
             self.ctx.reset()
         self.emit("reset")
@@ -421,6 +427,7 @@ class Renderer:
         self._moments = bool(enabled)
         if not enabled:
             self._meanByCount = False              # (the count is the image's n: the context switches the mode off with it)
+            self._validateLeft = 0                 # (... and drops a held history)
 
     # ---- the mean by count, and the reprojection of the mean across a camera move (no counterpart in the reference) ----
     def setMeanByCount(self, on=True):
@@ -432,21 +439,25 @@ class Renderer:
         self.ctx.set_mean_by_count(bool(on))
         self._meanByCount = bool(on)
 
-    def reproject(self, scene, camera, planeTolerance=0.02, normalCosMin=0.9, maxHistory=64):
+    def reproject(self, scene, camera, planeTolerance=0.02, normalCosMin=0.9, maxHistory=64, validate=0):
         """What a host calls INSTEAD of reset() when only the camera changed: the running mean and its moments are carried into the
         new view (include/mi3pt.h: mi3pt_reproject), texels the old view did not see restart, and the frame budget starts over.
         Returns True; falls back to reset() and returns False when the scene needs an upload, setMeanByCount is off, nothing has
-        been sampled yet, or the context is a rank of a tile split or a device group."""
+        been sampled yet, or the context is a rank of a tile split or a device group.  validate = K > 0: the carried mean is held
+        (holdHistory) and merged by mergeHistory() with its defaults once render() has submitted K further sampled frames."""
+        validate = self._validateFrames(validate)
         ctx = self.ctx
         partial = ctx.group_size != 1 or ctx._tile[1] != 1          # (a device group, or a rank of a tile split as of the last resize)
         if scene.needsUpdate or not self._meanByCount or self._frame <= 1 or not self._width or partial:
             self.reset()
             return False
+        self._settleValidation()
         if self._aovKey is None or self._aovKey != self._aovKeyNow():
             self.renderAovs()                      # the old view's features, under the uniforms the mean was sampled with
         self.update(scene, camera)
         ctx.reproject(planeTolerance, normalCosMin, maxHistory)
         self._aovKey = self._aovKeyNow()           # (the call rendered all four images of the new view)
+        self._startValidation(validate)
         self.emit("reproject")
         self._seedOffset = (self._seedOffset + self._frame - 1) & 0xFFFFFFFF
         prev = self.status
@@ -456,21 +467,23 @@ class Renderer:
             self.emit("start")
         return True
 
-    def reprojectScene(self, scene, camera, planeTolerance=0.02, normalCosMin=0.9, maxHistory=64, maxHistoryMoved=8):
+    def reprojectScene(self, scene, camera, planeTolerance=0.02, normalCosMin=0.9, maxHistory=64, maxHistoryMoved=8, validate=0):
         """What a host calls INSTEAD of reset() when scene.needsUpdate is set and the triangle count is unchanged -- an object moved,
         an animation played; the camera may have moved too: texels whose triangle did not move carry as in reproject(), texels whose
         triangle moved follow it back to its old place and carry at most maxHistoryMoved samples (include/mi3pt.h:
         mi3pt_reproject_scene).  Triangle i of the new content must be the surface element triangle i was.  Returns True; falls back
         to reset() and returns False under reproject()'s conditions, when the scene has no content, nothing was uploaded yet or the
-        triangle count differs from the last upload.  With scene.needsUpdate clear it is reproject()."""
+        triangle count differs from the last upload.  With scene.needsUpdate clear it is reproject().  validate: as in reproject()."""
         if not scene.needsUpdate:
-            return self.reproject(scene, camera, planeTolerance, normalCosMin, maxHistory)
+            return self.reproject(scene, camera, planeTolerance, normalCosMin, maxHistory, validate)
+        validate = self._validateFrames(validate)
         ctx = self.ctx
         partial = ctx.group_size != 1 or ctx._tile[1] != 1          # (a device group, or a rank of a tile split as of the last resize)
         count = 0 if scene.content is None else len(scene.content.triangles)
         if not self._meanByCount or self._frame <= 1 or not self._width or partial or count == 0 or count != self._trianglesUploaded:
             self.reset()
             return False
+        self._settleValidation()
         if self._aovKey is None or self._aovKey != self._aovKeyNow():
             self.renderAovs()                      # the old view's features of the old scene
         ctx.keep_geometry(True)
@@ -480,6 +493,7 @@ class Renderer:
         finally:
             ctx.keep_geometry(False)
         self._aovKey = self._aovKeyNow()           # (the call rendered all four images of the new scene and view)
+        self._startValidation(validate)
         self.emit("reproject")
         self._seedOffset = (self._seedOffset + self._frame - 1) & 0xFFFFFFFF
         prev = self.status
@@ -488,6 +502,38 @@ class Renderer:
         if self.status == "sampling":
             self.emit("start")
         return True
+
+    # ---- a held history, validated against fresh samples before it is merged (no counterpart in the reference) ----
+    def holdHistory(self):
+        """Set the running mean and its moments aside and restart the live pair, as reset() would (include/mi3pt.h:
+        mi3pt_hold_history); the frame counter, the canvas and the feature images stay.  Needs setMeanByCount(True).  A reset(), a
+        resize() and a reproject() drop what is held."""
+        self.ctx.hold_history()
+        self._validateLeft = 0
+
+    def mergeHistory(self, radius=1, zKeep=2.0, zDrop=4.0):
+        """Merge the held history into the mean sampled since holdHistory(): per texel as much of it as a two-sample test of the fresh
+        mean against the held one over a (2 * radius + 1)^2 window supports -- all of it up to a z-score of zKeep, none of it from zDrop
+        (include/mi3pt.h: mi3pt_merge_history)."""
+        self.ctx.merge_history(radius, zKeep, zDrop)
+        self._validateLeft = 0
+
+    def _settleValidation(self):
+        """a move while a held history waits for its frames: it is merged on what has been sampled so far, not lost"""
+        if self._validateLeft > 0:
+            self.mergeHistory()
+
+    def _startValidation(self, validate):
+        if validate > 0:
+            self.holdHistory()
+            self._validateLeft = validate
+
+    @staticmethod
+    def _validateFrames(validate):
+        validate = int(validate)
+        if validate < 0:
+            raise ValueError("validate must be >= 0")
+        return validate
 
     def readMoments(self):
         """(rows, width, 4) float32: M2.r, M2.g, M2.b, n."""
