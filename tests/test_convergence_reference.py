@@ -3,6 +3,7 @@
 test_moments_reference.py::test_variance_guided_filter_wins_from_sixteen_frames_on."""
 import numpy as np
 
+import convergence_cases as cc
 import convergence_reference as cr
 import moments_reference as mr
 import ptcommon as pc
@@ -140,6 +141,38 @@ def test_a_group_combines_its_members():
     c = dict(a, tiles=3, texels=150, worst_tile=F(0.25), worst_texel=F(3), n_min=F(4))
     s = cr.combine([a, b, c])
     assert s == dict(a, tiles=5, tiles_above=2, texels=250, worst_tile=F(0.5), worst_texel=F(3), n_min=F(4))
+
+
+def test_placed_extremes_move_every_field_a_dropped_record_would_lose():
+    """tests/convergence_cases.py, the inputs of tests/test_gpu_convergence.py::test_summary_placed_extremes: 260 block records, more
+    than the 256 one round of the fold takes; for every placed record p the one texel lies in a tile of record p and the summary differs
+    from the base image's in tiles_above, tiles_young, worst_tile, worst_texel and n_min -- each decided by that tile alone"""
+    assert (cc.RECORDS, cc.TILES_X * cc.TILES_Y) == (260, 4160) and cc.RECORDS > cc.FOLD_WIDTH
+    assert set(cc.PLACED) >= {1, 2, 4, 8, 16, 32, 64, 128} and max(cc.PLACED) == cc.RECORDS - 1      # every stage's upper half; the last record
+    assert any(cc.FOLD_WIDTH <= p < cc.RECORDS for p in cc.PLACED) and cc.FOLD_WIDTH - 1 in cc.PLACED
+    base_tiles = cr.tile_map(*cc.base())
+    assert np.all(base_tiles == base_tiles[0, 0]) and base_tiles[0, 0, 2] == 64 and base_tiles[0, 0, 3] == 16
+    for threshold, min_frames in cc.PLACED_PARAMS:
+        s0 = cr.summary(base_tiles, threshold, min_frames)
+        assert (s0["tiles"], s0["tiles_above"], s0["tiles_young"], s0["tiles_nonfinite"], s0["texels"]) == (4160, 0, 0, 0, cc.W * cc.H)
+        assert s0["n_min"] == 16 and s0["worst_texel"] == base_tiles[0, 0, 1] and s0["worst_tile"] == base_tiles[0, 0, 0] / F(64)
+        seen = set()
+        for p in cc.PLACED:
+            y, x = cc.placed_texel(p)
+            t = (y // 8) * cc.TILES_X + x // 8
+            assert t // cc.RECORD_TILES == p
+            seen.add((t % cc.RECORD_TILES, (y % 8) * 8 + x % 8))
+            tiles = cr.tile_map(*cc.placed(p))
+            flat = tiles.reshape(-1, 4)
+            others = np.delete(flat, t, axis=0)
+            assert np.all(others == base_tiles[0, 0])                        # one tile differs
+            s = cr.summary(tiles, threshold, min_frames)
+            assert (s["tiles"], s["tiles_above"], s["tiles_young"], s["texels"]) == (4160, 1, 1 if min_frames else 0, cc.W * cc.H)
+            assert s["n_min"] == 15 == flat[t, 3] and s["n_min"] < s0["n_min"]
+            assert s["worst_texel"] == flat[t, 1] > s0["worst_texel"]
+            assert s["worst_tile"] == flat[t, 0] / F(64) > s0["worst_tile"]
+            assert not cr.same_summary(s, s0)
+        assert len(seen) == len(cc.PLACED)                                   # (another place in the record and the tile every time)
 
 
 def test_the_replayed_loop_stops_where_the_estimates_say():

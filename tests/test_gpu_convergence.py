@@ -1,14 +1,17 @@
 """The per-tile error estimate of the running mean (mi3pt_estimate_convergence) on the GPU against tests/convergence_reference.py: the tile
 map bit for bit (ptcommon.same_bits), the nine summary fields exactly (convergence_reference.same_summary), no tolerance anywhere.
 Written inputs carry the special values of tests/test_convergence_reference.py; accumulated inputs are the ORACLE's mean and
-moments_reference's moments of the same frames.  The launch never caps its grid (one block per sixteen tiles, at most 2^20 blocks at the
-largest image mi3pt_resize accepts), so there is no case "past the cap"."""
+moments_reference's moments of the same frames.  The first kernel never caps its grid (one block per sixteen tiles, at most 2^20 blocks
+at the largest image mi3pt_resize accepts) and writes one record per block; the second folds those records 256 at a time in one block,
+a strided share per thread and a seven-stage tree.  The cases at 520 x 512 (260 records; tests/convergence_cases.py) cross that: every
+thread of the fold holds a record, four hold two, and every stage of the tree folds data."""
 import ctypes
 import struct
 
 import numpy as np
 import pytest
 
+import convergence_cases as cc
 import convergence_reference as cr
 import moments_reference as mr
 import ptcommon as pc
@@ -88,6 +91,35 @@ def test_written_inputs(ctx, w, h):
     if (w, h) == (100, 52):   # (not vacuous: finite and NaN sums, counted and uncounted texels)
         assert np.isnan(tiles[..., 0]).any() and (np.isfinite(tiles[..., 0]) & (tiles[..., 0] > 0)).any()
         assert (tiles[:6, :12, 2] < 64).all() and (tiles[..., 2] > 0).all()
+
+
+def test_summary_over_more_records_than_one_round_of_the_fold(ctx):
+    """520 x 512 written inputs: 4160 tiles in 260 block records.  The five counts are sums over all of them: a record dropped or folded
+    twice changes them.  (The CPU reference of seed 1: 4160 counted tiles, 2552 with a finite sum above zero, 649 with a NaN sum.)"""
+    acc, mo = _written(1, cc.H, cc.W)
+    _load(ctx, acc, mo)
+    tiles = _hold(ctx, acc, mo, f"{cc.W} x {cc.H}")
+    assert tiles.shape == (cc.TILES_Y, cc.TILES_X, 4) and cc.RECORDS == 260 > cc.FOLD_WIDTH
+    sums = tiles[..., 0]
+    counted, positive, nan = int((tiles[..., 2] > 0).sum()), int((np.isfinite(sums) & (sums > 0)).sum()), int(np.isnan(sums).sum())
+    print(f"{cc.W} x {cc.H}: {counted} counted tiles, {positive} with a finite sum above zero, {nan} with a NaN sum")
+    assert counted == 4160 and positive >= 1000 and nan >= 100
+    # (not vacuous: the records of the loop's second round hold counted tiles of every verdict)
+    second = tiles.reshape(-1, 4)[cc.FOLD_WIDTH * cc.RECORD_TILES:]
+    assert len(second) == 64 and (second[:, 2] > 0).all() and np.isnan(second[:, 0]).any() and (np.isfinite(second[:, 0]) & (second[:, 0] > 0)).any()
+
+
+@pytest.mark.parametrize("p", cc.PLACED)
+def test_summary_placed_extremes(ctx, p):
+    """The three maxima of the summary (worst_tile, worst_texel, n_min) and the two verdict counts decided by ONE texel of block record
+    p, on an otherwise plain 520 x 512 image (tests/convergence_cases.py; tests/test_convergence_reference.py states that the summary
+    differs from the plain image's for every p): the records of every tree stage's upper half, thread 255's, and records 256 and 259 of
+    the strided loop's second round"""
+    acc, mo = cc.placed(p)
+    _load(ctx, acc, mo)
+    tiles = _hold(ctx, acc, mo, f"record {p}", params=cc.PLACED_PARAMS)
+    y, x = cc.placed_texel(p)
+    assert tiles[y // 8, x // 8, 3] == 15 and (tiles[..., 3] == 15).sum() == 1
 
 
 def test_the_special_tiles(ctx):

@@ -71,8 +71,12 @@ def _run(ctx, orc, demo, env, w, h, levels, sigmas):
 
 
 # 1 x 1 and 3 x 2: every off-centre tap is outside the image; 16 x 17 and 17 x 16: one texel past a block; 100 x 52: ragged; 33 x 33 and
-# 64 x 64 at five levels: taps at +-32 reach across most of the image, stride classes of one or two texels
-SIZES = [(1, 1, 3), (3, 2, 3), (16, 17, 3), (17, 16, 3), (100, 52, 3), (33, 33, 5), (64, 64, 5)]
+# 64 x 64 at five levels: taps at +-32 reach across most of the image, stride classes of one or two texels; 264 x 260 = 16 * 16 + 8 by
+# 16 * 16 + 4: every level has more than one 16 x 16 tile per stride class in both axes (five at stride 4, three at 8, two at 16), so
+# blocks with u0, v0 > 0 and halos that cross two tiles of a class run, and at stride 16 the classes 8 .. 15 (4 .. 15 in y) are one
+# texel shorter: their second tile finds no texel of theirs.  Four levels beside five tell stride 16 from stride 8
+# (tests/test_guided_reference.py states the tile counts and the reference's statistics at this size without a device)
+SIZES = [(1, 1, 3), (3, 2, 3), (16, 17, 3), (17, 16, 3), (100, 52, 3), (33, 33, 5), (64, 64, 5), (264, 260, 4), (264, 260, 5)]
 
 
 @pytest.mark.parametrize("w,h,levels", SIZES, ids=[f"{w}x{h}-{n}-levels" for w, h, n in SIZES])

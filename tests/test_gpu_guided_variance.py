@@ -146,14 +146,17 @@ def test_calibrated_case_from_the_queue_and_nothing_else_changes(ctx, orc, demo,
 
 
 # 1 x 1 and 3 x 2: every off-centre tap of the levels is outside the image (the 3 x 3 of the variance kernel is not, at 3 x 2); 16 x 17 and
-# 17 x 16: one texel past a block; 100 x 52: ragged; 33 x 33 and 64 x 64 at five levels: taps at +-32, stride classes of one or two texels
-SIZES = [(1, 1, 3), (3, 2, 3), (16, 17, 3), (17, 16, 3), (100, 52, 3), (33, 33, 5), (64, 64, 5)]
+# 17 x 16: one texel past a block; 100 x 52: ragged; 33 x 33 and 64 x 64 at five levels: taps at +-32, stride classes of one or two texels;
+# 264 x 260 at four and five levels: more than one 16 x 16 tile per stride class in both axes at strides 4, 8 and 16, and at stride 16
+# classes of 17 and of 16 texels (as tests/test_gpu_guided.py; the tile counts are stated in tests/test_guided_reference.py)
+SIZES = [(1, 1, 3), (3, 2, 3), (16, 17, 3), (17, 16, 3), (100, 52, 3), (33, 33, 5), (64, 64, 5), (264, 260, 4), (264, 260, 5)]
 
 
 @pytest.mark.parametrize("w,h,levels", SIZES, ids=[f"{w}x{h}-{n}-levels" for w, h, n in SIZES])
 def test_sizes(ctx, orc, demo, env, w, h, levels):
     """Thresholds checked on the CPU with the oracle's features for the sizes >= 64 wide, M2 scale 24: 100 x 52 at three levels
-    rejected / below / above = 0.052 / 0.64 / 0.36, 64 x 64 at five 0.166 / 0.71 / 0.29 (no adjustment of the scale was needed)."""
+    rejected / below / above = 0.052 / 0.64 / 0.36, 64 x 64 at five 0.166 / 0.71 / 0.29 (no adjustment of the scale was needed);
+    264 x 260 at four levels 0.039 / 0.72 / 0.28, at five 0.059 / 0.76 / 0.24."""
     *_, stats = _run(ctx, orc, demo, env, w, h, levels, SIGMAS)
     if w >= 64:
         _assert_not_vacuous(stats, f"{w}x{h} levels {levels}")

@@ -1,11 +1,14 @@
 """The mean by count on the GPU (mi3pt_set_mean_by_count): the by-count twins of the two accumulate kernels against the DEFAULT law run
 with accumulate frames 1 .. N on the same context -- bit for bit, mean and moments (ptcommon.same_bits, no tolerance anywhere) -- and,
-where the two laws part (a tile thawed under a sample mask), against the numpy restatement tests/reproject_reference.py."""
+where the two laws part (a tile thawed under a sample mask), against the numpy restatement tests/reproject_reference.py.  Past the grid
+caps of the two callers of k_accumulate_frames (2048 and 4096 blocks), where the kernel strides, the restatement is applied to the
+oracle's frames."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import moments_reference as mr
 import ptcommon as pc
 import reproject_reference as rr
 from mi3pt_host import capi
@@ -107,6 +110,53 @@ def test_by_count_on_other_kernel_variants(ctx, demo, env, variant):
             default, counted = _both_laws(ctx, demo, w, h, how)
             assert np.all(default[1][..., 3] == N)
             _same(counted, default, f"variant {variant}, {how}")
+    finally:
+        _restore(ctx)
+
+
+CAP_CASES = {
+    # the accumulate-only path of mi3pt_submit launches at most 2048 blocks of 256: 1024 x 520 is 2080
+    "accumulate-only-1024x520": (1024, 520, 2048, "split", False),
+    # the batched path at most 4096: 1024 x 1032 is 4128
+    "batched-f32-1024x1032": (1024, 1032, 4096, "frames", False),
+    "batched-f16-1024x1032": (1024, 1032, 4096, "frames", True),
+}
+
+
+@pytest.mark.parametrize("case", list(CAP_CASES))
+def test_one_row_of_blocks_past_each_grid_cap(ctx, orc, demo, env, case):
+    """The by-count kernel where it strides: three frames at two bounces, at the smallest sizes of 1024 columns whose block count
+    exceeds each caller's cap, so the last 32 blocks' texels are the second iteration of 8192 threads.  Against the numpy law
+    (reproject_reference.by_count_step) applied frame by frame to the ORACLE's radiance (moments_reference.oracle_steps: 0.5 - 0.7 s for
+    the three frames; the device's per-frame image is pinned to it elsewhere).  With raytrace frames 1 .. 3 the law's mean is also the
+    oracle's own running mean: asserted on the reference.  The accumulate block's frame numbers (1000 ..) do not enter."""
+    w, h, cap, how, f16 = CAP_CASES[case]
+    frames = 3
+    assert cap * 256 < w * h <= 2 * cap * 256
+    want_mean, want_m, radiance, _ = mr.oracle_steps(orc, pc.oracle_scene(orc, demo, env), [(f, f, 1) for f in range(1, frames + 1)], w, h,
+                                                     lambda f: pc.rt_uniforms(demo, w, h, frame=f, bounces=2).tobytes(),
+                                                     lambda f, e: pc.acc_uniforms(w, h, f, e).tobytes(), store_f16=f16)
+    mean, moments = np.zeros((h, w, 4), F), np.zeros((h, w, 4), F)
+    for k in range(frames):
+        mean, moments = rr.by_count_step(mean, moments, radiance[k], store_f16=f16)
+    assert pc.same_bits(mean, want_mean) and pc.same_bits(moments, want_m)
+    strided = moments.reshape(-1, 4)[cap * 256:]
+    spread = (strided[:, :3] != 0).any(axis=1)
+    print(f"{case}: {len(strided)} strided texels, {spread.mean():.4f} of them with a non-zero M2")
+    assert np.all(strided[:, 3] == frames) and spread.mean() > 0.5       # (measured on the CPU: 1.00 in F32, 0.91 in F16)
+    try:
+        _configure(ctx, demo, env, w, h, f16=f16)
+        ctx.set_mean_by_count(True)
+        ctx.reset()
+        for k in range(1 if how == "frames" else frames):
+            ctx.set_uniforms(capi.PASS_RAYTRACE, pc.rt_uniforms(demo, w, h, frame=1 + k, bounces=2).tobytes())
+            ctx.set_uniforms(capi.PASS_ACCUMULATE, pc.acc_uniforms(w, h, 1000 + k).tobytes())
+            if how == "frames":
+                ctx.submit_frames(RT | ACC, frames)
+            else:
+                ctx.submit(RT)
+                ctx.submit(ACC)
+        _same(_snap(ctx), (mean, moments), case)
     finally:
         _restore(ctx)
 

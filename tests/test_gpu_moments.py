@@ -252,6 +252,32 @@ def test_past_the_grid_cap(ctx, orc, demo, env, submit):
     assert np.all(want[..., 3] == 3) and (want[-1, :, :3] > 0).any()
 
 
+CAP_CASES = {
+    # the accumulate-only path of mi3pt_submit launches at most 2048 blocks of 256: 1024 x 520 is 2080
+    "accumulate-only-1024x520": dict(w=1024, h=520, cap=2048, submit="separate"),
+    # the batched path at most 4096: 1024 x 1032 is 4128
+    "batched-f32-1024x1032": dict(w=1024, h=1032, cap=4096, submit="frames"),
+    "batched-f16-1024x1032": dict(w=1024, h=1032, cap=4096, submit="frames", f16=True),
+}
+
+
+@pytest.mark.parametrize("case", list(CAP_CASES))
+def test_one_row_of_blocks_past_each_grid_cap(ctx, orc, demo, env, case):
+    """Three frames at two bounces, at the smallest sizes of 1024 columns whose block count exceeds each caller's cap: the last 32 blocks'
+    texels are the strided second iteration of 8192 threads and of no other.  The radiance and the means are the ORACLE's
+    (moments_reference.oracle_steps, as everywhere in this module: 0.5 - 0.7 s for the three frames); the strided texels have n = 3 and a
+    spread in the reference."""
+    c = dict(CAP_CASES[case])
+    w, h, cap = c.pop("w"), c.pop("h"), c.pop("cap")
+    steps = tuple((f, f, 1) for f in range(1, 4))
+    assert cap * 256 < w * h <= 2 * cap * 256
+    m, want = _check(ctx, orc, demo, env, w, h, steps, case, bounces=2, **c)
+    strided = want.reshape(-1, 4)[cap * 256:]
+    spread = (strided[:, :3] != 0).any(axis=1)
+    print(f"{case}: {len(strided)} strided texels, {spread.mean():.4f} of them with a non-zero M2")
+    assert np.all(strided[:, 3] == 3) and spread.mean() > 0.5       # (measured on the CPU: 1.00 in F32, 0.91 in F16)
+
+
 def test_non_finite_radiance_is_carried(ctx, orc, env):
     """Two frames of the palette of tests/shading_cases.py (six bounces: NaN and inf radiance): NaNs sit where the reference puts them"""
     sc = sh.palette_scene()

@@ -85,6 +85,34 @@ def test_texel_alone_in_its_hit_class_is_returned_unchanged(orc):
     assert not pc.same_bits(got[1, 1], img[1, 1])            # (the others are filtered)
 
 
+def test_the_size_with_several_tiles_per_stride_class(orc, demo, env):
+    """264 x 260, the size at which tests/test_gpu_guided.py and tests/test_gpu_guided_variance.py run more than one block per stride
+    class.  The launch arithmetic of csrc/pt_guided.hip restated: level i has s = 2^i classes per axis, class c holds the texels c, c + s,
+    ... (ceil((size - c) / s) of them), and the grid has ceil(ceil(size / s) / 16) tiles of 16 per class.  And the reference's statistics
+    with the ORACLE's features and the two modules' own seeded inputs, held to the bounds the GPU cases assert (measured, rejected /
+    below / above: plain 0.039 / 0.114 / 0.886 at four levels and 0.059 / 0.112 / 0.888 at five, variance 0.039 / 0.719 / 0.281 and
+    0.059 / 0.762 / 0.238)."""
+    import moments_reference as mr
+    import test_gpu_guided as gg
+    import test_gpu_guided_variance as gv
+    w, h = 264, 260
+    assert (w, h, 4) in gg.SIZES and (w, h, 5) in gg.SIZES and (w, h, 4) in gv.SIZES and (w, h, 5) in gv.SIZES
+    tile = 16
+    for size in (w, h):
+        for s, want in ((4, 5), (8, 3), (16, 2)):
+            longest = (size + s - 1) // s
+            assert (longest + tile - 1) // tile == want >= 2, (size, s)
+        lengths = {len(range(c, size, 16)) for c in range(16)}
+        assert lengths == {17, 16}, size                   # classes with a texel in their second tile, and classes without
+    feat = ar.reference(orc, pc.oracle_scene(orc, demo, env), pc.rt_uniforms(demo, w, h).tobytes(), w, h)
+    accum, moments = gg._random_accum(w, h), gv._random_moments(w, h)
+    for levels in (4, 5):
+        _, stats = gr.guided(orc, accum, feat["normal"], feat["position"], feat["albedo"], feat["ids"], levels, *gg.ALL_ON)
+        gg._assert_not_vacuous(stats, f"plain, {levels} levels")
+        _, _, stats = mr.guided_variance(orc, accum, moments, feat["normal"], feat["position"], feat["albedo"], feat["ids"], levels, *gv.SIGMAS)
+        gv._assert_not_vacuous(stats, f"variance, {levels} levels")
+
+
 def _tone_rmse(x, truth):
     a = np.asarray(x, np.float64)[..., :3]
     b = np.asarray(truth, np.float64)[..., :3]
