@@ -731,9 +731,10 @@ int mi3pt_reproject_scene(mi3pt_ctx *ctx, const mi3pt_reproject_scene_params *pa
  * Texels outside the rectangle keep their bits.  z2 is the largest squared z-score of the pooled difference among the channels;
  * at or below z_keep the whole held history is kept, at or above z_drop none of it, a share linear in z2 in between.  The merge is
  * Chan's pairwise combine of the live samples with nk samples of the held mean and the held per-sample variance: a shortened history
- * keeps its variance, as max_history does, and counts stay whole numbers.  A z_drop whose square overflows, or squares that round to
- * the same number, give lam = 0 (everything dropped).  Non-finite inputs give unspecified values; every index is range-checked before
- * it is used, so they neither hang nor fault.
+ * keeps its variance, as max_history does, and counts stay whole numbers.  A z_drop whose square overflows gives lam = 0 (everything
+ * dropped); so do squares that round to the same number, except that a texel whose pooled difference is exactly 0 (z2 = 0, the quotient
+ * +inf) gets lam = 1 unless both squares are 0.  Non-finite inputs give unspecified values; every index is range-checked before it is
+ * used, so they neither hang nor fault.
  *   MI3PT_ERR_STATE before mi3pt_resize; while moments or the mean by count are off; for a rank of a tile split with more than one
  *   rank and for a device group (a window crosses rows; the halo exchange is NOT BUILT); mi3pt_merge_history also while nothing is
  *   held.  MI3PT_ERR_INVALID for a null pointer, a radius outside 0 .. 3, a z_keep that is negative or not finite, a z_drop that is

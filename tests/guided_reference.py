@@ -6,6 +6,7 @@ pt_oracle.math_fn(4, .) for exp.  Nothing here looks at the device.  No test liv
 import numpy as np
 
 H5 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], np.float32)
+TINY = np.float32(2.0 ** -126)      # the smallest normal fp32: exp(x) lies below it for x in about (-103.97, -87.34)
 
 
 def inv_sigma(sigma):
@@ -35,7 +36,8 @@ def _sq3(d):
 def guided(orc, accum, normal, position, albedo, ids, levels=3, sigma_color=1.0, sigma_normal=0.35, sigma_albedo=0.1, sigma_plane=0.05):
     """accum, normal, position, albedo: (rows, w, 4) float32; ids: (rows, w, 4) int32.  Returns (filtered (rows, w, 4) float32, stats):
     stats["rejected"]: share of the in-image taps the hit rule rejects; stats["below"] / stats["above"]: shares of the counted
-    off-centre taps whose exp(...) lies below / above 0.5; stats["taps"]: in-image taps -- all over every level."""
+    off-centre taps whose exp(...) lies below / above 0.5; stats["subnormal"]: the counted taps whose exp(...) is a subnormal (0 < e < 2^-126); stats["taps"]: in-image taps
+    -- all over every level."""
     c = np.ascontiguousarray(accum, np.float32)
     n = np.ascontiguousarray(normal, np.float32)[..., :3]
     pos = np.ascontiguousarray(position, np.float32)[..., :3]
@@ -46,7 +48,7 @@ def guided(orc, accum, normal, position, albedo, ids, levels=3, sigma_color=1.0,
     inv_color, inv_normal = inv_sigma(sigma_color), inv_sigma(sigma_normal)
     inv_albedo, inv_plane = inv_sigma(sigma_albedo), inv_sigma(sigma_plane)
     inside_all = np.ones((rows, w), bool)
-    taps = rejected = counted_off = below = above = 0
+    taps = rejected = counted_off = below = above = subnormal = 0
     cur = c
     for i in range(levels):
         s = 1 << i
@@ -78,6 +80,7 @@ def guided(orc, accum, normal, position, albedo, ids, levels=3, sigma_color=1.0,
                     counted_off += int(counts.sum())
                     below += int((counts & (e < 0.5)).sum())
                     above += int((counts & (e > 0.5)).sum())
+                    subnormal += int((counts & (e > 0) & (e < TINY)).sum())
         out = np.empty_like(c)
         with np.errstate(all="ignore"):
             for k in range(3):
@@ -85,5 +88,5 @@ def guided(orc, accum, normal, position, albedo, ids, levels=3, sigma_color=1.0,
         out[..., 3] = cur[..., 3]
         cur = out
     stats = {"taps": taps, "rejected": rejected / taps if taps else 0.0,
-             "below": below / counted_off if counted_off else 0.0, "above": above / counted_off if counted_off else 0.0}
+             "below": below / counted_off if counted_off else 0.0, "above": above / counted_off if counted_off else 0.0, "subnormal": subnormal}
     return cur, stats

@@ -6,7 +6,7 @@ pt_oracle.math_fn(4, .) for exp.  Nothing here looks at the device.  No test liv
 """
 import numpy as np
 
-from guided_reference import H5, _shift, _sq3, inv_sigma
+from guided_reference import H5, TINY, _shift, _sq3, inv_sigma
 
 G3 = np.array([1 / 4, 1 / 2, 1 / 4], np.float32)
 VARIANCE_EPS = np.float32(1e-8)       # MI3PT_GUIDED_VARIANCE_EPS
@@ -91,7 +91,7 @@ def guided_variance(orc, accum, moments, normal, position, albedo, ids, levels=3
         k_c = sc * sc
     inv_normal, inv_albedo, inv_plane = inv_sigma(sigma_normal), inv_sigma(sigma_albedo), inv_sigma(sigma_plane)
     inside_all = np.ones((rows, w), bool)
-    taps = rejected = counted_off = below = above = 0
+    taps = rejected = counted_off = below = above = subnormal = 0
     cur = c
     var = initial_variance(moments, hit)
     for i in range(levels):
@@ -130,6 +130,7 @@ def guided_variance(orc, accum, moments, normal, position, albedo, ids, levels=3
                     counted_off += int(counts.sum())
                     below += int((counts & (e < 0.5)).sum())
                     above += int((counts & (e > 0.5)).sum())
+                    subnormal += int((counts & (e > 0) & (e < TINY)).sum())
         out = np.empty_like(c)
         with np.errstate(all="ignore"):
             for k in range(3):
@@ -139,7 +140,7 @@ def guided_variance(orc, accum, moments, normal, position, albedo, ids, levels=3
         out[..., 3] = cur[..., 3]
         cur = out
     stats = {"taps": taps, "rejected": rejected / taps if taps else 0.0,
-             "below": below / counted_off if counted_off else 0.0, "above": above / counted_off if counted_off else 0.0}
+             "below": below / counted_off if counted_off else 0.0, "above": above / counted_off if counted_off else 0.0, "subnormal": subnormal}
     return cur, var, stats
 
 

@@ -55,6 +55,29 @@ def same_bits(a, b):
     return bool(eq.all())
 
 
+def same_bits_or_nan(got, want):
+    """For images with non-finite texels: the 32 bits of `want` wherever `want` is not a NaN, and a NaN wherever it is (include/mi3pt.h
+    leaves the sign and the payload of a NaN open, nothing else)."""
+    got = np.ascontiguousarray(got, np.float32)
+    want = np.ascontiguousarray(want, np.float32)
+    if got.shape != want.shape:
+        return False
+    nan = np.isnan(want)
+    return bool(np.where(nan, np.isnan(got), got.view(np.uint32) == want.view(np.uint32)).all())
+
+
+def assert_same_or_nan(got, want, what):
+    """same_bits_or_nan for a (mean, moments) pair, every texel; prints the share of texels in which the reference holds a NaN"""
+    for g, r, name in ((got[0], want[0], "mean"), (got[1], want[1], "moments")):
+        g, r = np.ascontiguousarray(g, np.float32), np.ascontiguousarray(r, np.float32)
+        assert g.shape == r.shape, f"{what}: {name}: shape {g.shape} for {r.shape}"
+        bad = np.where(np.isnan(r), ~np.isnan(g), g.view(np.uint32) != r.view(np.uint32))
+        assert same_bits_or_nan(g, r), f"{what}: {name}: {int(bad.sum())} of {bad.size} values differ, first at {np.argwhere(bad)[:5].tolist()}: " \
+                                       f"{g[bad][:5].tolist()} for {r[bad][:5].tolist()}"
+    nans = [float(np.isnan(r).any(axis=-1).mean()) for r in want[:2]]
+    print(f"{what}: the reference holds a NaN in {nans[0]:.3f} of the mean's texels and {nans[1]:.3f} of the moments'")
+
+
 def describe_diff(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)

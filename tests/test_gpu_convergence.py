@@ -21,7 +21,8 @@ pytestmark = pytest.mark.gpu
 MASK = capi.SUBMIT_RAYTRACE | capi.SUBMIT_ACCUMULATE
 F = np.float32
 PARAMS = ((0.0, 0), (0.3, 0), (1.0, 1), (0.05, 2), (1.0, 16), (3e-3, 1 << 24))         # (threshold, min_frames)
-N_VALUES = np.array([0, 1, 1.5, 2, 3, 17, 2 ** 24], F)
+# (0.5 and the float below 1: not counted; 1.5: counted, no variance yet; +inf: counted, and inf * inf in the variance's divisor)
+N_VALUES = np.array([0, 0.5, np.nextafter(F(1), F(0)), 1, 1.5, 2, 3, 17, 2 ** 24, np.inf], F)
 _cache = {}
 
 
@@ -95,7 +96,7 @@ def test_written_inputs(ctx, w, h):
 
 def test_summary_over_more_records_than_one_round_of_the_fold(ctx):
     """520 x 512 written inputs: 4160 tiles in 260 block records.  The five counts are sums over all of them: a record dropped or folded
-    twice changes them.  (The CPU reference of seed 1: 4160 counted tiles, 2552 with a finite sum above zero, 649 with a NaN sum.)"""
+    twice changes them.  (The CPU reference of seed 1: 4160 counted tiles, 2944 with a finite sum above zero, 517 with a NaN sum.)"""
     acc, mo = _written(1, cc.H, cc.W)
     _load(ctx, acc, mo)
     tiles = _hold(ctx, acc, mo, f"{cc.W} x {cc.H}")

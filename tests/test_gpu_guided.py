@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import guided_reference as gr
+import moments_edge_cases as ec
 import ptcommon as pc
 from mi3pt_host import capi
 
@@ -102,6 +103,57 @@ def test_each_sigma_alone(gpu_ctx, orc, demo, env, name, sigmas):
         assert stats["below"] == 0.0 and stats["above"] == 1.0       # every counted tap weighs h[dx] * h[dy]
     else:
         assert stats["below"] > 0.0, f"sigma_{name} alone changes no weight of this case"
+
+
+EDGE_SIZE = (100, 52)
+# sigma_color 0.18: a squared colour distance of 3 weighs exp(-92.6), a subnormal (tests/moments_edge_cases.py: subnormal_patches); the
+# term tightens by 4 per level, so the plain texels around a patch never reach into it
+SUBNORMAL_SIGMAS, SUBNORMAL_LEVELS = (ec.SUBNORMAL_SIGMA_PLAIN, 0.35, 0.1, 0.05), 3
+NON_FINITE_AT = [(5, 9), (5, 60), (26, 35), (45, 9), (45, 85), (26, 90)]
+
+
+def subnormal_accum(w, h):
+    accum = _random_accum(w, h)
+    ec.subnormal_patches(accum)
+    return accum
+
+
+def non_finite_accum(w, h):
+    """the finite means of the catalogue six texels apart (0, -0, subnormals, the ends of binary16, 1e19 whose square is finite and 3e38
+    whose square is not), and the six non-finite ones once each: every one of those spreads over 5 x 5 texels per level"""
+    accum = _random_accum(w, h)
+    ec.overlay(accum, np.zeros((h, w, 4), np.float32), 4, True, only=lambda name: name.startswith("mean="), pitch=6)
+    ec.non_finite_means(accum, NON_FINITE_AT)
+    return accum
+
+
+def _run_written(ctx, orc, demo, env, accum, levels, sigmas, what):
+    """_run with the accumulation given; the comparison is ptcommon.same_bits_or_nan"""
+    h, w = accum.shape[:2]
+    feat = _prepare(ctx, demo, env, w, h)
+    ctx.write_texture(capi.TEX_ACCUMULATION, accum)
+    want, stats = _reference(orc, feat, accum, levels, sigmas)
+    ctx.denoise_guided(levels, *sigmas)
+    got = ctx.read_guided()
+    assert pc.same_bits_or_nan(got, want), what + ": " + pc.describe_diff(got, want)
+    return got, want, stats
+
+
+def test_subnormal_weights(gpu_ctx, orc, demo, env):
+    """weights in the fp32 subnormal range: a build that flushes them, or an exp that cuts off early, gives 0 where the reference has 6e-42
+    (tests/test_moments_edge_cases.py shows that on the reference alone)"""
+    w, h = EDGE_SIZE
+    _, want, stats = _run_written(gpu_ctx, orc, demo, env, subnormal_accum(w, h), SUBNORMAL_LEVELS, SUBNORMAL_SIGMAS, "subnormal weights")
+    print(f"subnormal weights: {stats['subnormal']} counted taps; {stats}")
+    assert stats["subnormal"] > 0 and np.isfinite(want).all()
+
+
+def test_non_finite_colours(gpu_ctx, orc, demo, env):
+    w, h = EDGE_SIZE
+    _, want, stats = _run_written(gpu_ctx, orc, demo, env, non_finite_accum(w, h), 2, ALL_ON, "non-finite colours")
+    share = float(np.isnan(want).any(axis=-1).mean())
+    print(f"non-finite colours: a NaN in {share:.3f} of the texels; {stats['subnormal']} counted taps with a subnormal weight")
+    assert 0 < share <= 0.5
 
 
 def _sample_frames(ctx, demo, w, h, first, count):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import guided_reference as gr
+import moments_edge_cases as ec
 import moments_reference as mr
 import ptcommon as pc
 from mi3pt_host import capi
@@ -77,9 +78,9 @@ def _compare(ctx, want, want_var, what, w, h):
     return got, got_var
 
 
-def _run(ctx, orc, demo, env, w, h, levels, sigmas, moments=None, key_extra=None):
+def _run(ctx, orc, demo, env, w, h, levels, sigmas, moments=None, key_extra=None, accum=None):
     feat = _prepare(ctx, demo, env, w, h)
-    accum = _random_accum(w, h)
+    accum = _random_accum(w, h) if accum is None else accum
     moments = _random_moments(w, h) if moments is None else moments
     ctx.write_texture(capi.TEX_ACCUMULATION, accum)
     ctx.write_moments(moments)
@@ -202,6 +203,67 @@ def test_negative_and_nan_moments(ctx, orc, demo, env):
     m[51, 99, :3] = np.inf
     _, got_var, _, want_var, _ = _run(ctx, orc, demo, env, w, h, 3, SIGMAS, moments=m, key_extra="bad")
     assert np.isfinite(want_var[0, 0]) and np.array_equal(np.isnan(got_var), np.isnan(want_var))
+
+
+EDGE_SIZE = (100, 52)
+# sigma_color 2 with the patches' variance of the mean of 0.0081: a squared colour distance of 3 weighs exp(-92.6), a subnormal.  One level:
+# from the second on the plain texels around a patch reach into it (the colour term does not tighten per level under the flag)
+SUBNORMAL_SIGMAS, SUBNORMAL_LEVELS = (ec.SUBNORMAL_SIGMA_VARIANCE, 0.35, 0.1, 0.05), 1
+NON_FINITE_AT = [(5, 9), (5, 60), (26, 35), (45, 9), (45, 85), (26, 90)]
+
+
+def subnormal_pair(w, h):
+    accum, moments = _random_accum(w, h), _random_moments(w, h)
+    ec.subnormal_patches(accum, moments)
+    return accum, moments
+
+
+def catalogue_pair(w, h):
+    """the seeded pair with the count and M2 entries of the whole catalogue, NaN and infinite ones included, six texels apart: after three
+    levels a NaN has spread over 29 x 29 texels of its hit class, and half of the image is to stay comparable"""
+    accum, moments = _random_accum(w, h), _random_moments(w, h)
+    where = ec.overlay(accum, moments, 3, False, only=lambda name: "mean" not in name, pitch=6)
+    return accum, moments, where
+
+
+def non_finite_accum(w, h):
+    """the finite means of the catalogue six texels apart, and the six non-finite ones once each"""
+    accum = _random_accum(w, h)
+    ec.overlay(accum, np.zeros((h, w, 4), np.float32), 4, True, only=lambda name: name.startswith("mean="), pitch=6)
+    ec.non_finite_means(accum, NON_FINITE_AT)
+    return accum
+
+
+def test_count_and_m2_catalogue(ctx, orc, demo, env):
+    """k_guided_variance's `n >= 2 ? fmaxf(sum / (n (n - 1)), 0) : 0` at the counts on either side of 2 (1.5, the float below 2, 2), at NaN,
+    negative and infinite counts, with sums that are negative, subnormal, overflow or are NaN, on both sides of the 16 x 16 tile seams of
+    the level kernel -- then three levels on top.  The bits of the reference, a NaN where it has one"""
+    w, h = EDGE_SIZE
+    accum, moments, where = catalogue_pair(w, h)
+    assert not ec.seam_sides(where, w, h)
+    got, got_var, want, want_var, stats = _run(ctx, orc, demo, env, w, h, 3, SIGMAS, accum=accum, moments=moments, key_extra="catalogue")
+    print(f"count and M2 catalogue: a NaN in {float(np.isnan(want_var).mean()):.3f} of the variance's texels; {stats}")
+    assert np.isnan(want_var).any() and np.isnan(want_var).mean() <= 0.5
+    assert pc.same_bits_or_nan(got, want) and pc.same_bits_or_nan(got_var, want_var)
+
+
+def test_subnormal_weights(ctx, orc, demo, env):
+    """weights in the fp32 subnormal range (tests/moments_edge_cases.py: subnormal_patches); a build that flushes them, or an exp that
+    cuts off early, gives 0 where the reference has 6e-42 (tests/test_moments_edge_cases.py shows that on the reference alone)"""
+    w, h = EDGE_SIZE
+    accum, moments = subnormal_pair(w, h)
+    *_, stats = _run(ctx, orc, demo, env, w, h, SUBNORMAL_LEVELS, SUBNORMAL_SIGMAS, accum=accum, moments=moments, key_extra="subnormal")
+    print(f"subnormal weights: {stats['subnormal']} counted taps; {stats}")
+    assert stats["subnormal"] > 0
+
+
+def test_non_finite_colours(ctx, orc, demo, env):
+    """means at the ends of fp32 and binary16, and six texels with infinities and NaNs, two levels"""
+    w, h = EDGE_SIZE
+    got, got_var, want, want_var, stats = _run(ctx, orc, demo, env, w, h, 2, SIGMAS, accum=non_finite_accum(w, h), key_extra="non-finite colours")
+    share = float(np.isnan(want).any(axis=-1).mean())
+    print(f"non-finite colours: a NaN in {share:.3f} of the texels; {stats['subnormal']} counted taps with a subnormal weight")
+    assert 0 < share <= 0.5 and pc.same_bits_or_nan(got, want) and pc.same_bits_or_nan(got_var, want_var)
 
 
 def test_present_draws_the_canvas_from_the_filtered_image(ctx, orc, demo, env):

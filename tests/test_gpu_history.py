@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import history_reference as hr
+import moments_edge_cases as ec
 import ptcommon as pc
 import reproject_scene_cases as cases
 import test_gpu_reproject as tgr
@@ -79,6 +80,45 @@ def _every_branch(info):
     return all(info[k].any() for k in ("merged", "dropped", "only_held", "neither"))
 
 
+def _merge(c, w, h, held, live, rect=None, f16=False, **params):
+    """_case with the two pairs given.  Returns (device (A', M'), reference (A', M', info), the two pairs as the device returned them)"""
+    c.reset()
+    c.set_uniforms(capi.PASS_ACCUMULATE, pc.acc_uniforms(*(rect or (w, h)), 2).tobytes())
+    if f16:
+        held, live = (hr.store_round(held[0], True), held[1]), (hr.store_round(live[0], True), live[1])
+    held = _write(c, held)
+    c.hold_history()
+    live = _write(c, live)
+    c.merge_history(**params)
+    got = c.read_texture(TEX), c.read_moments()
+    kw = {k: params[k] for k in ("radius", "z_keep", "z_drop") if k in params}
+    want = hr.merge_history(live[0], live[1], held[0], held[1], rect, store_f16=f16, **kw)
+    return got, want, (live, held)
+
+
+def edge_pairs(w, h, seed, finite):
+    """(held, live): _random_pair's pairs with the catalogue of tests/moments_edge_cases.py written over BOTH sides, under different
+    permutations, so that an edge texel meets plain ones and other edge texels; on both sides of x = 31 | 32 and y = 7 | 8 (and every
+    other multiple of 8): the halo staging carries edge values"""
+    held = _random_pair(w, h, seed)
+    live = _random_pair(w, h, seed + 100, near=held[0])
+    where_held = ec.overlay(held[0], held[1], seed, finite)
+    where_live = ec.overlay(live[0], live[1], seed + 1, finite)
+    assert not ec.seam_sides(where_held, w, h) and not ec.seam_sides(where_live, w, h)
+    return held, live
+
+
+def describe_branches(info, live, held, what):
+    """the merge's value branches taken by a reference run, printed; returns the counts"""
+    both = (live[1][..., 3] >= 1) & (held[1][..., 3] >= 1)
+    lam = info["lam"][both]
+    count = {k: int(info[k].sum()) for k in ("merged", "dropped", "only_held", "neither")}
+    count.update(lam0=int((lam == 0).sum()), lam1=int((lam == 1).sum()), between=int(((lam > 0) & (lam < 1)).sum()), lam_nan=int(np.isnan(lam).sum()),
+                 one_kept=int((info["merged"] & (info["nk"] == 1)).sum()))
+    print(f"{what}: {count}")
+    return count
+
+
 @pytest.mark.parametrize("radius", [0, 1, 2, 3])
 @pytest.mark.parametrize("w,h", SIZES)
 def test_the_device_equals_the_reference(ctx, demo, env, w, h, radius):
@@ -103,6 +143,104 @@ def test_a_window_larger_than_the_image(ctx, demo, env):
     for seed in (1, 2):
         got, want, _ = _case(ctx, 8, 8, seed=seed, radius=3)
         tgr._same(got, want, f"8 x 8, radius 3, seed {seed}")
+
+
+@pytest.mark.parametrize("radius", [0, 1, 2, 3])
+@pytest.mark.parametrize("w,h", SIZES)
+def test_value_edges(ctx, demo, env, w, h, radius):
+    """the finite catalogue on both sides: counts on either side of `n >= 1` and `n >= 2`, M2 that the fmaxf clamps or that overflow the
+    pooled variance, means whose difference overflows.  Finite inputs, but not finite results: compared with ptcommon.same_bits_or_nan,
+    every texel.  At radius 1 also under F16 storage (the means 65504 and 65520: the largest binary16 and an infinity once stored)"""
+    tgr._configure(ctx, demo, env, w, h)
+    held, live = edge_pairs(w, h, 20 + radius, finite=True)
+    got, want, (live, held) = _merge(ctx, w, h, held, live, radius=radius)
+    count = describe_branches(want[2], live, held, f"radius {radius}, {w} x {h}")
+    assert _every_branch(want[2]) and count["lam0"] and count["lam1"] and count["between"] and count["one_kept"]
+    tgr._same_or_nan(got, want, f"radius {radius}, {w} x {h}")
+    if radius == 1:
+        try:
+            tgr._configure(ctx, demo, env, w, h, f16=True)
+            held, live = edge_pairs(w, h, 30, finite=True)
+            got, want, (live, held) = _merge(ctx, w, h, held, live, f16=True, radius=1)
+            assert (live[0] == 65504).any() and np.isinf(live[0]).any() and want[2]["merged"].any()
+            tgr._same_or_nan(got, want, f"F16, radius 1, {w} x {h}")
+        finally:
+            tgr._restore(ctx)
+
+
+def test_threshold_edges(ctx, demo, env):
+    """the worked examples of tests/moments_edge_cases.py (THRESHOLDS) as texels of a 40 x 24 image without samples anywhere else, radius
+    0, each at three places (one on either side of y = 7 | 8; the eight that share z 2 / 4 lie across x = 31 | 32): z2 exactly at keep2 and at
+    drop2, one ulp inside either, lam = 1/2 with nk - 1 = 0, counts of 1.5, an M2 that is a NaN on one side only in the channel that
+    decides (var()'s fmaxf drops it), and a z-score that is a NaN in one channel (the fmaxf over the channels drops it).  The device against the reference, and the reference against the stated
+    values"""
+    w, h = SIZES[1]
+    tgr._configure(ctx, demo, env, w, h)
+    for z in sorted({t["z"] for t in ec.THRESHOLDS}):
+        group = [t for t in ec.THRESHOLDS if t["z"] == z]
+        held, live = (np.zeros((h, w, 4), F), np.zeros((h, w, 4), F)), (np.zeros((h, w, 4), F), np.zeros((h, w, 4), F))
+        at = {}
+        for i, t in enumerate(group):
+            at[t["name"]] = [(1 + 3 * i, 2), (7, 29 + i), (8, 29 + i)]
+            for y, x in at[t["name"]]:
+                for pair, (mean, m2, n) in ((live, t["live"]), (held, t["held"])):
+                    pair[0][y, x] = (*mean, 1)
+                    pair[1][y, x] = (*m2, n)
+        got, want, _ = _merge(ctx, w, h, held, live, radius=0, z_keep=z[0], z_drop=z[1])
+        tgr._same(got, want, f"thresholds, z {z}")
+        info = want[2]
+        for t in group:
+            for y, x in at[t["name"]]:
+                print(f"{t['name']} at ({x}, {y}): z2 {info['z2'][y, x]!r}, lam {info['lam'][y, x]!r}, nk {info['nk'][y, x]}, mean {want[0][y, x, 0]!r}, "
+                      f"M2 {want[1][y, x, 0]!r}, N {want[1][y, x, 3]}")
+                assert abs(float(info["lam"][y, x]) - float(t["lam"])) <= 1e-9 and info["nk"][y, x] == t["nk"], t["name"]
+                assert bool(info["merged"][y, x]) == (t["merged"] is not None) and bool(info["dropped"][y, x]) == (t["merged"] is None), t["name"]
+                if t["merged"] is not None:
+                    assert (want[0][y, x, 0], want[1][y, x, 0], want[1][y, x, 3]) == t["merged"], t["name"]
+                    assert (got[0][y, x, 0], got[1][y, x, 0], got[1][y, x, 3]) == t["merged"], t["name"]
+                else:
+                    assert pc.same_bits(got[0][y, x], live[0][y, x]) and pc.same_bits(got[1][y, x], live[1][y, x]), t["name"]
+
+
+@pytest.mark.parametrize("case", ec.Z_EXTREMES, ids=[c["name"] for c in ec.Z_EXTREMES])
+def test_parameter_extremes(ctx, demo, env, case):
+    """z_drop whose square overflows; squares that are both 0; squares that are the same subnormal: lam = 0 wherever both sides hold
+    samples -- except, for the equal non-zero squares, at a texel whose pooled difference is exactly 0: z2 = 0, the quotient is +inf and
+    lam = 1 (the header's formula; _random_pair leaves the live mean equal to the held one at a sixth of the texels)"""
+    w, h = SIZES[0]
+    tgr._configure(ctx, demo, env, w, h)
+    z_keep, z_drop = case["z"]
+    got, want, (live, held) = _case(ctx, w, h, seed=7, radius=0, z_keep=z_keep, z_drop=z_drop)
+    tgr._same(got, want, case["name"])
+    both = (live[1][..., 3] >= 1) & (held[1][..., 3] >= 1)
+    d0 = both & (live[0][..., :3] == held[0][..., :3]).all(axis=-1)
+    lam = want[2]["lam"]
+    print(f"{case['name']}: {int(both.sum())} texels with both sides, {int(d0.sum())} of them with a difference of exactly 0; lam there "
+          f"{np.unique(lam[d0]).tolist()}, elsewhere {np.unique(lam[both & ~d0]).tolist()}")
+    assert d0.sum() >= 20 and (both & ~d0).sum() >= 20
+    assert np.all(lam[d0] == case["lam_d0"]) and np.all(lam[both & ~d0] == case["lam"])
+    if case["lam_d0"] == 1:
+        assert np.all(got[1][..., 3][d0] == live[1][..., 3][d0] + np.floor(held[1][..., 3][d0]))          # the whole held history is kept there
+    got, want, _ = _case(ctx, w, h, seed=8, radius=2, z_keep=z_keep, z_drop=z_drop)
+    tgr._same(got, want, case["name"] + ", radius 2")
+
+
+@pytest.mark.parametrize("radius", [0, 3])
+def test_non_finite_images(ctx, demo, env, radius):
+    """the whole catalogue, NaN and infinite counts, sums and means included, on both sides, over a rectangle smaller than the image: inside,
+    the reference's bits and a NaN where it has one (every texel); outside, the live bits exactly.  pt_history.hip: "images of NaNs or
+    infinities neither hang nor fault" -- no index depends on a value"""
+    w, h = SIZES[0]
+    tgr._configure(ctx, demo, env, w, h)
+    rect = (w - 9, h - 5)
+    held, live = edge_pairs(w, h, 40 + radius, finite=False)
+    got, want, (live, held) = _merge(ctx, w, h, held, live, rect=rect, radius=radius)
+    describe_branches(want[2], live, held, f"non-finite, radius {radius}")
+    assert _every_branch(want[2])
+    tgr._same_or_nan(got, want, f"non-finite, radius {radius}")
+    for g, written in zip(got, live):
+        assert np.array_equal(g[rect[1]:].view(np.uint32), written[rect[1]:].view(np.uint32))
+        assert np.array_equal(g[:, rect[0]:].view(np.uint32), written[:, rect[0]:].view(np.uint32))
 
 
 @pytest.mark.parametrize("w,h", SIZES)

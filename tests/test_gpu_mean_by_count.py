@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import moments_edge_cases as ec
 import moments_reference as mr
 import ptcommon as pc
 import reproject_reference as rr
@@ -199,6 +200,76 @@ def test_a_thawed_tile_continues_as_a_sample_mean(ctx, demo, env, f16):
             _same(_snap(ctx), (mean, moments), f"{how}, f16 {f16}")
         assert pc.same_bits(default[0][sampled], mean[sampled]) and pc.same_bits(default[1][sampled], moments[sampled])
         assert not pc.same_bits(default[0][~sampled], mean[~sampled])
+    finally:
+        _restore(ctx)
+
+
+_radiance = {}
+
+
+def _four_frames(c, sc, w, h, f16):
+    """the radiance of raytrace frames 2 .. 5 at two bounces, read from TEX_OUTPUT after a RAYTRACE-only submit (once per storage format)"""
+    if f16 not in _radiance:
+        frames = []
+        for k in range(4):
+            c.set_uniforms(capi.PASS_RAYTRACE, pc.rt_uniforms(sc, w, h, frame=2 + k, bounces=2).tobytes())
+            c.submit(RT)
+            frames.append(c.read_texture(capi.TEX_OUTPUT))
+        _radiance[f16] = frames
+    return _radiance[f16]
+
+
+@pytest.mark.parametrize("f16", [False, True], ids=["f32", "f16"])
+@pytest.mark.parametrize("how", ["queued", "split", "mask of ones", "half mask"])
+def test_written_counts(ctx, demo, env, how, f16):
+    """Per-texel heterogeneous counts, as mi3pt_reproject and mi3pt_write_moments leave them, against the numpy law: the whole catalogue of
+    tests/moments_edge_cases.py written with write_texture + write_moments at 50 x 37 (on both sides of every 256th texel, where
+    k_accumulate_frames' blocks meet, and of the 8 x 8 tile seams, where k_accumulate_tiles' waves do), then four frames at two bounces on
+    k_accumulate_frames' batched route, on the ACCUMULATE-only submit, and under an all-ones and a half sample mask (k_accumulate_tiles).
+    reproject_reference.by_count_step applied to the frames' radiance; NaN, negative, zero and fractional counts below 1 restart, 1.5
+    continues, 2^24 and beyond stop growing.  Every texel, ptcommon.same_bits_or_nan; a frozen tile keeps its bits exactly"""
+    try:
+        w, h = SIZES[1]
+        _configure(ctx, demo, env, w, h, f16=f16)
+        ctx.set_mean_by_count(True)
+        ctx.reset()
+        radiance = _four_frames(ctx, demo, w, h, f16)
+        mean, moments, where = ec.placed(w, h, 5, finite=False, linear=256)
+        assert not ec.seam_sides(where, w, h)
+        ctx.reset()
+        ctx.write_texture(TEX, mean)
+        ctx.write_moments(moments)
+        mean, moments = _snap(ctx)
+        start = mean.copy(), moments.copy()
+        ty, tx = (h + 7) // 8, (w + 7) // 8
+        mask = np.ones((ty, tx), np.uint8)
+        if how == "half mask":
+            mask[:, :tx // 2] = 0
+        sampled = np.repeat(np.repeat(mask != 0, 8, axis=0), 8, axis=1)[:h, :w]
+        if "mask" in how:
+            ctx.set_sample_mask(mask)
+        restarts = ~(moments[..., 3] >= 1) & sampled
+        for k in range(4):
+            mean, moments = rr.by_count_step(mean, moments, radiance[k], store_f16=f16, inside=sampled)
+        n0, n4 = start[1][..., 3], moments[..., 3]
+        print(f"{how}, f16 {f16}: {int(restarts.sum())} texels restart, {int((sampled & ~restarts).sum())} continue, "
+              f"{int((sampled & ~restarts & (n4 == n0)).sum())} of those with a count that no longer grows; NaN in "
+              f"{float(np.isnan(mean).any(axis=-1).mean()):.3f} of the mean's texels")
+        assert restarts.any() and np.all(n4[restarts] == 4) and (sampled & ~restarts & (n4 == n0)).any() and (n4 == F(5.5)).any()
+        if how == "split":
+            for k in range(4):
+                ctx.set_uniforms(capi.PASS_RAYTRACE, pc.rt_uniforms(demo, w, h, frame=2 + k, bounces=2).tobytes())
+                ctx.set_uniforms(capi.PASS_ACCUMULATE, pc.acc_uniforms(w, h, 1000 + k).tobytes())
+                ctx.submit(RT)
+                ctx.submit(ACC)
+        else:
+            ctx.set_uniforms(capi.PASS_RAYTRACE, pc.rt_uniforms(demo, w, h, frame=2, bounces=2).tobytes())
+            ctx.set_uniforms(capi.PASS_ACCUMULATE, pc.acc_uniforms(w, h, 1000).tobytes())
+            ctx.submit_frames(RT | ACC, 4)
+        got = _snap(ctx)
+        pc.assert_same_or_nan(got, (mean, moments), f"{how}, f16 {f16}")
+        for g, s in zip(got, start):
+            assert np.array_equal(g[~sampled].view(np.uint32), s[~sampled].view(np.uint32))
     finally:
         _restore(ctx)
 

@@ -8,6 +8,7 @@ import math
 import numpy as np
 import pytest
 
+import moments_edge_cases as ec
 import ptcommon as pc
 import reproject_reference as rr
 from mi3pt_host import capi
@@ -97,6 +98,11 @@ def _case(c, sc, w, h, view, seed=1, rect=None, images=None, f16=False, **params
 def _same(got, want, what):
     assert pc.same_bits(got[0], want[0]), f"{what}: mean: " + pc.describe_diff(got[0], want[0])
     assert pc.same_bits(got[1], want[1]), f"{what}: moments: " + pc.describe_diff(got[1], want[1])
+
+
+def _same_or_nan(got, want, what):
+    """_same for images with non-finite texels (ptcommon.same_bits_or_nan): every texel is compared"""
+    pc.assert_same_or_nan(got, want, what)
 
 
 @pytest.mark.parametrize("name", ["identical", "orbit", "dolly", "pan"])
@@ -208,7 +214,38 @@ def _case_keeping_state(c, sc, w, h, view):
     return got, want, (acc, mo)
 
 
+def assert_value_branches(info, moments_after, max_history, what, capped=True):
+    """on the reference alone: carried and restarted texels, and carried counts at the cap and below it (DESIGN.md "Pinned value range")"""
+    n_new = moments_after[..., 3][info["carried"]]
+    at_cap, below = int((n_new == max_history).sum()), int((n_new < max_history).sum())
+    print(f"{what}: carried {int(info['carried'].sum())}, restarted {int(info['restarted'].sum())}, at the cap of {max_history} {at_cap}, below it {below}")
+    assert info["carried"].any() and info["restarted"].any() and below > 0 and (at_cap > 0 or not capped)
+
+
+@pytest.mark.parametrize("f16", [False, True], ids=["f32", "f16"])
+@pytest.mark.parametrize("max_history", [64, 1 << 24])
+@pytest.mark.parametrize("name", ["identical", "orbit"])
+def test_value_edges(ctx, demo, env, name, max_history, f16):
+    """the finite catalogue of tests/moments_edge_cases.py in the old view's images at 50 x 37 (35 tiles of 8 x 8, edge texels on both sides of
+    every tile seam): counts on either side of `n0 >= 1` and `n0 >= 2`, M2 that the fmaxf clamps, counts at and above both caps, means
+    at the ends of binary16.  Finite inputs, but not finite results (3e38 * bw sums overflow, inf * (n' - 1 = 0) is a NaN): compared
+    with ptcommon.same_bits_or_nan, every texel"""
+    w, h = SIZES[1]
+    try:
+        _configure(ctx, demo, env, w, h, f16=f16)
+        acc, mo, where = ec.placed(w, h, 11, finite=True)
+        assert not ec.seam_sides(where, w, h)
+        got, want, _ = _case(ctx, demo, w, h, _views(demo, w, h)[name], images=(acc, mo), f16=f16, max_history=max_history)
+        what = f"{name}, max_history {max_history}, f16 {f16}"
+        assert_value_branches(want[2], want[1], max_history, what, capped=max_history == 64 or name == "identical")
+        _same_or_nan(got, want, what)
+    finally:
+        _restore(ctx)
+
+
 def test_non_finite_images_complete_and_leave_the_outside_untouched(ctx, demo, env):
+    """... and inside the rectangle every texel is the reference's (a NaN where it has one).  Only the two images are non-finite: the
+    feature images are rendered, no index depends on a written value"""
     w, h = SIZES[0]
     _configure(ctx, demo, env, w, h)
     rng = np.random.default_rng(9)
@@ -217,20 +254,12 @@ def test_non_finite_images_complete_and_leave_the_outside_untouched(ctx, demo, e
         bad = rng.choice(np.array([np.nan, np.inf, -np.inf, 1e38, -1.0], F), size=img.shape)
         img[...] = np.where(rng.random(img.shape) < 0.3, bad, img)
     rect = (w - 16, h - 8)
-    ua = _uniforms(demo, w, h)
-    ctx.reset()
-    ctx.set_uniforms(capi.PASS_RAYTRACE, ua.tobytes())
-    ctx.set_uniforms(capi.PASS_ACCUMULATE, pc.acc_uniforms(*rect, 2).tobytes())
-    ctx.render_aovs(capi.AOV_ALL)
-    ctx.write_texture(TEX, acc)
-    ctx.write_moments(mo)
-    ctx.set_uniforms(capi.PASS_RAYTRACE, _uniforms(demo, w, h, _views(demo, w, h)["orbit"]).tobytes())
-    ctx.reproject(max_history=1 << 24)
+    got, want, _ = _case(ctx, demo, w, h, _views(demo, w, h)["orbit"], rect=rect, images=(acc, mo), max_history=1 << 24)
     ctx.sync()
-    got = ctx.read_texture(TEX), ctx.read_moments()
     for g, written in zip(got, (acc, mo)):
         assert pc.same_bits(g[rect[1]:], written[rect[1]:]) and pc.same_bits(g[:, rect[0]:], written[:, rect[0]:])
     assert np.all(got[0][:rect[1], :rect[0], 3] == 1)
+    _same_or_nan(got, want, "non-finite images")
 
 
 def test_error_codes(ctx, demo, env):

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import moments_edge_cases as ec
 import ptcommon as pc
 import reproject_reference as rr
 import reproject_scene_cases as cases
@@ -220,7 +221,29 @@ def test_a_second_keep_replaces_the_first_and_features_may_follow_it(demo, env, 
         assert want[2]["moved"].any() and (want[2]["carried"] & want[2]["moved"]).any()
 
 
+@pytest.mark.parametrize("f16", [False, True], ids=["f32", "f16"])
+@pytest.mark.parametrize("max_history", [64, 1 << 24])
+def test_value_edges(ctx, demo, env, variants, max_history, f16):
+    """test_gpu_reproject.py::test_value_edges through this kernel: the finite catalogue of tests/moments_edge_cases.py at 50 x 37, the box
+    and the sphere moved and the camera orbited, so that static and moved texels both gather edge taps; the moved texels' cap is 8"""
+    w, h = SIZES[1]
+    try:
+        tgr._configure(ctx, demo, env, w, h, f16=f16)
+        acc, mo, where = ec.placed(w, h, 12, finite=True)
+        assert not ec.seam_sides(where, w, h)
+        got, want, _ = _case(ctx, demo, variants["box and sphere"], w, h, images=(acc, mo), f16=f16, max_history=max_history, max_history_moved=8)
+        what = f"max_history {max_history}, f16 {f16}"
+        info = want[2]
+        tgr.assert_value_branches(info, want[1], max_history, what, capped=max_history == 64)
+        n_moved = want[1][..., 3][info["carried"] & info["moved"]]
+        assert (n_moved == 8).any() and (n_moved < 8).any()
+        tgr._same_or_nan(got, want, what)
+    finally:
+        tgr._restore(ctx)
+
+
 def test_non_finite_images_complete_and_leave_the_outside_untouched(ctx, demo, env, variants):
+    """... and inside the rectangle every texel is the reference's (a NaN where it has one)"""
     w, h = SIZES[0]
     tgr._configure(ctx, demo, env, w, h)
     rng = np.random.default_rng(9)
@@ -234,6 +257,7 @@ def test_non_finite_images_complete_and_leave_the_outside_untouched(ctx, demo, e
     for g, written in zip(got, (acc, mo)):
         assert pc.same_bits(g[rect[1]:], written[rect[1]:]) and pc.same_bits(g[:, rect[0]:], written[:, rect[0]:])
     assert np.all(got[0][:rect[1], :rect[0], 3] == 1)
+    tgr._same_or_nan(got, want, "non-finite images")
 
 
 def test_error_codes(ctx, demo, env, variants):
