@@ -72,7 +72,8 @@ extern "C" {
  * mi3pt_read_convergence, mi3pt_read_convergence_tiles, struct mi3pt_convergence, MI3PT_PASS_CONVERGENCE (5); mi3pt_set_sample_mask,
  * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles; mi3pt_set_mean_by_count, mi3pt_host_view_frame, mi3pt_reproject,
  * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6); mi3pt_keep_geometry, mi3pt_reproject_scene, struct mi3pt_reproject_scene_params;
- * mi3pt_hold_history, mi3pt_merge_history, struct mi3pt_history_params, MI3PT_HISTORY_EPS, MI3PT_PASS_HISTORY (7). */
+ * mi3pt_hold_history, mi3pt_merge_history, struct mi3pt_history_params, MI3PT_HISTORY_EPS, MI3PT_PASS_HISTORY (7);
+ * MI3PT_GUIDED_YOUNG, MI3PT_GUIDED_YOUNG_COUNT. */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -434,6 +435,32 @@ int mi3pt_moments_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes);
 #define MI3PT_GUIDED_VARIANCE 2u
 #define MI3PT_GUIDED_VARIANCE_EPS 1e-8f
 int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfloats);
+
+/* ---- MI3PT_GUIDED_YOUNG: MI3PT_GUIDED_VARIANCE for an image whose texels differ in age -- after mi3pt_reproject, mi3pt_reproject_scene or
+ * mi3pt_hold_history most texels carry a long history and the disoccluded ones restart at n = 1, where v = 0 and the filter leaves them
+ * raw.  A texel with a short history takes its variance from a 7 x 7 neighbourhood, boosted for the short history (SVGF, section 4.2) --
+ * here not from luminance moments but from the neighbours' own (M2, n), pooled exactly by Chan's pairwise rule.  Valid only together with
+ * MI3PT_GUIDED_VARIANCE (alone: MI3PT_ERR_INVALID; on a context that never opted into moments it is an unknown bit like that one).
+ * Everything of the variance mode stands except var_0; pinned arithmetic as there.  With (M2, n) = the moments texel, c = the colour
+ * level 0 reads:   young(q) <=> n_q < MI3PT_GUIDED_YOUNG_COUNT (a NaN count is not young);   s_q = (M2.r + M2.g) + M2.b.
+ * Centre p NOT young: var_0(p) as above, but a tap q of the 3 x 3 counts only if it is not young either (the centre always counts).  With
+ *   no young texel in the image the bits are those of the variance mode without this flag.
+ * Centre p young with n_p < 1 (never sampled): var_0(p) = 0.
+ * Centre p young with n_p >= 1: taps q = p + (dx, dy), dy = -3 .. 3 outer, dx = -3 .. 3 inner.  A tap COUNTS iff q lies inside the image,
+ *   hit(q) == hit(p) and n_q >= 1.  For each that counts, in that order, en / ea / ep exactly as in the level law (the centre's normal
+ *   for pd), N, A, SS starting at 0:
+ *     w  = exp(-((en + ea) + ep))              (the centre: 1; no h weights, no colour term)
+ *     a  = w * n_q
+ *     pass 1:  N = N + a;   A.k = A.k + a * c_q.k            then mu.k = A.k / N
+ *     pass 2:  d = c_q - mu;   d2 = (d.x*d.x + d.y*d.y) + d.z*d.z;   SS = SS + w * (s_q + n_q * d2)
+ *     v = N >= 2 ? fmax(SS / (N - 1), 0) : 0                 (fmax drops a NaN)
+ *     var_0(p) = (v / n_p) * (MI3PT_GUIDED_YOUNG_COUNT / n_p)
+ *   -- the per-sample variance of all the samples the counted neighbours hold, over the texel's own count, times SVGF's boost for a
+ *   short history.  The var_0 of a young texel is not blurred.
+ * Non-finite inputs give unspecified values; they neither hang nor fault.  Nothing is allocated beyond what the variance mode has; a rank of
+ * a tile split and a device group stay refused; MI3PT_PASS_GUIDED's time includes the kernel. ---- */
+#define MI3PT_GUIDED_YOUNG 4u
+#define MI3PT_GUIDED_YOUNG_COUNT 4.0f
 
 /* ---- the per-tile error estimate of the running mean: when to stop sampling -- no counterpart in the reference, which renders a fixed
  * number of frames.  mi3pt_estimate_convergence reduces (accumulation image, moments image) on the device to one record per 8 x 8 tile

@@ -2662,9 +2662,11 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     for (float sigma : { params->sigma_color, params->sigma_normal, params->sigma_albedo, params->sigma_plane })
         if (!(sigma >= 0.0f) || std::isinf(sigma)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: every sigma must be finite and >= 0");
     // (a context that never opted into the moments image answers as it always did: the variance bit is unknown to it)
-    if (params->flags & ~(MI3PT_GUIDED_PRESENT | (ctx->moments_opted ? MI3PT_GUIDED_VARIANCE : 0u)))
-        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: unknown flag bits (MI3PT_GUIDED_VARIANCE: only on a context that has enabled the moments image, mi3pt_set_moments)");
-    const bool by_variance = (params->flags & MI3PT_GUIDED_VARIANCE) != 0;
+    if (params->flags & ~(MI3PT_GUIDED_PRESENT | (ctx->moments_opted ? MI3PT_GUIDED_VARIANCE | MI3PT_GUIDED_YOUNG : 0u)))
+        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: unknown flag bits (MI3PT_GUIDED_VARIANCE, MI3PT_GUIDED_YOUNG: only on a context that has enabled the moments image, mi3pt_set_moments)");
+    const bool by_variance = (params->flags & MI3PT_GUIDED_VARIANCE) != 0, young = (params->flags & MI3PT_GUIDED_YOUNG) != 0;
+    if (young && !by_variance)
+        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: MI3PT_GUIDED_YOUNG only together with MI3PT_GUIDED_VARIANCE (it changes that mode's initial variance)");
     if (int rc = require_ctx(ctx)) return rc;
     if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided before resize");
     if (ctx->partial())
@@ -2692,7 +2694,10 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     const float *var = nullptr;
     if (by_variance) {
         // var_0 into the image level 0 does not write; level i then reads image (i + 1) & 1 and writes image i & 1
-        pt::launch_guided_variance(ctx->d_moments, ctx->d_guided_nh, ctx->d_guided_var[1], ctx->width, ctx->local_rows, ctx->stream);
+        if (young)
+            pt::launch_guided_variance_young(G, src, ctx->d_moments, ctx->d_guided_var[1], ctx->stream);
+        else
+            pt::launch_guided_variance(ctx->d_moments, ctx->d_guided_nh, ctx->d_guided_var[1], ctx->width, ctx->local_rows, ctx->stream);
         var = ctx->d_guided_var[1];
     }
     for (int level = 0; level < params->levels; level++) {

@@ -135,6 +135,163 @@ __global__ void __launch_bounds__(256) k_guided_level_variance(const GuidedLaunc
     guided_level<true>(G, src, dst, var_src, var_dst, s, k_c, color_on);
 }
 
+// ---- MI3PT_GUIDED_YOUNG: var_0 for an image whose texels differ in age (after a reprojection most carry a long history and the
+// disoccluded ones restart at n = 1).  A texel with fewer than MI3PT_GUIDED_YOUNG_COUNT samples takes the variance of the samples its
+// 7 x 7 neighbours hold, pooled by Chan's pairwise rule from their own (mean, M2, n); the others keep k_guided_variance's 3 x 3, a
+// young neighbour left out.
+//
+// Shaped as pt_history.hip: one 32 x 8 tile per block of four waves, a wave is two tile rows of 32 texels, so a tile row is 512
+// contiguous bytes of every image.  What the 49 taps read is staged once per block with a halo of 3, as guided_level stages it: four
+// float4 records per texel, 38 x 14 x 64 B = 33.25 KiB.  A lane reads whole records (ds_read_b128), the 32 lanes of a half wave at
+// consecutive 16-byte slots whatever the row stride: each of the instruction's 16-lane groups covers the 16 slots of a bank row once,
+// no conflict.  Four blocks = four waves per SIMD fit in a CU's 160 KiB; a 16 x 16 tile would stage 484 records instead of 532 but put
+// two rows into a half wave, and a 64 x 4 tile 700.  The weights of pass 1 stay in registers for pass 2 (both loops are unrolled: 49
+// registers, inside the 128 that four waves per SIMD leave each lane), so the features are read and the exp is taken once per tap.
+// Left to itself the compiler hoists the 196 record reads of the unrolled pass in front of the arithmetic: 233 registers, two waves
+// per SIMD, or 116 spilled under the bound.  A scheduling barrier after every tap keeps a tap's reads with its arithmetic: 85
+// registers, no scratch (-Rpass-analysis=kernel-resource-usage).
+// The usual block after a camera move holds no young texel: it decides that with one __syncthreads_or BEFORE any staging, runs the
+// 3 x 3 from global memory and stages nothing.  Every index is range-checked before it is used. ----
+constexpr int Y_W = 32, Y_H = 8, Y_R = 3, Y_SW = Y_W + 2 * Y_R, Y_SH = Y_H + 2 * Y_R, Y_NE = Y_SW * Y_SH;      // 38 x 14 records
+constexpr int Y_TAPS = (2 * Y_R + 1) * (2 * Y_R + 1);
+
+// var_0 of a centre that is not young: k_guided_variance's sum, operation for operation, over the taps that are not young either.  All nine
+// taps are loaded first, from coordinates clamped into the image, and looked at afterwards: nine independent pairs of loads in flight per
+// lane instead of a chain of load, test, load (the light path has half of k_guided_variance's waves per SIMD to hide them with).  Valid
+// for a lane outside the image too, whose result nobody reads.  n_p: the centre's own count.
+PT_DEV float guided_variance_settled(const float4 *__restrict__ moments, const float4 *__restrict__ normal_hit, const int x, const int y,
+                                     const int width, const int rows, float &n_p)
+{
+    float4 m[9];
+    uint32_t hit[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        const int qx = min(max(x + k % 3 - 1, 0), width - 1), qy = min(max(y + k / 3 - 1, 0), rows - 1);
+        const size_t q = (size_t)qy * (size_t)width + (size_t)qx;
+        hit[k] = __float_as_uint(normal_hit[q].w);
+        m[k] = moments[q];
+    }
+    n_p = m[4].w;
+    const float g[3] = { 0.25f, 0.5f, 0.25f };
+    float num = 0.0f, den = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {        // dy outer, dx inner
+        const int dx = k % 3 - 1, dy = k / 3 - 1, qx = x + dx, qy = y + dy;
+        if (qx < 0 || qx >= width || qy < 0 || qy >= rows || hit[k] != hit[4]) continue;
+        if (k != 4 && m[k].w < MI3PT_GUIDED_YOUNG_COUNT) continue;
+        const float w = g[dx + 1] * g[dy + 1];
+        num = num + w * moments_variance(m[k]);
+        den = den + w;
+    }
+    return num / den;
+}
+
+__global__ void __launch_bounds__(256, 4) k_guided_variance_young(const GuidedLaunch G, const float4 *__restrict__ accum,
+                                                                  const float4 *__restrict__ moments, float *__restrict__ var)
+{
+    __shared__ float4 l_cn[Y_NE];        // c.rgb, n (0 outside the image: such a tap never counts)
+    __shared__ float4 l_nh[Y_NE];        // n.xyz, hit
+    __shared__ float4 l_ps[Y_NE];        // P.xyz, s = (M2.r + M2.g) + M2.b
+    __shared__ float4 l_alb[Y_NE];       // a.rgb
+    const int tid = (int)threadIdx.x, tx = tid & (Y_W - 1), ty = tid >> 5;
+    const int x0 = (int)blockIdx.x * Y_W, y0 = (int)blockIdx.y * Y_H;
+    const int x = x0 + tx, y = y0 + ty;
+    const bool in_image = x < G.width && y < G.rows;
+    const size_t i = (size_t)y * (size_t)G.width + (size_t)x;
+    float n_p;
+    const float settled = guided_variance_settled(moments, G.normal_hit, x, y, G.width, G.rows, n_p);        // (its loads are in flight before the vote)
+    const bool young = in_image && n_p < MI3PT_GUIDED_YOUNG_COUNT;        // (a NaN count is not young)
+    if (!__syncthreads_or(young ? 1 : 0)) {
+        if (in_image) var[i] = settled;
+        return;
+    }
+    for (int e = tid; e < Y_NE; e += 256) {
+        const int iy = e / Y_SW, ix = e - iy * Y_SW;
+        const int gx = x0 - Y_R + ix, gy = y0 - Y_R + iy;
+        float4 cn = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nh = cn, ps = cn, al = cn;
+        if (gx >= 0 && gx < G.width && gy >= 0 && gy < G.rows) {
+            const size_t q = (size_t)gy * (size_t)G.width + (size_t)gx;
+            const float4 c = accum[q], mq = moments[q], p = G.position[q];
+            cn = make_float4(c.x, c.y, c.z, mq.w);
+            ps = make_float4(p.x, p.y, p.z, (mq.x + mq.y) + mq.z);
+            nh = G.normal_hit[q]; al = G.albedo[q];
+        }
+        l_cn[e] = cn; l_nh[e] = nh; l_ps[e] = ps; l_alb[e] = al;
+    }
+    __syncthreads();
+    if (!in_image) return;
+    const int ec0 = (ty + Y_R) * Y_SW + tx + Y_R;
+    const float4 np = l_nh[ec0], pp = l_ps[ec0], ap = l_alb[ec0];
+    const uint32_t hit_p = __float_as_uint(np.w);
+    if (!young) {
+        var[i] = settled;
+        return;
+    }
+    if (!(n_p >= 1.0f)) {        // never sampled
+        var[i] = 0.0f;
+        return;
+    }
+    // pass 1: the weights, the pooled count and the pooled mean
+    float wgt[Y_TAPS];
+    uint64_t counted = 0;
+    float N = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
+#pragma unroll
+    for (int dy = -Y_R; dy <= Y_R; dy++) {
+#pragma unroll
+        for (int dx = -Y_R; dx <= Y_R; dx++) {
+            const int k = (dy + Y_R) * (2 * Y_R + 1) + dx + Y_R, e = ec0 + dy * Y_SW + dx;
+            const float4 cq = l_cn[e], nq = l_nh[e];
+            wgt[k] = 0.0f;
+            if (__float_as_uint(nq.w) != hit_p || !(cq.w >= 1.0f)) continue;
+            float w = 1.0f;
+            if ((dx | dy) != 0) {
+                const float4 pq = l_ps[e], aq = l_alb[e];
+                const float dnx = nq.x - np.x, dny = nq.y - np.y, dnz = nq.z - np.z;
+                const float en = ((dnx * dnx + dny * dny) + dnz * dnz) * G.inv_normal;
+                const float dax = aq.x - ap.x, day = aq.y - ap.y, daz = aq.z - ap.z;
+                const float ea = ((dax * dax + day * day) + daz * daz) * G.inv_albedo;
+                const float dpx = pq.x - pp.x, dpy = pq.y - pp.y, dpz = pq.z - pp.z;
+                const float pd = (np.x * dpx + np.y * dpy) + np.z * dpz;
+                const float ep = (pd * pd) * G.inv_plane;
+                w = ptm::exp1_nonpos(-((en + ea) + ep));
+            }
+            wgt[k] = w;
+            counted |= 1ull << k;
+            const float a = w * cq.w;
+            N = N + a;
+            ar = ar + a * cq.x; ag = ag + a * cq.y; ab = ab + a * cq.z;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const float mr = ar / N, mg = ag / N, mb = ab / N;
+    // pass 2: Chan's rule -- every counted texel's own M2 plus its count times the squared distance of its mean from the pooled one
+    float ss = 0.0f;
+#pragma unroll
+    for (int dy = -Y_R; dy <= Y_R; dy++) {
+#pragma unroll
+        for (int dx = -Y_R; dx <= Y_R; dx++) {
+            const int k = (dy + Y_R) * (2 * Y_R + 1) + dx + Y_R, e = ec0 + dy * Y_SW + dx;
+            if (!((counted >> k) & 1ull)) continue;
+            const float4 cq = l_cn[e];
+            const float s_q = l_ps[e].w;
+            const float ddx = cq.x - mr, ddy = cq.y - mg, ddz = cq.z - mb;
+            const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
+            ss = ss + wgt[k] * (s_q + cq.w * d2);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const float v = N >= 2.0f ? fmaxf(ss / (N - 1.0f), 0.0f) : 0.0f;
+    var[i] = (v / n_p) * (MI3PT_GUIDED_YOUNG_COUNT / n_p);
+}
+
+void launch_guided_variance_young(const GuidedLaunch &G, const float4 *accum, const float4 *moments, float *var, hipStream_t s)
+{
+    if (G.width <= 0 || G.rows <= 0) return;
+    // (at most 32768 x 32768: 1024 x 4096 blocks, inside the grid's limits)
+    const dim3 grid((uint32_t)((G.width + Y_W - 1) / Y_W), (uint32_t)((G.rows + Y_H - 1) / Y_H));
+    hipLaunchKernelGGL(k_guided_variance_young, grid, dim3(256), 0, s, G, accum, moments, var);
+}
+
 void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, int width, int rows, hipStream_t s)
 {
     const size_t texels = (size_t)width * (size_t)rows;

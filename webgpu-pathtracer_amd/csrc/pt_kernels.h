@@ -432,6 +432,9 @@ void launch_guided_level(const GuidedLaunch &G, const float4 *src, float4 *dst, 
 // MI3PT_GUIDED_VARIANCE.  var (rows x width floats) = the 3 x 3 average of the moments image's variance of the mean; then level `level`
 // from src / var_src into dst / var_dst with the colour term |dc|^2 / (sigma_color^2 * var_src(p) + MI3PT_GUIDED_VARIANCE_EPS)
 void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, int width, int rows, hipStream_t s);
+// MI3PT_GUIDED_YOUNG: var in the place of launch_guided_variance's -- a texel with fewer than MI3PT_GUIDED_YOUNG_COUNT samples takes the
+// pooled variance of its 7 x 7 neighbours' samples (accum: the colour level 0 reads; G's sigmas weigh the neighbours)
+void launch_guided_variance_young(const GuidedLaunch &G, const float4 *accum, const float4 *moments, float *var, hipStream_t s);
 void launch_guided_level_variance(const GuidedLaunch &G, const float4 *src, float4 *dst, const float *var_src, float *var_dst, int level,
                                   float sigma_color, hipStream_t s);
 // The per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip).  ConvergePart: what

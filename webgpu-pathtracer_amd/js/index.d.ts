@@ -122,9 +122,11 @@ export class Renderer {
   /** feature-guided a-trous de-noise of the running mean (include/mi3pt.h: mi3pt_denoise_guided); renders the feature images itself when
    *  none are current.  sigmaColor null: 2 / sqrt(frames in the mean).  present: also draw the canvas from the filtered image.
    *  variance true (MI3PT_GUIDED_VARIANCE; needs setMoments(true)): the colour weight follows the per-pixel variance of the mean and
-   *  sigmaColor null is 2; 'auto': true when the moments image is on and at least VARIANCE_AUTO_FRAMES frames are in the mean; default false */
+   *  sigmaColor null is 2; 'auto': true when the moments image is on and at least VARIANCE_AUTO_FRAMES frames are in the mean; default false.
+   *  young true (MI3PT_GUIDED_YOUNG; variance mode only): a texel with fewer than four samples takes its variance from the samples of its
+   *  7 x 7 neighbours, and 'auto' chooses the variance mode whenever the moments image is on, from the first frame; default false */
   denoiseGuided(options?: { levels?: number; sigmaColor?: number | null; sigmaNormal?: number; sigmaAlbedo?: number; sigmaPlane?: number;
-    present?: boolean; variance?: boolean | 'auto' }): void;
+    present?: boolean; variance?: boolean | 'auto'; young?: boolean }): void;
   /** localRows x width x 4, row 0 = bottom: the filtered image of the last denoiseGuided */
   readGuided(): Float32Array;
   /** localRows x width, row 0 = bottom: the last level's variance of the last denoiseGuided({ variance: true }) */

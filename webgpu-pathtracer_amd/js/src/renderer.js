@@ -240,16 +240,21 @@ class Renderer {
   // variance of the mean, sigmaColor defaults to 2, readGuidedVariance() returns the filtered variance; false (the default): as above;
   // 'auto': true when the moments image is on and at least VARIANCE_AUTO_FRAMES frames are in the mean (below that a variance from so few
   // samples is itself noise), false otherwise.
+  // young: true (MI3PT_GUIDED_YOUNG; variance mode only, an Error with variance false): a texel with fewer than four samples -- disoccluded
+  // by reproject(), or any texel right after a reset -- takes its variance from the samples of its 7 x 7 neighbours; variance 'auto' then
+  // chooses the variance mode whenever the moments image is on, from the first frame (with moments off it stays the fixed sigma, no flag).
   denoiseGuided(options) {
-    const o = Object.assign({ levels: 3, sigmaColor: null, sigmaNormal: 0.35, sigmaAlbedo: 0.1, sigmaPlane: 0.05, present: false, variance: false }, options || {});
+    const o = Object.assign({ levels: 3, sigmaColor: null, sigmaNormal: 0.35, sigmaAlbedo: 0.1, sigmaPlane: 0.05, present: false, variance: false, young: false }, options || {});
     const frames = Math.max(1, this._frame - 1);
     if (o.variance !== true && o.variance !== false && o.variance !== 'auto') throw new Error("denoiseGuided: variance must be true, false or 'auto'");
-    const variance = o.variance === 'auto' ? this._moments && frames >= VARIANCE_AUTO_FRAMES : o.variance;
+    const variance = o.variance === 'auto' ? this._moments && (!!o.young || frames >= VARIANCE_AUTO_FRAMES) : o.variance;
+    const young = !!o.young && (o.variance === 'auto' ? variance : true);
+    if (young && !variance) throw new Error("denoiseGuided: young needs the variance mode (variance true or 'auto')");
     this.passes.raytrace.update();
     if (this._aovKey === null || this._aovKey !== this._aovKeyNow()) this.renderAovs();
     const sigmaColor = o.sigmaColor === null || o.sigmaColor === undefined ? (variance ? 2 : 2 / Math.sqrt(frames)) : o.sigmaColor;
     if (o.present) this.passes.fullscreen.update();
-    this.native.denoiseGuided(this.handle, o.levels, sigmaColor, o.sigmaNormal, o.sigmaAlbedo, o.sigmaPlane, (o.present ? 1 : 0) | (variance ? 2 : 0));
+    this.native.denoiseGuided(this.handle, o.levels, sigmaColor, o.sigmaNormal, o.sigmaAlbedo, o.sigmaPlane, (o.present ? 1 : 0) | (variance ? 2 : 0) | (young ? 4 : 0));
   }
   // localRows x width floats: the last level's variance of the last denoiseGuided({ variance: true })
   readGuidedVariance() { return this.native.readGuidedVariance(this.handle, this.localRows * this._width); }

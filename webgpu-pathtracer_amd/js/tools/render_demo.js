@@ -12,6 +12,8 @@
 //   --guided-variance  the moments image on from the start, then renderer.denoiseGuided({ variance: true, present: true }): the outputs of
 //                      --guided from the variance-guided filter, <prefix>_guided_variance.f32 (raw float, one per texel) and
 //                      <prefix>_moments.f32 (raw RGBA float: M2.rgb, n).  Not together with --guided: both write <prefix>_guided.*
+//   --young            with --guided-variance: denoiseGuided({ ..., young: true }) -- a texel with fewer than four samples (disoccluded by
+//                      --reproject, or every texel of a one-frame view) takes its variance from the samples of its 7 x 7 neighbours
 //   --until <rmse>     sample until converged instead of a fixed count: renderer.renderUntil(scene, camera, rmse, { maxFrames: --frames })
 //                      with the moments image on; --min-frames N (16), --check-every N (the batch capacity), --no-lookahead.  Prints the
 //                      frames taken and the summary of the estimate under "until"
@@ -50,6 +52,8 @@ function arg(name, dflt) {
 async function main() {
   const guidedVariance = process.argv.includes('--guided-variance');
   if (guidedVariance && process.argv.includes('--guided')) throw new Error('--guided and --guided-variance both write <prefix>_guided.f32 / .png: give one of them');
+  const young = process.argv.includes('--young');
+  if (young && !guidedVariance) throw new Error('--young changes the variance-guided filter: give --guided-variance too');
   const width = parseInt(arg('width', '256'), 10), height = parseInt(arg('height', '256'), 10);
   const frames = parseInt(arg('frames', '4'), 10), bounces = parseInt(arg('bounces', String(PARAMS.maxBounces)), 10);
   const envPath = arg('env', null), out = arg('out', 'demo');
@@ -137,7 +141,7 @@ async function main() {
       sample(spp, held, 'view ' + view);
       fs.writeFileSync(out + '_view' + view + '.acc.f32', Buffer.from(renderer.readAccumulation().buffer));
       fs.writeFileSync(out + '_view' + view + '.uniforms.bin', Buffer.from(renderer.passes.raytrace.uniforms.bytes));
-      if (guidedVariance) renderer.denoiseGuided({ variance: true, present: true });
+      if (guidedVariance) renderer.denoiseGuided({ variance: true, present: true, young });
       renderer.screenshot(out + '_view' + view + '.png');
     }
   } else if (slide > 0) {
@@ -199,7 +203,7 @@ async function main() {
     renderer.screenshot(out + '_guided.png');
   }
   if (guidedVariance) {
-    renderer.denoiseGuided({ variance: true, present: true });
+    renderer.denoiseGuided({ variance: true, present: true, young });
     fs.writeFileSync(out + '_guided.f32', Buffer.from(renderer.readGuided().buffer));
     fs.writeFileSync(out + '_guided_variance.f32', Buffer.from(renderer.readGuidedVariance().buffer));
     fs.writeFileSync(out + '_moments.f32', Buffer.from(renderer.readMoments().buffer));

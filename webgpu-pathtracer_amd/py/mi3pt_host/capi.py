@@ -23,6 +23,8 @@ PASS_REPROJECT = 6    # mi3pt_pass_time_us only: the gather kernel of reproject 
 PASS_HISTORY = 7      # mi3pt_pass_time_us only: the kernel of merge_history
 GUIDED_PRESENT = 1    # mi3pt_guided_params.flags: draw the canvas from the filtered image
 GUIDED_VARIANCE = 2   # ... the colour weight steered by the per-pixel variance of the mean (needs set_moments(True))
+GUIDED_YOUNG = 4      # ... with GUIDED_VARIANCE: a texel with fewer than GUIDED_YOUNG_COUNT samples takes the pooled variance of its 7 x 7 neighbours
+GUIDED_YOUNG_COUNT = 4.0
 # mi3pt_aov: the first-hit feature images (render_aovs takes an OR of 1 << AOV_*)
 AOV_ALBEDO, AOV_NORMAL, AOV_POSITION, AOV_IDS, AOV_COUNT = 0, 1, 2, 3, 4
 AOV_ALL = (1 << AOV_COUNT) - 1

@@ -391,20 +391,27 @@ class Renderer:
     # ---- feature-guided de-noise of the running mean (no counterpart in the reference) ----
     VARIANCE_AUTO_FRAMES = 8       # variance="auto": frames in the mean from which the per-pixel variance steers the filter (a choice: DESIGN.md 3)
 
-    def denoiseGuided(self, levels=3, sigmaColor=None, sigmaNormal=0.35, sigmaAlbedo=0.1, sigmaPlane=0.05, present=False, variance=False):
+    def denoiseGuided(self, levels=3, sigmaColor=None, sigmaNormal=0.35, sigmaAlbedo=0.1, sigmaPlane=0.05, present=False, variance=False, young=False):
         """Filter the running mean with the edge-avoiding a-trous filter of include/mi3pt.h (mi3pt_denoise_guided); readGuided()
         returns the result, present=True also draws the canvas from it.  variance False: sigmaColor None = 2 / sqrt(frames in the
         mean) -- the noise of the mean falls with the root of its frames.  variance True (MI3PT_GUIDED_VARIANCE; needs
         setMoments(True) before the frames were sampled): the colour weight follows the per-pixel variance of the mean, sigmaColor
         None = 2, readGuidedVariance() returns the filtered variance.  variance "auto": True when the moments image is on and at
         least VARIANCE_AUTO_FRAMES frames are in the mean (below that a variance from so few samples is itself noise), else False.
+        young True (MI3PT_GUIDED_YOUNG; variance mode only, a ValueError with variance False): a texel with fewer than four samples --
+        disoccluded by reproject(), or any texel right after a reset -- takes its variance from the samples of its 7 x 7 neighbours;
+        variance "auto" then chooses the variance mode whenever the moments image is on, from the first frame (with moments off it
+        stays the fixed sigma, without the flag).
         The feature images are rendered first unless all four are current for the camera and scene of the last update() at this
         size.  The accumulation image is untouched."""
         frames = max(1, self._frame - 1)
         if variance == "auto":
-            variance = self._moments and frames >= self.VARIANCE_AUTO_FRAMES
+            variance = self._moments and (bool(young) or frames >= self.VARIANCE_AUTO_FRAMES)
+            young = bool(young) and variance
         elif not isinstance(variance, bool):
             raise ValueError("variance must be True, False or 'auto'")
+        if young and not variance:
+            raise ValueError("young=True needs the variance mode (variance=True or 'auto')")
         self.passes["raytrace"].update()
         if self._aovKey is None or self._aovKey != self._aovKeyNow():
             self.renderAovs()
@@ -413,7 +420,8 @@ class Renderer:
         if present:
             self.passes["fullscreen"].update()
         self.ctx.denoise_guided(levels, sigmaColor, sigmaNormal, sigmaAlbedo, sigmaPlane,
-                                (capi.GUIDED_PRESENT if present else 0) | (capi.GUIDED_VARIANCE if variance else 0))
+                                (capi.GUIDED_PRESENT if present else 0) | (capi.GUIDED_VARIANCE if variance else 0) |
+                                (capi.GUIDED_YOUNG if young else 0))
 
     def readGuidedVariance(self):
         """(rows, width) float32: the last level's variance of the last denoiseGuided(variance=True)."""
