@@ -73,7 +73,7 @@ extern "C" {
  * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles; mi3pt_set_mean_by_count, mi3pt_host_view_frame, mi3pt_reproject,
  * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6); mi3pt_keep_geometry, mi3pt_reproject_scene, struct mi3pt_reproject_scene_params;
  * mi3pt_hold_history, mi3pt_merge_history, struct mi3pt_history_params, MI3PT_HISTORY_EPS, MI3PT_PASS_HISTORY (7);
- * MI3PT_GUIDED_YOUNG, MI3PT_GUIDED_YOUNG_COUNT. */
+ * MI3PT_GUIDED_YOUNG, MI3PT_GUIDED_YOUNG_COUNT; mi3pt_set_guided_despike, mi3pt_read_guided_despiked. */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -461,6 +461,34 @@ int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfloats);
  * a tile split and a device group stay refused; MI3PT_PASS_GUIDED's time includes the kernel. ---- */
 #define MI3PT_GUIDED_YOUNG 4u
 #define MI3PT_GUIDED_YOUNG_COUNT 4.0f
+
+/* ---- the firefly pre-pass of mi3pt_denoise_guided: context state, not a flag bit (bit 8 and every higher bit stay MI3PT_ERR_INVALID).  A
+ * few paths find a small bright light and leave single texels far above their neighbours; the colour weight isolates exactly those
+ * texels and the filter keeps them.  While mi3pt_set_guided_despike(ctx, 1) holds, every mi3pt_denoise_guided -- any mode -- runs one
+ * more kernel after the pack kernel and before the variance kernel and the levels, which scales such a texel down to the brightest
+ * neighbour of its own class.  The accumulation image stays as it is: only the image handed to the filter changes.  Pinned arithmetic:
+ * fp32, nothing contracted, correctly rounded division; a NaN is carried by the comparisons as written.  With c = the colour level 0 would
+ * read, cls(q) = words 1 and 2 of IDS (material and hit flag):
+ *   L(q) = ((c.r + c.g) + c.b) * (1.0f / 3.0f)
+ *   taps q = p + (dx, dy), dy = -1 .. 1 outer, dx = -1 .. 1 inner, the centre left out.  A tap COUNTS iff q lies inside the image and
+ *   cls(q) == cls(p) (both words);   m = the number of counting taps
+ *   cap = 0;   for each counting tap, in that order: cap = fmaxf(cap, L(q))          (fmaxf drops a NaN)
+ *   p is CLAMPED iff m >= 1 && L(p) > cap:   s = cap / L(p);   c'(p).k = c(p).k * s  (k = r, g, b; the alpha channel keeps its bits)
+ *   otherwise:                               s = 1;            c'(p) = c(p), bit for bit
+ * Level 0 reads c' in c's place; so do MI3PT_GUIDED_YOUNG's c and the output's alpha rule.  Under MI3PT_GUIDED_VARIANCE, with or without
+ * MI3PT_GUIDED_YOUNG, var_0 is taken exactly as there and then var_0(p) = var_0(p) * (s * s) for the clamped texels: the variance of a
+ * scaled variable.  Nothing else of any mode's definition changes; an image in which no texel is clamped gives the bits of the same call
+ * with the state off.  (A texel of a class of its own among its neighbours, m == 0, is left alone: a small emitter is not clamped against
+ * the wall behind it.  L(p) = +inf over a finite cap gives s = 0 and c' = NaN; a NaN L(p) is never clamped.)
+ * The clamped texels are counted on the device, one vector atomic add per wave; mi3pt_read_guided_despiked (blocking) returns the count
+ * of the last filter: MI3PT_ERR_STATE unless the last filter since the last resize ran with the state on, MI3PT_ERR_INVALID for a null
+ * pointer.  One more rows x width x 16 B image (and 8 KiB of counter words) is allocated by the first filter that runs with the state on and
+ * freed at mi3pt_resize / mi3pt_destroy; a context that never enables the state allocates and launches exactly what it did before.  The
+ * pre-pass changes neither the accumulation, the moments, the feature images nor any counter; MI3PT_GUIDED_PRESENT draws from the filtered
+ * image as before; a rank of a tile split and a device group stay refused by mi3pt_denoise_guided (the setter itself goes to every
+ * member of a group); MI3PT_PASS_GUIDED's time includes the kernel.  MI3PT_ERR_INVALID for a null context. ---- */
+int mi3pt_set_guided_despike(mi3pt_ctx *ctx, int enabled);           /* default 0 */
+int mi3pt_read_guided_despiked(mi3pt_ctx *ctx, uint32_t *texels);    /* blocking: texels the last filter clamped */
 
 /* ---- the per-tile error estimate of the running mean: when to stop sampling -- no counterpart in the reference, which renders a fixed
  * number of frames.  mi3pt_estimate_convergence reduces (accumulation image, moments image) on the device to one record per 8 x 8 tile

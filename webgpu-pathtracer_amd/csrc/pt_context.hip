@@ -324,6 +324,13 @@ struct mi3pt_ctx {
     // with the textures; guided_var_result: the one the last level wrote (null: the last filter ran without the flag)
     float *d_guided_var[2] = {};
     const float *guided_var_result = nullptr;
+    // mi3pt_set_guided_despike: the state; the image the pre-pass writes and the filter reads in the accumulation image's place (local_rows
+    // x width x 16 B) with the words that count the clamped texels (pt::DESPIKE_SLOTS of them, summed at the read), both allocated by the
+    // first filter that runs with the state on and freed with the textures; guided_despiked: the last filter since the last resize ran
+    // with the state on (the count is that filter's)
+    bool guided_despike = false, guided_despiked = false;
+    float4 *d_guided_despike = nullptr;
+    uint32_t *d_guided_despike_count = nullptr;
     // The moments image (mi3pt_set_moments): local_rows x width x (M2.rgb, n) fp32 beside the accumulation image, kept by the
     // moments-keeping accumulate kernels; allocated while `moments` is on and the context has textures.
     bool moments = false;
@@ -804,6 +811,11 @@ static void free_textures(mi3pt_ctx *ctx)
     ctx->d_guided_var[0] = ctx->d_guided_var[1] = nullptr;
     ctx->guided_var_result = nullptr;
     ctx->d_moments = nullptr;
+    for (void *p : { (void *)ctx->d_guided_despike, (void *)ctx->d_guided_despike_count })
+        if (p) (void)hipFree(p);
+    ctx->d_guided_despike = nullptr;
+    ctx->d_guided_despike_count = nullptr;
+    ctx->guided_despiked = false;
     for (float4 *&p : ctx->d_aov_prev) { if (p) (void)hipFree(p); p = nullptr; }
     for (float4 *&p : ctx->d_reproject) { if (p) (void)hipFree(p); p = nullptr; }
     ctx->reproject_timer.forget();
@@ -2688,16 +2700,33 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     G.width = ctx->width; G.rows = ctx->local_rows;
     G.inv_color = guided_inv(params->sigma_color); G.inv_normal = guided_inv(params->sigma_normal);
     G.inv_albedo = guided_inv(params->sigma_albedo); G.inv_plane = guided_inv(params->sigma_plane);
+    const bool despike = ctx->guided_despike;
+    if (despike) {
+        if (!ctx->d_guided_despike) HIP_TRY(alloc_plane(&ctx->d_guided_despike, plane_bytes(ctx)));
+        constexpr size_t count_bytes = (size_t)pt::DESPIKE_SLOTS * pt::DESPIKE_SLOT_WORDS * 4;
+        if (!ctx->d_guided_despike_count) HIP_TRY(alloc_plane(&ctx->d_guided_despike_count, count_bytes));
+        HIP_TRY(hipMemsetAsync(ctx->d_guided_despike_count, 0, count_bytes, ctx->stream));      // (outside the timed span: the pre-pass is one launch)
+    }
+    ctx->guided_despiked = false;
     if (ctx->timing) HIP_TRY(ctx->guided_timer.begin(ctx->stream));
     pt::launch_guided_pack(ctx->d_aov[MI3PT_AOV_NORMAL], ctx->d_aov[MI3PT_AOV_IDS], ctx->d_guided_nh, texels, ctx->stream);
     const float4 *src = ctx->d_accum;
     const float *var = nullptr;
+    float *scale = nullptr;
+    if (despike) {
+        // the pre-pass: c' in the accumulation image's place from here on; s into the variance image var_0 does not use (level 0 writes
+        // it after the var_0 kernel has read it)
+        if (by_variance) scale = ctx->d_guided_var[0];
+        pt::launch_guided_despike(src, ctx->d_aov[MI3PT_AOV_IDS], ctx->d_guided_despike, scale, ctx->d_guided_despike_count, ctx->width,
+                                  ctx->local_rows, ctx->stream);
+        src = ctx->d_guided_despike;
+    }
     if (by_variance) {
         // var_0 into the image level 0 does not write; level i then reads image (i + 1) & 1 and writes image i & 1
         if (young)
-            pt::launch_guided_variance_young(G, src, ctx->d_moments, ctx->d_guided_var[1], ctx->stream);
+            pt::launch_guided_variance_young(G, src, ctx->d_moments, ctx->d_guided_var[1], scale, ctx->stream);
         else
-            pt::launch_guided_variance(ctx->d_moments, ctx->d_guided_nh, ctx->d_guided_var[1], ctx->width, ctx->local_rows, ctx->stream);
+            pt::launch_guided_variance(ctx->d_moments, ctx->d_guided_nh, ctx->d_guided_var[1], scale, ctx->width, ctx->local_rows, ctx->stream);
         var = ctx->d_guided_var[1];
     }
     for (int level = 0; level < params->levels; level++) {
@@ -2715,6 +2744,7 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     if (ctx->timing) HIP_TRY(ctx->guided_timer.end(ctx->stream));
     ctx->guided_result = src;
     ctx->guided_var_result = var;
+    ctx->guided_despiked = despike;
     if (params->flags & MI3PT_GUIDED_PRESENT) {
         // the fullscreen pass on the filtered image, with the pass's uniforms as they are and its own de-noiser off.  The canvas then shows
         // no state of the running mean: the next fullscreen submit draws again whatever it showed before, and a draw still owed to queued
@@ -2767,6 +2797,31 @@ extern "C" int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfl
     if (!ctx->guided_var_result) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_guided_variance: the last filter ran without MI3PT_GUIDED_VARIANCE");
     if (nfloats != plane_texels(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width floats)");
     HIP_TRY(read_plane(ctx, ctx->guided_var_result, nfloats * 4, dst));
+    return MI3PT_OK;
+}
+
+// ---- the firefly pre-pass of the guided de-noise (include/mi3pt.h: mi3pt_set_guided_despike; pt_guided.hip: k_guided_despike) ----
+extern "C" int mi3pt_set_guided_despike(mi3pt_ctx *ctx, int enabled)
+{
+    PT_GROUP_ALL(ctx, false, mi3pt_set_guided_despike(m, enabled));
+    if (int rc = require_ctx(ctx)) return rc;
+    ctx->guided_despike = enabled != 0;      // (host state alone: read by the next mi3pt_denoise_guided, which allocates what it needs)
+    return MI3PT_OK;
+}
+
+extern "C" int mi3pt_read_guided_despiked(mi3pt_ctx *ctx, uint32_t *texels)
+{
+    PT_GROUP(ctx, group_unsupported("mi3pt_read_guided_despiked: mi3pt_denoise_guided is not built for a device group"));
+    if (int rc = require_ctx(ctx)) return rc;
+    if (!texels) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = guided_image(ctx, "mi3pt_read_guided_despiked")) return rc;
+    if (!ctx->guided_despiked || !ctx->d_guided_despike_count)
+        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_guided_despiked: the last filter ran without the pre-pass (mi3pt_set_guided_despike)");
+    std::vector<uint32_t> slots((size_t)pt::DESPIKE_SLOTS * pt::DESPIKE_SLOT_WORDS);
+    HIP_TRY(read_plane(ctx, ctx->d_guided_despike_count, slots.size() * 4, slots.data()));
+    uint32_t sum = 0;
+    for (uint32_t k = 0; k < pt::DESPIKE_SLOTS; k++) sum += slots[(size_t)k * pt::DESPIKE_SLOT_WORDS];
+    *texels = sum;
     return MI3PT_OK;
 }
 

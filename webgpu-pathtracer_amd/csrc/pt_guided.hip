@@ -102,9 +102,21 @@ __global__ void __launch_bounds__(256) k_guided_level(const GuidedLaunch G, cons
 // ---- MI3PT_GUIDED_VARIANCE: the colour term steered by the per-pixel variance of the mean (SVGF's spatial filter: Schied et al.,
 // HPG 2017), from the moments image, carried from level to level: the variance kernel and guided_level's second instantiation. ----
 
+// The firefly pre-pass's part in var_0 (mi3pt_set_guided_despike): the variance of a scaled variable, var_0(p) * (s * s), for the texels
+// the pre-pass clamped -- `scale` holds 1 for every other texel, whose var_0 keeps its bits.  DESPIKED false: `v` itself, nothing read;
+// the kernels of a context that never enables the state are those instantiations, compiled to what they were.
+template <bool DESPIKED>
+PT_DEV float despiked_variance(const float v, const float *__restrict__ scale, const size_t i)
+{
+    if (!DESPIKED) return v;
+    const float s = scale[i];
+    return s != 1.0f ? v * (s * s) : v;
+}
+
 // var_0: v (moments_variance, pt_moments.h) averaged over the 3 x 3 neighbours of the centre's hit class, g = [1/4, 1/2, 1/4]
-__global__ void __launch_bounds__(256) k_guided_variance(const float4 *__restrict__ moments, const float4 *__restrict__ normal_hit,
-                                                         float *__restrict__ var, const int width, const int rows)
+template <bool DESPIKED>
+PT_DEV void guided_variance(const float4 *__restrict__ moments, const float4 *__restrict__ normal_hit, float *__restrict__ var,
+                            const float *__restrict__ scale, const int width, const int rows)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)width * (size_t)rows) return;
@@ -125,7 +137,20 @@ __global__ void __launch_bounds__(256) k_guided_variance(const float4 *__restric
             den = den + w;
         }
     }
-    var[i] = num / den;
+    var[i] = despiked_variance<DESPIKED>(num / den, scale, i);
+}
+
+__global__ void __launch_bounds__(256) k_guided_variance(const float4 *__restrict__ moments, const float4 *__restrict__ normal_hit,
+                                                         float *__restrict__ var, const int width, const int rows)
+{
+    guided_variance<false>(moments, normal_hit, var, nullptr, width, rows);
+}
+
+__global__ void __launch_bounds__(256) k_guided_variance_despiked(const float4 *__restrict__ moments, const float4 *__restrict__ normal_hit,
+                                                                  float *__restrict__ var, const float *__restrict__ scale, const int width,
+                                                                  const int rows)
+{
+    guided_variance<true>(moments, normal_hit, var, scale, width, rows);
 }
 
 __global__ void __launch_bounds__(256) k_guided_level_variance(const GuidedLaunch G, const float4 *__restrict__ src, float4 *__restrict__ dst,
@@ -186,8 +211,9 @@ PT_DEV float guided_variance_settled(const float4 *__restrict__ moments, const f
     return num / den;
 }
 
-__global__ void __launch_bounds__(256, 4) k_guided_variance_young(const GuidedLaunch G, const float4 *__restrict__ accum,
-                                                                  const float4 *__restrict__ moments, float *__restrict__ var)
+template <bool DESPIKED>
+PT_DEV void guided_variance_young(const GuidedLaunch &G, const float4 *__restrict__ accum, const float4 *__restrict__ moments,
+                                  float *__restrict__ var, const float *__restrict__ scale)
 {
     __shared__ float4 l_cn[Y_NE];        // c.rgb, n (0 outside the image: such a tap never counts)
     __shared__ float4 l_nh[Y_NE];        // n.xyz, hit
@@ -202,7 +228,7 @@ __global__ void __launch_bounds__(256, 4) k_guided_variance_young(const GuidedLa
     const float settled = guided_variance_settled(moments, G.normal_hit, x, y, G.width, G.rows, n_p);        // (its loads are in flight before the vote)
     const bool young = in_image && n_p < MI3PT_GUIDED_YOUNG_COUNT;        // (a NaN count is not young)
     if (!__syncthreads_or(young ? 1 : 0)) {
-        if (in_image) var[i] = settled;
+        if (in_image) var[i] = despiked_variance<DESPIKED>(settled, scale, i);
         return;
     }
     for (int e = tid; e < Y_NE; e += 256) {
@@ -224,7 +250,7 @@ __global__ void __launch_bounds__(256, 4) k_guided_variance_young(const GuidedLa
     const float4 np = l_nh[ec0], pp = l_ps[ec0], ap = l_alb[ec0];
     const uint32_t hit_p = __float_as_uint(np.w);
     if (!young) {
-        var[i] = settled;
+        var[i] = despiked_variance<DESPIKED>(settled, scale, i);
         return;
     }
     if (!(n_p >= 1.0f)) {        // never sampled
@@ -281,22 +307,137 @@ __global__ void __launch_bounds__(256, 4) k_guided_variance_young(const GuidedLa
         }
     }
     const float v = N >= 2.0f ? fmaxf(ss / (N - 1.0f), 0.0f) : 0.0f;
-    var[i] = (v / n_p) * (MI3PT_GUIDED_YOUNG_COUNT / n_p);
+    var[i] = despiked_variance<DESPIKED>((v / n_p) * (MI3PT_GUIDED_YOUNG_COUNT / n_p), scale, i);
 }
 
-void launch_guided_variance_young(const GuidedLaunch &G, const float4 *accum, const float4 *moments, float *var, hipStream_t s)
+__global__ void __launch_bounds__(256, 4) k_guided_variance_young(const GuidedLaunch G, const float4 *__restrict__ accum,
+                                                                  const float4 *__restrict__ moments, float *__restrict__ var)
+{
+    guided_variance_young<false>(G, accum, moments, var, nullptr);
+}
+
+__global__ void __launch_bounds__(256, 4) k_guided_variance_young_despiked(const GuidedLaunch G, const float4 *__restrict__ accum,
+                                                                           const float4 *__restrict__ moments, float *__restrict__ var,
+                                                                           const float *__restrict__ scale)
+{
+    guided_variance_young<true>(G, accum, moments, var, scale);
+}
+
+// ---- The firefly pre-pass (include/mi3pt.h: mi3pt_set_guided_despike): a texel brighter than every 3 x 3 neighbour of its own class
+// (material and hit flag, words 1 and 2 of the ids image) is scaled down to the brightest of them, into `out`, the image level 0 and the
+// young kernel then read in the accumulation image's place; `scale` (null outside the variance modes) takes s for the var_0 kernels.
+//
+// One launch over two images, shaped as the young kernel: a 32 x 8 tile per block of four waves, a tile row 512 contiguous bytes.  A
+// lane loads its own texel once -- colour and ids, both kept in registers for the output -- and leaves what the eight taps need in LDS:
+// the luminance and the two class words, three 4-byte arrays of 34 x 10 (4 080 B per block: no bound on occupancy), the 84 halo records
+// by the block's first 84 lanes.  A half wave reads 32 consecutive words of an array per tap: no bank conflict.  A tap outside the image
+// is decided from its coordinates; its record holds zeros and is never looked at.  Every index is range-checked before it is used.
+// The count: one ballot per wave and one vector atomic add by its first lane, none from a wave that clamped nothing.  With a firefly in
+// most waves that is one add per 64 texels, and onto ONE word they queue behind each other in the L2: 32 400 adds at 1080p cost 284 us
+// against the 25 us of the pass itself (profiles/guided_despike.log).  So the count is kept in DESPIKE_SLOTS words 128 B apart
+// (pt_kernels.h), a wave adds to the slot of its number in the grid, and the host sums the slots after the read-back. ----
+constexpr int D_W = 32, D_H = 8, D_SW = D_W + 2, D_SH = D_H + 2, D_NE = D_SW * D_SH, D_RING = 2 * D_SW + 2 * D_H;      // 34 x 10 records, 84 of them halo
+
+__global__ void __launch_bounds__(256) k_guided_despike(const float4 *__restrict__ accum, const float4 *__restrict__ ids, float4 *__restrict__ out,
+                                                        float *__restrict__ scale, uint32_t *__restrict__ count, const int width, const int rows)
+{
+    __shared__ float l_lum[D_NE];
+    __shared__ uint32_t l_mat[D_NE], l_hit[D_NE];
+    const int tid = (int)threadIdx.x, tx = tid & (D_W - 1), ty = tid >> 5;
+    const int x0 = (int)blockIdx.x * D_W, y0 = (int)blockIdx.y * D_H;
+    const int x = x0 + tx, y = y0 + ty;
+    const bool in_image = x < width && y < rows;
+    const size_t i = (size_t)y * (size_t)width + (size_t)x;
+    const int ec0 = (ty + 1) * D_SW + tx + 1;
+    float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float lum_p = 0.0f;
+    uint32_t mat_p = 0u, hit_p = 0u;
+    if (in_image) {
+        c = accum[i];
+        const uint4 id = reinterpret_cast<const uint4 *>(ids)[i];
+        lum_p = ((c.x + c.y) + c.z) * (1.0f / 3.0f);
+        mat_p = id.y; hit_p = id.z;
+    }
+    l_lum[ec0] = lum_p; l_mat[ec0] = mat_p; l_hit[ec0] = hit_p;
+    if (tid < D_RING) {
+        // the halo: the row before the tile, the row after it, the column left of it, the column right of it
+        const int ix = tid < 2 * D_SW ? tid % D_SW : (tid < 2 * D_SW + D_H ? 0 : D_SW - 1);
+        const int iy = tid < D_SW ? 0 : (tid < 2 * D_SW ? D_SH - 1 : 1 + (tid - 2 * D_SW) % D_H);
+        const int gx = x0 - 1 + ix, gy = y0 - 1 + iy;
+        float lum = 0.0f;
+        uint32_t mat = 0u, hit = 0u;
+        if (gx >= 0 && gx < width && gy >= 0 && gy < rows) {
+            const size_t q = (size_t)gy * (size_t)width + (size_t)gx;
+            const float4 cq = accum[q];
+            const uint4 id = reinterpret_cast<const uint4 *>(ids)[q];
+            lum = ((cq.x + cq.y) + cq.z) * (1.0f / 3.0f);
+            mat = id.y; hit = id.z;
+        }
+        const int e = iy * D_SW + ix;
+        l_lum[e] = lum; l_mat[e] = mat; l_hit[e] = hit;
+    }
+    __syncthreads();
+    bool clamped = false;
+    if (in_image) {
+        float cap = 0.0f;
+        int m = 0;
+#pragma unroll
+        for (int dy = -1; dy <= 1; dy++) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                if ((dx | dy) == 0) continue;
+                const int qx = x + dx, qy = y + dy;
+                if (qx < 0 || qx >= width || qy < 0 || qy >= rows) continue;
+                const int e = ec0 + dy * D_SW + dx;
+                if (l_mat[e] != mat_p || l_hit[e] != hit_p) continue;
+                m++;
+                cap = fmaxf(cap, l_lum[e]);        // (drops a NaN)
+            }
+        }
+        clamped = m >= 1 && lum_p > cap;
+        float s = 1.0f;
+        if (clamped) {
+            s = cap / lum_p;
+            c.x = c.x * s; c.y = c.y * s; c.z = c.z * s;        // (alpha keeps its bits)
+        }
+        out[i] = c;
+        if (scale) scale[i] = s;
+    }
+    const unsigned long long voted = __ballot(clamped);
+    if ((tid & 63) == 0 && voted != 0ull) {
+        const uint32_t wave = ((uint32_t)blockIdx.y * (uint32_t)gridDim.x + (uint32_t)blockIdx.x) * 4u + (uint32_t)(tid >> 6);
+        atomicAdd(count + (size_t)(wave % DESPIKE_SLOTS) * DESPIKE_SLOT_WORDS, (uint32_t)__popcll(voted));
+    }
+}
+
+void launch_guided_despike(const float4 *accum, const float4 *ids, float4 *out, float *scale, uint32_t *count, int width, int rows, hipStream_t s)
+{
+    if (width <= 0 || rows <= 0) return;
+    // (at most 32768 x 32768: 1024 x 4096 blocks, inside the grid's limits)
+    const dim3 grid((uint32_t)((width + D_W - 1) / D_W), (uint32_t)((rows + D_H - 1) / D_H));
+    hipLaunchKernelGGL(k_guided_despike, grid, dim3(256), 0, s, accum, ids, out, scale, count, width, rows);
+}
+
+void launch_guided_variance_young(const GuidedLaunch &G, const float4 *accum, const float4 *moments, float *var, const float *scale, hipStream_t s)
 {
     if (G.width <= 0 || G.rows <= 0) return;
     // (at most 32768 x 32768: 1024 x 4096 blocks, inside the grid's limits)
     const dim3 grid((uint32_t)((G.width + Y_W - 1) / Y_W), (uint32_t)((G.rows + Y_H - 1) / Y_H));
-    hipLaunchKernelGGL(k_guided_variance_young, grid, dim3(256), 0, s, G, accum, moments, var);
+    if (scale)
+        hipLaunchKernelGGL(k_guided_variance_young_despiked, grid, dim3(256), 0, s, G, accum, moments, var, scale);
+    else
+        hipLaunchKernelGGL(k_guided_variance_young, grid, dim3(256), 0, s, G, accum, moments, var);
 }
 
-void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, int width, int rows, hipStream_t s)
+void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, const float *scale, int width, int rows, hipStream_t s)
 {
     const size_t texels = (size_t)width * (size_t)rows;
     if (width <= 0 || rows <= 0) return;
-    hipLaunchKernelGGL(k_guided_variance, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, s, moments, normal_hit, var, width, rows);
+    const dim3 grid((unsigned)((texels + 255) / 256));
+    if (scale)
+        hipLaunchKernelGGL(k_guided_variance_despiked, grid, dim3(256), 0, s, moments, normal_hit, var, scale, width, rows);
+    else
+        hipLaunchKernelGGL(k_guided_variance, grid, dim3(256), 0, s, moments, normal_hit, var, width, rows);
 }
 
 void launch_guided_level_variance(const GuidedLaunch &G, const float4 *src, float4 *dst, const float *var_src, float *var_dst, int level,

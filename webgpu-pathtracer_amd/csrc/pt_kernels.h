@@ -431,10 +431,17 @@ void launch_guided_pack(const float4 *normal, const float4 *ids, float4 *out, si
 void launch_guided_level(const GuidedLaunch &G, const float4 *src, float4 *dst, int level, hipStream_t s);
 // MI3PT_GUIDED_VARIANCE.  var (rows x width floats) = the 3 x 3 average of the moments image's variance of the mean; then level `level`
 // from src / var_src into dst / var_dst with the colour term |dc|^2 / (sigma_color^2 * var_src(p) + MI3PT_GUIDED_VARIANCE_EPS)
-void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, int width, int rows, hipStream_t s);
+// scale (here and in launch_guided_variance_young): null, or launch_guided_despike's s per texel -- var(p) * (s * s) where s != 1
+void launch_guided_variance(const float4 *moments, const float4 *normal_hit, float *var, const float *scale, int width, int rows, hipStream_t s);
 // MI3PT_GUIDED_YOUNG: var in the place of launch_guided_variance's -- a texel with fewer than MI3PT_GUIDED_YOUNG_COUNT samples takes the
 // pooled variance of its 7 x 7 neighbours' samples (accum: the colour level 0 reads; G's sigmas weigh the neighbours)
-void launch_guided_variance_young(const GuidedLaunch &G, const float4 *accum, const float4 *moments, float *var, hipStream_t s);
+void launch_guided_variance_young(const GuidedLaunch &G, const float4 *accum, const float4 *moments, float *var, const float *scale, hipStream_t s);
+// The firefly pre-pass (include/mi3pt.h: mi3pt_set_guided_despike).  out: accum with every texel brighter than all 3 x 3 neighbours of its
+// class (words 1 and 2 of ids) scaled down to the brightest of them; scale: null, or rows x width floats that take s (1 where nothing
+// was clamped); count: DESPIKE_SLOTS words, DESPIKE_SLOT_WORDS apart (one per 128-byte line), zero before the launch: the clamped
+// texels are added to them, their sum is the count
+constexpr uint32_t DESPIKE_SLOTS = 64, DESPIKE_SLOT_WORDS = 32;
+void launch_guided_despike(const float4 *accum, const float4 *ids, float4 *out, float *scale, uint32_t *count, int width, int rows, hipStream_t s);
 void launch_guided_level_variance(const GuidedLaunch &G, const float4 *src, float4 *dst, const float *var_src, float *var_dst, int level,
                                   float sigma_color, hipStream_t s);
 // The per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip).  ConvergePart: what

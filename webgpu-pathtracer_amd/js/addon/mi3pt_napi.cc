@@ -289,6 +289,7 @@ CTX_INT_FN(SetPipelining, mi3pt_set_pipelining)
 CTX_INT_FN(SetPresentMode, mi3pt_set_present_mode)
 CTX_INT_FN(SetEnvSampling, mi3pt_set_env_sampling)
 CTX_INT_FN(SetMoments, mi3pt_set_moments)
+CTX_INT_FN(SetGuidedDespike, mi3pt_set_guided_despike)
 CTX_INT_FN(SetMeanByCount, mi3pt_set_mean_by_count)
 CTX_VOID_FN(Reset, mi3pt_reset)
 CTX_VOID_FN(Sync, mi3pt_sync)
@@ -460,6 +461,19 @@ napi_value ReadGuidedVariance(napi_env env, napi_callback_info info)
     MI3PT_TRY(mi3pt_read_guided_variance(ctx, static_cast<float *>(data), (size_t)ntexels));
     NAPI_OK(napi_create_typedarray(env, napi_float32_array, (size_t)ntexels, ab, 0, &ta));
     return ta;
+}
+
+// readGuidedDespiked(ctx) -> number: the texels the pre-pass of the last denoiseGuided clamped (mi3pt_set_guided_despike); blocking
+napi_value ReadGuidedDespiked(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    if (!get_args(env, info, a, 1) || !get_ctx(env, a.v[0], &ctx)) return nullptr;
+    uint32_t texels = 0;
+    MI3PT_TRY(mi3pt_read_guided_despiked(ctx, &texels));
+    napi_value out;
+    NAPI_OK(napi_create_uint32(env, texels, &out));
+    return out;
 }
 
 // readMoments(ctx, ntexels) -> Float32Array of ntexels x 4: the moments image (M2.r, M2.g, M2.b, n)
@@ -891,6 +905,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "hostEnvCdf", HostEnvCdf }, { "setPipelining", SetPipelining }, { "setPresentMode", SetPresentMode }, { "setEnvSampling", SetEnvSampling }, { "deviceBuildBvh", DeviceBuildBvh }, { "writeTexture", WriteTexture },
         { "raytraceLaunchStats", RaytraceLaunchStats }, { "renderAovs", RenderAovs }, { "readAov", ReadAov },
         { "denoiseGuided", DenoiseGuided }, { "readGuided", ReadGuided }, { "readGuidedVariance", ReadGuidedVariance },
+        { "setGuidedDespike", SetGuidedDespike }, { "readGuidedDespiked", ReadGuidedDespiked },
         { "setMoments", SetMoments }, { "readMoments", ReadMoments },
         { "estimateConvergence", EstimateConvergence }, { "readConvergence", ReadConvergence }, { "readConvergenceTiles", ReadConvergenceTiles },
         { "batchCapacity", BatchCapacity },

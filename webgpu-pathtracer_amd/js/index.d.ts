@@ -124,13 +124,18 @@ export class Renderer {
    *  variance true (MI3PT_GUIDED_VARIANCE; needs setMoments(true)): the colour weight follows the per-pixel variance of the mean and
    *  sigmaColor null is 2; 'auto': true when the moments image is on and at least VARIANCE_AUTO_FRAMES frames are in the mean; default false.
    *  young true (MI3PT_GUIDED_YOUNG; variance mode only): a texel with fewer than four samples takes its variance from the samples of its
-   *  7 x 7 neighbours, and 'auto' chooses the variance mode whenever the moments image is on, from the first frame; default false */
+   *  7 x 7 neighbours, and 'auto' chooses the variance mode whenever the moments image is on, from the first frame; default false.
+   *  despike true (mi3pt_set_guided_despike; any mode): a firefly pre-pass ahead of the filter scales a texel brighter than all 3 x 3
+   *  neighbours of its material and hit flag down to the brightest of them, in the image the filter reads; the option sets the context's
+   *  state for this call and leaves it so; default false */
   denoiseGuided(options?: { levels?: number; sigmaColor?: number | null; sigmaNormal?: number; sigmaAlbedo?: number; sigmaPlane?: number;
-    present?: boolean; variance?: boolean | 'auto'; young?: boolean }): void;
+    present?: boolean; variance?: boolean | 'auto'; young?: boolean; despike?: boolean }): void;
   /** localRows x width x 4, row 0 = bottom: the filtered image of the last denoiseGuided */
   readGuided(): Float32Array;
   /** localRows x width, row 0 = bottom: the last level's variance of the last denoiseGuided({ variance: true }) */
   readGuidedVariance(): Float32Array;
+  /** the number of texels the pre-pass of the last denoiseGuided({ despike: true }) clamped */
+  readGuidedDespiked(): number;
   /** keep the moments image (M2.r, M2.g, M2.b, n: Welford's sums around the running mean; include/mi3pt.h: mi3pt_set_moments) beside the
    *  accumulation image from now on; it starts at zero.  The mean is bit-identical with and without.  Default off */
   setMoments(enabled: boolean): void;

@@ -53,6 +53,7 @@ class Renderer {
     this._sceneVersion = 0;      // scene uploads so far; with the camera and the size: what the feature images depend on
     this._aovKey = null;         // ... as they were when all four feature images were last rendered (denoiseGuided)
     this._moments = false;       // setMoments: the moments image is kept beside the running mean
+    this._despike = false;       // the context's firefly pre-pass state, as the last denoiseGuided left it
     this._meanByCount = false;   // setMeanByCount: a step's weight comes from the texel's own sample count
     this._trianglesUploaded = 0; // reprojectScene: the triangle count of the last upload (RaytracePass.updateScene)
     this._seedOffset = 0;        // reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
@@ -243,8 +244,11 @@ class Renderer {
   // young: true (MI3PT_GUIDED_YOUNG; variance mode only, an Error with variance false): a texel with fewer than four samples -- disoccluded
   // by reproject(), or any texel right after a reset -- takes its variance from the samples of its 7 x 7 neighbours; variance 'auto' then
   // chooses the variance mode whenever the moments image is on, from the first frame (with moments off it stays the fixed sigma, no flag).
+  // despike: true (mi3pt_set_guided_despike; any mode): a firefly pre-pass ahead of the filter -- a texel brighter than all 3 x 3 neighbours
+  // of its material and hit flag is scaled down to the brightest of them in the image the filter reads; readGuidedDespiked() returns how
+  // many were.  The option sets the context's state for this call and leaves it so; the default is off.
   denoiseGuided(options) {
-    const o = Object.assign({ levels: 3, sigmaColor: null, sigmaNormal: 0.35, sigmaAlbedo: 0.1, sigmaPlane: 0.05, present: false, variance: false, young: false }, options || {});
+    const o = Object.assign({ levels: 3, sigmaColor: null, sigmaNormal: 0.35, sigmaAlbedo: 0.1, sigmaPlane: 0.05, present: false, variance: false, young: false, despike: false }, options || {});
     const frames = Math.max(1, this._frame - 1);
     if (o.variance !== true && o.variance !== false && o.variance !== 'auto') throw new Error("denoiseGuided: variance must be true, false or 'auto'");
     const variance = o.variance === 'auto' ? this._moments && (!!o.young || frames >= VARIANCE_AUTO_FRAMES) : o.variance;
@@ -254,10 +258,16 @@ class Renderer {
     if (this._aovKey === null || this._aovKey !== this._aovKeyNow()) this.renderAovs();
     const sigmaColor = o.sigmaColor === null || o.sigmaColor === undefined ? (variance ? 2 : 2 / Math.sqrt(frames)) : o.sigmaColor;
     if (o.present) this.passes.fullscreen.update();
+    if (!!o.despike !== this._despike) {
+      this.native.setGuidedDespike(this.handle, o.despike ? 1 : 0);
+      this._despike = !!o.despike;
+    }
     this.native.denoiseGuided(this.handle, o.levels, sigmaColor, o.sigmaNormal, o.sigmaAlbedo, o.sigmaPlane, (o.present ? 1 : 0) | (variance ? 2 : 0) | (young ? 4 : 0));
   }
   // localRows x width floats: the last level's variance of the last denoiseGuided({ variance: true })
   readGuidedVariance() { return this.native.readGuidedVariance(this.handle, this.localRows * this._width); }
+  // the number of texels the pre-pass of the last denoiseGuided({ despike: true }) clamped
+  readGuidedDespiked() { return this.native.readGuidedDespiked(this.handle); }
   // ---- the moments image (no counterpart in the reference): (M2.r, M2.g, M2.b, n) -- Welford's sums around the running mean, include/mi3pt.h:
   // mi3pt_set_moments -- kept beside the accumulation image from now on (it starts at zero: enable it before sampling starts, or reset()).
   // The mean is bit-identical with and without.

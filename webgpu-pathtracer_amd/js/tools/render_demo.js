@@ -14,6 +14,9 @@
 //                      <prefix>_moments.f32 (raw RGBA float: M2.rgb, n).  Not together with --guided: both write <prefix>_guided.*
 //   --young            with --guided-variance: denoiseGuided({ ..., young: true }) -- a texel with fewer than four samples (disoccluded by
 //                      --reproject, or every texel of a one-frame view) takes its variance from the samples of its 7 x 7 neighbours
+//   --despike          with --guided or --guided-variance: denoiseGuided({ ..., despike: true }) -- the firefly pre-pass ahead of the filter (a
+//                      texel brighter than all 3 x 3 neighbours of its material and hit flag is scaled down to the brightest of them);
+//                      prints the clamped share and lists the count under "despiked"
 //   --until <rmse>     sample until converged instead of a fixed count: renderer.renderUntil(scene, camera, rmse, { maxFrames: --frames })
 //                      with the moments image on; --min-frames N (16), --check-every N (the batch capacity), --no-lookahead.  Prints the
 //                      frames taken and the summary of the estimate under "until"
@@ -54,6 +57,13 @@ async function main() {
   if (guidedVariance && process.argv.includes('--guided')) throw new Error('--guided and --guided-variance both write <prefix>_guided.f32 / .png: give one of them');
   const young = process.argv.includes('--young');
   if (young && !guidedVariance) throw new Error('--young changes the variance-guided filter: give --guided-variance too');
+  const despike = process.argv.includes('--despike');
+  if (despike && !guidedVariance && !process.argv.includes('--guided')) throw new Error('--despike runs ahead of the guided filter: give --guided or --guided-variance too');
+  let despiked;
+  const sayDespiked = () => {
+    despiked = renderer.readGuidedDespiked();
+    console.error('despike: ' + despiked + ' of ' + width * height + ' texels clamped (' + (100 * despiked / (width * height)).toFixed(2) + ' %)');
+  };
   const width = parseInt(arg('width', '256'), 10), height = parseInt(arg('height', '256'), 10);
   const frames = parseInt(arg('frames', '4'), 10), bounces = parseInt(arg('bounces', String(PARAMS.maxBounces)), 10);
   const envPath = arg('env', null), out = arg('out', 'demo');
@@ -141,7 +151,7 @@ async function main() {
       sample(spp, held, 'view ' + view);
       fs.writeFileSync(out + '_view' + view + '.acc.f32', Buffer.from(renderer.readAccumulation().buffer));
       fs.writeFileSync(out + '_view' + view + '.uniforms.bin', Buffer.from(renderer.passes.raytrace.uniforms.bytes));
-      if (guidedVariance) renderer.denoiseGuided({ variance: true, present: true, young });
+      if (guidedVariance) renderer.denoiseGuided({ variance: true, present: true, despike, young });
       renderer.screenshot(out + '_view' + view + '.png');
     }
   } else if (slide > 0) {
@@ -198,12 +208,14 @@ async function main() {
     fs.writeFileSync(out + '_position.f32', Buffer.from(renderer.readAov('position').buffer));
   }
   if (process.argv.includes('--guided')) {
-    renderer.denoiseGuided({ present: true });
+    renderer.denoiseGuided({ present: true, despike });
+    if (despike) sayDespiked();
     fs.writeFileSync(out + '_guided.f32', Buffer.from(renderer.readGuided().buffer));
     renderer.screenshot(out + '_guided.png');
   }
   if (guidedVariance) {
-    renderer.denoiseGuided({ variance: true, present: true, young });
+    renderer.denoiseGuided({ variance: true, present: true, despike, young });
+    if (despike) sayDespiked();
     fs.writeFileSync(out + '_guided.f32', Buffer.from(renderer.readGuided().buffer));
     fs.writeFileSync(out + '_guided_variance.f32', Buffer.from(renderer.readGuidedVariance().buffer));
     fs.writeFileSync(out + '_moments.f32', Buffer.from(renderer.readMoments().buffer));
@@ -214,7 +226,7 @@ async function main() {
     fs.writeFileSync(out + '_moments.f32', Buffer.from(renderer.readMoments().buffer));
   }
   const summary = {
-    width, height, frames, until, validate: validate > 0 ? { frames: validate, kept: keptShares } : undefined, status: renderer.status, frame: renderer.frame, events,
+    width, height, frames, until, despiked, validate: validate > 0 ? { frames: validate, kept: keptShares } : undefined, status: renderer.status, frame: renderer.frame, events,
     counters: renderer.counters(), stats: renderer.passes.raytrace.stats, first_stats: firstStats, wall_ms: ms,
     timings_us: { raytrace: renderer.timings.raytrace.value, accumulate: renderer.timings.accumulate.value,
       fullscreen: renderer.timings.fullscreen.value },

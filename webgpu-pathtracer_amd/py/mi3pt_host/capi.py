@@ -65,6 +65,7 @@ SYMBOLS = (
     "mi3pt_set_mean_by_count", "mi3pt_host_view_frame", "mi3pt_reproject",
     "mi3pt_keep_geometry", "mi3pt_reproject_scene",
     "mi3pt_hold_history", "mi3pt_merge_history",
+    "mi3pt_set_guided_despike", "mi3pt_read_guided_despiked",
 )
 
 
@@ -156,6 +157,8 @@ def load_library(path=None):
     lib.mi3pt_write_moments.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.mi3pt_moments_device_ptr.argtypes = [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]
     lib.mi3pt_read_guided_variance.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.mi3pt_set_guided_despike.argtypes = [c_void_p, c_int]
+    lib.mi3pt_read_guided_despiked.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_uint32)]
     lib.mi3pt_estimate_convergence.argtypes = [c_void_p, ctypes.c_float, c_int]
     lib.mi3pt_read_convergence.argtypes = [c_void_p, ctypes.POINTER(Convergence)]
     lib.mi3pt_read_convergence_tiles.argtypes = [c_void_p, c_void_p, c_size_t]
@@ -582,6 +585,18 @@ class Context:
         out = np.empty((self.local_rows, self.width), np.float32)
         self._c(self.lib.mi3pt_read_guided_variance(self.handle, _ptr(out), out.size))
         return out
+
+    def set_guided_despike(self, enabled=True):
+        """The firefly pre-pass of denoise_guided (off by default): while on, every denoise_guided first scales a texel brighter
+        than all 3 x 3 neighbours of its class (material, hit flag) down to the brightest of them, in the image the filter reads;
+        the accumulation image is untouched."""
+        self._c(self.lib.mi3pt_set_guided_despike(self.handle, int(bool(enabled))))
+
+    def read_guided_despiked(self):
+        """The number of texels the pre-pass of the last denoise_guided clamped (blocking)."""
+        n = ctypes.c_uint32()
+        self._c(self.lib.mi3pt_read_guided_despiked(self.handle, ctypes.byref(n)))
+        return n.value
 
     def set_moments(self, enabled=True):
         """Keep the moments image (M2.rgb, n: Welford's sums around the running mean) beside the accumulation image from now

@@ -196,6 +196,7 @@ class Renderer:
         self._sceneVersion = 0             # scene uploads so far; with the camera and the size: what the feature images depend on
         self._aovKey = None                # ... as they were when all four feature images were last rendered (denoiseGuided)
         self._moments = False              # setMoments: the moments image is kept beside the running mean
+        self._despike = False              # the context's firefly pre-pass state, as the last denoiseGuided left it
         self._meanByCount = False          # setMeanByCount: a step's weight comes from the texel's own sample count
         self._trianglesUploaded = 0        # reprojectScene: the triangle count of the last upload (updateScene)
         self._seedOffset = 0               # reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
@@ -391,7 +392,8 @@ class Renderer:
     # ---- feature-guided de-noise of the running mean (no counterpart in the reference) ----
     VARIANCE_AUTO_FRAMES = 8       # variance="auto": frames in the mean from which the per-pixel variance steers the filter (a choice: DESIGN.md 3)
 
-    def denoiseGuided(self, levels=3, sigmaColor=None, sigmaNormal=0.35, sigmaAlbedo=0.1, sigmaPlane=0.05, present=False, variance=False, young=False):
+    def denoiseGuided(self, levels=3, sigmaColor=None, sigmaNormal=0.35, sigmaAlbedo=0.1, sigmaPlane=0.05, present=False, variance=False, young=False,
+                      despike=False):
         """Filter the running mean with the edge-avoiding a-trous filter of include/mi3pt.h (mi3pt_denoise_guided); readGuided()
         returns the result, present=True also draws the canvas from it.  variance False: sigmaColor None = 2 / sqrt(frames in the
         mean) -- the noise of the mean falls with the root of its frames.  variance True (MI3PT_GUIDED_VARIANCE; needs
@@ -402,6 +404,10 @@ class Renderer:
         disoccluded by reproject(), or any texel right after a reset -- takes its variance from the samples of its 7 x 7 neighbours;
         variance "auto" then chooses the variance mode whenever the moments image is on, from the first frame (with moments off it
         stays the fixed sigma, without the flag).
+        despike True (mi3pt_set_guided_despike; any mode): a firefly pre-pass ahead of the filter -- a texel brighter than all 3 x 3
+        neighbours of its material and hit flag is scaled down to the brightest of them in the image the filter reads;
+        readGuidedDespiked() returns how many were.  The option sets the context's state for this call and leaves it so; the
+        default is off.
         The feature images are rendered first unless all four are current for the camera and scene of the last update() at this
         size.  The accumulation image is untouched."""
         frames = max(1, self._frame - 1)
@@ -419,6 +425,9 @@ class Renderer:
             sigmaColor = 2.0 if variance else 2.0 / math.sqrt(frames)
         if present:
             self.passes["fullscreen"].update()
+        if bool(despike) != self._despike:
+            self.ctx.set_guided_despike(bool(despike))
+            self._despike = bool(despike)
         self.ctx.denoise_guided(levels, sigmaColor, sigmaNormal, sigmaAlbedo, sigmaPlane,
                                 (capi.GUIDED_PRESENT if present else 0) | (capi.GUIDED_VARIANCE if variance else 0) |
                                 (capi.GUIDED_YOUNG if young else 0))
@@ -426,6 +435,10 @@ class Renderer:
     def readGuidedVariance(self):
         """(rows, width) float32: the last level's variance of the last denoiseGuided(variance=True)."""
         return self.ctx.read_guided_variance()
+
+    def readGuidedDespiked(self):
+        """The number of texels the pre-pass of the last denoiseGuided(despike=True) clamped."""
+        return self.ctx.read_guided_despiked()
 
     # ---- the moments image: the spread of the frames around the running mean (no counterpart in the reference) ----
     def setMoments(self, enabled=True):
