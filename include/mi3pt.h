@@ -472,14 +472,15 @@ int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfloats);
  *   L(q) = ((c.r + c.g) + c.b) * (1.0f / 3.0f)
  *   taps q = p + (dx, dy), dy = -1 .. 1 outer, dx = -1 .. 1 inner, the centre left out.  A tap COUNTS iff q lies inside the image and
  *   cls(q) == cls(p) (both words);   m = the number of counting taps
- *   cap = 0;   for each counting tap, in that order: cap = fmaxf(cap, L(q))          (fmaxf drops a NaN)
+ *   cap = 0;   for each counting tap, in that order: cap = fmaxf(cap, L(q))          (fmaxf drops a NaN; fmaxf(+0, -0) = +0: cap is never -0)
  *   p is CLAMPED iff m >= 1 && L(p) > cap:   s = cap / L(p);   c'(p).k = c(p).k * s  (k = r, g, b; the alpha channel keeps its bits)
  *   otherwise:                               s = 1;            c'(p) = c(p), bit for bit
  * Level 0 reads c' in c's place; so do MI3PT_GUIDED_YOUNG's c and the output's alpha rule.  Under MI3PT_GUIDED_VARIANCE, with or without
  * MI3PT_GUIDED_YOUNG, var_0 is taken exactly as there and then var_0(p) = var_0(p) * (s * s) for the clamped texels: the variance of a
  * scaled variable.  Nothing else of any mode's definition changes; an image in which no texel is clamped gives the bits of the same call
  * with the state off.  (A texel of a class of its own among its neighbours, m == 0, is left alone: a small emitter is not clamped against
- * the wall behind it.  L(p) = +inf over a finite cap gives s = 0 and c' = NaN; a NaN L(p) is never clamped.)
+ * the wall behind it.  L(p) = +inf over a finite cap gives s = 0: c'.k = NaN for an infinite channel k and 0 for a finite one -- finite channels
+ * whose sum overflows give c' = 0.  Two texels with L = +inf beside each other are not clamped; a NaN L(p) is never clamped.)
  * The clamped texels are counted on the device, one vector atomic add per wave; mi3pt_read_guided_despiked (blocking) returns the count
  * of the last filter: MI3PT_ERR_STATE unless the last filter since the last resize ran with the state on, MI3PT_ERR_INVALID for a null
  * pointer.  One more rows x width x 16 B image (and 8 KiB of counter words) is allocated by the first filter that runs with the state on and

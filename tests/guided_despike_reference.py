@@ -2,8 +2,10 @@
 include/mi3pt.h: the image c' the filter reads in the accumulation image's place, the scale s per texel, and the three modes on top of
 guided_reference.py, moments_reference.py and guided_young_reference.py.
 
-numpy fp32, one operation per line of the definition (numpy neither contracts nor reassociates; fp32 `/` is correctly rounded; np.fmax
-drops a NaN as fmaxf does).  Nothing here looks at the device.  No test lives in this file.
+numpy fp32, one operation per line of the definition (numpy neither contracts nor reassociates; fp32 `/` is correctly rounded).  The cap's
+fmaxf is written as a comparison: it starts at +0 and is never a NaN, so `L(q) > cap ? L(q) : cap` drops a NaN as fmaxf does and keeps +0
+against a -0, as the header pins it -- np.fmax(+0, -0) is -0 in numpy's vector loops and +0 in its scalar one.  Nothing here looks at
+the device.  No test lives in this file.
 """
 import numpy as np
 
@@ -45,7 +47,8 @@ def despike(accum, ids):
                 continue
             counts = _shift(inside_all, dy, dx, False) & (_shift(mat, dy, dx) == mat) & (_shift(hit, dy, dx) == hit)
             m = m + counts
-            cap = np.where(counts, np.fmax(cap, _shift(L, dy, dx)), cap)
+            with np.errstate(invalid="ignore"):
+                cap = np.where(counts & (_shift(L, dy, dx) > cap), _shift(L, dy, dx), cap)          # fmaxf from +0 (see above)
     with np.errstate(all="ignore"):
         clamped = (m >= 1) & (L > cap)
         s = np.where(clamped, cap / L, np.float32(1)).astype(np.float32)

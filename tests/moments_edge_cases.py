@@ -136,6 +136,50 @@ def subnormal_patches(mean, moments=None, pitch=12, first=6):
     return centres
 
 
+# ---- squared weights in the fp32 subnormal range (MI3PT_GUIDED_VARIANCE: nv = nv + (w * w) * var(q)) under a weight that is normal
+# itself -- subnormal_patches makes w subnormal, so its w * w is 0.  A 13 x 13 patch of colour 0.5, M2 = 0, n = 4 with a 3 x 3 block
+# brighter by delta in every channel in its middle and M2 = 1e6 per channel at the block's centre alone: var_0 is non-zero exactly on the
+# block (v = 3e6 / 12 at its centre, blurred over 3 x 3).  A texel of the two rings around the block has var = 0, so its colour
+# denominator is MI3PT_GUIDED_VARIANCE_EPS = 1e-8 and with sigma_color = 1 a bright tap has ec = 3 delta^2 / 1e-8; the bright taps are
+# the only ones that carry variance, so the ring's output variance is the sum of their (w * w) * var(q) over den^2 and nothing else.
+#   delta = 3.873e-4: ec = 45, w = exp(-45) h = 2.9e-20 h is normal for every h = h[dx] h[dy] >= 1 / 256, w * w = 8.2e-40 h^2 is not; the
+#   rings' variances lie between 2e-40 and 7e-37 (measured on the reference at 100 x 52), a build that flushes the squares returns 0;
+#   ec = 40: exp(-80) h^2 is still subnormal under h = 1 / 256, but every ring sums squares of 1e-37 and more: no output is subnormal;
+#   ec = 50: exp(-100) h^2 <= 3.7e-44 * (3 / 32)^2 = 3.3e-46 lies below half of the smallest subnormal: every square and every ring is 0
+SQUARED_SIGMA = 1.0
+SQUARED_DELTA = {40: F(3.651e-4), 45: F(3.873e-4), 50: F(4.082e-4)}       # ec -> delta = sqrt(ec * 1e-8 / 3)
+SQUARED_M2, SQUARED_N, SQUARED_BASE = F(1e6), F(4), F(0.5)
+
+
+def squared_weight_patches(mean, moments, hit=None, delta=SQUARED_DELTA[45], pitch=12, first=6):
+    """writes the patches into a (mean, moments) pair in place, centres `pitch` apart from (first, first) on; hit: an image (the ids'
+    word 2) -- only the patches whose 13 x 13 texels lie in one hit class are written
+    (neighbouring patches share their outermost column or row, which holds the same values in both).  Returns the centres"""
+    h, w = mean.shape[:2]
+    centres = []
+    for y in range(first, h - 6, pitch):
+        for x in range(first, w - 6, pitch):
+            if hit is not None and (hit[y - 6:y + 7, x - 6:x + 7] != hit[y, x]).any():
+                continue
+            mean[y - 6:y + 7, x - 6:x + 7, :3] = SQUARED_BASE
+            moments[y - 6:y + 7, x - 6:x + 7, :3] = 0
+            moments[y - 6:y + 7, x - 6:x + 7, 3] = SQUARED_N
+            centres.append((y, x))
+    for y, x in centres:
+        mean[y - 1:y + 2, x - 1:x + 2, :3] = SQUARED_BASE + F(delta)
+        moments[y, x, :3] = SQUARED_M2
+    return centres
+
+
+def rings(centres, shape):
+    """the texels two and three away from a block's centre (Chebyshev): var = 0 themselves, the block in reach of their 5 x 5"""
+    mask = np.zeros(shape, bool)
+    for y, x in centres:
+        mask[y - 3:y + 4, x - 3:x + 4] = True
+        mask[y - 1:y + 2, x - 1:x + 2] = False
+    return mask
+
+
 def non_finite_means(mean, at):
     """writes the non-finite mean entries at the given (y, x), one after the other (few: every one of them spreads over 5 x 5 texels per
     level of the guided filter)"""

@@ -76,9 +76,11 @@ def initial_variance(moments, hit):
 
 
 def guided_variance(orc, accum, moments, normal, position, albedo, ids, levels=3, sigma_color=2.0, sigma_normal=0.35, sigma_albedo=0.1,
-                    sigma_plane=0.05):
+                    sigma_plane=0.05, flush_squares=False):
     """guided_reference.guided with MI3PT_GUIDED_VARIANCE.  moments: (rows, w, 4) float32.  Returns (filtered (rows, w, 4) float32,
-    variance (rows, w) float32 after the last level, stats as guided_reference.guided)."""
+    variance (rows, w) float32 after the last level, stats as guided_reference.guided and "squared_subnormal": the counted taps with a
+    normal weight w whose square w * w is an fp32 subnormal).  flush_squares: what a build computes that returns such a square as 0 --
+    never the reference, only the proof that a test case can tell the two apart."""
     c = np.ascontiguousarray(accum, np.float32)
     n = np.ascontiguousarray(normal, np.float32)[..., :3]
     pos = np.ascontiguousarray(position, np.float32)[..., :3]
@@ -91,7 +93,7 @@ def guided_variance(orc, accum, moments, normal, position, albedo, ids, levels=3
         k_c = sc * sc
     inv_normal, inv_albedo, inv_plane = inv_sigma(sigma_normal), inv_sigma(sigma_albedo), inv_sigma(sigma_plane)
     inside_all = np.ones((rows, w), bool)
-    taps = rejected = counted_off = below = above = subnormal = 0
+    taps = rejected = counted_off = below = above = subnormal = squared_subnormal = 0
     cur = c
     var = initial_variance(moments, hit)
     for i in range(levels):
@@ -123,7 +125,11 @@ def guided_variance(orc, accum, moments, normal, position, albedo, ids, levels=3
                     for k in range(3):
                         num[..., k] = np.where(counts, num[..., k] + wgt * cq[..., k], num[..., k])
                     ww = wgt * wgt
+                    tiny_square = (wgt >= TINY) & (ww > 0) & (ww < TINY)
+                    if flush_squares:
+                        ww = np.where(tiny_square, np.float32(0), ww)
                     nv = np.where(counts, nv + ww * vq, nv)
+                squared_subnormal += int((counts & tiny_square).sum())
                 taps += int(inside.sum())
                 rejected += int((inside & ~counts).sum())
                 if dy or dx:
@@ -140,7 +146,8 @@ def guided_variance(orc, accum, moments, normal, position, albedo, ids, levels=3
         out[..., 3] = cur[..., 3]
         cur = out
     stats = {"taps": taps, "rejected": rejected / taps if taps else 0.0,
-             "below": below / counted_off if counted_off else 0.0, "above": above / counted_off if counted_off else 0.0, "subnormal": subnormal}
+             "below": below / counted_off if counted_off else 0.0, "above": above / counted_off if counted_off else 0.0, "subnormal": subnormal,
+             "squared_subnormal": squared_subnormal}
     return cur, var, stats
 
 

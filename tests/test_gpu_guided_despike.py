@@ -3,13 +3,15 @@ _despiked twins of the two var_0 kernels) against tests/guided_despike_reference
 variance where the mode has one (read_guided_variance) and the count of clamped texels (read_guided_despiked) are compared bit for bit
 (ptcommon.same_bits) -- no tolerance anywhere.  Modelled on tests/test_gpu_guided_young.py: the features are the device's own read_aov of
 the demo scene, the accumulation is written with write_texture and the moments with write_moments.  The kernel works on 32 x 8 tiles
-with a halo of 1.  The conditions that keep a case from passing vacuously are asserted on the reference's statistics, never on the
-device's output."""
+with a halo of 1 and counts in 64 slots by wave number; tests/despike_edge_cases.py holds the images (they are built once more, with the
+oracle's features, by tests/test_despike_edge_cases.py) and the worked examples of the value range.  The conditions that keep a case
+from passing vacuously are asserted on the reference's statistics, never on the device's output."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import despike_edge_cases as de
 import guided_despike_reference as dr
 import guided_reference as gr
 import moments_reference as mr
@@ -24,7 +26,7 @@ MASK = capi.SUBMIT_RAYTRACE | capi.SUBMIT_ACCUMULATE
 TEX = capi.TEX_ACCUMULATION
 SIGMAS = (2.0, 0.35, 0.1, 0.05)
 MODES = {"fixed": 0, "variance": capi.GUIDED_VARIANCE, "young": capi.GUIDED_VARIANCE | capi.GUIDED_YOUNG}
-BELOW_FOUR = np.nextafter(F(4), F(0))
+class_of, spiked_accum, smooth_accum, mixed_moments = de.class_of, de.spiked_accum, de.smooth_accum, de.mixed_moments
 _features = {}
 _references = {}
 
@@ -53,57 +55,6 @@ def _prepare(ctx, demo, env, w, h):
     if (w, h) not in _features:
         _features[(w, h)] = {name: ctx.read_aov(k) for k, name in enumerate(NAMES)}
     return _features[(w, h)]
-
-
-def class_of(ids):
-    words = np.ascontiguousarray(ids).view(np.int32)
-    return words[..., 1].astype(np.int64) * 2 + words[..., 2]
-
-
-def spiked_accum(ids, seed=20261020):
-    """seeded colours in [0, 4) -- a texel that happens to be the brightest of its class in its 3 x 3 is clamped by a little -- with
-    spikes of 30 .. 200 times that planted in the four image corners, on the texels of a class border (one whose right or upper
-    neighbour is of another class; every third of them), and as an adjacent pair inside a class where the image has room for one"""
-    h, w = ids.shape[:2]
-    rng = np.random.default_rng(seed + 1000 * w + h)
-    a = (rng.random((h, w, 4), dtype=F) * F(4)).astype(F)
-    cls = class_of(ids)
-    border = np.zeros((h, w), bool)
-    border[:, :-1] |= cls[:, :-1] != cls[:, 1:]
-    border[:-1, :] |= cls[:-1, :] != cls[1:, :]
-    planted = np.zeros((h, w), bool)
-    ys, xs = np.nonzero(border)
-    planted[ys[::3], xs[::3]] = True
-    for y, x in ((0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1)):
-        planted[y, x] = True
-    if w >= 8 and h >= 4:
-        same = (cls[:, :-1] == cls[:, 1:]) & ~border[:, :-1] & ~border[:, 1:]
-        same[0, :] = same[-1, :] = False
-        ys, xs = np.nonzero(same)
-        if len(ys):
-            k = len(ys) // 2
-            planted[ys[k], xs[k]] = planted[ys[k], xs[k] + 1] = True
-    boost = (F(30) + rng.random((h, w), dtype=F) * F(170)).astype(F)
-    a[..., :3] = np.where(planted[..., None], a[..., :3] * boost[..., None], a[..., :3])
-    return a
-
-
-def smooth_accum(ids):
-    """a colour per class: nothing to clamp"""
-    cls = class_of(ids)
-    values, index = np.unique(cls, return_inverse=True)
-    palette = (np.random.default_rng(5).random((len(values), 4), dtype=F) * F(4)).astype(F)
-    return palette[index.reshape(cls.shape)]
-
-
-def mixed_moments(w, h, seed=20261019):
-    """seeded M2 in [0, 24) where the count holds a variance, counts on either side of MI3PT_GUIDED_YOUNG_COUNT"""
-    rng = np.random.default_rng(seed)
-    counts = np.array([1, 2, 3, BELOW_FOUR, 4, 64], F)
-    m = (rng.random((h, w, 4), dtype=F) * F(24)).astype(F)
-    m[..., 3] = counts[rng.integers(0, len(counts), (h, w))]
-    m[..., :3] = np.where(m[..., 3:] >= 2, m[..., :3], 0)
-    return m
 
 
 def reference(orc, feat, accum, moments, mode, levels, sigmas=SIGMAS, key=None):
@@ -394,3 +345,134 @@ def test_pass_time_includes_the_kernel(ctx, orc, demo, env):
         assert ctx.pass_time_us(capi.PASS_GUIDED) > 0.0
     finally:
         ctx.enable_timing(False)
+
+
+# ---- the count past its DESPIKE_SLOTS slots (DESIGN.md "Pinned decomposition"; tests/despike_edge_cases.py: count_slots).  96 x 48: 18
+# blocks, 72 waves, 8 slots shared by two waves; 160 x 32: 20 blocks in five columns, 80 waves, 16 shared slots; 264 x 260: 297 blocks in
+# nine columns and 33 rows, 1188 waves, every slot shared -- there the _despiked twins of the two var_0 kernels also run over several
+# tiles in both axes.  tests/test_despike_edge_cases.py asserts the same conditions with the oracle's features
+SLOT_SIZES = [(96, 48, m, 3) for m in MODES] + [(160, 32, m, 3) for m in MODES] + [(264, 260, "fixed", 1), (264, 260, "young", 1)]
+
+
+@pytest.mark.parametrize("w,h,mode,levels", SLOT_SIZES, ids=[f"{w}x{h}-{m}" for w, h, m, _ in SLOT_SIZES])
+def test_the_count_is_folded_over_more_waves_than_slots(ctx, orc, demo, env, w, h, mode, levels):
+    feat, accum, *_, stats = _run(ctx, orc, demo, env, w, h, mode, levels)
+    texels, waves, adding = de.assert_crosses_the_slots(dr.despike(accum, feat["ids"])[1] != 1)
+    print(f"{w}x{h}: {de.launch_shape(w, h)} blocks / waves, {len(adding)} waves add to {int((texels > 0).sum())} slots, {int((waves >= 2).sum())} "
+          f"slots shared; slots 0 .. 31 hold {int(texels[:32].sum())} of {stats['count']}")
+
+
+def test_the_count_slots_are_cleared_by_every_call(ctx, orc, demo, env):
+    """three filters on one context without a resize between them: the spiked image, an image with nothing to clamp -- a slot the call
+    does not clear shows here --, the spiked image again"""
+    w, h = 96, 48
+    feat, accum, moments, want, _, stats = _run(ctx, orc, demo, env, w, h, "fixed", 3)
+    de.assert_crosses_the_slots(dr.despike(accum, feat["ids"])[1] != 1)
+    flat = smooth_accum(feat["ids"])
+    ctx.write_texture(TEX, flat)
+    flat_want, _, flat_stats = reference(orc, feat, flat, moments, "fixed", 3)
+    assert flat_stats["count"] == 0
+    ctx.denoise_guided(3, *SIGMAS)
+    _compare(ctx, flat_want, None, 0, "nothing to clamp after a spiked image")
+    ctx.write_texture(TEX, accum)
+    ctx.denoise_guided(3, *SIGMAS)
+    _compare(ctx, want, None, stats["count"], "the spiked image again")
+
+
+# ---- the value range of the pre-pass (DESIGN.md "Pinned value range"; tests/despike_edge_cases.py: catalogue, EXAMPLES)
+EDGE_SIZES = [(96, 48), (100, 52)]
+# sigma_color 1e-3: a squared colour distance above 1e-4 weighs exp(-100 ...) = 0, so the output follows c' texel by texel
+TIGHT = (1e-3,) + SIGMAS[1:]
+EDGE_CASES = [(w, h, m, SIGMAS) for w, h in EDGE_SIZES for m in MODES] + [(w, h, "fixed", TIGHT) for w, h in EDGE_SIZES]
+
+
+def edge_reference(orc, feat, w, h, mode, sigmas, finite=False, examples=True, stored=None):
+    """the catalogue's images, the reference of one level over them and the conditions that keep the case from being vacuous, asserted on
+    the reference alone.  stored: the accumulation as the device holds it (F16 storage)"""
+    moments = mixed_moments(w, h)
+    accum, where, placed = de.catalogue(feat["ids"], finite, moments, examples)
+    if stored is not None:
+        accum = stored
+    want, want_var, stats = reference(orc, feat, accum, moments, mode, 1, sigmas)
+    cd, s, _ = dr.despike(accum, feat["ids"])
+    share = float(np.isnan(want).any(axis=-1).mean())
+    print(f"{w}x{h} {mode} sigma_color {sigmas[0]}: {stats['count']} clamped ({stats['clamped']:.3f}), s = 0 at {int((s == 0).sum())}, subnormal s at "
+          f"{int(((s > 0) & (s < gr.TINY)).sum())}, a NaN in {float(np.isnan(cd).any(axis=-1).mean()):.3f} of c' and {share:.3f} of the filtered texels")
+    assert stats["count"] > 0 and 0.01 <= stats["clamped"] <= 0.40
+    if stored is None:
+        assert not de.ec.seam_sides(where, w, h) and min(de.coverage(where, placed, feat["ids"]).values()) >= 1
+    assert 0 < share <= 0.5
+    if examples:
+        de.check_examples(placed, cd, s, accum)
+        assert (s == 0).any() and ((s > 0) & (s < gr.TINY)).any()
+        if mode != "fixed":
+            _, hit = dr._class_of(feat["ids"])
+            if mode == "young":
+                import guided_young_reference as yr
+                var0 = yr.initial_variance_young(orc, cd, moments, feat["normal"], feat["position"], feat["albedo"], feat["ids"], *sigmas[1:])[0]
+            else:
+                var0 = mr.initial_variance(moments, hit)
+            de.check_example_variances(placed, var0, dr._scaled(var0, s))
+    if sigmas is TIGHT:
+        ok = np.isfinite(cd[..., :3]).all(axis=-1) & np.isfinite(want[..., :3]).all(axis=-1)
+        close = np.abs(want[..., :3].astype(np.float64) - cd[..., :3]) <= 2.0 ** -22 * np.abs(cd[..., :3].astype(np.float64))
+        assert ok.mean() >= 0.5 and close.all(axis=-1)[ok].mean() >= 0.95
+    return accum, moments, want, want_var, stats
+
+
+@pytest.mark.parametrize("w,h,mode,sigmas", EDGE_CASES, ids=[f"{w}x{h}-{m}-{'tight' if s is TIGHT else 'default'}" for w, h, m, s in EDGE_CASES])
+def test_value_edges(ctx, orc, demo, env, w, h, mode, sigmas):
+    """the means of the catalogue, NaN and +-inf included, six texels apart and on both sides of every tile seam of the spiked image, and
+    the worked examples: ties, negative and -0 luminances under the 0 floor of the cap, luminances that overflow from finite channels,
+    subnormals on both sides of the division, an s whose square underflows.  One level (it spreads a NaN over 5 x 5 texels); the bits of
+    the reference, a NaN where it has one, the same count"""
+    feat = _prepare(ctx, demo, env, w, h)
+    accum, moments, want, want_var, stats = edge_reference(orc, feat, w, h, mode, sigmas)
+    ctx.write_texture(TEX, accum)
+    ctx.write_moments(moments)
+    ctx.denoise_guided(1, *sigmas, flags=MODES[mode])
+    _compare(ctx, want, want_var, stats["count"], f"value edges {w}x{h} {mode}", same=pc.same_bits_or_nan)
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+def test_value_edges_of_a_mean_stored_as_binary16(ctx, orc, demo, env, mode):
+    """the finite catalogue, six texels apart, as a context under F16 storage holds it -- every channel a binary16 value: 65520, 1e19 and
+    3e38 are +inf, 1e-42 is 0 --: the pre-pass reads the mean as stored and does not round what it writes"""
+    w, h = EDGE_SIZES[0]
+    feat = _prepare(ctx, demo, env, w, h)
+    try:
+        ctx.set_storage(capi.STORAGE_F16)
+        ctx.resize(w, h)
+        ctx.render_aovs(capi.AOV_ALL)
+        accum, _, _ = de.catalogue(feat["ids"], True, None, examples=False)
+        with np.errstate(over="ignore"):
+            accum[..., :3] = accum[..., :3].astype(np.float16).astype(F)          # what an accumulate step stores (write_texture keeps the bits it is given)
+        ctx.write_texture(TEX, accum)
+        stored = ctx.read_texture(TEX)
+        assert stored.tobytes() == accum.tobytes() and np.isinf(stored).any()
+        _, moments, want, want_var, stats = edge_reference(orc, feat, w, h, mode, SIGMAS, finite=True, examples=False, stored=stored)
+        assert not pc.same_bits_or_nan(want[..., :3], want[..., :3].astype(np.float16).astype(F))
+        ctx.write_moments(moments)
+        ctx.denoise_guided(1, *SIGMAS, flags=MODES[mode])
+        _compare(ctx, want, want_var, stats["count"], f"value edges under F16 storage, {mode}", same=pc.same_bits_or_nan)
+    finally:
+        ctx.set_storage(capi.STORAGE_F32)
+
+
+@pytest.mark.parametrize("value", [F(3e38), F(np.inf)], ids=["3e38", "inf"])
+def test_a_texel_alone_in_its_class_keeps_the_largest_mean(ctx, orc, demo, env, value):
+    """48 x 12 has a texel without a 3 x 3 neighbour of its class (96 x 48 and 100 x 52 have none): m = 0, left alone whatever it holds"""
+    w, h = 48, 12
+    feat = _prepare(ctx, demo, env, w, h)
+    lone = np.argwhere(de.taps_of_class(class_of(feat["ids"])) == 0)
+    assert len(lone) >= 1
+    accum, moments = spiked_accum(feat["ids"]), mixed_moments(w, h)
+    for y, x in lone:
+        accum[y, x, :3] = value
+    cd, s, stats = dr.despike(accum, feat["ids"])
+    assert all(s[y, x] == 1 and cd[y, x].tobytes() == accum[y, x].tobytes() for y, x in lone) and stats["count"] > 0
+    want, want_var, stats = reference(orc, feat, accum, moments, "variance", 1)
+    ctx.write_texture(TEX, accum)
+    ctx.write_moments(moments)
+    ctx.denoise_guided(1, *SIGMAS, flags=MODES["variance"])
+    _compare(ctx, want, want_var, stats["count"], "alone in its class", same=pc.same_bits_or_nan)

@@ -257,6 +257,32 @@ def test_subnormal_weights(ctx, orc, demo, env):
     assert stats["subnormal"] > 0
 
 
+SQUARED_SIGMAS = {"features off": (ec.SQUARED_SIGMA, 0.0, 0.0, 0.0), "default features": (ec.SQUARED_SIGMA, 0.35, 0.1, 0.05)}
+
+
+def squared_pair(w, h, ids, delta=ec.SQUARED_DELTA[45]):
+    """the seeded pair with moments_edge_cases.squared_weight_patches inside the hit classes: (accum, moments, the rings' mask)"""
+    accum, moments = _random_accum(w, h), _random_moments(w, h)
+    centres = ec.squared_weight_patches(accum, moments, np.ascontiguousarray(ids).view(np.int32)[..., 2], delta)
+    return accum, moments, ec.rings(centres, (h, w))
+
+
+@pytest.mark.parametrize("name", list(SQUARED_SIGMAS))
+def test_subnormal_squared_weights(ctx, orc, demo, env, name):
+    """`nv = nv + (w * w) * var(q)` with a normal w whose square is an fp32 subnormal (tests/moments_edge_cases.py:
+    squared_weight_patches; test_subnormal_weights makes w itself subnormal, so its square is 0): the rings around the bright blocks
+    carry variances of 2e-40 .. 7e-37 that a build which flushes the squares returns as 0 (tests/test_moments_edge_cases.py shows that
+    on the reference alone).  One level, bit for bit"""
+    w, h = EDGE_SIZE
+    feat = _prepare(ctx, demo, env, w, h)
+    accum, moments, ring = squared_pair(w, h, feat["ids"])
+    *_, want_var, stats = _run(ctx, orc, demo, env, w, h, 1, SQUARED_SIGMAS[name], accum=accum, moments=moments, key_extra="squared weights")
+    tiny = (want_var[ring] > 0) & (want_var[ring] < gr.TINY)
+    print(f"squared weights, {name}: {stats['squared_subnormal']} counted taps with a normal weight and a subnormal square; {int(tiny.sum())} of "
+          f"{int(ring.sum())} ring texels hold a subnormal variance")
+    assert stats["squared_subnormal"] >= 1000 and tiny.sum() >= 100 and (want_var[ring] > 0).mean() >= 0.9
+
+
 def test_non_finite_colours(ctx, orc, demo, env):
     """means at the ends of fp32 and binary16, and six texels with infinities and NaNs, two levels"""
     w, h = EDGE_SIZE

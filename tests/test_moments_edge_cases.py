@@ -252,6 +252,34 @@ def test_guided_variance_weights_in_the_subnormal_range(orc, feat):
     assert stats["subnormal"] >= 1 and changed >= 1 and np.isfinite(want).all()
 
 
+@pytest.mark.parametrize("name", list(gv.SQUARED_SIGMAS))
+def test_guided_variance_squared_weights_in_the_subnormal_range(orc, feat, name):
+    """the images of test_gpu_guided_variance.py::test_subnormal_squared_weights: counted taps with a normal weight whose square is a
+    subnormal, and a restatement that flushes those squares gives another variance image (and the same colour image: the squares enter
+    the variance alone).  Bracketed: at ec = 40 no ring's variance is subnormal, at ec = 50 every square and every ring is exactly 0"""
+    w, h = gv.EDGE_SIZE
+    args = (feat["normal"], feat["position"], feat["albedo"], feat["ids"], 1, *gv.SQUARED_SIGMAS[name])
+    got = {}
+    for ec_value, delta in ec.SQUARED_DELTA.items():
+        accum, moments, ring = gv.squared_pair(w, h, feat["ids"], delta)
+        want, var, stats = mr.guided_variance(orc, accum, moments, *args)
+        flushed, flushed_var, _ = mr.guided_variance(orc, accum, moments, *args, flush_squares=True)
+        r = var[ring]
+        got[ec_value] = (stats["squared_subnormal"], r, int(_differs(var, flushed_var)[ring].sum()))
+        print(f"squared weights, {name}, ec {ec_value}: {stats['squared_subnormal']} counted taps with a normal weight and a subnormal square ("
+              f"{stats['subnormal']} with a subnormal weight); of {r.size} ring texels {int((r == 0).sum())} hold 0 and {int(((r > 0) & (r < gr.TINY)).sum())} "
+              f"a subnormal, the others {r[r > 0].min() if (r > 0).any() else 0:.3g} .. {r.max():.3g}; flushing the squares changes {got[ec_value][2]}")
+        assert np.isfinite(want).all() and np.isfinite(var).all() and want.tobytes() == flushed.tobytes()
+        assert (var[~ring] == flushed_var[~ring]).mean() > 0.99
+    assert ring.sum() >= 20 * 40                                                      # twenty patches and more inside the hit classes
+    stat, r, changed = got[45]
+    assert stat >= got[50][0] + 1000 and changed >= 0.9 * r.size and ((r > 0) & (r < gr.TINY)).sum() >= 100
+    assert ((r == 0) | (r >= F(1e-40))).all() and r.max() <= F(2e-36)
+    r40 = got[40][1]
+    assert not ((r40 > 0) & (r40 < gr.TINY)).any() and (r40 > 0).mean() >= 0.99
+    assert not got[50][1].any() and got[50][2] == 0
+
+
 def test_guided_variance_branches_and_nan_shares(orc, feat):
     """the images of test_gpu_guided_variance.py::test_count_and_m2_catalogue and ::test_non_finite_colours, and of
     test_gpu_guided.py::test_non_finite_colours"""
