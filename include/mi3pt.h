@@ -35,7 +35,7 @@
  *     BLOCKING (the host waits for the context's stream, at least): every upload and mi3pt_write_* (copy at call time),
  *     mi3pt_resize (the internal streams too), mi3pt_set_stream (the stream it leaves), mi3pt_bind_accumulation,
  *     mi3pt_set_moments when it changes the state, every mi3pt_read_*, mi3pt_sync, mi3pt_get_counters, mi3pt_pass_time_us,
- *     mi3pt_raytrace_launch_stats / _span, the mi3pt_debug_* probes, mi3pt_device_build_bvh, mi3pt_destroy.
+ *     mi3pt_raytrace_launch_stats / _span, the mi3pt_debug_* probes, mi3pt_device_build_bvh, mi3pt_device_refit_bvh, mi3pt_destroy.
  *     BLOCKING, but for ONE EVENT only and without launching the frame queue: mi3pt_read_convergence and
  *     mi3pt_read_convergence_tiles wait for the most recent mi3pt_estimate_convergence, not for what was enqueued behind it;
  *     mi3pt_freeze_converged waits for the same event, then acts as mi3pt_set_sample_mask.  mi3pt_read_sample_mask reads host state.
@@ -73,7 +73,7 @@ extern "C" {
  * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles; mi3pt_set_mean_by_count, mi3pt_host_view_frame, mi3pt_reproject,
  * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6); mi3pt_keep_geometry, mi3pt_reproject_scene, struct mi3pt_reproject_scene_params;
  * mi3pt_hold_history, mi3pt_merge_history, struct mi3pt_history_params, MI3PT_HISTORY_EPS, MI3PT_PASS_HISTORY (7);
- * MI3PT_GUIDED_YOUNG, MI3PT_GUIDED_YOUNG_COUNT; mi3pt_set_guided_despike, mi3pt_read_guided_despiked. */
+ * MI3PT_GUIDED_YOUNG, MI3PT_GUIDED_YOUNG_COUNT; mi3pt_set_guided_despike, mi3pt_read_guided_despiked; mi3pt_device_refit_bvh, mi3pt_host_bvh_cost. */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -1012,6 +1012,33 @@ int mi3pt_debug_pairs(mi3pt_ctx *ctx, int fn, const float *rays, const float *ge
  * (mi3pt_host_build_bvh_f64 is): box / triangle test counts differ, the image does not, except
  * where two triangles are hit at exactly the same t.  build_ms (optional): device time. */
 int mi3pt_device_build_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t nodes_capacity_bytes, size_t *nnodes_out, float *build_ms);
+/* REFIT: the boxes of the tree last uploaded with mi3pt_upload_bvh, re-fitted on the device to the triangle records as they stand now --
+ * after a later mi3pt_upload_triangles: rigid motion, skinning, anything that keeps the triangle count and index i naming the same surface
+ * element (the contract of mi3pt_reproject_scene).  The topology stays: nodes_out (host) receives nnodes x 48 B, ready for
+ * mi3pt_upload_bvh; *nnodes_out = nnodes, the record count of the uploaded tree; refit_ms (optional): device time.
+ * Not an approximation of the boxes: the reference's are exact (a leaf box is Box3.setFromPoints(a, b, c), an internal box the union of
+ * its inputs, raytrace.ts:546-550, 581-584) and rounding to fp32 is monotone, so this gives the boxes the reference's build would give the
+ * old topology, bit for bit -- on unchanged triangles the uploaded bytes of a tree from mi3pt_host_build_bvh_f64 or mi3pt_device_build_bvh.
+ * What is lost is tree quality: it is no longer the SAH tree of the new positions (mi3pt_host_bvh_cost before and after says by how much).
+ * Pinned arithmetic, per 48-byte record (raytrace.wgsl:51-64: floats 0 - 2 min, 4 - 6 max, word 7 isLeaf, 8 left, 9 right, 10 triangleIndex):
+ *   lo(x, y) = (y < x || (y == x && signbit(y))) ? y : x        hi(x, y) = (y > x || (y == x && !signbit(y))) ? y : x
+ *   -- Math.min / Math.max on zeros; a NaN y is dropped, a NaN x is kept.  Per component:
+ *   leaf (word 7 == 1), a, b, c = the three positions of triangle record `triangleIndex`:  min = lo(lo(a, b), c), max = hi(hi(a, b), c)
+ *   internal:  min = lo(min(left), min(right)), max = hi(max(left), max(right)) -- always left then right, whichever child finished first
+ *   words 3 and 7 .. 11 are copied bit for bit from the uploaded record.
+ * Non-finite vertices give unspecified boxes; they neither hang nor fault.
+ * It changes NO state of the context: nothing the context renders with is touched, no counter, epoch or mi3pt_debug_last_launch field
+ * moves, and rendering after the call without uploading the result is bit-identical to rendering before it.  Queued frames are launched
+ * first, as for a read-back; the call BLOCKS until the records are on the host.  A device group runs it on member 0, where the scene lives.
+ * On the context's stream: a device copy of the records, a parent table from the left / right words (one thread per node), zeroed arrival
+ * counters, the fit (every leaf writes its box and climbs; at a parent the first child to arrive leaves, the second forms the union and
+ * climbs on; no thread waits for another), a copy to the host.  Temporaries: nnodes x (48 + 4 + 4) bytes, allocated per call and freed before
+ * it returns; a context that never calls this allocates and launches exactly what it did before.
+ *   MI3PT_ERR_STATE before both uploads; unless the uploaded tree is proper (word 4 of mi3pt_host_scene_compile: every node reached once,
+ *   one leaf per triangle, depth under 64) and the root, node 0, reaches EVERY record of the buffer (a record out of its reach has no place
+ *   in a bottom-up pass; the message says which of the two it was); unless it names only triangles that exist (max_tri_ref < ntris).
+ *   MI3PT_ERR_INVALID for a null context, a null nodes_out or nnodes_out, a capacity below nnodes x 48. */
+int mi3pt_device_refit_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t nodes_capacity_bytes, size_t *nnodes_out, float *refit_ms);
 
 /* Debug: node-packet / triangle numbering used on the device.  0 (default, shipped) = packets
  * breadth-first like the uploaded nodes, triangles as uploaded.  1 = packets in the reference's
@@ -1049,6 +1076,12 @@ int mi3pt_host_build_bvh(const void *triangles, size_t ntris, void *nodes_out,
  * so near-tie splits come out exactly as in the reference. */
 int mi3pt_host_build_bvh_f64(const double *positions, size_t ntris, void *nodes_out,
                              size_t nodes_capacity_bytes, size_t *nnodes_out, int nthreads);
+/* The SAH figure of a tree (48-byte records) as it stands, what a host compares before and after mi3pt_device_refit_bvh: with
+ * (x, y, z) = max - min of a record's box, each difference taken in double from the fp32 fields, area = 2 * ((x*y + x*z) + y*z);
+ * *cost = (the areas of ALL nnodes records, added in index order) / (the area of node 0, the root); 0 for a root area of 0.  Leaves count
+ * like internal nodes: one figure for "boxes a ray has to be tested against", relative to the root.  MI3PT_ERR_INVALID for a null
+ * pointer or nnodes == 0. */
+int mi3pt_host_bvh_cost(const void *nodes, size_t nnodes, double *cost);
 /* updateEnvironmentTexture's CDF texture, renderer.ts:159-266: R marginal CDF,
  * G conditional CDF, B sin-weighted luminance, A 1. */
 int mi3pt_host_env_cdf(const float *rgba, int width, int height, float *cdf_rgba_out);

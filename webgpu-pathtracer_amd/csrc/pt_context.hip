@@ -136,6 +136,7 @@ struct mi3pt_ctx {
     std::map<const void *, size_t> buf_bytes;     // size of every scene buffer replace_buffer() made (what clone_scene copies to a group's other members)
     uint64_t scene_epoch = 1;             // bumped whenever the device's scene data or its analysis changes (uploads, prepare_layout, prepare_cull)
     uint64_t host_analyses = 0;           // scene compiles done on the host by THIS context: uploads that build packets + cull analyses (MI3PT_OPT_HOST_ANALYSES)
+    size_t nodes_reached = 0;       // mi3pt_upload_bvh: records the root reaches (mi3pt_device_refit_bvh needs every one reached)
     bool tree_proper = false;       // mi3pt_upload_bvh: every node reached once, one leaf per triangle, the 64-entry abort cannot fire
     bool layout_active = false;     // the device holds relabelled packets / triangles
     void *d_tris_perm = nullptr;    // 112-B records in the relabelled order (the uploaded order stays in d_tris)
@@ -1215,6 +1216,7 @@ extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes
     ctx->leaf_cap = t.leaf_cap;
     ctx->cull_stack_ok = t.cull_stack_ok;
     ctx->tree_proper = t.tree_proper;
+    ctx->nodes_reached = t.reached;
     ctx->walk_stack_worst = t.walk_stack_worst;
     ctx->nnodes = n;
     ctx->npackets = t.npackets;
@@ -3489,6 +3491,31 @@ extern "C" int mi3pt_device_build_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t no
     return MI3PT_OK;
 }
 
+// The boxes of the uploaded tree re-fitted to the uploaded triangles (pt_refit.hip).  Reads d_nodes and d_tris, writes temporaries of its own:
+// no field of the context moves.
+extern "C" int mi3pt_device_refit_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t nodes_capacity_bytes, size_t *nnodes_out, float *refit_ms)
+{
+    PT_GROUP(ctx, mi3pt_device_refit_bvh(group_member0(ctx), nodes_out, nodes_capacity_bytes, nnodes_out, refit_ms));
+    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
+    if (!nodes_out || !nnodes_out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (int rc = require_idle(ctx)) return rc;
+    if (!ctx->d_nodes || ctx->nnodes == 0) return pt_set_error(MI3PT_ERR_STATE, "no BVH uploaded (mi3pt_upload_bvh)");
+    if (!ctx->d_tris || ctx->ntris == 0) return pt_set_error(MI3PT_ERR_STATE, "no triangles uploaded (mi3pt_upload_triangles)");
+    if (!ctx->tree_proper)
+        return pt_set_error(MI3PT_ERR_STATE, "refit needs a proper tree: every node reached once from node 0, one leaf per triangle, depth under 64");
+    if (ctx->nodes_reached != ctx->nnodes)
+        return pt_set_error(MI3PT_ERR_STATE, "refit needs every record of the buffer within reach of node 0: the uploaded tree holds records the root does not reach");
+    if (ctx->max_tri_ref >= (int64_t)ctx->ntris)
+        return pt_set_error(MI3PT_ERR_STATE, "BVH references a triangle index beyond the triangle buffer");
+    if (nodes_capacity_bytes < ctx->nnodes * MI3PT_BVHNODE_STRIDE) return pt_set_error(MI3PT_ERR_INVALID, "node buffer too small");
+    std::string err;
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    if (pt::refit_bvh(ctx->d_tris, ctx->ntris, ctx->d_nodes, ctx->nnodes, nodes_out, refit_ms, ctx->stream, err) != 0)
+        return pt_set_error(MI3PT_ERR_HIP, "device BVH refit: " + err);
+    *nnodes_out = ctx->nnodes;
+    return MI3PT_OK;
+}
+
 extern "C" int mi3pt_debug_math(mi3pt_ctx *ctx, int fn, const float *a, const float *b, float *out, size_t n)
 {
     PT_GROUP(ctx, mi3pt_debug_math(group_member0(ctx), fn, a, b, out, n));
@@ -3713,7 +3740,7 @@ static int clone_scene(mi3pt_ctx *dst, const mi3pt_ctx *src)
     dst->ntris = src->ntris; dst->nnodes = src->nnodes; dst->nmats = src->nmats; dst->npackets = src->npackets;
     dst->root_ref = src->root_ref; dst->scene_flags = src->scene_flags; dst->wide_root_nested = src->wide_root_nested;
     dst->max_tri_ref = src->max_tri_ref; dst->max_mat_ref = src->max_mat_ref;
-    dst->leaf_cap = src->leaf_cap; dst->cull_stack_ok = src->cull_stack_ok; dst->tree_proper = src->tree_proper;
+    dst->leaf_cap = src->leaf_cap; dst->cull_stack_ok = src->cull_stack_ok; dst->tree_proper = src->tree_proper; dst->nodes_reached = src->nodes_reached;
     dst->walk_stack_worst = src->walk_stack_worst; dst->wide_stack_worst = src->wide_stack_worst;
     dst->cull_dirty = src->cull_dirty; dst->cull_ok = src->cull_ok; dst->cull_ka = src->cull_ka; dst->cull_kb = src->cull_kb;
     dst->auto_wide_variant = src->auto_wide_variant; dst->wide_ok = src->wide_ok; dst->cwide_ok = src->cwide_ok; dst->nwide = src->nwide;

@@ -171,6 +171,8 @@ const char *compile_tree(const uint8_t *src, size_t n, TreeCompile &out)
     // worst case stays below 64.  LDS holds SM_LDS_DEPTH (24) entries per lane: the node stack (internal
     // nodes only in the deferred walk) from the bottom, parked leaves from the top.
     out.tree_proper = proper && worst < 64;
+    out.reached = 0;
+    for (size_t i = 0; i < n; i++) out.reached += seen[i];
     out.leaf_cap = out.tree_proper && (int)worst_internal <= SM_LDS_DEPTH - 4 ? SM_LDS_DEPTH - (int)worst_internal : 0;
     out.walk_stack_worst = out.tree_proper ? (int)worst : 64;      // (every box hit: the real walk's stack is a subset of this one's at every node it visits)
     // the culling walks' node stack has to fit the LDS slots plus the overflow slice (pt_kernels.h SM_CULL_STACK_MAX)

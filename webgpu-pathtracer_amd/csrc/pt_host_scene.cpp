@@ -286,6 +286,25 @@ extern "C" int mi3pt_host_build_bvh(const void *triangles, size_t ntris, void *n
     return mi3pt_host_build_bvh_f64(pos.data(), ntris, nodes_out, nodes_capacity_bytes, nnodes_out, nthreads);
 }
 
+// The SAH figure of a tree as it stands: every record's box area over the root's, in double from the fp32 fields, added in index order.
+extern "C" int mi3pt_host_bvh_cost(const void *nodes, size_t nnodes, double *cost)
+{
+    if (!nodes || !cost || nnodes == 0) return pt_set_error(MI3PT_ERR_INVALID, nnodes == 0 && nodes && cost ? "no nodes" : "null argument");
+    const uint8_t *src = static_cast<const uint8_t *>(nodes);
+    double sum = 0.0, root = 0.0;
+    for (size_t i = 0; i < nnodes; i++) {
+        float mn[3], mx[3];
+        std::memcpy(mn, src + i * MI3PT_BVHNODE_STRIDE, 12);
+        std::memcpy(mx, src + i * MI3PT_BVHNODE_STRIDE + 16, 12);
+        const double x = (double)mx[0] - (double)mn[0], y = (double)mx[1] - (double)mn[1], z = (double)mx[2] - (double)mn[2];
+        const double area = 2.0 * ((x * y + x * z) + y * z);
+        if (i == 0) root = area;
+        sum = sum + area;
+    }
+    *cost = root == 0.0 ? 0.0 : sum / root;
+    return MI3PT_OK;
+}
+
 // renderer.ts:159-266.  JS numbers are doubles; the typed arrays the reference stores
 // intermediate results in are Float32Array, so those stores round to fp32.
 extern "C" int mi3pt_host_env_cdf(const float *rgba, int width, int height, float *cdf)

@@ -10,6 +10,10 @@ int pt_set_error(int code, const std::string &msg);
 #include <hip/hip_runtime.h>
 namespace pt {
 int lbvh_build(const void *d_tris, size_t n, void *nodes_out, float *build_ms, hipStream_t stream, std::string &err);
+// pt_refit.hip: the boxes of the n 48-byte node records at d_nodes re-fitted, bottom-up, to the ntris 112-byte triangle records at d_tris
+// (both on the device, neither is written); the re-fitted records go to the HOST buffer nodes_out.  The caller vouches for a proper tree
+// whose every record the root reaches and whose leaves name triangles below ntris.  Returns 0, or -1 with `err` set.
+int refit_bvh(const void *d_tris, size_t ntris, const void *d_nodes, size_t n, void *nodes_out, float *refit_ms, hipStream_t stream, std::string &err);
 }
 
 // ---- host-side helpers shared by pt_context.hip and the pt_host_*.cpp files (plain C++: the CPU sanitizer builds cover them)
@@ -91,6 +95,7 @@ struct TreeCompile {
     bool tree_proper = false, cull_stack_ok = false;
     uint32_t root_ref = REF_NONE, scene_flags = 0;
     int64_t max_tri_ref = -1;
+    size_t reached = 0;                     // records the walk from the root visited (== the record count: no record is out of its reach)
 };
 // nullptr, or why the tree is refused (MI3PT_ERR_INVALID)
 const char *compile_tree(const uint8_t *src, size_t n, TreeCompile &out);

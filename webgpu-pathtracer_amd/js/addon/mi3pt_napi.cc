@@ -847,6 +847,49 @@ napi_value DeviceBuildBvh(napi_env env, napi_callback_info info)
     return buf;
 }
 
+// deviceRefitBvh(ctx, nnodes) -> { nodes: Buffer of nnodes 48-byte records, ms: device time }: the boxes of the uploaded tree re-fitted
+// on the device to the triangles as they stand (mi3pt_device_refit_bvh); nnodes = the record count of the last uploadBvh
+napi_value DeviceRefitBvh(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t nnodes;
+    if (!get_args(env, info, a, 2) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &nnodes)) return nullptr;
+    if (nnodes <= 0) {
+        napi_throw_error(env, nullptr, "deviceRefitBvh: the node count of the uploaded tree must be positive");
+        return nullptr;
+    }
+    void *out = nullptr;
+    napi_value buf, obj, v;
+    NAPI_OK(napi_create_buffer(env, (size_t)nnodes * MI3PT_BVHNODE_STRIDE, &out, &buf));
+    size_t count = 0;
+    float ms = 0.0f;
+    MI3PT_TRY(mi3pt_device_refit_bvh(ctx, out, (size_t)nnodes * MI3PT_BVHNODE_STRIDE, &count, &ms));
+    if (count != (size_t)nnodes) {
+        napi_throw_error(env, nullptr, "deviceRefitBvh: the uploaded tree has fewer records than nnodes");
+        return nullptr;
+    }
+    NAPI_OK(napi_create_object(env, &obj));
+    NAPI_OK(napi_set_named_property(env, obj, "nodes", buf));
+    NAPI_OK(napi_create_double(env, (double)ms, &v));
+    NAPI_OK(napi_set_named_property(env, obj, "ms", v));
+    return obj;
+}
+
+// hostBvhCost(nodes: Buffer of 48-byte records) -> the summed box areas over the root's (mi3pt_host_bvh_cost)
+napi_value HostBvhCost(napi_env env, napi_callback_info info)
+{
+    Args a;
+    void *data;
+    size_t n;
+    if (!get_args(env, info, a, 1) || !get_bytes(env, a.v[0], &data, &n)) return nullptr;
+    double cost = 0.0;
+    MI3PT_TRY(mi3pt_host_bvh_cost(data, n / MI3PT_BVHNODE_STRIDE, &cost));
+    napi_value v;
+    NAPI_OK(napi_create_double(env, cost, &v));
+    return v;
+}
+
 napi_value HostBuildBvh(napi_env env, napi_callback_info info)
 {
     Args a;
@@ -913,6 +956,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "setMeanByCount", SetMeanByCount }, { "reproject", Reproject }, { "hostViewFrame", HostViewFrame },
         { "keepGeometry", KeepGeometry }, { "reprojectScene", ReprojectScene },
         { "holdHistory", HoldHistory }, { "mergeHistory", MergeHistory },
+        { "deviceRefitBvh", DeviceRefitBvh }, { "hostBvhCost", HostBvhCost },
     };
     for (const auto &f : fns) {
         napi_value v;

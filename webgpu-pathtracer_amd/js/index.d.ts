@@ -180,6 +180,20 @@ export class Renderer {
   reprojectScene(scene: RaytracingScene, camera: RaytracingCamera, options?: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number; maxHistoryMoved?: number }): boolean;
   /** ... validate: as in reproject() */
   reprojectScene(scene: RaytracingScene, camera: RaytracingCamera, options: { planeTolerance?: number; normalCosMin?: number; maxHistory?: number; maxHistoryMoved?: number; validate?: number }): boolean;
+  /** opt-in: on scene.needsUpdate with the triangle count of the last upload, re-fit the boxes of the uploaded tree on the device
+   *  (include/mi3pt.h: mi3pt_device_refit_bvh: the exact boxes of the old topology) instead of rebuilding the SAH tree on the host; the
+   *  triangles are uploaded first, then the re-fitted records.  reprojectScene() goes through the same path.  Default false */
+  refit: boolean;
+  /** rebuild after all when the re-fitted tree's hostBvhCost exceeds that of the last full build by more than this factor.  Default Infinity */
+  refitCostLimit: number;
+  /** what the last scene update did: cost of the re-fitted tree over the last full build's, and the device time of the refit; null when
+   *  the update rebuilt without trying (refit off, first upload, another triangle count) */
+  readonly lastRefitCostRatio: number | null;
+  readonly lastRefitMs: number | null;
+  /** the boxes of the uploaded tree re-fitted on the device to the triangles as they stand, as 48-byte records, and the device time */
+  deviceRefitBvh(): { nodes: Buffer; ms: number };
+  /** mi3pt_host_bvh_cost: the summed box areas of every 48-byte record over the root's (no device) */
+  hostBvhCost(nodes: Uint8Array): number;
   /** set the running mean and its moments aside and restart the live pair as reset() would (include/mi3pt.h: mi3pt_hold_history); the frame
    *  counter, the canvas and the feature images stay.  Needs setMeanByCount(true).  A reset(), a resize() and a reproject() drop what is held */
   holdHistory(): void;

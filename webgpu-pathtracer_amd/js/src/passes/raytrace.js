@@ -131,24 +131,54 @@ class RaytracePass extends Pass {
     if (flat.triangles.length === 0) throw new Error('Input nodes array is empty');    // raytrace.ts:563-565
     const packed = RaytracePass.packScene(flat);
     const native = this.renderer.native, handle = this.renderer.handle;
-    let nodeBytes;
-    if (this.renderer.options.deviceBvh) {
+    let nodeBytes = this.renderer.refit ? this.refitScene(packed, flat.triangles.length) : null;
+    if (nodeBytes) {
+      // (refitScene uploaded the triangles and the tree)
+    } else if (this.renderer.options.deviceBvh) {
       // a linear BVH built on the GPU from the uploaded triangles (milliseconds on millions of triangles)
       // instead of the reference's SAH tree -- same closest hits, more box tests per ray (csrc/pt_lbvh.hip)
       native.uploadTriangles(handle, packed.triangleBytes);
       nodeBytes = native.deviceBuildBvh(handle, flat.triangles.length);
       native.uploadBvh(handle, nodeBytes);
+      this.builtNodeBytes = nodeBytes;
     } else {
       nodeBytes = native.hostBuildBvhF64(packed.positions, this.renderer.options.builderThreads || 0);
       native.uploadBvh(handle, nodeBytes);
       native.uploadTriangles(handle, packed.triangleBytes);
+      this.builtNodeBytes = nodeBytes;
     }
+    this.nodeBytes = nodeBytes;          // the host's copy of the records the device holds
     native.uploadMaterials(handle, packed.materialBytes);
     scene.needsUpdate = false;
     this.renderer._sceneVersion++;
     this.renderer._trianglesUploaded = flat.triangles.length;      // (reprojectScene: the count the next scene must have)
     this.stats = { Triangles: flat.triangles.length, Materials: flat.materials.length, 'BVH Nodes': nodeBytes.length / 48 };
     if (this.renderer.options.verbose) console.table(this.stats);                     // raytrace.ts:528-532
+  }
+
+  // renderer.refit (no counterpart in the reference, which rebuilds on every scene.needsUpdate, raytrace.ts:380-533): when only vertices
+  // moved -- the triangle count is the last upload's and a tree is uploaded -- the triangles go up first, the device re-fits the boxes of
+  // the uploaded tree to them (mi3pt_device_refit_bvh: the exact boxes of the old topology) and the host uploads those records.  The
+  // price is tree quality: mi3pt_host_bvh_cost of the result over that of the last full build is renderer.lastRefitCostRatio; above
+  // renderer.refitCostLimit (default Infinity: never) the caller rebuilds as it always did.  Returns the uploaded records, or null
+  // when the caller has to build (lastRefitCostRatio then says why: null = no refit was possible).
+  refitScene(packed, count) {
+    const r = this.renderer, native = r.native, handle = r.handle;
+    r.lastRefitCostRatio = null;
+    r.lastRefitMs = null;
+    if (!this.nodeBytes || !this.builtNodeBytes || count !== r._trianglesUploaded) return null;
+    native.uploadTriangles(handle, packed.triangleBytes);
+    const refitted = native.deviceRefitBvh(handle, this.nodeBytes.length / 48);
+    if (this.builtCost === undefined || this.builtCostOf !== this.builtNodeBytes) {
+      this.builtCost = native.hostBvhCost(this.builtNodeBytes);
+      this.builtCostOf = this.builtNodeBytes;
+    }
+    const cost = native.hostBvhCost(refitted.nodes);
+    r.lastRefitMs = refitted.ms;
+    r.lastRefitCostRatio = this.builtCost > 0 ? cost / this.builtCost : (cost > 0 ? Infinity : 1);
+    if (r.lastRefitCostRatio > r.refitCostLimit) return null;
+    native.uploadBvh(handle, refitted.nodes);
+    return refitted.nodes;
   }
 
   render(commandEncoder) { commandEncoder.passes |= SUBMIT_RAYTRACE; }     // raytrace.ts:696-708

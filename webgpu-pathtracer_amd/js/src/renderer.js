@@ -58,6 +58,14 @@ class Renderer {
     this._trianglesUploaded = 0; // reprojectScene: the triangle count of the last upload (RaytracePass.updateScene)
     this._seedOffset = 0;        // reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
     this._validateLeft = 0;      // reproject({ validate: K }): sampled frames still to submit before the held history is merged
+    // refit: on scene.needsUpdate with an unchanged triangle count, re-fit the uploaded tree's boxes on the device instead of rebuilding
+    // it (RaytracePass.refitScene); false: the reference's rebuild.  refitCostLimit: rebuild after all when the re-fitted tree's SAH
+    // figure exceeds the last full build's by more than this factor.  lastRefitCostRatio / lastRefitMs: what the last update did
+    // (null: it rebuilt without trying)
+    this.refit = false;
+    this.refitCostLimit = Infinity;
+    this.lastRefitCostRatio = null;
+    this.lastRefitMs = null;
     this.tile = args.tile || { rank: 0, nranks: 1, blockRows: 8 };
     if (this.options.enableTimestampQuery) this.native.enableTiming(this.handle, 1);
     this.passes = {
@@ -349,6 +357,15 @@ class Renderer {
     if (this.status === 'sampling') this.emit('start');
     return true;
   }
+  // deviceRefitBvh(): { nodes, ms } -- the boxes of the uploaded tree re-fitted on the device to the triangles as they stand (include/mi3pt.h:
+  // mi3pt_device_refit_bvh), ready for native.uploadBvh, and the device time; the context's state does not move.  What update() does by
+  // itself under `refit = true`.  hostBvhCost(nodes): the SAH figure of a tree, the summed box areas over the root's (no device).
+  deviceRefitBvh() {
+    const held = this.passes.raytrace.nodeBytes;
+    if (!held) throw new Error('deviceRefitBvh: no scene has been uploaded yet');
+    return this.native.deviceRefitBvh(this.handle, held.length / 48);
+  }
+  hostBvhCost(nodes) { return this.native.hostBvhCost(nodes); }
   // ---- a held history, validated against fresh samples before it is merged (no counterpart in the reference; include/mi3pt.h:
   // mi3pt_hold_history, mi3pt_merge_history).  holdHistory(): the running mean and its moments are set aside and the live pair restarts,
   // as reset() would restart it; the frame counter, the canvas and the feature images stay.  Needs setMeanByCount(true).  A reset(), a

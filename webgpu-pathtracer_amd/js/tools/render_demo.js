@@ -33,6 +33,10 @@
 //                      step takes --spp K frames (4); writes <prefix>_step<i>.png, <prefix>_step<i>.acc.f32 and <prefix>_step<i>.uniforms.bin per step.  Between steps
 //                      scene.needsUpdate = true and renderer.reset(), or with --reproject renderer.setMeanByCount(true) from the start and
 //                      renderer.reprojectScene(scene, camera) (the mean follows the box).  Not together with --orbit
+//   --refit            with --slide: renderer.refit = true -- from the second step on the tree is not rebuilt on the host: the device re-fits
+//                      the boxes of the uploaded tree to the moved triangles (mi3pt_device_refit_bvh).  Prints the cost ratio of the
+//                      re-fitted tree over the last full build per step, lists them under "refit" (null: that step was built), and writes
+//                      <prefix>_step<i>.nodes.bin, the 48-byte records the device holds in that step
 //   --validate K       with --reproject in the --orbit and --slide loops: the carried mean is not merged at once but held, validated against the
 //                      view's first K frames (K <= --spp) and then merged -- what reproject(scene, camera, { validate: K }) does, spelled out as
 //                      holdHistory() / mergeHistory() around two moments reads (the held counts nh; the counts n' after the merge, n = K before
@@ -100,6 +104,9 @@ async function main() {
   if (guidedVariance || untilArg !== null) renderer.setMoments(true);
   const orbit = parseInt(arg('orbit', '0'), 10), reproject = process.argv.includes('--reproject');
   const slide = parseInt(arg('slide', '0'), 10);
+  const refit = process.argv.includes('--refit'), refitRatios = [];
+  if (refit && !(slide > 0)) throw new Error('--refit re-fits the tree between the steps of --slide: give --slide N too');
+  if (refit) renderer.refit = true;
   const validate = parseInt(arg('validate', '0'), 10), keptShares = [];
   // after a reprojection that carried something: hold it and remember its counts
   const hold = (carried) => {
@@ -169,6 +176,12 @@ async function main() {
         else renderer.reset();
       }
       sample(spp, held, 'step ' + k);
+      if (refit) {
+        const ratio = renderer.lastRefitCostRatio;
+        refitRatios.push(ratio);
+        console.error('--refit: step ' + k + ': ' + (ratio === null ? 'built on the host' : 'cost ratio ' + ratio.toFixed(4) + ', ' + renderer.lastRefitMs.toFixed(3) + ' ms on the device'));
+        fs.writeFileSync(out + '_step' + k + '.nodes.bin', renderer.passes.raytrace.nodeBytes);
+      }
       fs.writeFileSync(out + '_step' + k + '.acc.f32', Buffer.from(renderer.readAccumulation().buffer));
       fs.writeFileSync(out + '_step' + k + '.uniforms.bin', Buffer.from(renderer.passes.raytrace.uniforms.bytes));
       renderer.screenshot(out + '_step' + k + '.png');
@@ -226,7 +239,7 @@ async function main() {
     fs.writeFileSync(out + '_moments.f32', Buffer.from(renderer.readMoments().buffer));
   }
   const summary = {
-    width, height, frames, until, despiked, validate: validate > 0 ? { frames: validate, kept: keptShares } : undefined, status: renderer.status, frame: renderer.frame, events,
+    width, height, frames, until, despiked, validate: validate > 0 ? { frames: validate, kept: keptShares } : undefined, refit: refit ? refitRatios : undefined, status: renderer.status, frame: renderer.frame, events,
     counters: renderer.counters(), stats: renderer.passes.raytrace.stats, first_stats: firstStats, wall_ms: ms,
     timings_us: { raytrace: renderer.timings.raytrace.value, accumulate: renderer.timings.accumulate.value,
       fullscreen: renderer.timings.fullscreen.value },

@@ -66,6 +66,7 @@ SYMBOLS = (
     "mi3pt_keep_geometry", "mi3pt_reproject_scene",
     "mi3pt_hold_history", "mi3pt_merge_history",
     "mi3pt_set_guided_despike", "mi3pt_read_guided_despiked",
+    "mi3pt_device_refit_bvh", "mi3pt_host_bvh_cost",
 )
 
 
@@ -194,6 +195,8 @@ def load_library(path=None):
     lib.mi3pt_debug_intersect_shipped.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mi3pt_debug_pairs.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
     lib.mi3pt_device_build_bvh.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.mi3pt_device_refit_bvh.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(ctypes.c_float)]
+    lib.mi3pt_host_bvh_cost.argtypes = [c_void_p, c_size_t, ctypes.POINTER(ctypes.c_double)]
     lib.mi3pt_debug_wave_times.argtypes = [c_void_p, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
     lib.mi3pt_host_build_bvh.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_int]
     lib.mi3pt_host_build_bvh_f64.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_int]
@@ -278,6 +281,16 @@ def host_build_bvh_f64(positions, nthreads=0):
     count = ctypes.c_size_t(0)
     _check(lib, lib.mi3pt_host_build_bvh_f64(_ptr(pos), n, _ptr(nodes), nodes.nbytes, ctypes.byref(count), nthreads))
     return nodes[:count.value]
+
+
+def host_bvh_cost(nodes):
+    """mi3pt_host_bvh_cost: the summed box areas of every 48-byte record over the root's -- the SAH figure a host compares before and
+    after Context.device_refit_bvh."""
+    lib = load_library()
+    nd = np.ascontiguousarray(nodes)
+    cost = ctypes.c_double(0.0)
+    _check(lib, lib.mi3pt_host_bvh_cost(_ptr(nd), nd.nbytes // 48, ctypes.byref(cost)))
+    return cost.value
 
 
 def host_sky_tiles(nodes, raytrace_uniforms, width, height, rank=0, nranks=1, block_rows=8):
@@ -487,6 +500,7 @@ class Context:
     def upload_bvh(self, nodes):
         a = np.ascontiguousarray(nodes)
         self._c(self.lib.mi3pt_upload_bvh(self.handle, _ptr(a), a.nbytes))
+        self._nnodes_uploaded = a.nbytes // 48
 
     def upload_environment(self, rgba):
         a = np.ascontiguousarray(rgba, np.float32)
@@ -811,6 +825,16 @@ class Context:
             raise Mi3ptError(4, "no triangles uploaded")
         nodes = np.zeros(2 * ntris - 1, layout.BVH_NODE)
         self._c(self.lib.mi3pt_device_build_bvh(self.handle, _ptr(nodes), nodes.nbytes, ctypes.byref(n), ctypes.byref(ms)))
+        return nodes[: n.value], ms.value
+
+    def device_refit_bvh(self):
+        """mi3pt_device_refit_bvh: the boxes of the uploaded tree re-fitted on the device to the triangles as uploaded since:
+        (nodes, refit_ms), the records ready for upload_bvh.  The context's state does not move."""
+        from . import layout
+        n = ctypes.c_size_t()
+        ms = ctypes.c_float()
+        nodes = np.zeros(max(getattr(self, "_nnodes_uploaded", 0), 1), layout.BVH_NODE)      # (before the uploads: the library says so)
+        self._c(self.lib.mi3pt_device_refit_bvh(self.handle, _ptr(nodes), nodes.nbytes, ctypes.byref(n), ctypes.byref(ms)))
         return nodes[: n.value], ms.value
 
     def debug_math(self, fn, a, b=None):

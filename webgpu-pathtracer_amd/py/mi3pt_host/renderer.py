@@ -97,6 +97,8 @@ class RaytracePass(Pass):
     def __init__(self, renderer):
         super().__init__(renderer)
         self.uniforms = layout.UniformBlock(layout.RAYTRACE_UNIFORMS)
+        self._nodesUploaded = 0                   # records of the tree the device holds
+        self._builtNodes = self._builtCost = None     # the last FULL build's records, and their host_bvh_cost once it was needed
 
     def setUniforms(self, value):                 # raytrace.ts:359-369
         self.uniforms.set(value)
@@ -120,15 +122,46 @@ class RaytracePass(Pass):
         content = scene.content
         if content is None or len(content.triangles) == 0:
             raise capi.Mi3ptError(1, "Input nodes array is empty")      # raytrace.ts:563-565
-        if content.nodes is None:
-            content.build_bvh()
         ctx = self.renderer.ctx
-        ctx.upload_bvh(content.nodes)
-        ctx.upload_triangles(content.triangles)
+        if not (self.renderer.refit and self._refitScene(content)):
+            if content.nodes is None:
+                content.build_bvh()
+            ctx.upload_bvh(content.nodes)
+            ctx.upload_triangles(content.triangles)
+            self._builtNodes, self._builtCost = content.nodes, None
+        self._nodesUploaded = len(content.nodes)
         ctx.upload_materials(content.material_bytes)
         scene.needsUpdate = False
         self.renderer._sceneVersion += 1
         self.renderer._trianglesUploaded = len(content.triangles)      # (reprojectScene: the count the next scene must have)
+
+    def _refitScene(self, content):
+        """renderer.refit (no counterpart in the reference, which rebuilds on every scene.needsUpdate, raytrace.ts:380-533): when only
+        vertices moved -- the triangle count is the last upload's and a tree is uploaded -- the triangles go up first, the device re-fits
+        the boxes of the uploaded tree to them (include/mi3pt.h: mi3pt_device_refit_bvh: the exact boxes of the old topology) and those
+        records are uploaded and become content.nodes.  The price is tree quality: capi.host_bvh_cost of the result over that of the last
+        full build is renderer.lastRefitCostRatio; above renderer.refitCostLimit (default inf: never) the caller rebuilds as it always
+        did.  True when the tree and the triangles are uploaded.  Either way a tree the caller supplied in content.nodes is not used: it is
+        replaced by the re-fitted records, or, above the limit, dropped (content.nodes = None) so that the caller builds the SAH tree of the new
+        positions -- the only tree the cost recorded at "the last full build" can stand for."""
+        r = self.renderer
+        r.lastRefitCostRatio = r.lastRefitMs = None
+        if not self._nodesUploaded or self._builtNodes is None or len(content.triangles) != r._trianglesUploaded:
+            return False
+        ctx = r.ctx
+        ctx.upload_triangles(content.triangles)
+        nodes, ms = ctx.device_refit_bvh()
+        if self._builtCost is None:
+            self._builtCost = capi.host_bvh_cost(self._builtNodes)
+        cost = capi.host_bvh_cost(nodes)
+        r.lastRefitMs = ms
+        r.lastRefitCostRatio = cost / self._builtCost if self._builtCost > 0 else (math.inf if cost > 0 else 1.0)
+        if r.lastRefitCostRatio > r.refitCostLimit:
+            content.nodes = None                  # (whatever the content carried is not the tree of these positions: build)
+            return False
+        ctx.upload_bvh(nodes)
+        content.nodes = nodes
+        return True
 
     def render(self, encoder):                    # raytrace.ts:696-708
         encoder.append(capi.SUBMIT_RAYTRACE)
@@ -201,6 +234,16 @@ class Renderer:
         self._trianglesUploaded = 0        # reprojectScene: the triangle count of the last upload (updateScene)
         self._seedOffset = 0               # reproject: frames sampled in earlier views, added to the raytrace pass's `frame` only
         self._validateLeft = 0             # reproject(validate=K): sampled frames still to submit before the held history is merged
+        # refit: on scene.needsUpdate with an unchanged triangle count, re-fit the uploaded tree's boxes on the device instead of rebuilding
+        # it (RaytracePass._refitScene); False: the reference's rebuild.  refitCostLimit: rebuild after all when the re-fitted tree's SAH
+        # figure exceeds the last full build's by more than this factor.  lastRefitCostRatio / lastRefitMs: what the last update did
+        # (None: it rebuilt without trying).  While refit is on and a refit is possible, a tree the host supplies in scene.content.nodes is
+        # NOT uploaded: the device's topology is kept and content.nodes is REPLACED by the re-fitted records (the host's copy stays the
+        # device's); above the limit it is set to None and built for the new positions.  Leave refit off for an update that brings its own tree
+        self.refit = False
+        self.refitCostLimit = math.inf
+        self.lastRefitCostRatio = None
+        self.lastRefitMs = None
         self.passes = {"raytrace": RaytracePass(self), "accumulate": AccumulatePass(self),
                        "fullscreen": FullscreenPass(self)}
         if self.options["enableTimestampQuery"]:
