@@ -1026,7 +1026,15 @@ int mi3pt_device_build_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t nodes_capacit
  *   leaf (word 7 == 1), a, b, c = the three positions of triangle record `triangleIndex`:  min = lo(lo(a, b), c), max = hi(hi(a, b), c)
  *   internal:  min = lo(min(left), min(right)), max = hi(max(left), max(right)) -- always left then right, whichever child finished first
  *   words 3 and 7 .. 11 are copied bit for bit from the uploaded record.
- * Non-finite vertices give unspecified boxes; they neither hang nor fault.
+ * What "the uploaded bytes come back" covers: ANY finite or infinite coordinates, zeros of either sign and subnormals included -- there lo / hi
+ * are Math.min / Math.max, mi3pt_host_build_bvh[_f64] forms its boxes with the same two functions and mi3pt_device_build_bvh with fminf /
+ * fmaxf, which order -0 below +0 on the device, so all three write the same words for the same vertices (-0 wins a minimum, +0 a maximum,
+ * whatever the order of the operands; a subnormal is compared as what it is, never as a zero).  It does NOT cover a NaN coordinate: there
+ * the three follow different rules, each documented where it lives -- this call the law above (it only selects: a NaN bound arrives with
+ * its sign, payload and signalling bit as it stood in the triangle record; one on the left of a union is kept, one on the right dropped),
+ * the host builder std::min / std::max's treatment of a NaN inside the reference's sort and sweep (csrc/pt_host_scene.cpp), the device
+ * builder fminf / fmaxf, which drop a NaN on either side (csrc/pt_lbvh.hip) -- and the reference itself a fourth, Math.min / Math.max,
+ * which return the NaN.  Non-finite vertices neither hang nor fault.
  * It changes NO state of the context: nothing the context renders with is touched, no counter, epoch or mi3pt_debug_last_launch field
  * moves, and rendering after the call without uploading the result is bit-identical to rendering before it.  Queued frames are launched
  * first, as for a read-back; the call BLOCKS until the records are on the host.  A device group runs it on member 0, where the scene lives.

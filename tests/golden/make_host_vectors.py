@@ -20,7 +20,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "webgpu-pathtracer_amd", "py"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from mi3pt_host import scenes  # noqa: E402
+import box_law_cases  # noqa: E402
 
 HARNESS = os.path.join(ROOT, "tests", "golden", "run_reference_host.js")
 CDF_SAMPLE_STEP = 97            # every 97th float of the CDF texture is stored next to its CRC
@@ -38,7 +40,9 @@ def triangle_sets():
     grid = np.concatenate([base[None] + np.stack([gx.ravel(), 0 * gx.ravel(), gz.ravel()], -1)[:, None, :],
                            base[None, ::-1] + np.stack([gx.ravel(), 0 * gx.ravel(), gz.ravel()], -1)[:, None, :] + 0.0])
     tall = rng.uniform(0, 1, size=(64, 3, 3)) * np.array([0.5, 0.5, 9.0])      # z is the longest axis, but x <= y picks y
-    return {"demo": demo, "soup": soup, "grid": grid, "tall": tall, "pair": soup[:2], "single": soup[:1], "triple": soup[5:8]}
+    # zeros of both signs in every pattern (tests/box_law_cases.py): Math.min / Math.max give -0 to a minimum and +0 to a maximum
+    return {"demo": demo, "soup": soup, "grid": grid, "tall": tall, "pair": soup[:2], "single": soup[:1], "triple": soup[5:8],
+            "zeros": box_law_cases.zeros().positions}
 
 
 def environments():

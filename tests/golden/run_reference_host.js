@@ -47,7 +47,8 @@ function stripTypes(ts) {
 // ------------------------------------------------------------------ THREE shim (three@0.171.0)
 
 class Vector3 {
-  constructor(x, y, z) { this.x = x || 0; this.y = y || 0; this.z = z || 0; }
+  // default parameters, as three's constructor has them: they replace `undefined` only, so a -0 stays -0 (`x || 0` made it +0)
+  constructor(x = 0, y = 0, z = 0) { this.x = x; this.y = y; this.z = z; }
   set(x, y, z) { this.x = x; this.y = y; this.z = z; return this; }
   min(v) { this.x = Math.min(this.x, v.x); this.y = Math.min(this.y, v.y); this.z = Math.min(this.z, v.z); return this; }
   max(v) { this.x = Math.max(this.x, v.x); this.y = Math.max(this.y, v.y); this.z = Math.max(this.z, v.z); return this; }

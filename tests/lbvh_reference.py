@@ -4,7 +4,9 @@ arithmetic the library is compiled with (fp32, no contraction, correctly rounded
 Per triangle the NaN-ignoring box of its three vertices and the centroid fl(fl(0.5 mn) + fl(0.5 mx)); the bounds of the non-NaN
 centroids; per axis t = (c - lo) / extent (0 unless extent > 0), clamped to [0, 1] with NaN -> 0, q = uint(min(t 2^21, 2^21 - 1));
 the 63-bit key interleaves x, y, z with x highest; a stable sort by key; the binary radix tree over (key << 32 | sorted position),
-built top-down and numbered in pre-order; boxes united bottom-up with fmin / fmax.  Nothing here looks at the device.  No test
+built top-down and numbered in pre-order; boxes united bottom-up with fmin / fmax, where -0 counts as below +0 (fmin_signed /
+fmax_signed: the refit's lo / hi on everything but a NaN).  first_difference compares boxes as values, first_word_difference as words
+(the zeros and subnormals of tests/box_law_cases.py).  Nothing here looks at the device.  No test
 lives in this file; check_tree is the structural check both LBVH test files share, and the input classes they share are below it.
 """
 from bisect import bisect_left
@@ -18,10 +20,25 @@ CELLS = np.float32(1 << BITS)
 PAD_OFFSETS = (12, 44)           # the two padding words of a 48-byte node record (after min, after triangleIndex)
 
 
+def fmin_signed(x, y):
+    """fminf with the zero rule spelled out: of two equal operands -- +0 and -0 compare equal -- the negative one, so -0 wins a minimum
+    whatever the order (the refit's lo, include/mi3pt.h, on everything but a NaN; C leaves fminf(+0, -0) open).  NaNs as np.fmin."""
+    x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+    with np.errstate(invalid="ignore"):
+        return np.where(x == y, np.where(np.signbit(y), y, x), np.fmin(x, y)).astype(np.float32)
+
+
+def fmax_signed(x, y):
+    """fmaxf; of two equal operands the positive one: +0 wins a maximum whatever the order"""
+    x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+    with np.errstate(invalid="ignore"):
+        return np.where(x == y, np.where(np.signbit(y), x, y), np.fmax(x, y)).astype(np.float32)
+
+
 def triangle_boxes(tris):
-    """(mn, mx): n x 3 fp32 each; a NaN coordinate is ignored unless all three vertices have it (fminf / fmaxf)."""
+    """(mn, mx): n x 3 fp32 each; a NaN coordinate is ignored unless all three vertices have it (fminf / fmaxf); -0 < +0."""
     a, b, c = (np.asarray(tris[k], np.float32) for k in ("aPosition", "bPosition", "cPosition"))
-    return np.fmin(np.fmin(a, b), c), np.fmax(np.fmax(a, b), c)
+    return fmin_signed(fmin_signed(a, b), c), fmax_signed(fmax_signed(a, b), c)
 
 
 def centroids(mn, mx):
@@ -99,8 +116,8 @@ def reference_nodes(tris):
     for lev in range(int(level.max()) - 1, -1, -1):                   # children first
         sel = np.flatnonzero((level == lev) & (nodes["isLeaf"] == 0))
         l, r = nodes["left"][sel], nodes["right"][sel]
-        nodes["min"][sel] = np.fmin(nodes["min"][l], nodes["min"][r])
-        nodes["max"][sel] = np.fmax(nodes["max"][l], nodes["max"][r])
+        nodes["min"][sel] = fmin_signed(nodes["min"][l], nodes["min"][r])
+        nodes["max"][sel] = fmax_signed(nodes["max"][l], nodes["max"][r])
     return nodes
 
 
@@ -173,6 +190,21 @@ def first_difference(got, want, equal_nan=False):
     i = int(np.flatnonzero(bad)[0])
     return (f"{int(bad.sum())} of {len(want)} nodes differ; first at {i}:\n  device    {got[i]} pad {padding_words(got)[i].tolist()}"
             f"\n  reference {want[i]} pad {padding_words(want)[i].tolist()}")
+
+
+def first_word_difference(got, want):
+    """None when the two node arrays hold the same twelve 32-bit words in every record -- the boxes too, so +0 is not -0 -- else a
+    description of the first word that differs.  For inputs without a NaN (the words of a NaN box are not pinned)."""
+    g = np.ascontiguousarray(got).view(np.uint8).reshape(-1).view("<u4").reshape(-1, 12)
+    w = np.ascontiguousarray(want).view(np.uint8).reshape(-1).view("<u4").reshape(-1, 12)
+    if g.shape != w.shape:
+        return f"{g.shape[0]} nodes, reference {w.shape[0]}"
+    bad = np.argwhere(g != w)
+    if not len(bad):
+        return None
+    i, k = (int(v) for v in bad[0])
+    return (f"{len(set(bad[:, 0].tolist()))} of {len(w)} nodes differ in {len(bad)} words; first at node {i}, word {k}: "
+            f"device {g[i, k]:#010x}, reference {w[i, k]:#010x}")
 
 
 # ---- the input classes both test files use (positions: n x 3 vertices x 3 coordinates, float64 that fp32 holds exactly or rounds)

@@ -39,7 +39,7 @@ def test_native_bvh_builder_equals_the_executed_reference_builder(built, vec):
     identical, ties and all."""
     gen = _generator()
     sets = gen.triangle_sets()
-    assert set(sets) >= {"demo", "soup", "grid", "tall", "pair", "single", "triple"}
+    assert set(sets) >= {"demo", "soup", "grid", "tall", "pair", "single", "triple", "zeros"}
     for name, pos in sets.items():
         want = vec[f"bvh_{name}_nodes"].tobytes()
         for threads in (1, 4):

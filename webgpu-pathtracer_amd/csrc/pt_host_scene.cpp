@@ -12,6 +12,10 @@
 // The O(n) re-scan per split candidate is replaced by prefix / suffix boxes -- box
 // unions are exact min/max operations, so the doubles are the same -- and subtrees are
 // built by a small thread pool.  All arithmetic is IEEE double like the JavaScript.
+// Identical means the 48-byte records, word for word, for finite and infinite coordinates
+// and zeros of either sign (box_lo / box_hi below are Math.min / Math.max there).  A NaN
+// coordinate is outside that claim: Math.min / Math.max return it, box_lo / box_hi keep
+// one on the left and drop one on the right, and the sort and the sweep see NaN keys.
 #include "../../include/mi3pt.h"
 #include "pt_internal.h"
 
@@ -28,7 +32,14 @@
 
 namespace {
 
-struct Item {            // a leaf BVHNode of buildBVH (raytrace.ts:544-556) or a built subtree
+// Box bounds as the reference forms them: Box3.expandByPoint -> Vector3.min / max -> Math.min / Math.max, where -0 wins a minimum and +0
+// a maximum whatever the order of the operands (std::min / std::max keep the first of two equal operands).  The form is the refit's
+// (include/mi3pt.h, mi3pt_device_refit_bvh); it differs from std::min / std::max on zeros of unlike sign only, so a NaN is treated as
+// std::min / std::max treated it: one in y is dropped, one in x is kept (NOT Math.min's rule, which returns the NaN).
+inline double box_lo(double x, double y) { return (y < x || (y == x && std::signbit(y))) ? y : x; }
+inline double box_hi(double x, double y) { return (y > x || (y == x && !std::signbit(y))) ? y : x; }
+
+struct Item {           // a leaf BVHNode of buildBVH (raytrace.ts:544-556) or a built subtree
     double mn[3], mx[3];
     int32_t node;        // index into Builder::nodes
 };
@@ -84,8 +95,8 @@ struct Builder {
         for (int k = 0; k < 3; k++) {       // :581-584 expandByPoint(min), expandByPoint(max)
             double mn = std::numeric_limits<double>::infinity(), mx = -mn;
             for (size_t i = lo; i < hi; i++) {
-                mn = std::min(mn, std::min(items[i].mn[k], items[i].mx[k]));
-                mx = std::max(mx, std::max(items[i].mn[k], items[i].mx[k]));
+                mn = box_lo(mn, box_lo(items[i].mn[k], items[i].mx[k]));
+                mx = box_hi(mx, box_hi(items[i].mn[k], items[i].mx[k]));
             }
             node.mn[k] = mn;
             node.mx[k] = mx;
@@ -118,8 +129,8 @@ struct Builder {
             for (size_t i = n; i-- > 1;) {
                 const Item &it = items[lo + i];
                 for (int k = 0; k < 3; k++) {
-                    mn[k] = std::min(mn[k], std::min(it.mn[k], it.mx[k]));
-                    mx[k] = std::max(mx[k], std::max(it.mn[k], it.mx[k]));
+                    mn[k] = box_lo(mn[k], box_lo(it.mn[k], it.mx[k]));
+                    mx[k] = box_hi(mx[k], box_hi(it.mn[k], it.mx[k]));
                 }
                 const double x = mx[0] - mn[0], y = mx[1] - mn[1], z = mx[2] - mn[2];
                 suffix[i] = 2 * (x * y + x * z + y * z);
@@ -132,8 +143,8 @@ struct Builder {
             for (size_t i = 1; i < n; i++) {
                 const Item &it = items[lo + i - 1];
                 for (int k = 0; k < 3; k++) {
-                    mn[k] = std::min(mn[k], std::min(it.mn[k], it.mx[k]));
-                    mx[k] = std::max(mx[k], std::max(it.mn[k], it.mx[k]));
+                    mn[k] = box_lo(mn[k], box_lo(it.mn[k], it.mx[k]));
+                    mx[k] = box_hi(mx[k], box_hi(it.mn[k], it.mx[k]));
                 }
                 const double x = mx[0] - mn[0], y = mx[1] - mn[1], z = mx[2] - mn[2];
                 const double left_area = 2 * (x * y + x * z + y * z);
@@ -211,8 +222,8 @@ extern "C" int mi3pt_host_build_bvh_f64(const double *positions, size_t ntris, v
         const double *p = positions + i * 9;
         TreeNode &leaf = b.nodes[i];
         for (int k = 0; k < 3; k++) {
-            leaf.mn[k] = std::min(p[k], std::min(p[3 + k], p[6 + k]));
-            leaf.mx[k] = std::max(p[k], std::max(p[3 + k], p[6 + k]));
+            leaf.mn[k] = box_lo(p[k], box_lo(p[3 + k], p[6 + k]));
+            leaf.mx[k] = box_hi(p[k], box_hi(p[3 + k], p[6 + k]));
             b.items[i].mn[k] = leaf.mn[k];
             b.items[i].mx[k] = leaf.mx[k];
         }

@@ -43,6 +43,10 @@ __device__ __forceinline__ float unorder_f(int i) { return __int_as_float(i >= 0
 
 struct Box { float mn[3], mx[3]; };
 
+// Boxes, here and in k_lbvh_fit: fminf / fmaxf.  A NaN operand is dropped on either side (a bound is NaN only where all its inputs are).
+// On zeros C leaves fminf(+0, -0) open; the device's minimum / maximum order -0 below +0, so -0 wins a minimum and +0 a maximum
+// whatever the order -- the words Math.min / Math.max, the host builder and the refit's lo / hi give, and with them the refit's
+// promise on a device-built tree (include/mi3pt.h; held word for word by tests/test_gpu_box_law.py).  Subnormals are kept.
 // per triangle: box and centroid; scene bounds of the centroids
 __global__ void __launch_bounds__(256) k_lbvh_prims(const float4 *__restrict__ tris, uint32_t n, Box *__restrict__ tri_box,
                                                     float *__restrict__ centroid, int *__restrict__ bounds /* 6 ordered ints */)
