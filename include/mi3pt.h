@@ -35,7 +35,7 @@
  *     BLOCKING (the host waits for the context's stream, at least): every upload and mi3pt_write_* (copy at call time),
  *     mi3pt_resize (the internal streams too), mi3pt_set_stream (the stream it leaves), mi3pt_bind_accumulation,
  *     mi3pt_set_moments when it changes the state, every mi3pt_read_*, mi3pt_sync, mi3pt_get_counters, mi3pt_pass_time_us,
- *     mi3pt_raytrace_launch_stats / _span, the mi3pt_debug_* probes, mi3pt_device_build_bvh, mi3pt_device_refit_bvh, mi3pt_destroy.
+ *     mi3pt_raytrace_launch_stats / _span, the mi3pt_debug_* probes, mi3pt_device_build_bvh, mi3pt_device_build_bvh_ex, mi3pt_device_refit_bvh, mi3pt_destroy.
  *     BLOCKING, but for ONE EVENT only and without launching the frame queue: mi3pt_read_convergence and
  *     mi3pt_read_convergence_tiles wait for the most recent mi3pt_estimate_convergence, not for what was enqueued behind it;
  *     mi3pt_freeze_converged waits for the same event, then acts as mi3pt_set_sample_mask.  mi3pt_read_sample_mask reads host state.
@@ -73,7 +73,8 @@ extern "C" {
  * mi3pt_read_sample_mask, mi3pt_freeze_converged, mi3pt_host_freeze_tiles; mi3pt_set_mean_by_count, mi3pt_host_view_frame, mi3pt_reproject,
  * struct mi3pt_reproject_params, MI3PT_PASS_REPROJECT (6); mi3pt_keep_geometry, mi3pt_reproject_scene, struct mi3pt_reproject_scene_params;
  * mi3pt_hold_history, mi3pt_merge_history, struct mi3pt_history_params, MI3PT_HISTORY_EPS, MI3PT_PASS_HISTORY (7);
- * MI3PT_GUIDED_YOUNG, MI3PT_GUIDED_YOUNG_COUNT; mi3pt_set_guided_despike, mi3pt_read_guided_despiked; mi3pt_device_refit_bvh, mi3pt_host_bvh_cost. */
+ * MI3PT_GUIDED_YOUNG, MI3PT_GUIDED_YOUNG_COUNT; mi3pt_set_guided_despike, mi3pt_read_guided_despiked; mi3pt_device_refit_bvh, mi3pt_host_bvh_cost;
+ * mi3pt_device_build_bvh_ex, struct mi3pt_bvh_build_params, struct mi3pt_bvh_build_info, MI3PT_BVH_METHOD_*, MI3PT_PLOC_SEARCH_BLOCK. */
 #define MI3PT_ABI_VERSION 4
 
 typedef enum mi3pt_status {
@@ -1012,6 +1013,60 @@ int mi3pt_debug_pairs(mi3pt_ctx *ctx, int fn, const float *rays, const float *ge
  * (mi3pt_host_build_bvh_f64 is): box / triangle test counts differ, the image does not, except
  * where two triangles are hit at exactly the same t.  build_ms (optional): device time. */
 int mi3pt_device_build_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t nodes_capacity_bytes, size_t *nnodes_out, float *build_ms);
+/* The device builders by name.  method 0 is the linear BVH above: the records of mi3pt_device_build_bvh word for word.  method 1 is a
+ * tree of the SAH class built bottom-up by parallel locally-ordered clustering (Meister and Bittner 2018; csrc/pt_ploc.hip), under THE
+ * LAW below, which tests/ploc_reference.py restates in numpy; the output is a function of the triangle records and the two parameters alone.
+ *
+ * Arithmetic.  fp32, round to nearest even, nothing contracted.  fminf / fmaxf as in csrc/pt_lbvh.hip: a NaN operand is dropped, -0
+ *   orders below +0.
+ * Leaves and order.  Exactly the linear builder's first half: per triangle, the NaN-ignoring box and centroid; the 63-bit keys; a stable
+ *   sort.  The result is order[p], the triangle at sorted position p, for p = 0 .. n - 1.
+ * Clusters.  A list of C entries, each a box plus a subtree.  At the start C = n, and cluster p is the leaf of triangle order[p] with
+ *   that triangle's box.
+ * Distance of two clusters.  U = the union of the boxes, per component fminf of the minima and fmaxf of the maxima.  e = U.max - U.min.
+ *   a = (e.x * e.y + e.y * e.z) + e.z * e.x.  d = a if a == a, else +inf.  d is symmetric bit for bit.
+ * Key of a pair of positions a < b.  K(a, b) = (d, b - a, a & 1, a), compared lexicographically, with d compared as fp32 values.
+ *   Distinct pairs have distinct keys.  The two middle terms decide exact ties: b - a prefers the closer position; among the closest,
+ *   a & 1 prefers an even lower position.  A run of identical boxes therefore pairs as (0,1), (2,3), ... and halves per iteration,
+ *   instead of merging one pair per iteration into a chain.
+ * A search iteration.  It runs while C > 1 and fewer than max_search_iterations of them have run.  For every position i, nn(i) is the
+ *   position j != i that satisfies both of: |i - j| <= radius and 0 <= j < C; it has the least K(min(i, j), max(i, j)).
+ * A forced iteration.  It runs while C > 1 after the search budget is used up.  nn(i) = i ^ 1 where that is < C, otherwise none.  This
+ *   bounds the number of iterations for adversarial inputs, where a search iteration may merge a single pair.
+ * Merge, in both kinds of iteration.  Every pair a < b with nn(a) = b and nn(b) = a merges.  The cluster at a becomes an internal node
+ *   with left = a's subtree, right = b's subtree, box = U.  The cluster at b is removed.  All others stay.  The order of the survivors
+ *   is preserved.
+ * Progress.  The pair with the least key among all candidate pairs is mutual, so every search iteration merges at least one pair.
+ * Records.  The 48-byte records of the linear builder, numbered in pre-order.  The root is index 0.  An internal node at index x whose
+ *   left subtree holds m leaves has left = x + 1 and right = x + 2m.  Floats 0-2 are the min, 4-6 the max.  Word 7 is isLeaf, 8 is
+ *   left, 9 is right, 10 is triangleIndex.  A leaf has left = right = -1 and triangleIndex = its triangle.  An internal node has
+ *   triangleIndex = -1.  Words 3 and 11 are 0.  There are 2n - 1 records.  n = 1 is a single leaf.
+ *
+ * The contract is mi3pt_device_build_bvh's: BLOCKING; nodes_out (host) receives (2*ntris - 1) x 48 B, ready for mi3pt_upload_bvh.  Like
+ * mi3pt_device_refit_bvh the call moves no state of the context: queued frames are launched first; no counter, epoch or
+ * mi3pt_debug_last_launch field moves; rendering after the call without uploading the result is bit-identical to rendering before it;
+ * temporaries are allocated and freed inside the call, on every path; a context that never calls it allocates and launches what it did
+ * before.  A device group runs it on member 0.  info (optional): build_ms is the device time from the first kernel to the last, the
+ * host's turn-arounds between the iterations included (the cluster count comes back once per iteration, 4 bytes through pinned memory;
+ * no thread waits for another); the two counts are the iterations of each kind that ran (method 0: both 0).
+ *   MI3PT_ERR_INVALID for a null ctx, params, nodes_out or nnodes_out, an unknown method, non-zero flags, under method 1 a radius outside
+ *   1 .. 64 or max_search_iterations outside 0 .. 65535 (method 0 ignores both), a capacity below (2*ntris - 1) x 48.
+ *   MI3PT_ERR_STATE before triangles are uploaded. */
+#define MI3PT_BVH_METHOD_LBVH 0
+#define MI3PT_BVH_METHOD_PLOC 1
+#define MI3PT_PLOC_SEARCH_BLOCK 256     /* positions per workgroup of the neighbour search: the sizes its tests cross */
+typedef struct mi3pt_bvh_build_params {
+    int method;                 /* MI3PT_BVH_METHOD_* */
+    int radius;                 /* method 1: 1 .. 64 */
+    int max_search_iterations;  /* method 1: 0 .. 65535 */
+    unsigned flags;             /* 0 */
+} mi3pt_bvh_build_params;
+typedef struct mi3pt_bvh_build_info {
+    float build_ms;
+    uint32_t search_iterations, forced_iterations;
+} mi3pt_bvh_build_info;
+int mi3pt_device_build_bvh_ex(mi3pt_ctx *ctx, const mi3pt_bvh_build_params *params, void *nodes_out, size_t nodes_capacity_bytes,
+                              size_t *nnodes_out, mi3pt_bvh_build_info *info);
 /* REFIT: the boxes of the tree last uploaded with mi3pt_upload_bvh, re-fitted on the device to the triangle records as they stand now --
  * after a later mi3pt_upload_triangles: rigid motion, skinning, anything that keeps the triangle count and index i naming the same surface
  * element (the contract of mi3pt_reproject_scene).  The topology stays: nodes_out (host) receives nnodes x 48 B, ready for

@@ -3491,6 +3491,38 @@ extern "C" int mi3pt_device_build_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t no
     return MI3PT_OK;
 }
 
+// The device builders by name (pt_lbvh.hip, pt_ploc.hip).  Reads d_tris, writes temporaries of its own: no field of the context moves.
+extern "C" int mi3pt_device_build_bvh_ex(mi3pt_ctx *ctx, const mi3pt_bvh_build_params *params, void *nodes_out, size_t nodes_capacity_bytes,
+                                         size_t *nnodes_out, mi3pt_bvh_build_info *info)
+{
+    PT_GROUP(ctx, mi3pt_device_build_bvh_ex(group_member0(ctx), params, nodes_out, nodes_capacity_bytes, nnodes_out, info));
+    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
+    if (!params || !nodes_out || !nnodes_out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
+    if (params->method != MI3PT_BVH_METHOD_LBVH && params->method != MI3PT_BVH_METHOD_PLOC)
+        return pt_set_error(MI3PT_ERR_INVALID, "device BVH build: unknown method");
+    if (params->flags != 0) return pt_set_error(MI3PT_ERR_INVALID, "device BVH build: flags must be 0");
+    if (params->method == MI3PT_BVH_METHOD_PLOC) {
+        if (params->radius < 1 || params->radius > 64) return pt_set_error(MI3PT_ERR_INVALID, "device BVH build: radius must be 1 .. 64");
+        if (params->max_search_iterations < 0 || params->max_search_iterations > 65535)
+            return pt_set_error(MI3PT_ERR_INVALID, "device BVH build: max_search_iterations must be 0 .. 65535");
+    }
+    if (int rc = require_idle(ctx)) return rc;
+    if (!ctx->d_tris || ctx->ntris == 0) return pt_set_error(MI3PT_ERR_STATE, "no triangles uploaded (mi3pt_upload_triangles)");
+    const size_t nodes = 2 * ctx->ntris - 1;
+    if (nodes_capacity_bytes < nodes * MI3PT_BVHNODE_STRIDE) return pt_set_error(MI3PT_ERR_INVALID, "node buffer too small");
+    std::string err;
+    mi3pt_bvh_build_info got = { 0.0f, 0u, 0u };
+    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
+    const int rc = params->method == MI3PT_BVH_METHOD_LBVH
+        ? pt::lbvh_build(ctx->d_tris, ctx->ntris, nodes_out, &got.build_ms, ctx->stream, err)
+        : pt::ploc_build(ctx->d_tris, ctx->ntris, params->radius, params->max_search_iterations, nodes_out, &got.build_ms,
+                         &got.search_iterations, &got.forced_iterations, ctx->stream, err);
+    if (rc != 0) return pt_set_error(MI3PT_ERR_HIP, "device BVH build: " + err);
+    *nnodes_out = nodes;
+    if (info) *info = got;
+    return MI3PT_OK;
+}
+
 // The boxes of the uploaded tree re-fitted to the uploaded triangles (pt_refit.hip).  Reads d_nodes and d_tris, writes temporaries of its own:
 // no field of the context moves.
 extern "C" int mi3pt_device_refit_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t nodes_capacity_bytes, size_t *nnodes_out, float *refit_ms)

@@ -8,8 +8,13 @@ int pt_set_error(int code, const std::string &msg);
 // pt_lbvh.hip: device-side linear BVH over n 112-byte triangle records at d_tris; writes (2n - 1)
 // 48-byte node records to the HOST buffer nodes_out.  Returns 0, or -1 with `err` set.
 #include <hip/hip_runtime.h>
+#include <cstdint>
 namespace pt {
 int lbvh_build(const void *d_tris, size_t n, void *nodes_out, float *build_ms, hipStream_t stream, std::string &err);
+// pt_ploc.hip: the same contract for the locally-ordered clustering of include/mi3pt.h (mi3pt_device_build_bvh_ex, method 1); radius 1 .. 64;
+// the iteration counts are optional.  Everything it allocates is freed before it returns.
+int ploc_build(const void *d_tris, size_t n, int radius, int max_search_iterations, void *nodes_out, float *build_ms,
+               uint32_t *search_iterations, uint32_t *forced_iterations, hipStream_t stream, std::string &err);
 // pt_refit.hip: the boxes of the n 48-byte node records at d_nodes re-fitted, bottom-up, to the ntris 112-byte triangle records at d_tris
 // (both on the device, neither is written); the re-fitted records go to the HOST buffer nodes_out.  The caller vouches for a proper tree
 // whose every record the root reaches and whose leaves name triangles below ntris.  Returns 0, or -1 with `err` set.

@@ -16,6 +16,7 @@
 // the range + number of left turns on the path from the root), so that a child always follows its
 // parent -- the order mi3pt_upload_bvh validates.
 #include "pt_internal.h"
+#include "pt_lbvh.h"
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <cstdint>
@@ -40,8 +41,6 @@ __device__ __forceinline__ int order_f(float f)                // monotone float
     return i >= 0 ? i : i ^ 0x7fffffff;
 }
 __device__ __forceinline__ float unorder_f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-struct Box { float mn[3], mx[3]; };
 
 // Boxes, here and in k_lbvh_fit: fminf / fmaxf.  A NaN operand is dropped on either side (a bound is NaN only where all its inputs are).
 // On zeros C leaves fminf(+0, -0) open; the device's minimum / maximum order -0 below +0, so -0 wins a minimum and +0 a maximum
@@ -177,6 +176,38 @@ __global__ void __launch_bounds__(256) k_lbvh_emit(const uint32_t *__restrict__ 
     w[11] = 0;
 }
 
+// ---- the leaf, key and sort step, shared with pt_ploc.hip (pt_lbvh.h)
+hipError_t sorted_leaves_prepare(size_t n, SortedLeaves &s, hipStream_t stream)
+{
+    static const int init_bounds[6] = { 0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000 };
+    hipError_t e;
+    if ((e = hipMalloc((void **)&s.tri_box, n * sizeof(Box))) != hipSuccess) return e;
+    if ((e = hipMalloc((void **)&s.centroid, n * 12)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **)&s.bounds, 24)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **)&s.keys, n * 8)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **)&s.keys_sorted, n * 8)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **)&s.vals, n * 4)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **)&s.order, n * 4)) != hipSuccess) return e;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, s.tmp_bytes, s.keys, s.keys_sorted, s.vals, s.order, (int)n, 0, 63, stream)) != hipSuccess) return e;
+    if ((e = hipMalloc(&s.tmp, s.tmp_bytes ? s.tmp_bytes : 16)) != hipSuccess) return e;
+    return hipMemcpyAsync(s.bounds, init_bounds, 24, hipMemcpyHostToDevice, stream);
+}
+
+hipError_t sorted_leaves_enqueue(const void *d_tris, size_t n, SortedLeaves &s, hipStream_t stream)
+{
+    const unsigned blocks_n = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(k_lbvh_prims, dim3(blocks_n), dim3(256), 0, stream, static_cast<const float4 *>(d_tris), (uint32_t)n, s.tri_box, s.centroid, s.bounds);
+    hipLaunchKernelGGL(k_lbvh_keys, dim3(blocks_n), dim3(256), 0, stream, s.centroid, (uint32_t)n, s.bounds, s.keys, s.vals);
+    return hipcub::DeviceRadixSort::SortPairs(s.tmp, s.tmp_bytes, s.keys, s.keys_sorted, s.vals, s.order, (int)n, 0, 63, stream);
+}
+
+void sorted_leaves_free(SortedLeaves &s)
+{
+    for (void *p : { (void *)s.tri_box, (void *)s.centroid, (void *)s.bounds, (void *)s.keys, (void *)s.keys_sorted, (void *)s.vals, (void *)s.order, s.tmp })
+        if (p) (void)hipFree(p);
+    s = SortedLeaves();
+}
+
 #define LB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); goto done; } } while (0)
 
 // tris: device pointer to n 112-byte records; nodes_out: HOST buffer of (2n-1) * 48 bytes.
@@ -184,27 +215,15 @@ int lbvh_build(const void *d_tris, size_t n, void *nodes_out, float *build_ms, h
 {
     if (n == 0) { err = "no triangles"; return -1; }
     const int N = (int)n;
-    Box *tri_box = nullptr, *node_box = nullptr;
-    float *centroid = nullptr;
-    int *bounds = nullptr, *left = nullptr, *right = nullptr, *first = nullptr, *last = nullptr, *parent = nullptr, *arrived = nullptr;
+    SortedLeaves lv;
+    Box *node_box = nullptr;
+    int *left = nullptr, *right = nullptr, *first = nullptr, *last = nullptr, *parent = nullptr, *arrived = nullptr;
     uint8_t *is_left = nullptr, *d_out = nullptr;
-    unsigned long long *keys = nullptr, *keys_sorted = nullptr;
-    uint32_t *vals = nullptr, *vals_sorted = nullptr;
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const size_t nodes = 2 * n - 1;
     const unsigned blocks_n = (unsigned)((n + 255) / 256), blocks_nodes = (unsigned)((nodes + 255) / 256);
-    const int init_bounds[6] = { 0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000 };
     float ms = 0.0f;
-    LB_TRY(hipMalloc((void **)&tri_box, n * sizeof(Box)));
     LB_TRY(hipMalloc((void **)&node_box, nodes * sizeof(Box)));
-    LB_TRY(hipMalloc((void **)&centroid, n * 12));
-    LB_TRY(hipMalloc((void **)&bounds, 24));
-    LB_TRY(hipMalloc((void **)&keys, n * 8));
-    LB_TRY(hipMalloc((void **)&keys_sorted, n * 8));
-    LB_TRY(hipMalloc((void **)&vals, n * 4));
-    LB_TRY(hipMalloc((void **)&vals_sorted, n * 4));
     LB_TRY(hipMalloc((void **)&left, n * 4));
     LB_TRY(hipMalloc((void **)&right, n * 4));
     LB_TRY(hipMalloc((void **)&first, n * 4));
@@ -213,22 +232,18 @@ int lbvh_build(const void *d_tris, size_t n, void *nodes_out, float *build_ms, h
     LB_TRY(hipMalloc((void **)&arrived, n * 4));
     LB_TRY(hipMalloc((void **)&is_left, nodes));
     LB_TRY(hipMalloc((void **)&d_out, nodes * 48));
-    LB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_sorted, vals, vals_sorted, N, 0, 63, stream));
-    LB_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
     LB_TRY(hipEventCreate(&e0));
     LB_TRY(hipEventCreate(&e1));
-    LB_TRY(hipMemcpyAsync(bounds, init_bounds, 24, hipMemcpyHostToDevice, stream));
+    LB_TRY(sorted_leaves_prepare(n, lv, stream));
     LB_TRY(hipMemsetAsync(arrived, 0, n * 4, stream));
     LB_TRY(hipMemsetAsync(parent, 0xff, nodes * 4, stream));
     LB_TRY(hipMemsetAsync(is_left, 0, nodes, stream));
     LB_TRY(hipEventRecord(e0, stream));
-    hipLaunchKernelGGL(k_lbvh_prims, dim3(blocks_n), dim3(256), 0, stream, static_cast<const float4 *>(d_tris), (uint32_t)n, tri_box, centroid, bounds);
-    hipLaunchKernelGGL(k_lbvh_keys, dim3(blocks_n), dim3(256), 0, stream, centroid, (uint32_t)n, bounds, keys, vals);
-    LB_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_sorted, vals, vals_sorted, N, 0, 63, stream));
+    LB_TRY(sorted_leaves_enqueue(d_tris, n, lv, stream));
     if (n > 1)
-        hipLaunchKernelGGL(k_lbvh_hierarchy, dim3(blocks_n), dim3(256), 0, stream, keys_sorted, N, left, right, first, last, parent, is_left);
-    hipLaunchKernelGGL(k_lbvh_fit, dim3(blocks_n), dim3(256), 0, stream, vals_sorted, N, tri_box, left, right, parent, node_box, arrived);
-    hipLaunchKernelGGL(k_lbvh_emit, dim3(blocks_nodes), dim3(256), 0, stream, vals_sorted, N, left, first, last, parent, is_left, node_box, d_out);
+        hipLaunchKernelGGL(k_lbvh_hierarchy, dim3(blocks_n), dim3(256), 0, stream, lv.keys_sorted, N, left, right, first, last, parent, is_left);
+    hipLaunchKernelGGL(k_lbvh_fit, dim3(blocks_n), dim3(256), 0, stream, lv.order, N, lv.tri_box, left, right, parent, node_box, arrived);
+    hipLaunchKernelGGL(k_lbvh_emit, dim3(blocks_nodes), dim3(256), 0, stream, lv.order, N, left, first, last, parent, is_left, node_box, d_out);
     LB_TRY(hipGetLastError());
     LB_TRY(hipEventRecord(e1, stream));
     LB_TRY(hipMemcpyAsync(nodes_out, d_out, nodes * 48, hipMemcpyDeviceToHost, stream));
@@ -236,8 +251,8 @@ int lbvh_build(const void *d_tris, size_t n, void *nodes_out, float *build_ms, h
     LB_TRY(hipEventElapsedTime(&ms, e0, e1));
     if (build_ms) *build_ms = ms;
 done:
-    for (void *p : { (void *)tri_box, (void *)node_box, (void *)centroid, (void *)bounds, (void *)keys, (void *)keys_sorted, (void *)vals, (void *)vals_sorted, (void *)left,
-                     (void *)right, (void *)first, (void *)last, (void *)parent, (void *)arrived, (void *)is_left, (void *)d_out, tmp })
+    sorted_leaves_free(lv);
+    for (void *p : { (void *)node_box, (void *)left, (void *)right, (void *)first, (void *)last, (void *)parent, (void *)arrived, (void *)is_left, (void *)d_out })
         if (p) (void)hipFree(p);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);

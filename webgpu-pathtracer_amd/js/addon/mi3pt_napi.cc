@@ -847,6 +847,34 @@ napi_value DeviceBuildBvh(napi_env env, napi_callback_info info)
     return buf;
 }
 
+// deviceBuildBvhEx(ctx, ntris, method, radius, maxSearchIterations) -> { nodes: Buffer of (2*ntris - 1) 48-byte records, ms: device time,
+// searchIterations, forcedIterations }: mi3pt_device_build_bvh_ex -- method 0 the linear BVH (deviceBuildBvh's records), 1 the
+// locally-ordered clustering of mi3pt.h
+napi_value DeviceBuildBvhEx(napi_env env, napi_callback_info info)
+{
+    Args a;
+    mi3pt_ctx *ctx;
+    int32_t ntris, method, radius, budget;
+    if (!get_args(env, info, a, 5) || !get_ctx(env, a.v[0], &ctx) || !get_i32(env, a.v[1], &ntris) || ntris <= 0 ||
+        !get_i32(env, a.v[2], &method) || !get_i32(env, a.v[3], &radius) || !get_i32(env, a.v[4], &budget)) return nullptr;
+    void *out = nullptr;
+    napi_value buf = make_node_buffer(env, (size_t)ntris, &out), obj, v;
+    if (!buf) return nullptr;
+    size_t count = 0;
+    const mi3pt_bvh_build_params params = { method, radius, budget, 0u };
+    mi3pt_bvh_build_info got = { 0.0f, 0u, 0u };
+    MI3PT_TRY(mi3pt_device_build_bvh_ex(ctx, &params, out, (2 * (size_t)ntris - 1) * MI3PT_BVHNODE_STRIDE, &count, &got));
+    NAPI_OK(napi_create_object(env, &obj));
+    NAPI_OK(napi_set_named_property(env, obj, "nodes", buf));
+    NAPI_OK(napi_create_double(env, (double)got.build_ms, &v));
+    NAPI_OK(napi_set_named_property(env, obj, "ms", v));
+    NAPI_OK(napi_create_uint32(env, got.search_iterations, &v));
+    NAPI_OK(napi_set_named_property(env, obj, "searchIterations", v));
+    NAPI_OK(napi_create_uint32(env, got.forced_iterations, &v));
+    NAPI_OK(napi_set_named_property(env, obj, "forcedIterations", v));
+    return obj;
+}
+
 // deviceRefitBvh(ctx, nnodes) -> { nodes: Buffer of nnodes 48-byte records, ms: device time }: the boxes of the uploaded tree re-fitted
 // on the device to the triangles as they stand (mi3pt_device_refit_bvh); nnodes = the record count of the last uploadBvh
 napi_value DeviceRefitBvh(napi_env env, napi_callback_info info)
@@ -956,7 +984,7 @@ napi_value Init(napi_env env, napi_value exports)
         { "setMeanByCount", SetMeanByCount }, { "reproject", Reproject }, { "hostViewFrame", HostViewFrame },
         { "keepGeometry", KeepGeometry }, { "reprojectScene", ReprojectScene },
         { "holdHistory", HoldHistory }, { "mergeHistory", MergeHistory },
-        { "deviceRefitBvh", DeviceRefitBvh }, { "hostBvhCost", HostBvhCost },
+        { "deviceRefitBvh", DeviceRefitBvh }, { "hostBvhCost", HostBvhCost }, { "deviceBuildBvhEx", DeviceBuildBvhEx },
     };
     for (const auto &f : fns) {
         napi_value v;

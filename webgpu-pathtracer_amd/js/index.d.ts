@@ -81,8 +81,12 @@ export interface RendererOptions {
   presentLatest?: boolean;
   verbose?: boolean;
   builderThreads?: number;
-  /** build a linear BVH on the GPU instead of the reference's SAH tree (fast on huge meshes, same closest hits) */
-  deviceBvh?: boolean;
+  /** build the tree on the GPU instead of the reference's SAH tree on the host (same closest hits).  true / 'lbvh': a linear BVH (fast on huge
+   *  meshes, more box tests per ray); 'ploc': locally-ordered clustering (include/mi3pt.h: mi3pt_device_build_bvh_ex), trees of the SAH
+   *  class.  Under `refit`, also the rebuild above refitCostLimit (lastRefitMs then reports that build).  Default: off */
+  deviceBvh?: boolean | 'lbvh' | 'ploc';
+  /** 'ploc': how many positions to either side a cluster looks for its partner, 1 .. 64 (default 16) */
+  deviceBvhRadius?: number;
   /** multi-GPU tile split: this process renders the blockRows-row blocks dealt to `rank`, round after round, BACK AND FORTH
    *  (rank r owns block r of even rounds and block nranks - 1 - r of odd ones: include/mi3pt.h, mi3pt_set_tile).  Use
    *  native.tileGlobalRow(localRow, rank, nranks, blockRows) / native.tileOwner(y, nranks, blockRows) to de-interleave

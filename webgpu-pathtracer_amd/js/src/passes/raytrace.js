@@ -112,6 +112,17 @@ class RaytracePass extends Pass {
     return { triangleBytes: triView.bytes, materialBytes: matView.bytes, positions };
   }
 
+  // options.deviceBvh / deviceBvhRadius -> null (the default: the host's SAH build), or the arguments of native.deviceBuildBvhEx
+  static deviceBuilder(options) {
+    const which = options.deviceBvh;
+    if (which === undefined || which === null || which === false) return null;
+    const method = which === true ? 'lbvh' : which;
+    if (method !== 'lbvh' && method !== 'ploc') throw new Error("options.deviceBvh: expected true, 'lbvh' or 'ploc', got " + String(which));
+    const radius = options.deviceBvhRadius === undefined ? 16 : options.deviceBvhRadius;
+    if (!Number.isInteger(radius) || radius < 1 || radius > 64) throw new Error('options.deviceBvhRadius: expected an integer 1 .. 64, got ' + String(radius));
+    return { method: method === 'ploc' ? 1 : 0, radius, maxSearchIterations: 1024 };
+  }
+
   updateScene(scene, camera) {               // raytrace.ts:380-533
     this.setUniforms({
       camera: {
@@ -131,14 +142,20 @@ class RaytracePass extends Pass {
     if (flat.triangles.length === 0) throw new Error('Input nodes array is empty');    // raytrace.ts:563-565
     const packed = RaytracePass.packScene(flat);
     const native = this.renderer.native, handle = this.renderer.handle;
+    const builder = RaytracePass.deviceBuilder(this.renderer.options);
     let nodeBytes = this.renderer.refit ? this.refitScene(packed, flat.triangles.length) : null;
     if (nodeBytes) {
       // (refitScene uploaded the triangles and the tree)
-    } else if (this.renderer.options.deviceBvh) {
-      // a linear BVH built on the GPU from the uploaded triangles (milliseconds on millions of triangles)
-      // instead of the reference's SAH tree -- same closest hits, more box tests per ray (csrc/pt_lbvh.hip)
+    } else if (builder) {
+      // options.deviceBvh: a tree built on the GPU from the uploaded triangles instead of the reference's SAH tree -- same closest hits.
+      // true / 'lbvh': the linear BVH (milliseconds on millions of triangles, more box tests per ray; csrc/pt_lbvh.hip); 'ploc': the
+      // locally-ordered clustering of include/mi3pt.h (trees of the SAH class; csrc/pt_ploc.hip).  Also the rebuild a refit above
+      // refitCostLimit falls back to, which is what makes a finite limit affordable: lastRefitMs then reports that build
       native.uploadTriangles(handle, packed.triangleBytes);
-      nodeBytes = native.deviceBuildBvh(handle, flat.triangles.length);
+      const built = native.deviceBuildBvhEx(handle, flat.triangles.length, builder.method, builder.radius, builder.maxSearchIterations);
+      nodeBytes = built.nodes;
+      if (this.renderer.lastRefitCostRatio !== null) this.renderer.lastRefitMs = built.ms;
+      this.lastDeviceBuild = { ms: built.ms, searchIterations: built.searchIterations, forcedIterations: built.forcedIterations };
       native.uploadBvh(handle, nodeBytes);
       this.builtNodeBytes = nodeBytes;
     } else {

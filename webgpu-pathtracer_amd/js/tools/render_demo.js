@@ -42,6 +42,8 @@
 //                      holdHistory() / mergeHistory() around two moments reads (the held counts nh; the counts n' after the merge, n = K before
 //                      it).  Prints the share of carried samples kept per view, sum(n' - n) / sum(nh), and lists it under "validate"
 //   --device-bvh       Renderer.create({ deviceBvh: true }): the tree is built on the GPU from the uploaded triangles (csrc/pt_lbvh.hip)
+//   --device-bvh=lbvh|ploc  the same by name: the linear BVH, or the locally-ordered clustering (csrc/pt_ploc.hip), with
+//                      --device-bvh-radius=R (1 .. 64, default 16)
 //   --second-scene     after the loop: remove the scene's last mesh (the sphere of the default scene), mark the scene changed,
 //                      reset and run the loop again -- a second updateScene with another triangle count; the outputs are the
 //                      second scene's
@@ -82,6 +84,10 @@ async function main() {
   const options = { enableTimestampQuery: true };
   if (devices) options.devices = devices.split(',').map((d) => parseInt(d, 10));
   if (process.argv.includes('--device-bvh')) options.deviceBvh = true;
+  for (const a of process.argv) {
+    if (a.startsWith('--device-bvh=')) options.deviceBvh = a.slice('--device-bvh='.length);
+    if (a.startsWith('--device-bvh-radius=')) options.deviceBvhRadius = parseInt(a.slice('--device-bvh-radius='.length), 10);
+  }
   const renderer = await pt.Renderer.create(options);
   const { scene, camera } = buildDefaultScene(envData);
   if (arg('hdr', null)) scene.environment = new pt.RGBELoader().setDataType(pt.FloatType).load(arg('hdr'));

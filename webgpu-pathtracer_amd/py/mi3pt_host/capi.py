@@ -67,7 +67,30 @@ SYMBOLS = (
     "mi3pt_hold_history", "mi3pt_merge_history",
     "mi3pt_set_guided_despike", "mi3pt_read_guided_despiked",
     "mi3pt_device_refit_bvh", "mi3pt_host_bvh_cost",
+    "mi3pt_device_build_bvh_ex",
 )
+BVH_METHODS = {"lbvh": 0, "ploc": 1}        # MI3PT_BVH_METHOD_*
+PLOC_SEARCH_BLOCK = 256                     # MI3PT_PLOC_SEARCH_BLOCK: positions per workgroup of the clustering's neighbour search
+
+
+class BvhBuildParams(ctypes.Structure):
+    """mi3pt_bvh_build_params"""
+    _fields_ = [("method", ctypes.c_int), ("radius", ctypes.c_int), ("max_search_iterations", ctypes.c_int), ("flags", ctypes.c_uint)]
+
+
+class BvhBuildInfoStruct(ctypes.Structure):
+    """mi3pt_bvh_build_info"""
+    _fields_ = [("build_ms", ctypes.c_float), ("search_iterations", ctypes.c_uint32), ("forced_iterations", ctypes.c_uint32)]
+
+
+class BvhBuildInfo(float):
+    """What Context.device_build_bvh returns beside the records: the device time in milliseconds -- a float, as that call has always
+    returned -- with mi3pt_bvh_build_info's fields as attributes: build_ms, search_iterations, forced_iterations."""
+
+    def __new__(cls, build_ms, search_iterations=0, forced_iterations=0):
+        self = super().__new__(cls, build_ms)
+        self.build_ms, self.search_iterations, self.forced_iterations = float(build_ms), int(search_iterations), int(forced_iterations)
+        return self
 
 
 class GuidedParams(ctypes.Structure):
@@ -196,6 +219,7 @@ def load_library(path=None):
     lib.mi3pt_debug_pairs.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
     lib.mi3pt_device_build_bvh.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.mi3pt_device_refit_bvh.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(ctypes.c_float)]
+    lib.mi3pt_device_build_bvh_ex.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.mi3pt_host_bvh_cost.argtypes = [c_void_p, c_size_t, ctypes.POINTER(ctypes.c_double)]
     lib.mi3pt_debug_wave_times.argtypes = [c_void_p, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]
     lib.mi3pt_host_build_bvh.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_int]
@@ -814,18 +838,28 @@ class Context:
         self._c(self.lib.mi3pt_debug_wave_times(self.handle, 1, _ptr(out), len(out), ctypes.byref(n)))
         return out[:n.value]
 
-    def device_build_bvh(self):
-        """Linear BVH over the uploaded triangles, built on the device: (nodes, build_ms).  An alternative
-        to the reference's SAH tree (host_build_bvh_f64), in the same 48-byte records."""
-        n = ctypes.c_size_t()
-        ms = ctypes.c_float()
+    def device_build_bvh(self, method="lbvh", radius=16, max_search_iterations=1024):
+        """A tree over the uploaded triangles, built on the device: (nodes, info), the records ready for upload_bvh.  An alternative to
+        the reference's SAH tree (host_build_bvh_f64), in the same 48-byte records.  method "lbvh": the linear BVH (with no arguments,
+        mi3pt_device_build_bvh as ever); "ploc": the locally-ordered clustering of include/mi3pt.h (mi3pt_device_build_bvh_ex), with
+        its two parameters.  info is a BvhBuildInfo: the device time in milliseconds as a float, with the iteration counts as attributes."""
         from . import layout
+        if method not in BVH_METHODS:
+            raise ValueError(f"device_build_bvh: method {method!r} is none of {sorted(BVH_METHODS)}")
+        n = ctypes.c_size_t()
         ntris = getattr(self, "_ntris_uploaded", 0)
         if ntris == 0:
             raise Mi3ptError(4, "no triangles uploaded")
         nodes = np.zeros(2 * ntris - 1, layout.BVH_NODE)
-        self._c(self.lib.mi3pt_device_build_bvh(self.handle, _ptr(nodes), nodes.nbytes, ctypes.byref(n), ctypes.byref(ms)))
-        return nodes[: n.value], ms.value
+        if method == "lbvh":
+            ms = ctypes.c_float()
+            self._c(self.lib.mi3pt_device_build_bvh(self.handle, _ptr(nodes), nodes.nbytes, ctypes.byref(n), ctypes.byref(ms)))
+            return nodes[: n.value], BvhBuildInfo(ms.value)
+        params = BvhBuildParams(BVH_METHODS[method], int(radius), int(max_search_iterations), 0)
+        info = BvhBuildInfoStruct()
+        self._c(self.lib.mi3pt_device_build_bvh_ex(self.handle, ctypes.byref(params), _ptr(nodes), nodes.nbytes, ctypes.byref(n),
+                                                   ctypes.byref(info)))
+        return nodes[: n.value], BvhBuildInfo(info.build_ms, info.search_iterations, info.forced_iterations)
 
     def device_refit_bvh(self):
         """mi3pt_device_refit_bvh: the boxes of the uploaded tree re-fitted on the device to the triangles as uploaded since:

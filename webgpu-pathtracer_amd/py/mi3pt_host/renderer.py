@@ -124,16 +124,39 @@ class RaytracePass(Pass):
             raise capi.Mi3ptError(1, "Input nodes array is empty")      # raytrace.ts:563-565
         ctx = self.renderer.ctx
         if not (self.renderer.refit and self._refitScene(content)):
-            if content.nodes is None:
-                content.build_bvh()
-            ctx.upload_bvh(content.nodes)
-            ctx.upload_triangles(content.triangles)
+            builder = self._deviceBuilder() if content.nodes is None else None
+            if builder:
+                # options["deviceBvh"]: the tree is built on the GPU from the uploaded triangles -- also the rebuild a refit above
+                # refitCostLimit falls back to, which is what makes a finite limit affordable; lastRefitMs then reports that build
+                ctx.upload_triangles(content.triangles)
+                content.nodes, info = ctx.device_build_bvh(*builder)
+                if self.renderer.lastRefitCostRatio is not None:
+                    self.renderer.lastRefitMs = info.build_ms
+                ctx.upload_bvh(content.nodes)
+            else:
+                if content.nodes is None:
+                    content.build_bvh()
+                ctx.upload_bvh(content.nodes)
+                ctx.upload_triangles(content.triangles)
             self._builtNodes, self._builtCost = content.nodes, None
         self._nodesUploaded = len(content.nodes)
         ctx.upload_materials(content.material_bytes)
         scene.needsUpdate = False
         self.renderer._sceneVersion += 1
         self.renderer._trianglesUploaded = len(content.triangles)      # (reprojectScene: the count the next scene must have)
+
+    def _deviceBuilder(self):
+        """options["deviceBvh"]: False / absent (the default: the reference's SAH tree, built on the host), True or "lbvh" (the linear
+        BVH, csrc/pt_lbvh.hip), "ploc" (the locally-ordered clustering of include/mi3pt.h, csrc/pt_ploc.hip, with
+        options["deviceBvhRadius"], default 16) -> None, or the arguments of Context.device_build_bvh"""
+        opt = self.renderer.options
+        which = opt.get("deviceBvh", False)
+        if which is None or which is False:
+            return None
+        method = "lbvh" if which is True else which
+        if method not in capi.BVH_METHODS:
+            raise ValueError(f"options['deviceBvh'] = {which!r}: expected True, 'lbvh' or 'ploc'")
+        return (method, int(opt.get("deviceBvhRadius", 16)))
 
     def _refitScene(self, content):
         """renderer.refit (no counterpart in the reference, which rebuilds on every scene.needsUpdate, raytrace.ts:380-533): when only
