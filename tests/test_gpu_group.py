@@ -126,3 +126,59 @@ def test_group_compiles_the_scene_once_and_gathers_through_the_host_when_it_must
         assert [g.member(i).get_option(capi.OPT_HOST_ANALYSES) for i in range(1, 8)] == [0] * 7
     assert single > 0
     gpu_ctx.resize(64, 64)
+
+
+def test_group_follows_every_scene_change(gpu_ctx, demo, env):
+    """A group [0, 0] beside the single context at 40 x 24 (three 8-row blocks, dealt back and forth: one to member 0, two to member 1)
+    through the scene states that add, relabel and shrink device buffers.  Member 1 never compiles a scene: whatever member 0 built -- the eight-wide
+    packets that only variant 14 asks for, the relabelled triangle records of layout 1, the smaller buffers of a smaller scene -- has
+    to reach it as a device copy together with every fact that describes it, or its block of the image differs."""
+    from mi3pt_host import scenes
+    dragon = scenes.dragon_class_scene(segments=60)
+    dragon.build_bvh()
+    w, h = 40, 24
+    gpu_ctx.set_tile(0, 1, 8)
+    with capi.Context(devices=[0, 0]) as g:
+        assert [capi.tile_local_rows(h, k, 2, 8) for k in (0, 1)] == [8, 16]
+        both = (g, gpu_ctx)
+        for ctx in both:
+            ctx.set_kernel_variant(0)
+            ctx.set_packet_layout(0)
+            pc.upload_scene(ctx, dragon, env)
+            ctx.resize(w, h)
+            ctx.reset_counters()
+        frame = [2]
+
+        def two_frames_agree(what, sc):
+            images = []
+            for ctx in both:
+                ctx.set_uniforms(capi.PASS_RAYTRACE, pc.rt_uniforms(sc, w, h, frame=frame[0], bounces=5).tobytes())
+                ctx.set_uniforms(capi.PASS_ACCUMULATE, pc.acc_uniforms(w, h, frame[0]).tobytes())
+                ctx.submit_frames(MASK, 2)
+                images.append(ctx.read_texture(capi.TEX_ACCUMULATION))
+            frame[0] += 2
+            assert pc.same_bits(*images), f"{what}: " + pc.describe_diff(*images)
+            got, want = g.counters(), gpu_ctx.counters()
+            for k in pc.PATH_COUNTERS:
+                assert got[k] == want[k], (what, k, got[k], want[k])
+            variants = [g.member(0).active_variant(), g.member(1).active_variant(), gpu_ctx.active_variant()]
+            print(f"{what}: active variants (member 0, member 1, single) {variants}")
+            assert variants[1] == variants[0] == variants[2], (what, variants)
+            assert g.member(1).get_option(capi.OPT_HOST_ANALYSES) == 0, what
+            return variants[0]
+
+        two_frames_agree("(a) dragon-class scene, default walk", dragon)
+        for ctx in both:
+            ctx.set_kernel_variant(14)
+        assert two_frames_agree("(b) variant 14: the eight-wide buffers, built on demand", dragon) == 14
+        for ctx in both:
+            ctx.set_kernel_variant(0)
+            ctx.set_packet_layout(1)
+        two_frames_agree("(c) layout 1: the relabelled triangle records", dragon)
+        for ctx in both:
+            ctx.set_packet_layout(0)
+            pc.upload_scene(ctx, demo, env)
+        two_frames_agree("(d) the demo scene: every count shrinks", demo)
+    gpu_ctx.set_kernel_variant(0)
+    gpu_ctx.set_packet_layout(0)
+    gpu_ctx.resize(64, 64)

@@ -84,21 +84,25 @@ def test_release_library_reads_no_knobs(built):
     an explicit call, mi3pt_debug_set_option; the two switches that change what is computed exist only in the
     -DMI3PT_EXPERIMENTS build (make -C csrc experiments)."""
     blob = open(capi.LIB_PATH, "rb").read()
-    src = open(os.path.join(ROOT, "webgpu-pathtracer_amd", "csrc", "pt_context.hip")).read()
-    knobs = set(re.findall(r'"(MI3PT_[A-Z_]+)"', src))
+    csrc = os.path.join(ROOT, "webgpu-pathtracer_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".cpp", ".h"))}
+    assert {"pt_context.hip", "pt_ctx.h"} <= set(sources)
+    knobs = set(re.findall(r'"(MI3PT_[A-Z_]+)"', "\n".join(sources.values())))
     assert {"MI3PT_CULL_SCALE", "MI3PT_FORCE_SLOW_SLAB", "MI3PT_GATE", "MI3PT_BATCH", "MI3PT_JOB_CHUNK"} <= knobs
     for k in sorted(knobs):
         assert k.encode() + b"\0" not in blob, f"{k} is in the release library"
-    # every getenv of an MI3PT_ name sits inside an #ifdef MI3PT_EXPERIMENTS block
-    depth, guarded = 0, []
-    for line in src.split("\n"):
-        t = line.strip()
-        if t.startswith("#ifdef MI3PT_EXPERIMENTS"):
-            depth += 1
-        elif t.startswith("#endif") and depth:
-            depth -= 1
-        if "getenv" in line and "MI3PT_" in line or ("getenv(eo.name)" in line):
-            guarded.append(depth > 0)
+    # every getenv of an MI3PT_ name sits inside an #ifdef MI3PT_EXPERIMENTS block, in whichever file it stands
+    guarded = []
+    for src in sources.values():
+        depth = 0
+        for line in src.split("\n"):
+            t = line.strip()
+            if t.startswith("#ifdef MI3PT_EXPERIMENTS"):
+                depth += 1
+            elif t.startswith("#endif") and depth:
+                depth -= 1
+            if "getenv" in line and "MI3PT_" in line or ("getenv(eo.name)" in line):
+                guarded.append(depth > 0)
     assert guarded and all(guarded)
 
 

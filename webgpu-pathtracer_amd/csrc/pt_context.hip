@@ -6,8 +6,7 @@
 // one HIP stream.  There is no CPU execution path in this file: every pass is a
 // kernel from pt_kernels.hip.
 #include "../../include/mi3pt.h"
-#include "pt_internal.h"
-#include "pt_kernels.h"
+#include "pt_ctx.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -19,7 +18,6 @@
 #include <utility>
 #include <algorithm>
 #include <vector>
-#include <map>
 #include <chrono>
 #include <thread>
 
@@ -30,351 +28,6 @@ int pt_set_error(int code, const std::string &msg)
     g_last_error = msg;
     return code;
 }
-
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return pt_set_error(MI3PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// GPU time of one pass: an event pair around it on the pass's stream, created by the first timed call (a context that never times a
-// pass creates none).  The batched raytrace launches keep their own events (ev_rt: per parity, folded into running totals).
-struct PassTimer {
-    hipEvent_t ev[2] = {};
-    bool recorded = false;
-    hipError_t begin(hipStream_t s)
-    {
-        for (hipEvent_t &e : ev)
-            if (!e)
-                if (hipError_t r = hipEventCreate(&e)) return r;
-        return hipEventRecord(ev[0], s);
-    }
-    hipError_t end(hipStream_t s)
-    {
-        const hipError_t r = hipEventRecord(ev[1], s);
-        recorded = r == hipSuccess;
-        return r;
-    }
-    int elapsed_us(mi3pt_ctx *ctx, float *us, const char *not_timed);      // (MI3PT_ERR_STATE with that text while nothing is recorded)
-    void forget() { recorded = false; }
-    void destroy()
-    {
-        for (hipEvent_t &e : ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        recorded = false;
-    }
-};
-
-struct mi3pt_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-
-    // scene (device)
-    void *d_tris = nullptr, *d_nodes = nullptr, *d_mats = nullptr, *d_env = nullptr, *d_cdf = nullptr;
-    void *d_packets = nullptr, *d_tripk = nullptr;
-    void *d_leaf_rank = nullptr;          // per triangle: position of its leaf in the reference's visiting order
-    int leaf_cap = 0;                     // LDS slots left for deferred leaves (0 = scene must be walked in order)
-    bool cull_stack_ok = false;           // proper tree, the 64-entry abort cannot fire, and the near-first walks'
-                                          // order-independent worst-case stack fits (upload_bvh)
-    size_t ntris = 0, nnodes = 0, nmats = 0, npackets = 0;
-    uint32_t root_ref = 0;
-    uint32_t scene_flags = 0;
-    bool wide_root_nested = false;  // prepare_cull: the root's box contains its children's boxes (the wide walk may skip the root test)
-    int64_t max_tri_ref = -1;       // largest triangleIndex referenced by a leaf
-    int64_t max_mat_ref = -1;       // largest materialIndex referenced by a triangle
-    // distance-culling walk (kernel variant 9): per-child |e1||e2| bounds in the packets' `cull` field
-    bool cull_enabled = true;       // MI3PT_CULL=0: variant 0 resolves to the reference-counter walk (7)
-    bool cull_dirty = true;         // triangles or tree changed since the last analysis
-    bool cull_ok = false;           // analysis done and the tree admits the walk
-    float cull_ka = 0.0f, cull_kb = 0.0f;   // scene constants of the distance bound
-    // wide (4-ary) packets for kernel variant 10, built with the cull analysis
-    bool wide_enabled = true;       // MI3PT_WIDE=0: variant 0 stops at 9
-#ifdef MI3PT_EXPERIMENTS
-    bool exp_force_slow_slab = false;
-    double exp_cull_scale = 1.0;
-#endif
-    int auto_wide_variant = 10;     // which of the wide walks (10 exact slab test, 11 filtered, 12 filtered + one-axis culling
-                                    // condition) `auto` resolves to for this scene: prepare_cull's walk statistics
-    bool wide_ok = false;
-    bool cwide_ok = false;          // compressed wide packets + 64-byte triangle records built (kernel variant 13): needs wide_ok, every box nested and finite
-    void *d_cwide = nullptr, *d_tripk64 = nullptr;
-    bool cw8_tried = false;         // the last scene analysis ran with variant 14 selected: the 8-wide packets were built, or found impossible for this tree
-    bool cw8_ok = false;            // 8-wide compressed packets + their triangle records built (kernel variant 14): needs cwide_ok
-    void *d_cw8 = nullptr, *d_tripk8 = nullptr;
-    size_t ncw8 = 0, cw8_records = 0;
-    int cw8_height = 0;
-    void *d_wide = nullptr;
-    size_t nwide = 0;
-    int wide_leaf_cap = 0;
-    uint32_t wide_root = 0;
-    int num_cus = 256;              // hipDeviceProp_t::multiProcessorCount
-    pt::RtRoute last_route;      // the kernel the most recent raytrace launch ran (mi3pt_debug_last_launch)
-    // Debug: packet / triangle numbering (mi3pt_debug_set_packet_layout).  0 = breadth-first packets,
-    // triangles as uploaded (shipped).  1 = packets in the reference's visiting order (node, right
-    // subtree, left subtree) and triangles in leaf-visiting order: a pure relabelling.
-    int layout = 0;
-    bool layout_dirty = false;      // the relabelling still has to be applied to what was uploaded
-    // Cost order of a launch's jobs (launch_batch): one launch adds up the path segments traced per 8x8 tile (RtLaunch::tile_cost);
-    // when it has finished the tiles are sorted, costliest first, into a permutation that later launches with the same raytrace
-    // uniforms (frame aside) use as their job order (RtLaunch::tile_perm) -- their last tickets are then their cheapest tiles and
-    // the drain after the queue has run empty is short.  Two permutation buffers: a new order never overwrites the one that
-    // launches in flight may still read.  Any order renders the same bits.
-    int cost_order = 0;                   // (1: the cheapest quarter last; 2: all tiles, costliest first) MI3PT_OPT_COST_ORDER: off -- measured ± 0 on one GPU and −1.6 … −4 % for a rank of a split (profiles/r03_h_cost_order.log)
-    int cost_state = 0;                   // 0: nothing measured for the current uniforms, 1: the measuring launch is in flight, 2: a permutation is in use
-    uint32_t *d_tile_cost = nullptr, *d_tile_perm[2] = { nullptr, nullptr };
-    size_t cost_tiles = 0;                // entries of each of the three arrays
-    int perm_cur = 0;
-    hipEvent_t cost_event = nullptr, perm_used[2] = { nullptr, nullptr };
-    bool perm_used_valid[2] = { false, false };
-    hipStream_t cost_stream = nullptr;
-    uint8_t cost_key[MI3PT_RAYTRACE_UNIFORMS_SIZE] = {};
-    struct GroupState *group = nullptr;   // mi3pt_create_group: this handle fans every call out to member contexts (end of this file)
-    std::map<const void *, size_t> buf_bytes;     // size of every scene buffer replace_buffer() made (what clone_scene copies to a group's other members)
-    uint64_t scene_epoch = 1;             // bumped whenever the device's scene data or its analysis changes (uploads, prepare_layout, prepare_cull)
-    uint64_t host_analyses = 0;           // scene compiles done on the host by THIS context: uploads that build packets + cull analyses (MI3PT_OPT_HOST_ANALYSES)
-    size_t nodes_reached = 0;       // mi3pt_upload_bvh: records the root reaches (mi3pt_device_refit_bvh needs every one reached)
-    bool tree_proper = false;       // mi3pt_upload_bvh: every node reached once, one leaf per triangle, the 64-entry abort cannot fire
-    bool layout_active = false;     // the device holds relabelled packets / triangles
-    void *d_tris_perm = nullptr;    // 112-B records in the relabelled order (the uploaded order stays in d_tris)
-
-    // textures
-    int width = 0, height = 0, local_rows = 0;
-    int rank = 0, nranks = 1, block_rows = 8;                 // active tile
-    int next_rank = 0, next_nranks = 1, next_block_rows = 8;  // applied at resize
-    bool partial() const { return nranks != 1; }     // this context holds part of the image
-    float4 *d_radiance = nullptr, *d_accum_own = nullptr, *d_accum = nullptr, *d_canvas = nullptr;
-    // Batched frames write per-frame radiance slots, one set per launch parity.  Allocated on
-    // demand (an interactive host that presents every frame only ever needs one slot per
-    // parity; up to 8 frames: 8 slots; more: the full batch_cap once), see ensure_slots().
-    // Two sets, one per launch parity.  (MI3PT_SLOT_SETS=3, experiment: launch k+2 then reuses launch k's stream and
-    // counters but not its slots, so it need not wait for the ordered mean of batch k -- which only finds room on the
-    // GPU when launch k+1 drains.  Measured twice: dragon-class -1.8 %, demo +1.3 %: not the critical path.)
-    float4 *d_slots[3] = { nullptr, nullptr, nullptr };
-    int slots_alloc[3] = { 0, 0, 0 };    // frames each set can hold
-    int slot_sets = 2;
-    int batch_cap = 1;                   // frames per launch at this size (batch limit, tile split, free memory)
-    float4 *last_radiance = nullptr;     // the radiance image the most recent raytrace pass wrote
-    // RtLaunch::cam_base: the pixel-only part of the camera rays, one image per launch parity (a launch only ever reads the image
-    // of its own stream, so a moving camera needs no wait: the refill is enqueued on that stream in front of the launch), valid for
-    // the camera / size / tile in cam_base_key
-    float4 *d_cam_base[2] = { nullptr, nullptr };
-    uint8_t cam_base_key[2][80] = {};
-    bool cam_base_valid[2] = { false, false };
-    bool cam_base_enabled = true;        // MI3PT_OPT_CAMERA_BASE
-    // The empty tiles of the view (pt_host_sky.cpp; PROOFS.md section 5): 8x8 tiles whose camera rays reach no geometry are not jobs of the
-    // persistent kernel -- a streaming kernel shades them (launch_batch: sky_prepare).  sky_cut: the boxes of a cut of the uploaded tree
-    // (mi3pt_upload_bvh); the classification is cached under the camera-base key + what else it depends on + the scene's version, on
-    // the host (one per view) and as a device list per launch parity: [active tiles, ascending | empty tiles].
-#ifndef PT_SKY_TILES_DEFAULT
-#define PT_SKY_TILES_DEFAULT 1           // (A/B builds: 0 / 2)
-#endif
-    int sky_tiles = PT_SKY_TILES_DEFAULT; // MI3PT_OPT_SKY_TILES: 0 off, 1 on (the streaming kernel in front of the persistent one), 2 on (behind it)
-    std::vector<float> sky_cut;
-    bool sky_cut_ok = false;
-    uint8_t sky_key[104] = {}, sky_seen_key[104] = {};
-    bool sky_host_valid = false;
-    std::vector<uint8_t> sky_empty;      // the classification for sky_key: 1 per empty tile
-    std::vector<uint32_t> sky_host;      // the list for sky_list_key: [sampled and not empty | sampled and empty] (pt_host_adapt.cpp)
-    uint8_t sky_list_key[104] = {};      // the view's key (zero but for the tile where the list is of the mask alone) + the mask's epoch
-    bool sky_list_valid = false;
-    int sky_host_active = 0, sky_host_sky = 0;
-    uint64_t sky_host_pixels = 0;        // in-bounds pixels of the listed empty tiles
-    // (slot 2: the list of the launches mi3pt_submit runs at once on the context's stream -- written and read on that stream only)
-    uint32_t *d_sky_list[3] = { nullptr, nullptr, nullptr };
-    size_t sky_list_cap[3] = { 0, 0, 0 };
-    uint8_t sky_dev_key[3][104] = {};
-    bool sky_dev_valid[3] = { false, false, false };
-    std::vector<uint32_t> sky_staged[3]; // what the last copy into d_sky_list[par] reads (kept until sky_copied[par])
-    hipEvent_t sky_copied[3] = {};
-    bool sky_copied_valid[3] = { false, false, false };
-    // The sample mask (mi3pt_set_sample_mask): one byte per 8 x 8 tile of the compact image, empty = no mask.  Every mask that is set
-    // gets a new epoch, which is part of the lists' keys (0: no mask), so a list a launch in flight reads is never taken for the new
-    // mask's.  list_read[slot]: behind the last ordered mean that read d_sky_list[slot] -- the copy of a new list waits for it (the mean
-    // runs on the context's stream, the copy on the launch's).  The events are created by the first mask.
-    std::vector<uint8_t> mask;
-    uint64_t mask_epoch = 0, mask_epochs = 0;
-    uint32_t mask_sampled = 0;
-    hipEvent_t list_read[3] = {};
-    bool list_read_valid[3] = { false, false, false };
-    int collapse = -1;                   // MI3PT_OPT_COLLAPSE: 1 = the SAH-optimal grouping of the tree's nodes into wide packets, 0 = the greedy one of rounds 2 - 5, -1 = greedy for the 4-ary packets, optimal for the 8-ary ones (what each measured best with)
-    int six_waves = -1;                  // MI3PT_OPT_SIX_WAVES: the compressed-wide walk's build, -1 = by the size of the launch (pt::RtLaunch::six_waves)
-    int packet_order = 0;                // MI3PT_OPT_PACKET_ORDER: numbering of the wide packets in memory (prepare_cull): 0 breadth-first, 1 depth-first, 2 treelets
-    uint32_t *d_canvas8 = nullptr;
-    bool output_is_accum = false;
-    uint64_t *d_block_counters = nullptr;
-    uint32_t *d_tile_counter = nullptr;
-#ifndef PT_JOB_REVERSE_DEFAULT
-#define PT_JOB_REVERSE_DEFAULT 1         // (A/B builds: 0)
-#endif
-    int job_reverse = PT_JOB_REVERSE_DEFAULT; // MI3PT_JOB_REVERSE, see RtLaunch::job_reverse (the top band last: +0.5 % with the sky up there)
-    int job_group = -1;                  // MI3PT_JOB_GROUP, see RtLaunch::job_group; -1 = chosen per tile set in build_launch
-    int tri_pair = 1;                    // MI3PT_TRI_PAIR, see RtLaunch::tri_pair
-    int job_chunk = PT_DEFAULT_JOB_CHUNK;    // job tickets per draw from the queue (MI3PT_JOB_CHUNK; 1 = one atomic per job)
-    uint32_t *d_drain_flag = nullptr;     // signal memory: sequence number of the last batched launch that started draining
-    bool gate_enabled = false;            // launches wait on d_drain_flag (off when the memory or the wait is unavailable)
-    uint32_t launch_seq = 0;              // sequence number of the last batched launch
-    int gate_timeout_ms = 2000;           // MI3PT_OPT_GATE_TIMEOUT_MS: a blocking entry point that has waited this long releases a held launch from the host (ctx_wait)
-    int gate_releases = 0;                // MI3PT_OPT_GATE_RELEASES: how often that happened
-    int gate_stalls_in_a_row = 0;         // ... how many of them since anything last moved by itself (ctx_wait: three switch the gate off)
-    bool debug_suppress_drain = false;    // MI3PT_OPT_DEBUG_SUPPRESS_DRAIN (tests): the gate is armed but no kernel publishes its drain mark
-    hipStream_t gate_release_stream = nullptr;
-    volatile uint32_t *h_drain_flag = nullptr;   // the drain word as the host sees it, where signal memory is host memory (hipPointerGetAttributes at create); else null
-    // The walk threshold by the VIEW (round 6): after every launch of the shipped walk a one-block kernel leaves what the launch cost -- box
-    // tests and rays -- in host-visible memory; the next launch the host builds runs the deep-walk build (walk_min 44, its own leaf constants:
-    // made for very large trees) when the last launch seen tested more than WALK_ADAPT_ENTER boxes per ray, the ordinary one again below
-    // WALK_ADAPT_LEAVE.  The 870 k-triangle scene: its stated view 17 boxes per ray (deep build -5.6 %), its close-up 68 (+4.4 %).  Same bits.
-    int walk_adapt = 1;                   // MI3PT_OPT_WALK_ADAPT
-    bool deep_by_view = false;
-    uint64_t *h_walk_stats = nullptr;     // pinned host memory, [2 parities][4]: seq, box tests, rays of that parity's last launch
-    uint64_t *d_walk_stats = nullptr;     // ... as the device addresses it
-    uint64_t *d_walk_prev = nullptr;      // [2 parities][2] the counter sets' sums at the previous call (device)
-    uint64_t walk_stats_seq = 0, walk_stats_seen = 0;
-    float *d_park = nullptr;              // [2 parities][PT_MAX_RESIDENT_WAVES][6][64] parked path state of the builds that keep it in memory (RtLaunch::park)
-    uint32_t *d_stack_overflow = nullptr; // [2 parities][PT_MAX_RESIDENT_WAVES][SM_OVERFLOW_ENTRIES][64] overflow stack entries
-    void *d_fs_taps = nullptr;            // the de-noise pass's tap table (pt::launch_fullscreen), built for fs_taps_res
-    float fs_taps_res[2] = { 0.0f, 0.0f };
-    bool fs_taps_valid = false;
-    uint8_t *d_service = nullptr;         // ring of SERVICE_SLOTS pt::RtService blocks: one per batched launch in flight (launch_batch)
-    uint64_t *d_wave_times = nullptr;     // diagnostic stamps, allocated by mi3pt_debug_wave_times(enable)
-    int diag_lite = 0;                    // MI3PT_OPT_DIAG_LITE (experiment builds): with the stamps enabled, the lean build + lane counts runs instead of the diagnostic twin
-    int wave_times_slots = 0;
-    int nblocks = 0;
-
-    uint8_t u_rt[MI3PT_RAYTRACE_UNIFORMS_SIZE] = {};
-    uint8_t u_acc[MI3PT_ACCUMULATE_UNIFORMS_SIZE] = {};
-    uint8_t u_fs[MI3PT_FULLSCREEN_UNIFORMS_SIZE] = {};
-
-    int storage = MI3PT_STORAGE_F32;
-    int variant = 0;
-    bool env_sampling = false;  // mi3pt_set_env_sampling: the reference's dormant importance-sampling lines
-    int tail_policy = PT_DEFAULT_TAIL_POLICY;        // MI3PT_TAIL_POLICY: see RtLaunch::tail_policy
-    int shade_split = PT_DEFAULT_SHADE_SPLIT;       // MI3PT_SHADE_SPLIT: see RtLaunch::shade_split (64: while lanes walk, only the larger group is served)
-    int leaf_min = PT_DEFAULT_LEAF_MIN;          // deferred-leaf walk: lanes with a parked leaf that trigger a triangle step (MI3PT_LEAF_MIN)
-    int walk_min = 0;           // MI3PT_OPT_WALK_MIN: walk while at least this many lanes walk; 0 = by the size of the tree (build_launch)
-    int waves_per_cu = 0;       // one-wave workgroups per compute unit; 0 = what the kernel instantiation is compiled for (pt_kernels.h: 20 / 16)
-    int top_packets = 64;       // MI3PT_TOP_PACKETS
-
-    // Frame pipelining: raytrace kernels of consecutive frames run on two alternating
-    // internal streams so that frame f+1 fills the CUs while frame f's last paths drain;
-    // the ordered running mean (accumulate) stays on the main stream.
-    bool pipeline = true;                // MI3PT_PIPELINE=0 turns it off (one fused kernel per frame)
-    hipStream_t rt_stream[2] = { nullptr, nullptr };
-    hipEvent_t rt_done[2] = {}, acc_done[3] = {}, main_mark = nullptr;
-    bool acc_done_valid[3] = { false, false, false };
-    bool main_dirty = true;              // main-stream work the next raytrace kernel must wait for
-    uint64_t seq = 0;
-
-    // Deferred batching: RAYTRACE|ACCUMULATE frames are queued and up to batch_max consecutive
-    // frames (identical uniforms except `frame`) run as ONE raytrace launch + one ordered
-    // multi-frame accumulate, so the persistent kernel's drain tail is paid once per batch.
-    // Anything that observes or changes device state flushes the queue first.
-    struct PendingFrame {
-        uint8_t u_rt[MI3PT_RAYTRACE_UNIFORMS_SIZE] = {}; uint8_t u_acc[MI3PT_ACCUMULATE_UNIFORMS_SIZE] = {};
-        bool present = false;                                   // EXACT: the canvas is drawn after this frame's mean ...
-        uint8_t u_fs[MI3PT_FULLSCREEN_UNIFORMS_SIZE] = {};      // ... with the pass's uniforms as they were at its submit
-    };
-    std::vector<PendingFrame> pending;
-    int batch_limit_frames = 512;        // MI3PT_OPT_BATCH_LIMIT (512: a rank of an 8-way split runs its 320-frame job as ONE launch instead of 256 + 64: 11.16 instead of 11.62 ms, profiles/r03_d_job_split.log): upper bound of frames per launch, THIS context's (round 3 kept one value per process:
-                                         // contexts other than the caller's went on with a stale capacity)
-    int batch_max = 256;                 // MI3PT_BATCH (1 = no batching); x nranks for a tile split, see batch_limit().  16 -> 32: +3 % (fewer drains), 32 -> 64: +2 %, 64 -> 128: +1.5 %,
-                                         // 128 -> 256 / 320: +0.3 ... +1 % (profiles/r04_s_batch_depth.log); a quarter of the free memory bounds it (recompute_batch_cap)
-    // per-launch GPU time of the batched raytrace kernel (HIP events on its own stream)
-    hipEvent_t ev_rt[2][2] = {};
-    bool ev_rt_pending[2] = { false, false };
-    double rt_total_ms = 0.0, rt_last_ms = 0.0;
-    uint64_t rt_launches = 0, rt_frames = 0;
-    int ev_rt_frames[2] = { 0, 0 };
-    int ev_rt_newest = 0;                // parity of the most recent timed launch
-    hipEvent_t ev_span_start = nullptr;  // start of the first timed launch since the statistics were reset
-    bool span_started = false;
-
-    // Presentation (mi3pt_set_present_mode).  EXACT: every submit that includes FULLSCREEN gets its own accumulate and
-    // fullscreen pass, in order, the canvas drawn from the mean up to and including that frame (the reference's
-    // renderer.ts:379-390); up to present_depth such frames share one raytrace launch (launch_batch).
-    // LATEST: the frame is queued like any other and the canvas is drawn from the running mean of
-    // the batches launched so far -- and only when that mean (or the fullscreen uniforms) changed
-    // since the last draw; a FULLSCREEN-only submit always launches the queue and shows everything.
-    int present_mode = MI3PT_PRESENT_EXACT;
-    int present_depth = 16;              // EXACT: presenting frames per raytrace launch (1 = a launch per frame)
-    uint64_t accum_version = 1;          // bumped whenever d_accum (or what `output` points at) changes
-    uint64_t presented_version = 0;      // accum_version the canvas was last drawn from
-    bool want_present = false;           // LATEST: a requested draw is still owed to the canvas (frames were queued)
-    uint8_t presented_fs[MI3PT_FULLSCREEN_UNIFORMS_SIZE] = {};
-
-    bool timing = false;
-    PassTimer pass_timer[3];             // raytrace (a launch mi3pt_submit runs at once), accumulate, fullscreen: of the last submit
-
-    // First-hit feature images (mi3pt_render_aovs): each local_rows x width x 16 B, allocated by the first call that asks for it and
-    // freed with the textures; aov_valid: rendered (a group's presenting context: gathered) since the last resize.  The pass runs on
-    // the context's stream BESIDE the sample path: it reads the scene, writes these images and touches nothing a sample launch reads
-    // or writes, so the frame queue is neither flushed nor ordered against it.
-    float4 *d_aov[MI3PT_AOV_COUNT] = {};
-    bool aov_valid[MI3PT_AOV_COUNT] = {};
-    PassTimer aov_timer;
-    // The feature-guided de-noise (mi3pt_denoise_guided): two ping-pong images and the packed normal + hit records, each local_rows x width
-    // x 16 B, allocated by the first call and freed with the textures; guided_result: the image the last level wrote (null: no filter since
-    // the last resize).
-    float4 *d_guided[2] = {}, *d_guided_nh = nullptr;
-    const float4 *guided_result = nullptr;
-    PassTimer guided_timer;
-    // MI3PT_GUIDED_VARIANCE: two ping-pong variance images, local_rows x width floats, allocated by the first call with the flag and freed
-    // with the textures; guided_var_result: the one the last level wrote (null: the last filter ran without the flag)
-    float *d_guided_var[2] = {};
-    const float *guided_var_result = nullptr;
-    // mi3pt_set_guided_despike: the state; the image the pre-pass writes and the filter reads in the accumulation image's place (local_rows
-    // x width x 16 B) with the words that count the clamped texels (pt::DESPIKE_SLOTS of them, summed at the read), both allocated by the
-    // first filter that runs with the state on and freed with the textures; guided_despiked: the last filter since the last resize ran
-    // with the state on (the count is that filter's)
-    bool guided_despike = false, guided_despiked = false;
-    float4 *d_guided_despike = nullptr;
-    uint32_t *d_guided_despike_count = nullptr;
-    // The moments image (mi3pt_set_moments): local_rows x width x (M2.rgb, n) fp32 beside the accumulation image, kept by the
-    // moments-keeping accumulate kernels; allocated while `moments` is on and the context has textures.
-    bool moments = false;
-    bool moments_opted = false;          // mi3pt_set_moments(1) has been called: until then MI3PT_GUIDED_VARIANCE is an unknown flag bit, as it was before the image existed
-    float4 *d_moments = nullptr;
-    // The mean by count (mi3pt_set_mean_by_count): the accumulate kernels' by-count twins take a step's weight from the moments texel's n
-    bool by_count = false;
-    // The reprojection (mi3pt_reproject; pt_reproject.hip).  aov_u: the raytrace block each feature image was rendered from; d_aov_prev:
-    // the old view's NORMAL / POSITION / IDS (indexed by mi3pt_aov; pointers swapped with d_aov), d_reproject: the scratch (mean, moments)
-    // the kernel writes -- all allocated by the first call and freed with the textures.
-    uint8_t aov_u[MI3PT_AOV_COUNT][MI3PT_RAYTRACE_UNIFORMS_SIZE] = {};
-    float4 *d_aov_prev[MI3PT_AOV_COUNT] = {};
-    float4 *d_reproject[2] = {};
-    PassTimer reproject_timer;
-    // The held history (mi3pt_hold_history, mi3pt_merge_history; pt_history.hip).  d_hold: the held (mean, moments), allocated by the first
-    // hold and freed with the textures (or with the moments image); history_held: they hold a history that nothing has dropped or merged.
-    float4 *d_hold[2] = {};
-    bool history_held = false;
-    PassTimer history_timer;
-    // The previous geometry (mi3pt_keep_geometry, mi3pt_reproject_scene).  upload_epoch counts the uploads of triangles, BVH and materials (scene_epoch also
-    // moves with the lazy analyses, which change no record); aov_epoch: its value when each feature image was rendered.  geometry_kept:
-    // d_tris as it stood at kept_epoch is the previous geometry -- d_tris itself while d_tris_kept is null (nothing uploaded since), else
-    // d_tris_kept, the buffer the first mi3pt_upload_triangles after the call handed over instead of freeing it.
-    uint64_t upload_epoch = 0, kept_epoch = 0;
-    uint64_t aov_epoch[MI3PT_AOV_COUNT] = {};
-    bool geometry_kept = false;
-    void *d_tris_kept = nullptr;
-    size_t ntris_kept = 0;
-    // The per-tile error estimate (mi3pt_estimate_convergence; pt_converge.hip): the tile map ceil(local_rows / 8) x ceil(width / 8) x 16 B,
-    // the tile kernel's per-block records and the summary on the device, the summary's copy in pinned host memory, all allocated by the
-    // first call and freed with the textures; conv_done: recorded behind the copy of the most recent estimate -- what the two reads wait for, and nothing else.
-    float4 *d_conv_tiles = nullptr;
-    pt::ConvergePart *d_conv_parts = nullptr;
-    pt::ConvergeSummary *d_conv_summary = nullptr, *h_conv_summary = nullptr;
-    hipEvent_t conv_done = nullptr;
-    hipStream_t conv_read_stream = nullptr;      // the tile map's read-back, beside the context's stream (created by the first read)
-    bool conv_valid = false;             // an estimate has been enqueued since the last resize
-    float conv_threshold = 0.0f;         // ... with this threshold
-    int conv_min_frames = 0;             // ... and these min_frames (mi3pt_freeze_converged applies the rule with both)
-    PassTimer conv_timer;
-    int walk_stack_worst = 64;           // mi3pt_upload_bvh: entries the reference walk's stack can hold at most on this tree (64: unknown, or the abort can fire)
-    int wide_stack_worst = 64;           // prepare_cull: the wide walks' node stack, order-independent worst case (internal packets only; <= SM_CULL_STACK_MAX where wide_ok)
-};
 
 // Most frames one launch may cover.  A single GPU batches 16 (the drain tail of a persistent
 // launch is then ~10 % of it); a rank of an N-way tile split renders 1/N of the image per frame,
@@ -540,9 +193,9 @@ static bool gate_release_from_host(mi3pt_ctx *ctx, const GateView &seen, const c
     const bool silent = ctx->h_drain_flag && gate_launch_held(ctx) && (seen.busy[0] != seen.busy[1]);
     const uint32_t mark = gate_front_mark(ctx);
     bool written = false;
-    if (!ctx->gate_release_stream && hipStreamCreateWithFlags(&ctx->gate_release_stream, hipStreamNonBlocking) != hipSuccess) {
+    if (!ctx->gate_release_stream && hipStreamCreateWithFlags(ctx->gate_release_stream.put(), hipStreamNonBlocking) != hipSuccess) {
         (void)hipGetLastError();
-        ctx->gate_release_stream = nullptr;
+        ctx->gate_release_stream.h = nullptr;
     }
     if (ctx->gate_release_stream && hipStreamWriteValue32(ctx->gate_release_stream, ctx->d_drain_flag, mark, 0) == hipSuccess) written = true;
     else (void)hipGetLastError();
@@ -630,8 +283,6 @@ int PassTimer::elapsed_us(mi3pt_ctx *ctx, float *us, const char *not_timed)
 // ---- image planes: the local_rows x width images of a context (radiance, mean, feature images, filter images, moments) ----
 static size_t plane_texels(const mi3pt_ctx *ctx) { return (size_t)ctx->local_rows * ctx->width; }
 static size_t plane_bytes(const mi3pt_ctx *ctx) { return plane_texels(ctx) * 16; }
-// (a rank without rows still owns a pointer per image: 16 bytes)
-template <class T> static hipError_t alloc_plane(T **plane, size_t nbytes) { return hipMalloc((void **)plane, nbytes ? nbytes : 16); }
 
 // Blocking copies between device memory on the context's stream and (pageable) host memory.  Such a copy blocks the host until the
 // stream gets there: the bounded wait comes first.  Nothing to copy: the stream is not touched.
@@ -691,48 +342,48 @@ extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     int prio_least = 0, prio_greatest = 0;
     CREATE_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    if (hipStreamCreateWithPriority(&ctx->own_stream, hipStreamNonBlocking, prio_greatest) != hipSuccess) {
+    if (hipStreamCreateWithPriority(ctx->own_stream.put(), hipStreamNonBlocking, prio_greatest) != hipSuccess) {
         (void)hipGetLastError();
-        CREATE_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+        CREATE_TRY(hipStreamCreateWithFlags(ctx->own_stream.put(), hipStreamNonBlocking));
     }
     ctx->stream = ctx->own_stream;
     for (int k = 0; k < 2; k++) {
         // lowest priority: the persistent raytrace waves must never starve the (tiny, ordered)
         // accumulate kernels on the main stream, which gate the batch after next
-        if (hipStreamCreateWithPriority(&ctx->rt_stream[k], hipStreamNonBlocking, prio_least) != hipSuccess) {
+        if (hipStreamCreateWithPriority(ctx->rt_stream[k].put(), hipStreamNonBlocking, prio_least) != hipSuccess) {
             (void)hipGetLastError();
-            CREATE_TRY(hipStreamCreateWithFlags(&ctx->rt_stream[k], hipStreamNonBlocking));
+            CREATE_TRY(hipStreamCreateWithFlags(ctx->rt_stream[k].put(), hipStreamNonBlocking));
         }
-        CREATE_TRY(hipEventCreateWithFlags(&ctx->rt_done[k], hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&ctx->sky_copied[k], hipEventDisableTiming));
+        CREATE_TRY(hipEventCreateWithFlags(ctx->rt_done[k].put(), hipEventDisableTiming));
+        CREATE_TRY(hipEventCreateWithFlags(ctx->lists[k].copied.put(), hipEventDisableTiming));
     }
-    for (int k = 0; k < 3; k++) CREATE_TRY(hipEventCreateWithFlags(&ctx->acc_done[k], hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&ctx->main_mark, hipEventDisableTiming));
+    for (int k = 0; k < 3; k++) CREATE_TRY(hipEventCreateWithFlags(ctx->acc_done[k].put(), hipEventDisableTiming));
+    CREATE_TRY(hipEventCreateWithFlags(ctx->main_mark.put(), hipEventDisableTiming));
     for (int k = 0; k < 2; k++)
-        for (int j = 0; j < 2; j++) CREATE_TRY(hipEventCreate(&ctx->ev_rt[k][j]));
-    CREATE_TRY(hipEventCreate(&ctx->ev_span_start));
-    CREATE_TRY(hipEventCreateWithFlags(&ctx->cost_event, hipEventDisableTiming));
-    for (int k = 0; k < 2; k++) CREATE_TRY(hipEventCreateWithFlags(&ctx->perm_used[k], hipEventDisableTiming));
-    CREATE_TRY(hipStreamCreateWithFlags(&ctx->cost_stream, hipStreamNonBlocking));
+        for (int j = 0; j < 2; j++) CREATE_TRY(hipEventCreate(ctx->ev_rt[k][j].put()));
+    CREATE_TRY(hipEventCreate(ctx->ev_span_start.put()));
+    CREATE_TRY(hipEventCreateWithFlags(ctx->cost_event.put(), hipEventDisableTiming));
+    for (int k = 0; k < 2; k++) CREATE_TRY(hipEventCreateWithFlags(ctx->perm_used[k].put(), hipEventDisableTiming));
+    CREATE_TRY(hipStreamCreateWithFlags(ctx->cost_stream.put(), hipStreamNonBlocking));
     // environment + CDF textures exist from the start, zero filled (renderer.ts:76-85)
     const size_t env_bytes = (size_t)MI3PT_ENV_WIDTH * MI3PT_ENV_HEIGHT * 16;
-    CREATE_TRY(hipMalloc(&ctx->d_env, env_bytes));
-    CREATE_TRY(hipMalloc(&ctx->d_cdf, env_bytes));
-    CREATE_TRY(hipMalloc((void **)&ctx->d_tile_counter, 256));
-    CREATE_TRY(hipMalloc((void **)&ctx->d_stack_overflow, (size_t)2 * pt::PT_MAX_RESIDENT_WAVES * pt::SM_OVERFLOW_ENTRIES * 64 * 4));
-    CREATE_TRY(hipMalloc((void **)&ctx->d_park, (size_t)2 * pt::PT_MAX_RESIDENT_WAVES * 6 * 64 * sizeof(float)));
-    if (hipHostMalloc((void **)&ctx->h_walk_stats, 64, hipHostMallocMapped) == hipSuccess &&
+    CREATE_TRY(ctx->d_env.alloc(env_bytes));
+    CREATE_TRY(ctx->d_cdf.alloc(env_bytes));
+    CREATE_TRY(ctx->d_tile_counter.alloc(256));
+    CREATE_TRY(ctx->d_stack_overflow.alloc((size_t)2 * pt::PT_MAX_RESIDENT_WAVES * pt::SM_OVERFLOW_ENTRIES * 64 * 4));
+    CREATE_TRY(ctx->d_park.alloc((size_t)2 * pt::PT_MAX_RESIDENT_WAVES * 6 * 64 * sizeof(float)));
+    if (ctx->h_walk_stats.alloc(64, hipHostMallocMapped) == hipSuccess &&
         hipHostGetDevicePointer((void **)&ctx->d_walk_stats, ctx->h_walk_stats, 0) == hipSuccess &&
-        hipMalloc((void **)&ctx->d_walk_prev, 32) == hipSuccess) {
+        ctx->d_walk_prev.alloc(32) == hipSuccess) {
         std::memset(ctx->h_walk_stats, 0, 64);
         CREATE_TRY(hipMemsetAsync(ctx->d_walk_prev, 0, 32, ctx->stream));
     } else {          // (no host-visible memory for it: the threshold goes by the size of the tree alone, as before round 6)
         (void)hipGetLastError();
-        if (ctx->h_walk_stats) (void)hipHostFree(ctx->h_walk_stats);
-        ctx->h_walk_stats = nullptr; ctx->d_walk_stats = nullptr;
+        ctx->h_walk_stats.reset();
+        ctx->d_walk_stats = nullptr;
     }
-    CREATE_TRY(hipMalloc((void **)&ctx->d_service, (size_t)(SERVICE_SLOTS + 1) * service_slot_bytes()));      // (+ 1: the launches mi3pt_submit runs at once on the main stream)
-    CREATE_TRY(hipMalloc(&ctx->d_fs_taps, pt::fullscreen_taps_bytes()));
+    CREATE_TRY(ctx->d_service.alloc((size_t)(SERVICE_SLOTS + 1) * service_slot_bytes()));      // (+ 1: the launches mi3pt_submit runs at once on the main stream)
+    CREATE_TRY(ctx->d_fs_taps.alloc(pt::fullscreen_taps_bytes()));
     CREATE_TRY(hipMemsetAsync(ctx->d_tile_counter, 0, 256, ctx->stream));     // self-cleaning afterwards
     // a word the command processor can poll (hipStreamWaitValue32) and a running kernel can write;
     // optional: without it launches simply queue behind each other
@@ -741,7 +392,9 @@ extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
     // is held until its predecessor announces its drain can then end up in FRONT of that predecessor -- a deadlock (seen
     // as counter passes that never finish, and as a mi3pt_destroy that never returns).  Ungated launches simply queue
     // behind each other: same bits, tails not overlapped.
-    if (hipExtMallocWithFlags((void **)&ctx->d_drain_flag, 8, hipMallocSignalMemory) == hipSuccess) {
+    uint32_t *drain_flag = nullptr;
+    if (hipExtMallocWithFlags((void **)&drain_flag, 8, hipMallocSignalMemory) == hipSuccess) {
+        ctx->d_drain_flag.adopt(drain_flag, 8);
         CREATE_TRY(hipMemsetAsync(ctx->d_drain_flag, 0, 8, ctx->stream));
         ctx->gate_enabled = !profiler_attached();
         hipPointerAttribute_t attr;
@@ -751,7 +404,6 @@ extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
             (void)hipGetLastError();
     } else {
         (void)hipGetLastError();
-        ctx->d_drain_flag = nullptr;
     }
     CREATE_TRY(hipMemsetAsync(ctx->d_env, 0, env_bytes, ctx->stream));
     CREATE_TRY(hipMemsetAsync(ctx->d_cdf, 0, env_bytes, ctx->stream));
@@ -783,56 +435,8 @@ extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
     return MI3PT_OK;
 }
 
-static void free_textures(mi3pt_ctx *ctx)
-{
-    for (void *p : { (void *)ctx->d_radiance, (void *)ctx->d_slots[0], (void *)ctx->d_slots[1], (void *)ctx->d_slots[2], (void *)ctx->d_accum_own,
-                     (void *)ctx->d_canvas, (void *)ctx->d_canvas8, (void *)ctx->d_block_counters, (void *)ctx->d_cam_base[0], (void *)ctx->d_cam_base[1] })
-        if (p) (void)hipFree(p);
-    ctx->d_cam_base[0] = ctx->d_cam_base[1] = nullptr;
-    ctx->cam_base_valid[0] = ctx->cam_base_valid[1] = false;
-    ctx->d_radiance = ctx->d_slots[0] = ctx->d_slots[1] = ctx->d_slots[2] = ctx->last_radiance = nullptr;
-    ctx->slots_alloc[0] = ctx->slots_alloc[1] = ctx->slots_alloc[2] = 0;
-    ctx->d_accum_own = ctx->d_accum = ctx->d_canvas = nullptr;
-    ctx->d_canvas8 = nullptr;
-    ctx->d_block_counters = nullptr;
-    ctx->nblocks = 0;
-    for (int k = 0; k < MI3PT_AOV_COUNT; k++) {
-        if (ctx->d_aov[k]) (void)hipFree(ctx->d_aov[k]);
-        ctx->d_aov[k] = nullptr;
-        ctx->aov_valid[k] = false;
-    }
-    ctx->aov_timer.forget();
-    for (void *p : { (void *)ctx->d_guided[0], (void *)ctx->d_guided[1], (void *)ctx->d_guided_nh })
-        if (p) (void)hipFree(p);
-    ctx->d_guided[0] = ctx->d_guided[1] = ctx->d_guided_nh = nullptr;
-    ctx->guided_result = nullptr;
-    ctx->guided_timer.forget();
-    for (void *p : { (void *)ctx->d_guided_var[0], (void *)ctx->d_guided_var[1], (void *)ctx->d_moments })
-        if (p) (void)hipFree(p);
-    ctx->d_guided_var[0] = ctx->d_guided_var[1] = nullptr;
-    ctx->guided_var_result = nullptr;
-    ctx->d_moments = nullptr;
-    for (void *p : { (void *)ctx->d_guided_despike, (void *)ctx->d_guided_despike_count })
-        if (p) (void)hipFree(p);
-    ctx->d_guided_despike = nullptr;
-    ctx->d_guided_despike_count = nullptr;
-    ctx->guided_despiked = false;
-    for (float4 *&p : ctx->d_aov_prev) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float4 *&p : ctx->d_reproject) { if (p) (void)hipFree(p); p = nullptr; }
-    ctx->reproject_timer.forget();
-    for (float4 *&p : ctx->d_hold) { if (p) (void)hipFree(p); p = nullptr; }
-    ctx->history_held = false;
-    ctx->history_timer.forget();
-    if (ctx->d_conv_tiles) (void)hipFree(ctx->d_conv_tiles);
-    if (ctx->d_conv_parts) (void)hipFree(ctx->d_conv_parts);
-    if (ctx->d_conv_summary) (void)hipFree(ctx->d_conv_summary);
-    if (ctx->h_conv_summary) (void)hipHostFree(ctx->h_conv_summary);
-    ctx->d_conv_tiles = nullptr;
-    ctx->d_conv_parts = nullptr;
-    ctx->d_conv_summary = ctx->h_conv_summary = nullptr;
-    ctx->conv_valid = false;
-    ctx->conv_timer.forget();
-}
+// A context without textures: everything that lives from resize to resize is let go of (what that is: ImageState's members).
+static void free_textures(mi3pt_ctx *ctx) { ctx->images() = ImageState(); }
 
 extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
 {
@@ -853,43 +457,8 @@ extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 2; k++)
         if (ctx->rt_stream[k]) (void)hipStreamSynchronize(ctx->rt_stream[k]);
-    if (ctx->gate_release_stream) (void)hipStreamDestroy(ctx->gate_release_stream);
-    if (ctx->h_walk_stats) (void)hipHostFree(ctx->h_walk_stats);
-    if (ctx->d_walk_prev) (void)hipFree(ctx->d_walk_prev);
-    free_textures(ctx);
-    for (void *p : { ctx->d_cw8, ctx->d_tripk8, ctx->d_cwide, ctx->d_tripk64, ctx->d_wide, ctx->d_tris, ctx->d_tris_kept, ctx->d_tris_perm, ctx->d_nodes, ctx->d_mats, ctx->d_env, ctx->d_cdf, ctx->d_packets, ctx->d_tripk, ctx->d_leaf_rank,
-                     (void *)ctx->d_tile_counter, (void *)ctx->d_drain_flag, (void *)ctx->d_wave_times, (void *)ctx->d_stack_overflow, (void *)ctx->d_park, (void *)ctx->d_service, ctx->d_fs_taps })
-        if (p) (void)hipFree(p);
-    for (PassTimer *t : { &ctx->pass_timer[0], &ctx->pass_timer[1], &ctx->pass_timer[2], &ctx->aov_timer, &ctx->guided_timer, &ctx->conv_timer, &ctx->reproject_timer, &ctx->history_timer }) t->destroy();
-    if (ctx->conv_read_stream) {
-        (void)hipStreamSynchronize(ctx->conv_read_stream);
-        (void)hipStreamDestroy(ctx->conv_read_stream);
-    }
-    if (ctx->conv_done) (void)hipEventDestroy(ctx->conv_done);
-    for (int k = 0; k < 2; k++) {
-        if (ctx->rt_stream[k]) (void)hipStreamDestroy(ctx->rt_stream[k]);
-        if (ctx->rt_done[k]) (void)hipEventDestroy(ctx->rt_done[k]);
-    }
-    for (int k = 0; k < 3; k++) {
-        if (ctx->sky_copied[k]) (void)hipEventDestroy(ctx->sky_copied[k]);
-        if (ctx->list_read[k]) (void)hipEventDestroy(ctx->list_read[k]);
-        if (ctx->d_sky_list[k]) (void)hipFree(ctx->d_sky_list[k]);
-        ctx->d_sky_list[k] = nullptr;
-    }
-    for (int k = 0; k < 3; k++)
-        if (ctx->acc_done[k]) (void)hipEventDestroy(ctx->acc_done[k]);
-    if (ctx->main_mark) (void)hipEventDestroy(ctx->main_mark);
-    if (ctx->ev_span_start) (void)hipEventDestroy(ctx->ev_span_start);
-    if (ctx->cost_event) (void)hipEventDestroy(ctx->cost_event);
-    for (int k = 0; k < 2; k++)
-        if (ctx->perm_used[k]) (void)hipEventDestroy(ctx->perm_used[k]);
-    if (ctx->cost_stream) (void)hipStreamDestroy(ctx->cost_stream);
-    for (void *q : { (void *)ctx->d_tile_cost, (void *)ctx->d_tile_perm[0], (void *)ctx->d_tile_perm[1] })
-        if (q) (void)hipFree(q);
-    for (int k = 0; k < 2; k++)
-        for (int j = 0; j < 2; j++)
-            if (ctx->ev_rt[k][j]) (void)hipEventDestroy(ctx->ev_rt[k][j]);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
+    if (ctx->conv_read_stream) (void)hipStreamSynchronize(ctx->conv_read_stream);
+    // (the device is current and idle: every member lets go of what it owns)
     delete ctx;
     return MI3PT_OK;
 }
@@ -899,7 +468,7 @@ extern "C" int mi3pt_set_stream(mi3pt_ctx *ctx, void *hip_stream)
     PT_GROUP(ctx, group_unsupported("mi3pt_set_stream: a device group runs on its members' own streams"));
     if (int rc = require_idle(ctx)) return rc;
     HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
+    ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream.h;
     ctx->main_dirty = true;
     ctx->acc_done_valid[0] = ctx->acc_done_valid[1] = ctx->acc_done_valid[2] = false;
     return MI3PT_OK;
@@ -1125,20 +694,15 @@ extern "C" int mi3pt_set_tile(mi3pt_ctx *ctx, int rank, int nranks, int block_ro
 }
 
 // Replace *dst with a device copy of `bytes`.
-static int replace_buffer(mi3pt_ctx *ctx, void **dst, const void *bytes, size_t nbytes)
+static int replace_buffer(mi3pt_ctx *ctx, DevBuf<void> &dst, const void *bytes, size_t nbytes)
 {
-    void *fresh = nullptr;
-    HIP_TRY(hipMalloc(&fresh, nbytes));
+    DevBuf<void> fresh;
+    HIP_TRY(fresh.alloc(nbytes));
     hipError_t e = ctx_stream_sync(ctx, ctx->stream, "upload");      // (bounded; a large copy from pageable memory blocks the host until the stream gets there)
     if (e == hipSuccess) e = hipMemcpyAsync(fresh, bytes, nbytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);   // copy-on-call: caller may reuse `bytes`
-    if (e != hipSuccess) {
-        (void)hipFree(fresh);
-        return pt_set_error(MI3PT_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
-    }
-    if (*dst) { ctx->buf_bytes.erase(*dst); (void)hipFree(*dst); }
-    *dst = fresh;
-    ctx->buf_bytes[fresh] = nbytes;
+    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
+    dst = std::move(fresh);
     ctx->scene_epoch++;
     return MI3PT_OK;
 }
@@ -1156,15 +720,12 @@ extern "C" int mi3pt_upload_triangles(mi3pt_ctx *ctx, const void *bytes, size_t 
     if (const char *e = pt::compile_triangles(static_cast<const uint8_t *>(bytes), n, pk, max_mat)) return pt_set_error(MI3PT_ERR_INVALID, e);
     // (mi3pt_keep_geometry: the first upload after it hands the records over as the previous geometry instead of freeing them)
     const bool hand_over = ctx->geometry_kept && !ctx->d_tris_kept;
-    void *tris = hand_over ? nullptr : ctx->d_tris;
-    if (int rc = replace_buffer(ctx, &tris, bytes, nbytes)) return rc;
-    if (hand_over) {
-        ctx->d_tris_kept = ctx->d_tris;
-        ctx->buf_bytes.erase(ctx->d_tris_kept);
-    }
-    ctx->d_tris = tris;
+    DevBuf<void> tris;
+    if (int rc = replace_buffer(ctx, tris, bytes, nbytes)) return rc;
+    if (hand_over) ctx->d_tris_kept = std::move(ctx->d_tris);
+    ctx->d_tris = std::move(tris);
     ctx->upload_epoch++;
-    if (int rc = replace_buffer(ctx, &ctx->d_tripk, pk.data(), n * sizeof(pt::TriPacket))) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_tripk, pk.data(), n * sizeof(pt::TriPacket))) return rc;
     ctx->ntris = n;
     ctx->host_analyses++;
     ctx->max_mat_ref = max_mat;
@@ -1191,7 +752,7 @@ extern "C" int mi3pt_upload_materials(mi3pt_ctx *ctx, const void *bytes, size_t 
     if (int rc = require_idle(ctx)) return rc;
     if (!bytes || nbytes == 0 || nbytes % MI3PT_MATERIAL_STRIDE)
         return pt_set_error(MI3PT_ERR_INVALID, "material bytes must be a non-zero multiple of 64");
-    if (int rc = replace_buffer(ctx, &ctx->d_mats, bytes, nbytes)) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_mats, bytes, nbytes)) return rc;
     ctx->upload_epoch++;
     ctx->nmats = nbytes / MI3PT_MATERIAL_STRIDE;
     return MI3PT_OK;
@@ -1209,10 +770,10 @@ extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes
     const uint8_t *src = static_cast<const uint8_t *>(bytes);
     pt::TreeCompile t;
     if (const char *e = pt::compile_tree(src, n, t)) return pt_set_error(MI3PT_ERR_INVALID, e);
-    if (int rc = replace_buffer(ctx, &ctx->d_nodes, bytes, nbytes)) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_nodes, bytes, nbytes)) return rc;
     ctx->upload_epoch++;
-    if (int rc = replace_buffer(ctx, &ctx->d_packets, t.packets.data(), t.packets.size() * sizeof(pt::NodePacket))) return rc;
-    if (int rc = replace_buffer(ctx, &ctx->d_leaf_rank, t.leaf_rank.data(), t.leaf_rank.size() * sizeof(uint32_t))) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_packets, t.packets.data(), t.packets.size() * sizeof(pt::NodePacket))) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_leaf_rank, t.leaf_rank.data(), t.leaf_rank.size() * sizeof(uint32_t))) return rc;
     ctx->leaf_cap = t.leaf_cap;
     ctx->cull_stack_ok = t.cull_stack_ok;
     ctx->tree_proper = t.tree_proper;
@@ -1321,11 +882,10 @@ extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
     drop_sample_mask(ctx);
     HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
     for (int k = 0; k < 2; k++) HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[k]));
-    // Transactional: the new images are allocated into locals and the context only changes once
+    // Transactional: the new images are allocated into a local and the context only changes once
     // every allocation has succeeded; a failure leaves it WITHOUT textures (width = height = 0,
     // every later submit / read reports "before resize") instead of with dangling pointers.
     free_textures(ctx);
-    ctx->width = ctx->height = ctx->local_rows = 0;
     const int rank = ctx->next_rank, nranks = ctx->next_nranks, block_rows = ctx->next_block_rows;
     const int local_rows = mi3pt_tile_local_rows(height, rank, nranks, block_rows);
     const size_t tex_bytes = (size_t)local_rows * width * 16;
@@ -1338,28 +898,23 @@ extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
     const int nblocks = ntiles_frame > 0 ? std::max(ntiles_frame, pt::PT_MAX_RESIDENT_WAVES) : 0;
     // two counter sets: overlapping raytrace kernels of consecutive frames use alternate halves
     const size_t cbytes = 2 * (size_t)(nblocks ? nblocks : 1) * pt::CNT_COUNT * sizeof(uint64_t);
-    float4 *radiance = nullptr, *accum = nullptr, *canvas = nullptr, *moments = nullptr;
-    uint32_t *canvas8 = nullptr;
-    uint64_t *counters = nullptr;
-    hipError_t e = alloc_plane(&radiance, tex_bytes);
-    if (e == hipSuccess) e = alloc_plane(&accum, tex_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&canvas, canvas_px * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&canvas8, canvas_px * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&counters, cbytes);
-    if (e == hipSuccess && ctx->moments) e = alloc_plane(&moments, tex_bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(counters, 0, cbytes, ctx->stream);
+    ImageState fresh;
+    hipError_t e = fresh.d_radiance.alloc(tex_bytes);
+    if (e == hipSuccess) e = fresh.d_accum_own.alloc(tex_bytes);
+    if (e == hipSuccess) e = fresh.d_canvas.alloc(canvas_px * 16);
+    if (e == hipSuccess) e = fresh.d_canvas8.alloc(canvas_px * 4);
+    if (e == hipSuccess) e = fresh.d_block_counters.alloc(cbytes);
+    if (e == hipSuccess && ctx->moments) e = fresh.d_moments.alloc(tex_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(fresh.d_block_counters, 0, cbytes, ctx->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        for (void *p : { (void *)radiance, (void *)accum, (void *)canvas, (void *)canvas8, (void *)counters, (void *)moments })
-            if (p) (void)hipFree(p);
         return pt_set_error(MI3PT_ERR_HIP, std::string("mi3pt_resize: allocating the textures failed: ") + hipGetErrorString(e));
     }
+    fresh.width = width; fresh.height = height; fresh.local_rows = local_rows;
+    fresh.d_accum = fresh.d_accum_own;
+    fresh.nblocks = nblocks;
     ctx->rank = rank; ctx->nranks = nranks; ctx->block_rows = block_rows;
-    ctx->width = width; ctx->height = height; ctx->local_rows = local_rows;
-    ctx->d_radiance = radiance; ctx->d_accum_own = accum; ctx->d_accum = accum;
-    ctx->d_canvas = canvas; ctx->d_canvas8 = canvas8; ctx->d_block_counters = counters;
-    ctx->d_moments = moments;
-    ctx->nblocks = nblocks;
+    ctx->images() = std::move(fresh);
     // batch depth: the limit for this tile split, capped so that the slot sets together take
     // at most a quarter of the memory that is free now (slots are allocated when first needed)
     recompute_batch_cap(ctx);
@@ -1400,22 +955,22 @@ extern "C" int mi3pt_set_uniforms(mi3pt_ctx *ctx, int pass, const void *bytes, s
 static pt::SceneRefs scene_refs(const mi3pt_ctx *ctx)
 {
     pt::SceneRefs s;
-    s.tris = static_cast<const float4 *>(ctx->layout_active ? ctx->d_tris_perm : ctx->d_tris);
-    s.nodes = static_cast<const float4 *>(ctx->d_nodes);
-    s.mats = static_cast<const float4 *>(ctx->d_mats);
-    s.env = static_cast<const float4 *>(ctx->d_env);
-    s.packets = static_cast<const float4 *>(ctx->d_packets);
-    s.tripk = static_cast<const float4 *>(ctx->d_tripk);
-    s.leaf_rank = static_cast<const uint32_t *>(ctx->d_leaf_rank);
+    s.tris = (ctx->layout_active ? ctx->d_tris_perm : ctx->d_tris).as<const float4>();
+    s.nodes = ctx->d_nodes.as<const float4>();
+    s.mats = ctx->d_mats.as<const float4>();
+    s.env = ctx->d_env.as<const float4>();
+    s.packets = ctx->d_packets.as<const float4>();
+    s.tripk = ctx->d_tripk.as<const float4>();
+    s.leaf_rank = ctx->d_leaf_rank.as<const uint32_t>();
     s.leaf_cap = ctx->leaf_cap;
-    s.wide = static_cast<const float4 *>(ctx->d_wide);
-    s.cwide = static_cast<const float4 *>(ctx->cwide_ok ? ctx->d_cwide : nullptr);
-    s.tripk64 = static_cast<const float4 *>(ctx->cwide_ok ? ctx->d_tripk64 : nullptr);
-    s.cw8 = static_cast<const float4 *>(ctx->cw8_ok ? ctx->d_cw8 : nullptr);
-    s.tripk8 = static_cast<const float4 *>(ctx->cw8_ok ? ctx->d_tripk8 : nullptr);
+    s.wide = ctx->d_wide.as<const float4>();
+    s.cwide = ctx->cwide_ok ? ctx->d_cwide.as<const float4>() : nullptr;
+    s.tripk64 = ctx->cwide_ok ? ctx->d_tripk64.as<const float4>() : nullptr;
+    s.cw8 = ctx->cw8_ok ? ctx->d_cw8.as<const float4>() : nullptr;
+    s.tripk8 = ctx->cw8_ok ? ctx->d_tripk8.as<const float4>() : nullptr;
     s.wide_leaf_cap = ctx->wide_ok ? ctx->wide_leaf_cap : 0;
     s.wide_root = ctx->wide_root;
-    s.cdf = static_cast<const float4 *>(ctx->d_cdf);
+    s.cdf = ctx->d_cdf.as<const float4>();
     s.env_sampling = (ctx->env_sampling && ctx->d_cdf) ? 1 : 0;
     s.ntris = (uint32_t)ctx->ntris; s.nnodes = (uint32_t)ctx->nnodes; s.nmats = (uint32_t)ctx->nmats;
     s.npackets = (uint32_t)ctx->npackets;
@@ -1497,10 +1052,10 @@ static int prepare_layout(mi3pt_ctx *ctx)
         tripk[to] = pt::tri_packet_of(rec);
         rank[to] = (uint32_t)to;          // leaf-visiting order IS the new numbering
     }
-    if (int rc = replace_buffer(ctx, &ctx->d_packets, pk.data(), pk.size() * sizeof(pt::NodePacket))) return rc;
-    if (int rc = replace_buffer(ctx, &ctx->d_tripk, tripk.data(), nt * sizeof(pt::TriPacket))) return rc;
-    if (int rc = replace_buffer(ctx, &ctx->d_leaf_rank, rank.data(), nt * sizeof(uint32_t))) return rc;
-    if (int rc = replace_buffer(ctx, &ctx->d_tris_perm, tris_perm.data(), tris_perm.size())) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_packets, pk.data(), pk.size() * sizeof(pt::NodePacket))) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_tripk, tripk.data(), nt * sizeof(pt::TriPacket))) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_leaf_rank, rank.data(), nt * sizeof(uint32_t))) return rc;
+    if (int rc = replace_buffer(ctx, ctx->d_tris_perm, tris_perm.data(), tris_perm.size())) return rc;
     ctx->root_ref = pt::child_ref(src, packet_of, tri_new.data(), 0);
     ctx->layout_active = true;
     ctx->layout_dirty = false;
@@ -1544,12 +1099,11 @@ static int prepare_cull(mi3pt_ctx *ctx)
     std::vector<pt::TriVerts> tris(nt);
     HIP_TRY(hipMemcpy(nodes.data(), ctx->d_nodes, nodes.size(), hipMemcpyDeviceToHost));
     {
-        float4 *packed = nullptr;
-        HIP_TRY(hipMalloc((void **)&packed, nt * sizeof(pt::TriVerts)));
-        pt::launch_pack_vertices(static_cast<const float4 *>(ctx->d_tris), packed, (uint32_t)nt, ctx->stream);
+        DevBuf<float4> packed;
+        HIP_TRY(packed.alloc(nt * sizeof(pt::TriVerts)));
+        pt::launch_pack_vertices(ctx->d_tris.as<const float4>(), packed, (uint32_t)nt, ctx->stream);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = read_plane(ctx, packed, nt * sizeof(pt::TriVerts), tris.data());
-        (void)hipFree(packed);
         if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("cull analysis: reading the vertices back: ") + hipGetErrorString(e));
     }
     pt::WalkOptions opt;
@@ -1560,20 +1114,19 @@ static int prepare_cull(mi3pt_ctx *ctx)
 #ifdef MI3PT_EXPERIMENTS
     opt.cull_scale = ctx->exp_cull_scale;
 #endif
-    void **const buffer_of[] = { nullptr, &ctx->d_wide, &ctx->d_cwide, &ctx->d_tripk64, &ctx->d_cw8, &ctx->d_tripk8 };
+    DevBuf<void> *const buffer_of[] = { nullptr, &ctx->d_wide, &ctx->d_cwide, &ctx->d_tripk64, &ctx->d_cw8, &ctx->d_tripk8 };
     auto upload = [&](pt::WalkBuffer kind, const void *data, size_t bytes) -> int {
-        if (kind != pt::WALK_CULL) return replace_buffer(ctx, buffer_of[kind], data, bytes);
+        if (kind != pt::WALK_CULL) return replace_buffer(ctx, *buffer_of[kind], data, bytes);
         // the first buffer out: from here on the device no longer holds the walks' packets of the scene before
         ctx->wide_ok = ctx->cwide_ok = ctx->cw8_ok = false;
-        uint32_t *d_cull = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_cull, bytes));
+        DevBuf<uint32_t> d_cull;
+        HIP_TRY(d_cull.alloc(bytes));
         hipError_t e = hipMemcpyAsync(d_cull, data, bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) {
-            pt::launch_patch_cull(static_cast<float4 *>(ctx->d_packets), d_cull, (uint32_t)ctx->npackets, ctx->stream);
+            pt::launch_patch_cull(ctx->d_packets.as<float4>(), d_cull, (uint32_t)ctx->npackets, ctx->stream);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
-        (void)hipFree(d_cull);
         if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("cull analysis: ") + hipGetErrorString(e));
         return MI3PT_OK;
     };
@@ -1724,7 +1277,7 @@ static pt::RtLaunch build_launch(const mi3pt_ctx *ctx, const uint8_t *u, const p
     L.tile_perm = nullptr;
     L.top_packets = ctx->top_packets;
     if (pick_variant(ctx) == 13 && (size_t)L.top_packets > ctx->nwide) L.top_packets = (int)ctx->nwide;      // (A/B builds that stage compressed packets in LDS)
-    if (pick_variant(ctx) == 1) L.scene.tris = static_cast<const float4 *>(ctx->d_tris);    // uploaded records, uploaded indices
+    if (pick_variant(ctx) == 1) L.scene.tris = ctx->d_tris.as<const float4>();    // uploaded records, uploaded indices
     return L;
 }
 
@@ -1773,29 +1326,27 @@ static int ensure_slots(mi3pt_ctx *ctx, int par /* slot set */, int n)
         }
     }
     if (want < n) want = n;
-    float4 *fresh = nullptr;
-    hipError_t e = alloc_plane(&fresh, tex_bytes * (size_t)want);
+    DevBuf<float4> fresh;
+    hipError_t e = fresh.alloc(tex_bytes * (size_t)want);
     if (e != hipSuccess && want > n) {          // not enough memory for the full depth: take what this batch needs
         (void)hipGetLastError();
         want = n;
-        e = alloc_plane(&fresh, tex_bytes * (size_t)want);
+        e = fresh.alloc(tex_bytes * (size_t)want);
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return pt_set_error(MI3PT_ERR_HIP, std::string("radiance slots: ") + hipGetErrorString(e));
     }
-    if (ctx->d_slots[par]) (void)hipFree(ctx->d_slots[par]);
-    ctx->d_slots[par] = fresh;
+    ctx->d_slots[par] = std::move(fresh);
     ctx->slots_alloc[par] = want;
     // a caller that batches deeply will need the other set(s) at the same depth with its very next launch: allocate them
     // now, outside its steady state (the allocation of a gigabyte took ~0.4 ms of a 12 ms job otherwise)
     if (want == ctx->batch_cap && want > 8) {
         for (int other = 0; other < ctx->slot_sets; other++) {
             if (other == par || ctx->slots_alloc[other] >= want) continue;
-            float4 *more = nullptr;
-            if (alloc_plane(&more, tex_bytes * (size_t)want) != hipSuccess) { (void)hipGetLastError(); break; }
-            if (ctx->d_slots[other]) (void)hipFree(ctx->d_slots[other]);
-            ctx->d_slots[other] = more;
+            DevBuf<float4> more;
+            if (more.alloc(tex_bytes * (size_t)want) != hipSuccess) { (void)hipGetLastError(); break; }
+            ctx->d_slots[other] = std::move(more);
             ctx->slots_alloc[other] = want;
         }
     }
@@ -1858,11 +1409,8 @@ static int cost_order_prepare(mi3pt_ctx *ctx, pt::RtLaunch &L, const uint8_t *u_
     if (ctx->cost_tiles != n) {           // (resize / tile change: new arrays)
         HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[0]));
         HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[1]));
-        for (uint32_t **q : { &ctx->d_tile_cost, &ctx->d_tile_perm[0], &ctx->d_tile_perm[1] }) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-            HIP_TRY(hipMalloc((void **)q, n * 4));
-        }
+        for (DevBuf<uint32_t> *q : { &ctx->d_tile_cost, &ctx->d_tile_perm[0], &ctx->d_tile_perm[1] })
+            HIP_TRY(q->alloc(n * 4));
         ctx->cost_tiles = n;
         ctx->cost_state = 0;
         ctx->perm_used_valid[0] = ctx->perm_used_valid[1] = false;
@@ -1949,35 +1497,35 @@ static void tile_lists_compose(mi3pt_ctx *ctx, const pt::Tile &tile, const uint8
     ctx->sky_list_valid = true;
 }
 
-// d_sky_list[slot] = ctx->sky_host (composed for `key`), copied on `s` unless the slot holds that list already.  *staged = false: no
+// lists[slot] = ctx->sky_host (composed for `key`), copied on `s` unless the slot holds that list already.  *staged = false: no
 // memory for it (an unmasked launch then stays whole; under a mask the ordered mean cannot do without: `required`)
 static int tile_lists_stage(mi3pt_ctx *ctx, int slot, const uint8_t *key, size_t ntiles, hipStream_t s, bool required, bool *staged)
 {
     *staged = true;
-    if (ctx->sky_dev_valid[slot] && std::memcmp(key, ctx->sky_dev_key[slot], sizeof ctx->sky_dev_key[slot]) == 0) return MI3PT_OK;
-    if (!ctx->sky_copied[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->sky_copied[slot], hipEventDisableTiming));
-    if (ctx->sky_copied_valid[slot]) HIP_TRY(hipEventSynchronize(ctx->sky_copied[slot]));      // (long done: this slot's previous list)
-    if (ctx->sky_list_cap[slot] < ntiles) {
-        uint32_t *fresh = nullptr;
-        if (hipMalloc((void **)&fresh, ntiles * 4) != hipSuccess) {
+    TileList &t = ctx->lists[slot];
+    if (t.dev_valid && std::memcmp(key, t.dev_key, sizeof t.dev_key) == 0) return MI3PT_OK;
+    if (!t.copied) HIP_TRY(hipEventCreateWithFlags(t.copied.put(), hipEventDisableTiming));
+    if (t.copied_valid) HIP_TRY(hipEventSynchronize(t.copied));      // (long done: this slot's previous list)
+    if (t.cap < ntiles) {
+        DevBuf<uint32_t> fresh;
+        if (fresh.alloc(ntiles * 4) != hipSuccess) {
             (void)hipGetLastError();
             *staged = false;
             return required ? pt_set_error(MI3PT_ERR_HIP, "no device memory for the sample mask's tile list") : MI3PT_OK;
         }
-        if (ctx->d_sky_list[slot]) (void)hipFree(ctx->d_sky_list[slot]);          // (hipFree waits for the device: nothing still reads it)
-        ctx->d_sky_list[slot] = fresh;
-        ctx->sky_list_cap[slot] = ntiles;
+        t.d_list = std::move(fresh);          // (hipFree waits for the device: nothing still reads the old one)
+        t.cap = ntiles;
     }
-    ctx->sky_dev_valid[slot] = false;
-    ctx->sky_staged[slot] = ctx->sky_host;
+    t.dev_valid = false;
+    t.staged = ctx->sky_host;
     // (an ordered mean of an earlier launch may still read the slot's list from the context's stream)
-    if (ctx->list_read_valid[slot]) HIP_TRY(hipStreamWaitEvent(s, ctx->list_read[slot], 0));
-    if (!ctx->sky_staged[slot].empty())
-        HIP_TRY(hipMemcpyAsync(ctx->d_sky_list[slot], ctx->sky_staged[slot].data(), ctx->sky_staged[slot].size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(ctx->sky_copied[slot], s));
-    ctx->sky_copied_valid[slot] = true;
-    std::memcpy(ctx->sky_dev_key[slot], key, sizeof ctx->sky_dev_key[slot]);
-    ctx->sky_dev_valid[slot] = true;
+    if (t.read_valid) HIP_TRY(hipStreamWaitEvent(s, t.read, 0));
+    if (!t.staged.empty())
+        HIP_TRY(hipMemcpyAsync(t.d_list, t.staged.data(), t.staged.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(t.copied, s));
+    t.copied_valid = true;
+    std::memcpy(t.dev_key, key, sizeof t.dev_key);
+    t.dev_valid = true;
     return MI3PT_OK;
 }
 
@@ -2028,19 +1576,19 @@ static int sky_prepare(mi3pt_ctx *ctx, pt::RtLaunch &L, const uint8_t *u_rt, int
     if (int rc = tile_lists_stage(ctx, par, key, (size_t)ntiles, rs, masked, &staged)) return rc;
     if (!staged) return MI3PT_OK;                                        // no memory: no split
     if (takes_list && active == 0) {                  // only empty tiles are sampled: they are the job list, no sky kernel
-        L.tile_perm = ctx->d_sky_list[par];
+        L.tile_perm = ctx->lists[par].d_list;
         L.ntiles_active = nsky;
     } else if (takes_list && (nsky > 0 || active < ntiles)) {
-        L.tile_perm = ctx->d_sky_list[par];
+        L.tile_perm = ctx->lists[par].d_list;
         L.ntiles_active = active;
         if (nsky > 0) {
-            *sky_list = ctx->d_sky_list[par] + active;
+            *sky_list = ctx->lists[par].d_list + active;
             *sky_count = nsky;
             *sky_samples = ctx->sky_host_pixels * (uint64_t)n;
         }
     }
     if (masked) {
-        *acc_list = ctx->d_sky_list[par];
+        *acc_list = ctx->lists[par].d_list;
         *acc_count = active + nsky;
     }
     return MI3PT_OK;
@@ -2057,17 +1605,18 @@ static int mask_list_main(mi3pt_ctx *ctx, const pt::Tile &tile, const uint32_t *
     if (ctx->sky_host_active == 0) return MI3PT_OK;
     bool staged = false;
     if (int rc = tile_lists_stage(ctx, 2, key, (size_t)pt::raytrace_grid_blocks(tile), ctx->stream, true, &staged)) return rc;
-    *list = ctx->d_sky_list[2];
+    *list = ctx->lists[2].d_list;
     *count = ctx->sky_host_active;
     return MI3PT_OK;
 }
 
-// behind an ordered mean that read d_sky_list[slot]
+// behind an ordered mean that read lists[slot]
 static int mask_list_used(mi3pt_ctx *ctx, int slot)
 {
-    if (!ctx->list_read[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->list_read[slot], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ctx->list_read[slot], ctx->stream));
-    ctx->list_read_valid[slot] = true;
+    TileList &t = ctx->lists[slot];
+    if (!t.read) HIP_TRY(hipEventCreateWithFlags(t.read.put(), hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(t.read, ctx->stream));
+    t.read_valid = true;
     return MI3PT_OK;
 }
 
@@ -2146,9 +1695,8 @@ static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, i
         const int32_t tl[6] = { L.tile.tex_w, L.tile.tex_h, L.tile.local_rows, L.tile.rank, L.tile.nranks, L.tile.block_rows };
         std::memcpy(key + 48, tl, sizeof tl);
         if (!ctx->d_cam_base[par]) {
-            if (hipMalloc((void **)&ctx->d_cam_base[par], L.slot_pixels * sizeof(float4)) != hipSuccess) {
+            if (ctx->d_cam_base[par].alloc(L.slot_pixels * sizeof(float4)) != hipSuccess) {
                 (void)hipGetLastError();
-                ctx->d_cam_base[par] = nullptr;
                 ctx->cam_base_enabled = false;            // no memory for it: the kernel forms the rays itself, as before
             }
             ctx->cam_base_valid[par] = false;
@@ -2602,7 +2150,7 @@ extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
     if (int rc = prepare_cull(ctx)) return rc;
     const size_t tex_bytes = plane_bytes(ctx);
     for (int k = 0; k < MI3PT_AOV_COUNT; k++)
-        if (((aov_mask >> k) & 1u) && !ctx->d_aov[k]) HIP_TRY(alloc_plane(&ctx->d_aov[k], tex_bytes));
+        if (((aov_mask >> k) & 1u) && !ctx->d_aov[k]) HIP_TRY(ctx->d_aov[k].alloc(tex_bytes));
     pt::AovLaunch A;
     A.scene = scene_refs(ctx);
     const uint8_t *u = ctx->u_rt;
@@ -2619,7 +2167,7 @@ extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
     // the walk on the uploaded records runs, so that the ids image holds uploaded indices.  One set of bits whichever runs.
     int walk = 3, stack_worst = ctx->walk_stack_worst;
     if (first_hit_walk_is_shipped(ctx)) { walk = 13; stack_worst = ctx->wide_stack_worst; }
-    else if (ctx->layout_active) { walk = 1; A.scene.tris = static_cast<const float4 *>(ctx->d_tris); }
+    else if (ctx->layout_active) { walk = 1; A.scene.tris = ctx->d_tris.as<const float4>(); }
     if (tex_bytes) {
         if (ctx->timing) HIP_TRY(ctx->aov_timer.begin(ctx->stream));
         pt::launch_aovs(A, walk, stack_worst, ctx->leaf_min, ctx->stream);
@@ -2692,11 +2240,11 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
         return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided: MI3PT_GUIDED_VARIANCE needs the moments image (mi3pt_set_moments(ctx, 1) before the frames are accumulated)");
     if (int rc = flush_pending(ctx)) return rc;      // the mean a read-back would return now: the accumulate passes run on this stream
     const size_t texels = plane_texels(ctx);
-    for (float4 **p : { &ctx->d_guided[0], &ctx->d_guided[1], &ctx->d_guided_nh })
-        if (!*p) HIP_TRY(alloc_plane(p, plane_bytes(ctx)));
+    for (DevBuf<float4> *p : { &ctx->d_guided[0], &ctx->d_guided[1], &ctx->d_guided_nh })
+        if (!*p) HIP_TRY(p->alloc(plane_bytes(ctx)));
     if (by_variance)
-        for (float *&p : ctx->d_guided_var)
-            if (!p) HIP_TRY(alloc_plane(&p, texels * 4));
+        for (DevBuf<float> &p : ctx->d_guided_var)
+            if (!p) HIP_TRY(p.alloc(texels * 4));
     pt::GuidedLaunch G;
     G.normal_hit = ctx->d_guided_nh; G.position = ctx->d_aov[MI3PT_AOV_POSITION]; G.albedo = ctx->d_aov[MI3PT_AOV_ALBEDO];
     G.width = ctx->width; G.rows = ctx->local_rows;
@@ -2704,9 +2252,9 @@ extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *p
     G.inv_albedo = guided_inv(params->sigma_albedo); G.inv_plane = guided_inv(params->sigma_plane);
     const bool despike = ctx->guided_despike;
     if (despike) {
-        if (!ctx->d_guided_despike) HIP_TRY(alloc_plane(&ctx->d_guided_despike, plane_bytes(ctx)));
+        if (!ctx->d_guided_despike) HIP_TRY(ctx->d_guided_despike.alloc(plane_bytes(ctx)));
         constexpr size_t count_bytes = (size_t)pt::DESPIKE_SLOTS * pt::DESPIKE_SLOT_WORDS * 4;
-        if (!ctx->d_guided_despike_count) HIP_TRY(alloc_plane(&ctx->d_guided_despike_count, count_bytes));
+        if (!ctx->d_guided_despike_count) HIP_TRY(ctx->d_guided_despike_count.alloc(count_bytes));
         HIP_TRY(hipMemsetAsync(ctx->d_guided_despike_count, 0, count_bytes, ctx->stream));      // (outside the timed span: the pre-pass is one launch)
     }
     ctx->guided_despiked = false;
@@ -2836,9 +2384,8 @@ extern "C" int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled)
     if (on == ctx->moments) return MI3PT_OK;
     HIP_TRY(ctx_stream_sync(ctx, ctx->stream));      // (the accumulate passes in flight read and write the image this frees)
     if (!on) {
-        if (ctx->d_moments) (void)hipFree(ctx->d_moments);
-        ctx->d_moments = nullptr;
-        for (float4 *&p : ctx->d_hold) { if (p) (void)hipFree(p); p = nullptr; }      // (a held history is a mean WITH its moments)
+        ctx->d_moments.reset();
+        for (DevBuf<float4> &p : ctx->d_hold) p.reset();      // (a held history is a mean WITH its moments)
         ctx->history_held = false;
         ctx->moments = false;
         ctx->by_count = false;      // (the count is the image's n: the mode goes with it)
@@ -2846,17 +2393,16 @@ extern "C" int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled)
     }
     if (ctx->width != 0) {
         const size_t tex_bytes = plane_bytes(ctx);
-        float4 *image = nullptr;
-        HIP_TRY(alloc_plane(&image, tex_bytes));
+        DevBuf<float4> image;
+        HIP_TRY(image.alloc(tex_bytes));
         if (tex_bytes) {
             const hipError_t e = hipMemsetAsync(image, 0, tex_bytes, ctx->stream);
             if (e != hipSuccess) {          // (nothing half enabled: the launches key on the pointer)
                 (void)hipGetLastError();
-                (void)hipFree(image);
                 return pt_set_error(MI3PT_ERR_HIP, std::string("mi3pt_set_moments: clearing the image failed: ") + hipGetErrorString(e));
             }
         }
-        ctx->d_moments = image;
+        ctx->d_moments = std::move(image);
         ctx->main_dirty = true;
     }
     ctx->moments = ctx->moments_opted = true;      // (before mi3pt_resize: the image comes with the textures)
@@ -2968,9 +2514,9 @@ static int reproject_run(mi3pt_ctx *ctx, const ReprojectCall &c)
     R.res0_x = ldf(u0, 0); R.res0_y = ldf(u0, 4);
     const size_t tex_bytes = plane_bytes(ctx);
     for (int k : old_set)
-        if (!ctx->d_aov_prev[k]) HIP_TRY(alloc_plane(&ctx->d_aov_prev[k], tex_bytes));
-    for (float4 *&p : ctx->d_reproject)
-        if (!p) HIP_TRY(alloc_plane(&p, tex_bytes));
+        if (!ctx->d_aov_prev[k]) HIP_TRY(ctx->d_aov_prev[k].alloc(tex_bytes));
+    for (DevBuf<float4> &p : ctx->d_reproject)
+        if (!p) HIP_TRY(p.alloc(tex_bytes));
     // the old features become the previous set; the new view's are rendered into the images the set before it held
     for (int k : old_set) std::swap(ctx->d_aov[k], ctx->d_aov_prev[k]);
     if (int rc = mi3pt_render_aovs(ctx, (1u << MI3PT_AOV_COUNT) - 1u)) {
@@ -2989,8 +2535,8 @@ static int reproject_run(mi3pt_ctx *ctx, const ReprojectCall &c)
     if (ctx->timing) HIP_TRY(ctx->reproject_timer.begin(ctx->stream));
     if (c.scene) {
         // the records in upload order, which IDS indexes: the current ones, and the kept ones (the current ones until an upload handed them over)
-        S.tris1 = static_cast<const float4 *>(ctx->d_tris);
-        S.tris0 = static_cast<const float4 *>(ctx->d_tris_kept ? ctx->d_tris_kept : ctx->d_tris);
+        S.tris1 = ctx->d_tris.as<const float4>();
+        S.tris0 = (ctx->d_tris_kept ? ctx->d_tris_kept : ctx->d_tris).as<const float4>();
         S.ntris = (int32_t)ctx->ntris;
         S.max_history_moved = (float)c.max_history_moved;
         pt::launch_reproject_scene(S, ctx->stream);
@@ -3029,8 +2575,7 @@ extern "C" int mi3pt_keep_geometry(mi3pt_ctx *ctx, int keep)
         return pt_set_error(MI3PT_ERR_STATE, "mi3pt_keep_geometry: no triangles uploaded (mi3pt_upload_triangles)");
     if (ctx->d_tris_kept) {        // (a second keep, or the release: behind whatever still reads the buffer)
         HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "mi3pt_keep_geometry"));
-        (void)hipFree(ctx->d_tris_kept);
-        ctx->d_tris_kept = nullptr;
+        ctx->d_tris_kept.reset();
     }
     ctx->geometry_kept = keep != 0;
     ctx->ntris_kept = keep ? ctx->ntris : 0;
@@ -3064,8 +2609,8 @@ extern "C" int mi3pt_hold_history(mi3pt_ctx *ctx)
     if (int rc = history_state(ctx, "mi3pt_hold_history")) return rc;
     if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far belongs to the history that is held
     const size_t tex_bytes = plane_bytes(ctx);
-    for (float4 *&p : ctx->d_hold)
-        if (!p) HIP_TRY(alloc_plane(&p, tex_bytes));
+    for (DevBuf<float4> &p : ctx->d_hold)
+        if (!p) HIP_TRY(p.alloc(tex_bytes));
     ctx->history_held = false;        // (a failure below leaves nothing half held)
     // the images become the held pair: the context's own by a swap of pointers, a bound accumulation image by a copy on the stream
     std::swap(ctx->d_moments, ctx->d_hold[1]);
@@ -3101,8 +2646,8 @@ extern "C" int mi3pt_merge_history(mi3pt_ctx *ctx, const mi3pt_history_params *p
         return pt_set_error(MI3PT_ERR_STATE, "mi3pt_merge_history: no history is held (mi3pt_hold_history; a reset, a resize and a reprojection drop it)");
     if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far is a fresh sample of the test
     const size_t tex_bytes = plane_bytes(ctx);
-    for (float4 *&p : ctx->d_reproject)
-        if (!p) HIP_TRY(alloc_plane(&p, tex_bytes));
+    for (DevBuf<float4> &p : ctx->d_reproject)
+        if (!p) HIP_TRY(p.alloc(tex_bytes));
     const pt::AccUniforms acc = acc_uniforms(ctx);
     pt::HistoryLaunch L;
     L.accum = ctx->d_accum; L.moments = ctx->d_moments;
@@ -3146,11 +2691,11 @@ extern "C" int mi3pt_estimate_convergence(mi3pt_ctx *ctx, float threshold, int m
         return pt_set_error(MI3PT_ERR_STATE, "mi3pt_estimate_convergence needs the moments image (mi3pt_set_moments(ctx, 1) before the frames are accumulated)");
     if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far: the accumulate passes run on this stream
     const size_t ntiles = conv_tiles_x(ctx) * conv_tiles_y(ctx);
-    if (!ctx->d_conv_tiles) HIP_TRY(alloc_plane(&ctx->d_conv_tiles, ntiles * 16));
-    if (!ctx->d_conv_parts) HIP_TRY(alloc_plane(&ctx->d_conv_parts, (size_t)pt::converge_blocks(ctx->width, ctx->local_rows) * sizeof(pt::ConvergePart)));
-    if (!ctx->d_conv_summary) HIP_TRY(hipMalloc((void **)&ctx->d_conv_summary, sizeof(pt::ConvergeSummary)));
-    if (!ctx->h_conv_summary) HIP_TRY(hipHostMalloc((void **)&ctx->h_conv_summary, sizeof(pt::ConvergeSummary), hipHostMallocDefault));
-    if (!ctx->conv_done) HIP_TRY(hipEventCreateWithFlags(&ctx->conv_done, hipEventDisableTiming));
+    if (!ctx->d_conv_tiles) HIP_TRY(ctx->d_conv_tiles.alloc(ntiles * 16));
+    if (!ctx->d_conv_parts) HIP_TRY(ctx->d_conv_parts.alloc((size_t)pt::converge_blocks(ctx->width, ctx->local_rows) * sizeof(pt::ConvergePart)));
+    if (!ctx->d_conv_summary) HIP_TRY(ctx->d_conv_summary.alloc(sizeof(pt::ConvergeSummary)));
+    if (!ctx->h_conv_summary) HIP_TRY(ctx->h_conv_summary.alloc(sizeof(pt::ConvergeSummary)));
+    if (!ctx->conv_done) HIP_TRY(hipEventCreateWithFlags(ctx->conv_done.put(), hipEventDisableTiming));
     const float t2 = (threshold * threshold) * 3.0f;
     if (ctx->timing) HIP_TRY(ctx->conv_timer.begin(ctx->stream));
     pt::launch_converge(ctx->d_accum, ctx->d_moments, ctx->d_conv_tiles, ctx->d_conv_parts, ctx->d_conv_summary, ctx->width, ctx->local_rows, t2,
@@ -3204,7 +2749,7 @@ extern "C" int mi3pt_read_convergence_tiles(mi3pt_ctx *ctx, float *dst, size_t n
     if (int rc = conv_wait(ctx, "mi3pt_read_convergence_tiles")) return rc;
     if (nfloats == 0) return MI3PT_OK;
     // the map is the estimate's until the next estimate: copied beside the context's stream, which may be busy with later frames
-    if (!ctx->conv_read_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->conv_read_stream, hipStreamNonBlocking));
+    if (!ctx->conv_read_stream) HIP_TRY(hipStreamCreateWithFlags(ctx->conv_read_stream.put(), hipStreamNonBlocking));
     HIP_TRY(hipMemcpyAsync(dst, ctx->d_conv_tiles, nfloats * 4, hipMemcpyDeviceToHost, ctx->conv_read_stream));
     HIP_TRY(hipStreamSynchronize(ctx->conv_read_stream));
     return MI3PT_OK;
@@ -3376,12 +2921,11 @@ extern "C" int mi3pt_debug_wave_times(mi3pt_ctx *ctx, int enable, uint64_t *out,
     if (!out) {
         HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
         if (enable && !ctx->d_wave_times) {
-            HIP_TRY(hipMalloc((void **)&ctx->d_wave_times, (size_t)slots * 128));
+            HIP_TRY(ctx->d_wave_times.alloc((size_t)slots * 128));
             HIP_TRY(hipMemset(ctx->d_wave_times, 0, (size_t)slots * 128));
             ctx->wave_times_slots = slots;
         } else if (!enable && ctx->d_wave_times) {
-            (void)hipFree(ctx->d_wave_times);
-            ctx->d_wave_times = nullptr;
+            ctx->d_wave_times.reset();
             ctx->wave_times_slots = 0;
         }
         return MI3PT_OK;
@@ -3400,20 +2944,15 @@ extern "C" int mi3pt_debug_intersect(mi3pt_ctx *ctx, const float *rays, size_t n
     if (!rays || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = check_scene(ctx)) return rc;
     if (n == 0) return MI3PT_OK;
-    float *d_rays = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_rays, n * 24));
-    if (hipMalloc((void **)&d_out, n * 48) != hipSuccess) {
-        (void)hipFree(d_rays);
-        return pt_set_error(MI3PT_ERR_HIP, "hipMalloc failed");
-    }
+    DevBuf<float> d_rays, d_out;
+    HIP_TRY(d_rays.alloc(n * 24));
+    if (d_out.alloc(n * 48) != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, "hipMalloc failed");
     hipError_t e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         pt::launch_debug_intersect(scene_refs(ctx), d_rays, n, d_out, pick_walk(ctx), ctx->stream);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
-    (void)hipFree(d_rays);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_intersect: ") + hipGetErrorString(e));
     return MI3PT_OK;
 }
@@ -3431,20 +2970,15 @@ extern "C" int mi3pt_debug_intersect_shipped(mi3pt_ctx *ctx, const float *rays, 
     if (!first_hit_walk_is_shipped(ctx) || !scene.cwide || !scene.tripk64 || !scene.leaf_rank)
         return pt_set_error(MI3PT_ERR_STATE, "debug_intersect_shipped: mi3pt_render_aovs would not run the shipped first-hit walk on this scene / these options");
     if (n == 0) return MI3PT_OK;
-    float *d_rays = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_rays, n * 24));
-    if (hipMalloc((void **)&d_out, n * 48) != hipSuccess) {
-        (void)hipFree(d_rays);
-        return pt_set_error(MI3PT_ERR_HIP, "hipMalloc failed");
-    }
+    DevBuf<float> d_rays, d_out;
+    HIP_TRY(d_rays.alloc(n * 24));
+    if (d_out.alloc(n * 48) != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, "hipMalloc failed");
     hipError_t e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         pt::launch_debug_intersect_cull(scene, d_rays, n, d_out, ctx->wide_stack_worst, ctx->leaf_min, ctx->stream);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
-    (void)hipFree(d_rays);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_intersect_shipped: ") + hipGetErrorString(e));
     return MI3PT_OK;
 }
@@ -3457,10 +2991,10 @@ extern "C" int mi3pt_debug_pairs(mi3pt_ctx *ctx, int fn, const float *rays, cons
     if (fn != 0 && fn != 1) return pt_set_error(MI3PT_ERR_INVALID, "debug_pairs: fn must be 0 (box) or 1 (triangle)");
     if (n == 0) return MI3PT_OK;
     const size_t G = fn == 0 ? 7 : 9;
-    float *d_rays = nullptr, *d_geom = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_rays, n * 24);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_geom, n * G * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, n * 48);
+    DevBuf<float> d_rays, d_geom, d_out;
+    hipError_t e = d_rays.alloc(n * 24);
+    if (e == hipSuccess) e = d_geom.alloc(n * G * 4);
+    if (e == hipSuccess) e = d_out.alloc(n * 48);
     if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_geom, geom, n * G * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
@@ -3468,9 +3002,6 @@ extern "C" int mi3pt_debug_pairs(mi3pt_ctx *ctx, int fn, const float *rays, cons
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
-    if (d_rays) (void)hipFree(d_rays);
-    if (d_geom) (void)hipFree(d_geom);
-    if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_pairs: ") + hipGetErrorString(e));
     return MI3PT_OK;
 }
@@ -3554,10 +3085,10 @@ extern "C" int mi3pt_debug_math(mi3pt_ctx *ctx, int fn, const float *a, const fl
     if (int rc = require_idle(ctx)) return rc;
     if (!a || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (n == 0) return MI3PT_OK;
-    float *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
-    hipError_t e = hipMalloc((void **)&d_a, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_o, n * 4);
-    if (e == hipSuccess && b) e = hipMalloc((void **)&d_b, n * 4);
+    DevBuf<float> d_a, d_b, d_o;
+    hipError_t e = d_a.alloc(n * 4);
+    if (e == hipSuccess) e = d_o.alloc(n * 4);
+    if (e == hipSuccess && b) e = d_b.alloc(n * 4);
     if (e == hipSuccess) e = hipMemcpyAsync(d_a, a, n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && b) e = hipMemcpyAsync(d_b, b, n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
@@ -3565,9 +3096,6 @@ extern "C" int mi3pt_debug_math(mi3pt_ctx *ctx, int fn, const float *a, const fl
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = read_plane(ctx, d_o, n * 4, out);
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (d_o) (void)hipFree(d_o);
     if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_math: ") + hipGetErrorString(e));
     return MI3PT_OK;
 }
@@ -3602,8 +3130,7 @@ struct GroupState {
     // Can the presenting device's copy engines address member i's memory directly?  (same device, or peer access enabled and
     // confirmed at create).  Where not -- or after a direct gather failed -- the gather is staged through pinned host memory.
     std::vector<char> peer_direct;
-    void *stage = nullptr;        // pinned host buffer of stage_bytes (allocated when first needed)
-    size_t stage_bytes = 0;
+    PinnedBuf<void> stage;        // pinned host buffer (allocated when first needed)
     // first-hit feature images: which the members hold (rendered since the last resize), and which of those the presenting
     // context's whole image is a current copy of
     bool aov_rendered[MI3PT_AOV_COUNT] = {}, aov_gathered[MI3PT_AOV_COUNT] = {};
@@ -3689,7 +3216,6 @@ static int group_destroy(mi3pt_ctx *g)
     for (mi3pt_ctx *m : gs->members)
         if (m) { const int r = mi3pt_destroy(m); if (r && !rc) rc = r; }
     if (gs->present) { const int r = mi3pt_destroy(gs->present); if (r && !rc) rc = r; }
-    if (gs->stage) (void)hipHostFree(gs->stage);
     delete gs;
     g->group = nullptr;
     delete g;
@@ -3735,15 +3261,12 @@ static size_t group_global_row(int ly, int i, int n, int br)
 }
 
 // One scene buffer of `src` replicated into `dst` (another member, maybe another device): device to device, on dst's stream.
-static int clone_buffer(mi3pt_ctx *dst, void **dptr, const mi3pt_ctx *src, const void *sptr)
+static int clone_buffer(mi3pt_ctx *dst, DevBuf<void> &dbuf, const mi3pt_ctx *src, const DevBuf<void> &sbuf)
 {
-    if (*dptr) { dst->buf_bytes.erase(*dptr); (void)hipFree(*dptr); *dptr = nullptr; }
-    if (!sptr) return MI3PT_OK;
-    const auto it = src->buf_bytes.find(sptr);
-    if (it == src->buf_bytes.end()) return pt_set_error(MI3PT_ERR_STATE, "group: a scene buffer of unknown size");
-    HIP_TRY(hipMalloc(dptr, it->second ? it->second : 16));
-    if (it->second) HIP_TRY(hipMemcpyPeerAsync(*dptr, dst->device, sptr, src->device, it->second, dst->stream));
-    dst->buf_bytes[*dptr] = it->second;
+    dbuf.reset();
+    if (!sbuf) return MI3PT_OK;
+    HIP_TRY(dbuf.alloc(sbuf.bytes));
+    if (sbuf.bytes) HIP_TRY(hipMemcpyPeerAsync(dbuf, dst->device, sbuf, src->device, sbuf.bytes, dst->stream));
     return MI3PT_OK;
 }
 
@@ -3753,34 +3276,19 @@ static int clone_scene(mi3pt_ctx *dst, const mi3pt_ctx *src)
     if (int rc = require_idle(dst)) return rc;
     HIP_TRY(ctx_stream_sync(dst, dst->stream));
     for (int k = 0; k < 2; k++) HIP_TRY(ctx_stream_sync(dst, dst->rt_stream[k]));
-    if (int rc = clone_buffer(dst, &dst->d_tris, src, src->d_tris)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_tris_perm, src, src->d_tris_perm)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_nodes, src, src->d_nodes)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_mats, src, src->d_mats)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_packets, src, src->d_packets)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_tripk, src, src->d_tripk)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_leaf_rank, src, src->d_leaf_rank)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_wide, src, src->d_wide)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_cwide, src, src->d_cwide)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_tripk64, src, src->d_tripk64)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_cw8, src, src->d_cw8)) return rc;
-    if (int rc = clone_buffer(dst, &dst->d_tripk8, src, src->d_tripk8)) return rc;
+    const auto from = SceneBuffers::all(*src);
+    const auto to = SceneBuffers::all(*dst);
+    for (size_t k = 0; k < from.size(); k++)
+        if (int rc = clone_buffer(dst, *to[k], src, *from[k])) return rc;
     const size_t env_bytes = (size_t)MI3PT_ENV_WIDTH * MI3PT_ENV_HEIGHT * 16;
     HIP_TRY(hipMemcpyPeerAsync(dst->d_env, dst->device, src->d_env, src->device, env_bytes, dst->stream));
     HIP_TRY(hipMemcpyPeerAsync(dst->d_cdf, dst->device, src->d_cdf, src->device, env_bytes, dst->stream));
     HIP_TRY(ctx_stream_sync(dst, dst->stream));
-    dst->ntris = src->ntris; dst->nnodes = src->nnodes; dst->nmats = src->nmats; dst->npackets = src->npackets;
-    dst->root_ref = src->root_ref; dst->scene_flags = src->scene_flags; dst->wide_root_nested = src->wide_root_nested;
-    dst->max_tri_ref = src->max_tri_ref; dst->max_mat_ref = src->max_mat_ref;
-    dst->leaf_cap = src->leaf_cap; dst->cull_stack_ok = src->cull_stack_ok; dst->tree_proper = src->tree_proper; dst->nodes_reached = src->nodes_reached;
-    dst->walk_stack_worst = src->walk_stack_worst; dst->wide_stack_worst = src->wide_stack_worst;
-    dst->cull_dirty = src->cull_dirty; dst->cull_ok = src->cull_ok; dst->cull_ka = src->cull_ka; dst->cull_kb = src->cull_kb;
-    dst->auto_wide_variant = src->auto_wide_variant; dst->wide_ok = src->wide_ok; dst->cwide_ok = src->cwide_ok; dst->nwide = src->nwide;
-    dst->cw8_ok = src->cw8_ok; dst->cw8_tried = src->cw8_tried; dst->ncw8 = src->ncw8; dst->cw8_records = src->cw8_records; dst->cw8_height = src->cw8_height;
-    dst->wide_leaf_cap = src->wide_leaf_cap; dst->wide_root = src->wide_root;
-    dst->layout = src->layout; dst->layout_dirty = src->layout_dirty; dst->layout_active = src->layout_active;
+    dst->scene_facts() = src->scene_facts();
+    // what does not come from `src`: the copy's own caches are of another scene, its streams have new work to order, its scene has a new version.
+    // (Nor do the options -- cull_enabled, wide_enabled, collapse, packet_order: set on every member -- the kept geometry and host_analyses.)
     dst->cost_state = 0;
-    dst->sky_cut = src->sky_cut; dst->sky_cut_ok = src->sky_cut_ok; dst->sky_host_valid = false;
+    dst->sky_host_valid = false;
     dst->main_dirty = true;
     dst->scene_epoch++;
     return MI3PT_OK;
@@ -3850,16 +3358,11 @@ static int gather_member(GroupState *gs, int i, bool direct, const float4 *membe
     hipMemcpyKind kind = hipMemcpyDeviceToDevice;
     if (!direct) {
         const size_t need = (size_t)rows * row_bytes;
-        if (gs->stage_bytes < need) {
-            if (gs->stage) (void)hipHostFree(gs->stage);
-            gs->stage = nullptr; gs->stage_bytes = 0;
-            HIP_TRY(hipHostMalloc(&gs->stage, need, hipHostMallocDefault));
-            gs->stage_bytes = need;
-        }
+        if (gs->stage.bytes < need) HIP_TRY(gs->stage.alloc(need));
         HIP_TRY(hipSetDevice(m->device));
         HIP_TRY(hipMemcpy(gs->stage, src, need, hipMemcpyDeviceToHost));      // (synchronous: the one staging buffer is reused member by member)
         HIP_TRY(hipSetDevice(p->device));
-        src = static_cast<const uint8_t *>(gs->stage);
+        src = gs->stage.as<const uint8_t>();
         kind = hipMemcpyHostToDevice;
     }
     // The deal goes back and forth: the member's even local blocks sit at image block (2 k n + i), its odd ones at
@@ -3910,7 +3413,7 @@ template <class Plane, class Wait> static int gather_lazy_image(GroupState *gs, 
 {
     if (int rc = wait_for_members()) return rc;
     mi3pt_ctx *p = gs->present;
-    if (!plane(p)) HIP_TRY(alloc_plane(&plane(p), plane_bytes(p)));
+    if (!plane(p)) HIP_TRY(plane(p).alloc(plane_bytes(p)));
     return gather_copies(gs, plane);
 }
 
@@ -3959,7 +3462,7 @@ static int group_gather_aov(mi3pt_ctx *g, int which, const char *what)
         }
         return require_ctx(gs->present);
     };
-    if (int rc = gather_lazy_image(gs, [which](mi3pt_ctx *c) -> float4 *& { return c->d_aov[which]; }, members_streams)) return rc;
+    if (int rc = gather_lazy_image(gs, [which](mi3pt_ctx *c) -> DevBuf<float4> & { return c->d_aov[which]; }, members_streams)) return rc;
     gs->present->aov_valid[which] = true;
     gs->aov_gathered[which] = true;
     return MI3PT_OK;
@@ -3993,8 +3496,7 @@ static int group_set_moments(mi3pt_ctx *g, int enabled)
     if (!enabled && p->d_moments) {
         if (int rc = require_ctx(p)) return rc;
         HIP_TRY(ctx_stream_sync(p, p->stream));
-        (void)hipFree(p->d_moments);
-        p->d_moments = nullptr;
+        p->d_moments.reset();
     }
     if (!enabled) p->moments = false;
     return MI3PT_OK;
@@ -4009,7 +3511,7 @@ static int group_gather_moments(mi3pt_ctx *g, const char *what)
         if (int rc = group_sync(g)) return rc;
         return require_idle(gs->present);
     };
-    if (int rc = gather_lazy_image(gs, [](mi3pt_ctx *c) -> float4 *& { return c->d_moments; }, everything)) return rc;
+    if (int rc = gather_lazy_image(gs, [](mi3pt_ctx *c) -> DevBuf<float4> & { return c->d_moments; }, everything)) return rc;
     gs->present->moments = true;
     return MI3PT_OK;
 }
