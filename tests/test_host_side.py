@@ -77,6 +77,35 @@ def test_library_exports_every_declared_symbol(built):
     assert "orc_" not in out                    # no oracle / CPU render path inside the product
 
 
+# the translation units of the context ("The context behind the boundary")
+CONTEXT_UNITS = {"pt_context.hip", "pt_ctx_probe.hip", "pt_ctx_group.hip"}
+
+
+def test_makefile_lists_every_source_and_each_entry_point_has_one_body():
+    """The Makefile's SRCS is the set of *.hip / *.cpp files in csrc/ (a unit that is not listed is not linked; the library then fails to load
+    for want of a symbol), HDRS covers every *.h there (a header that is not listed does not rebuild the library), and every mi3pt_* function
+    of include/mi3pt.h has its body in exactly one file.  Needs no library."""
+    csrc = os.path.join(ROOT, "webgpu-pathtracer_amd", "csrc")
+    make = open(os.path.join(csrc, "Makefile")).read()
+    listed = {}
+    for v in ("SRCS", "HDRS"):
+        m = re.search(r"^%s\s*:=(.*)$" % v, make, flags=re.M)
+        assert m and not m.group(1).rstrip().endswith("\\"), f"this test reads {v} := ... from one line of the Makefile"
+        listed[v] = m.group(1).split()
+    files = sorted(os.listdir(csrc))
+    assert sorted(listed["SRCS"]) == [f for f in files if f.endswith((".hip", ".cpp"))]
+    assert len(set(listed["SRCS"])) == len(listed["SRCS"])
+    assert CONTEXT_UNITS <= set(listed["SRCS"])
+    assert {f for f in files if f.endswith(".h")} <= set(listed["HDRS"])
+    bodies = {}
+    for f in listed["SRCS"]:
+        text = open(os.path.join(csrc, f)).read()
+        for name in re.findall(r'extern "C"\s+[^;{}()]*?\b(mi3pt_\w+)\s*\([^;{}]*\)\s*\{', text):
+            bodies.setdefault(name, []).append(f)
+    declared = _declared_symbols()          # (without the experiment build's own declarations, as the export test takes them)
+    assert declared and {name: bodies.get(name, []) for name in declared if len(bodies.get(name, [])) != 1} == {}
+
+
 def test_release_library_reads_no_knobs(built):
     """The release object reads no MI3PT_* environment variable (round-2 finding: an environment variable could void
     the bit-exactness guarantee of a drop-in library): no knob name is in the binary, and the only environment names it
@@ -86,7 +115,7 @@ def test_release_library_reads_no_knobs(built):
     blob = open(capi.LIB_PATH, "rb").read()
     csrc = os.path.join(ROOT, "webgpu-pathtracer_amd", "csrc")
     sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".cpp", ".h"))}
-    assert {"pt_context.hip", "pt_ctx.h"} <= set(sources)
+    assert CONTEXT_UNITS | {"pt_ctx.h", "pt_ctx_calls.h"} <= set(sources)
     knobs = set(re.findall(r'"(MI3PT_[A-Z_]+)"', "\n".join(sources.values())))
     assert {"MI3PT_CULL_SCALE", "MI3PT_FORCE_SLOW_SLAB", "MI3PT_GATE", "MI3PT_BATCH", "MI3PT_JOB_CHUNK"} <= knobs
     for k in sorted(knobs):

@@ -5,8 +5,10 @@
 // src/passes/accumulate.ts:45-59) and turns mi3pt_submit() into kernel launches on
 // one HIP stream.  There is no CPU execution path in this file: every pass is a
 // kernel from pt_kernels.hip.
+//
+// The probes are pt_ctx_probe.hip, the device groups pt_ctx_group.hip; pt_ctx_calls.h declares what crosses those cuts.
 #include "../../include/mi3pt.h"
-#include "pt_ctx.h"
+#include "pt_ctx_calls.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -29,6 +31,8 @@ int pt_set_error(int code, const std::string &msg)
     return code;
 }
 
+const std::string &pt_last_error() { return g_last_error; }
+
 // Most frames one launch may cover.  A single GPU batches 16 (the drain tail of a persistent
 // launch is then ~10 % of it); a rank of an N-way tile split renders 1/N of the image per frame,
 // so it batches N times as many frames for the same amount of work per launch.
@@ -39,8 +43,7 @@ static_assert(MI3PT_ENV_WIDTH == pt::ENV_W && MI3PT_ENV_HEIGHT == pt::ENV_H, "th
 static const int SERVICE_SLOTS = 8;
 static size_t service_slot_bytes() { return (pt::service_block_bytes() + 255) / 256 * 256; }
 
-
-static int require_ctx(mi3pt_ctx *ctx)
+int require_ctx(mi3pt_ctx *ctx)
 {
     if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
     hipError_t e = hipSetDevice(ctx->device);
@@ -48,60 +51,7 @@ static int require_ctx(mi3pt_ctx *ctx)
     return MI3PT_OK;
 }
 
-static int require_idle(mi3pt_ctx *ctx);      // require_ctx + flush of the deferred frame queue (below)
-
-// ---- device groups (mi3pt_create_group; implementation at the end of this file).  A group handle is an mi3pt_ctx whose
-// `group` member is set: every entry point below first hands such a handle to its group_* counterpart.
-struct GroupState;
-#define PT_GROUP(ctx, call) do { if ((ctx) && (ctx)->group) return (call); } while (0)
-static mi3pt_ctx *group_member0(mi3pt_ctx *g);
-static int group_destroy(mi3pt_ctx *g);
-static int group_resize(mi3pt_ctx *g, int width, int height);
-static int group_reset(mi3pt_ctx *g);
-static int group_set_uniforms(mi3pt_ctx *g, int pass, const void *bytes, size_t nbytes);
-static int group_submit_frames(mi3pt_ctx *g, unsigned pass_mask, uint32_t count);
-static int group_flush(mi3pt_ctx *g);
-static int group_sync(mi3pt_ctx *g);
-static int group_read_texture(mi3pt_ctx *g, int which, float *dst, size_t nfloats);
-static int group_write_texture(mi3pt_ctx *g, int which, const float *src, size_t nfloats);
-static int group_read_canvas(mi3pt_ctx *g, uint8_t *dst, size_t nbytes);
-static int group_accumulation_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes);
-static int group_pass_time(mi3pt_ctx *g, int pass, float *us);
-static int group_launch_stats(mi3pt_ctx *g, int reset, double *total_ms, uint64_t *launches, uint64_t *frames);
-static int group_launch_span(mi3pt_ctx *g, double *span_ms);
-static int group_counters(mi3pt_ctx *g, uint64_t *out);
-static int group_render_aovs(mi3pt_ctx *g, unsigned aov_mask);
-static int group_read_aov(mi3pt_ctx *g, int which, void *dst, size_t nbytes);
-static int group_aov_ptr(mi3pt_ctx *g, int which, void **dev_ptr, size_t *nbytes);
-static int group_set_moments(mi3pt_ctx *g, int enabled);
-static int group_read_moments(mi3pt_ctx *g, void *dst, size_t nbytes);
-static int group_moments_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes);
-static int group_read_convergence(mi3pt_ctx *g, mi3pt_convergence *out);
-static int group_read_convergence_tiles(mi3pt_ctx *g, float *dst, size_t nfloats);
-static int group_set_sample_mask(mi3pt_ctx *g, const uint8_t *tiles, size_t ntiles);
-static int group_read_sample_mask(mi3pt_ctx *g, uint8_t *dst, size_t ntiles, uint32_t *sampled_out);
-static int group_freeze_converged(mi3pt_ctx *g, int guard, uint32_t *sampled_out);
-static void drop_sample_mask(mi3pt_ctx *ctx);
-static int group_unsupported(const char *what);
-static int group_set_option(mi3pt_ctx *g, int option, int value);
-// one call applied to every member (and, where marked, to the presenting context too)
-#define PT_GROUP_ALL(ctx, with_present, ...)                                                                              \
-    do {                                                                                                                  \
-        if ((ctx) && (ctx)->group) {                                                                                      \
-            auto fn_ = [&](mi3pt_ctx *m) -> int { return __VA_ARGS__; };                                                  \
-            return group_each((ctx), (with_present), fn_);                                                                \
-        }                                                                                                                 \
-    } while (0)
-template <class F> static int group_each(mi3pt_ctx *g, bool with_present, F fn);
-static int batch_limit(const mi3pt_ctx *ctx, int nranks);
 static int flush_pending(mi3pt_ctx *ctx);
-static int cost_order_collect(mi3pt_ctx *ctx, bool wait);
-static int settle_canvas(mi3pt_ctx *ctx);
-static int check_scene(const mi3pt_ctx *ctx);
-static int prepare_layout(mi3pt_ctx *ctx);
-static int prepare_cull(mi3pt_ctx *ctx);
-static int pick_variant(const mi3pt_ctx *ctx);
-
 extern "C" int mi3pt_abi_version(void) { return MI3PT_ABI_VERSION; }
 extern "C" const char *mi3pt_last_error(void) { return g_last_error.c_str(); }
 
@@ -227,7 +177,7 @@ static bool gate_release_from_host(mi3pt_ctx *ctx, const GateView &seen, const c
     return true;
 }
 
-static hipError_t ctx_wait(mi3pt_ctx *ctx, hipStream_t s, hipEvent_t ev, const char *why)
+hipError_t ctx_wait(mi3pt_ctx *ctx, hipStream_t s, hipEvent_t ev, const char *why)
 {
     if (!(ctx->gate_enabled && ctx->d_drain_flag && ctx->launch_seq != 0 && ctx->gate_timeout_ms > 0))
         return ev ? hipEventSynchronize(ev) : hipStreamSynchronize(s);
@@ -267,7 +217,6 @@ static hipError_t ctx_wait(mi3pt_ctx *ctx, hipStream_t s, hipEvent_t ev, const c
         else std::this_thread::sleep_for(std::chrono::microseconds(spins < 4096 ? 50 : 500));
     }
 }
-static hipError_t ctx_stream_sync(mi3pt_ctx *ctx, hipStream_t s, const char *why = "stream wait") { return ctx_wait(ctx, s, nullptr, why); }
 static hipError_t ctx_event_sync(mi3pt_ctx *ctx, hipEvent_t ev, const char *why = "event wait") { return ctx_wait(ctx, nullptr, ev, why); }
 
 int PassTimer::elapsed_us(mi3pt_ctx *ctx, float *us, const char *not_timed)
@@ -280,13 +229,9 @@ int PassTimer::elapsed_us(mi3pt_ctx *ctx, float *us, const char *not_timed)
     return MI3PT_OK;
 }
 
-// ---- image planes: the local_rows x width images of a context (radiance, mean, feature images, filter images, moments) ----
-static size_t plane_texels(const mi3pt_ctx *ctx) { return (size_t)ctx->local_rows * ctx->width; }
-static size_t plane_bytes(const mi3pt_ctx *ctx) { return plane_texels(ctx) * 16; }
-
 // Blocking copies between device memory on the context's stream and (pageable) host memory.  Such a copy blocks the host until the
 // stream gets there: the bounded wait comes first.  Nothing to copy: the stream is not touched.
-static hipError_t read_plane(mi3pt_ctx *ctx, const void *src, size_t nbytes, void *dst)
+hipError_t read_plane(mi3pt_ctx *ctx, const void *src, size_t nbytes, void *dst)
 {
     if (nbytes == 0) return hipSuccess;
     hipError_t e = ctx_stream_sync(ctx, ctx->stream, "read-back");
@@ -510,6 +455,14 @@ extern "C" int mi3pt_set_kernel_variant(mi3pt_ctx *ctx, int variant)
     return MI3PT_OK;
 }
 
+// Frames one launch may cover for this context's tile (before the memory cap of mi3pt_resize).
+static int batch_limit(const mi3pt_ctx *ctx, int nranks)
+{
+    long b = (long)ctx->batch_max * (nranks > 1 ? nranks : 1);
+    if (ctx->batch_max <= 1) b = 1;
+    return (int)(b > ctx->batch_limit_frames ? ctx->batch_limit_frames : b);
+}
+
 static void recompute_batch_cap(mi3pt_ctx *ctx)
 {
     if (ctx->width == 0) return;
@@ -601,8 +554,6 @@ extern "C" int mi3pt_debug_set_option(mi3pt_ctx *ctx, int option, int value)
     return MI3PT_OK;
 }
 
-static int group_get_option(mi3pt_ctx *g, int option, int *value);
-
 extern "C" int mi3pt_debug_get_option(mi3pt_ctx *ctx, int option, int *value)
 {
     PT_GROUP(ctx, group_get_option(ctx, option, value));
@@ -643,31 +594,6 @@ extern "C" int mi3pt_debug_get_option(mi3pt_ctx *ctx, int option, int *value)
     default:
         return pt_set_error(MI3PT_ERR_INVALID, "unknown option");
     }
-    return MI3PT_OK;
-}
-
-// Which kernel variant a raytrace submit would run right now (after the lazy scene analyses): the
-// selected one, or what it falls back to when the scene does not admit it.
-extern "C" int mi3pt_debug_active_variant(mi3pt_ctx *ctx, int *variant)
-{
-    PT_GROUP(ctx, mi3pt_debug_active_variant(group_member0(ctx), variant));
-    if (!ctx || !variant) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = require_idle(ctx)) return rc;
-    if (int rc = check_scene(ctx)) return rc;
-    if (int rc = prepare_layout(ctx)) return rc;
-    if (int rc = prepare_cull(ctx)) return rc;
-    *variant = pick_variant(ctx);
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_debug_last_launch(mi3pt_ctx *ctx, int *kind, int *variant, int *lean, int *workgroups)
-{
-    PT_GROUP(ctx, mi3pt_debug_last_launch(group_member0(ctx), kind, variant, lean, workgroups));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    if (kind) *kind = ctx->last_route.kind;
-    if (variant) *variant = ctx->last_route.variant;
-    if (lean) *lean = ctx->last_route.lean ? 1 : 0;
-    if (workgroups) *workgroups = ctx->last_route.blocks;
     return MI3PT_OK;
 }
 
@@ -757,7 +683,6 @@ extern "C" int mi3pt_upload_materials(mi3pt_ctx *ctx, const void *bytes, size_t 
     ctx->nmats = nbytes / MI3PT_MATERIAL_STRIDE;
     return MI3PT_OK;
 }
-
 
 extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes)
 {
@@ -865,14 +790,6 @@ static void drop_sample_mask(mi3pt_ctx *ctx)
     ctx->mask_sampled = 0;
 }
 
-// Frames one launch may cover for this context's tile (before the memory cap of mi3pt_resize).
-static int batch_limit(const mi3pt_ctx *ctx, int nranks)
-{
-    long b = (long)ctx->batch_max * (nranks > 1 ? nranks : 1);
-    if (ctx->batch_max <= 1) b = 1;
-    return (int)(b > ctx->batch_limit_frames ? ctx->batch_limit_frames : b);
-}
-
 extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
 {
     PT_GROUP(ctx, group_resize(ctx, width, height));
@@ -952,7 +869,7 @@ extern "C" int mi3pt_set_uniforms(mi3pt_ctx *ctx, int pass, const void *bytes, s
     }
 }
 
-static pt::SceneRefs scene_refs(const mi3pt_ctx *ctx)
+pt::SceneRefs scene_refs(const mi3pt_ctx *ctx)
 {
     pt::SceneRefs s;
     s.tris = (ctx->layout_active ? ctx->d_tris_perm : ctx->d_tris).as<const float4>();
@@ -988,7 +905,7 @@ static pt::SceneRefs scene_refs(const mi3pt_ctx *ctx)
 
 // The scene is complete when the three buffers agree with each other.  An empty
 // scene (no BVH uploaded) is legal: every ray misses (raytrace.wgsl:206-207).
-static int check_scene(const mi3pt_ctx *ctx)
+int check_scene(const mi3pt_ctx *ctx)
 {
     if (ctx->nnodes == 0) return MI3PT_OK;
     if (ctx->max_tri_ref >= (int64_t)ctx->ntris)
@@ -1006,7 +923,7 @@ static int check_scene(const mi3pt_ctx *ctx)
 // (tests/test_gpu_parity.py::test_depth_first_relabelling_is_bit_identical).  Applied lazily
 // because it needs both uploads; needs a proper tree (tree_proper).  The distance-culling walk
 // is not offered in this layout (variant 0 / 9 run 7).
-static int prepare_layout(mi3pt_ctx *ctx)
+int prepare_layout(mi3pt_ctx *ctx)
 {
     if (!ctx->layout_dirty) return MI3PT_OK;
     if (ctx->layout == 0 || ctx->nnodes == 0 || ctx->ntris == 0 || !ctx->tree_proper || ctx->max_tri_ref >= (int64_t)ctx->ntris)
@@ -1083,7 +1000,7 @@ extern "C" int mi3pt_debug_set_packet_layout(mi3pt_ctx *ctx, int layout)
 
 // The lazy scene analysis behind the culling walks (kernel variants 9 .. 14): pt::compile_walk (pt_host_compile.cpp) on the device's own
 // copies of the tree and the vertices; runs when the triangles, the tree or an option that shapes the packets changed.
-static int prepare_cull(mi3pt_ctx *ctx)
+int prepare_cull(mi3pt_ctx *ctx)
 {
     if (!ctx->cull_dirty) return MI3PT_OK;
     const bool wanted = (ctx->variant >= 9 && ctx->variant <= 14) || (ctx->variant == 0 && ctx->cull_enabled);
@@ -1209,8 +1126,6 @@ static int pick_variant(const mi3pt_ctx *ctx)
     if ((ctx->variant == 7 || ctx->variant == 8) && !defer_ok) return ctx->variant == 8 ? 6 : 4;
     return ctx->variant;
 }
-// the walk the probe runs: 1 = uploaded records, 2 = packets, 3 = packets + prepared-reciprocal slab test
-static int pick_walk(const mi3pt_ctx *ctx) { return ctx->variant == 0 ? 3 : (ctx->variant >= 4 ? 3 : (ctx->variant == 3 ? 2 : ctx->variant)); }
 
 static pt::AccUniforms acc_uniforms(const mi3pt_ctx *ctx)
 {
@@ -1817,7 +1732,7 @@ static int flush_pending(mi3pt_ctx *ctx)
 }
 
 // Every entry point that observes or changes device state goes through this.
-static int require_idle(mi3pt_ctx *ctx)
+int require_idle(mi3pt_ctx *ctx)
 {
     if (int rc = require_ctx(ctx)) return rc;
     return flush_pending(ctx);
@@ -2131,7 +2046,7 @@ extern "C" int mi3pt_bind_accumulation(mi3pt_ctx *ctx, void *dev_ptr, size_t nby
 // ---- first-hit feature images (include/mi3pt.h: mi3pt_aov, mi3pt_render_aovs) ----
 // Whether a first-hit pass walks the shipped walk's data (walk 13) -- after prepare_layout and prepare_cull: asked by mi3pt_render_aovs and
 // by the probe of that walk, mi3pt_debug_intersect_shipped.
-static bool first_hit_walk_is_shipped(const mi3pt_ctx *ctx)
+bool first_hit_walk_is_shipped(const mi3pt_ctx *ctx)
 {
     return !ctx->env_sampling && !ctx->layout_active && ctx->cull_enabled && ctx->wide_enabled && ctx->cull_stack_ok &&
            ctx->cull_ok && !ctx->cull_dirty && ctx->wide_ok && ctx->cwide_ok && ctx->d_leaf_rank;
@@ -2676,8 +2591,6 @@ extern "C" int mi3pt_merge_history(mi3pt_ctx *ctx, const mi3pt_history_params *p
 }
 
 // ---- the per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip) ----
-static size_t conv_tiles_x(const mi3pt_ctx *ctx) { return ((size_t)ctx->width + 7) / 8; }
-static size_t conv_tiles_y(const mi3pt_ctx *ctx) { return ((size_t)ctx->local_rows + 7) / 8; }
 
 extern "C" int mi3pt_estimate_convergence(mi3pt_ctx *ctx, float threshold, int min_frames)
 {
@@ -2910,99 +2823,28 @@ extern "C" int mi3pt_reset_counters(mi3pt_ctx *ctx)
     return MI3PT_OK;
 }
 
-// Diagnostic: per-wave begin / feed-empty / end stamps of the last persistent raytrace
-// launch.  out == NULL enables (allocates) or, with capacity 0 and enable 0, disables it.
-extern "C" int mi3pt_debug_wave_times(mi3pt_ctx *ctx, int enable, uint64_t *out, size_t capacity_slots,
-                                      size_t *slots_out)
+// Which kernel variant a raytrace submit would run right now (after the lazy scene analyses): the
+// selected one, or what it falls back to when the scene does not admit it.
+extern "C" int mi3pt_debug_active_variant(mi3pt_ctx *ctx, int *variant)
 {
-    PT_GROUP(ctx, mi3pt_debug_wave_times(group_member0(ctx), enable, out, capacity_slots, slots_out));
+    PT_GROUP(ctx, mi3pt_debug_active_variant(group_member0(ctx), variant));
+    if (!ctx || !variant) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = require_idle(ctx)) return rc;
-    const int slots = pt::PT_MAX_RESIDENT_WAVES;
-    if (!out) {
-        HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-        if (enable && !ctx->d_wave_times) {
-            HIP_TRY(ctx->d_wave_times.alloc((size_t)slots * 128));
-            HIP_TRY(hipMemset(ctx->d_wave_times, 0, (size_t)slots * 128));
-            ctx->wave_times_slots = slots;
-        } else if (!enable && ctx->d_wave_times) {
-            ctx->d_wave_times.reset();
-            ctx->wave_times_slots = 0;
-        }
-        return MI3PT_OK;
-    }
-    if (!ctx->d_wave_times) return pt_set_error(MI3PT_ERR_STATE, "wave times are not enabled");
-    if (capacity_slots < (size_t)ctx->wave_times_slots) return pt_set_error(MI3PT_ERR_INVALID, "buffer too small");
-    HIP_TRY(read_plane(ctx, ctx->d_wave_times, (size_t)ctx->wave_times_slots * 128, out));
-    if (slots_out) *slots_out = (size_t)ctx->wave_times_slots;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_debug_intersect(mi3pt_ctx *ctx, const float *rays, size_t n, float *out)
-{
-    PT_GROUP(ctx, mi3pt_debug_intersect(group_member0(ctx), rays, n, out));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!rays || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
     if (int rc = check_scene(ctx)) return rc;
-    if (n == 0) return MI3PT_OK;
-    DevBuf<float> d_rays, d_out;
-    HIP_TRY(d_rays.alloc(n * 24));
-    if (d_out.alloc(n * 48) != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, "hipMalloc failed");
-    hipError_t e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        pt::launch_debug_intersect(scene_refs(ctx), d_rays, n, d_out, pick_walk(ctx), ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
-    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_intersect: ") + hipGetErrorString(e));
-    return MI3PT_OK;
-}
-
-// the shipped first-hit walk (k_aov_cull's loop) on rays from memory; never another walk in its place
-extern "C" int mi3pt_debug_intersect_shipped(mi3pt_ctx *ctx, const float *rays, size_t n, float *out)
-{
-    PT_GROUP(ctx, mi3pt_debug_intersect_shipped(group_member0(ctx), rays, n, out));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!rays || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = check_scene(ctx)) return rc;
-    if (int rc = prepare_layout(ctx)) return rc;    // (what mi3pt_render_aovs does before it picks its walk)
+    if (int rc = prepare_layout(ctx)) return rc;
     if (int rc = prepare_cull(ctx)) return rc;
-    const pt::SceneRefs scene = scene_refs(ctx);
-    if (!first_hit_walk_is_shipped(ctx) || !scene.cwide || !scene.tripk64 || !scene.leaf_rank)
-        return pt_set_error(MI3PT_ERR_STATE, "debug_intersect_shipped: mi3pt_render_aovs would not run the shipped first-hit walk on this scene / these options");
-    if (n == 0) return MI3PT_OK;
-    DevBuf<float> d_rays, d_out;
-    HIP_TRY(d_rays.alloc(n * 24));
-    if (d_out.alloc(n * 48) != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, "hipMalloc failed");
-    hipError_t e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        pt::launch_debug_intersect_cull(scene, d_rays, n, d_out, ctx->wide_stack_worst, ctx->leaf_min, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
-    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_intersect_shipped: ") + hipGetErrorString(e));
+    *variant = pick_variant(ctx);
     return MI3PT_OK;
 }
 
-extern "C" int mi3pt_debug_pairs(mi3pt_ctx *ctx, int fn, const float *rays, const float *geom, float *out, size_t n)
+extern "C" int mi3pt_debug_last_launch(mi3pt_ctx *ctx, int *kind, int *variant, int *lean, int *workgroups)
 {
-    PT_GROUP(ctx, mi3pt_debug_pairs(group_member0(ctx), fn, rays, geom, out, n));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!rays || !geom || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (fn != 0 && fn != 1) return pt_set_error(MI3PT_ERR_INVALID, "debug_pairs: fn must be 0 (box) or 1 (triangle)");
-    if (n == 0) return MI3PT_OK;
-    const size_t G = fn == 0 ? 7 : 9;
-    DevBuf<float> d_rays, d_geom, d_out;
-    hipError_t e = d_rays.alloc(n * 24);
-    if (e == hipSuccess) e = d_geom.alloc(n * G * 4);
-    if (e == hipSuccess) e = d_out.alloc(n * 48);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_geom, geom, n * G * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        pt::launch_debug_pairs(fn, d_rays, d_geom, d_out, n, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = read_plane(ctx, d_out, n * 48, out);
-    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_pairs: ") + hipGetErrorString(e));
+    PT_GROUP(ctx, mi3pt_debug_last_launch(group_member0(ctx), kind, variant, lean, workgroups));
+    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
+    if (kind) *kind = ctx->last_route.kind;
+    if (variant) *variant = ctx->last_route.variant;
+    if (lean) *lean = ctx->last_route.lean ? 1 : 0;
+    if (workgroups) *workgroups = ctx->last_route.blocks;
     return MI3PT_OK;
 }
 
@@ -3076,770 +2918,5 @@ extern "C" int mi3pt_device_refit_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t no
     if (pt::refit_bvh(ctx->d_tris, ctx->ntris, ctx->d_nodes, ctx->nnodes, nodes_out, refit_ms, ctx->stream, err) != 0)
         return pt_set_error(MI3PT_ERR_HIP, "device BVH refit: " + err);
     *nnodes_out = ctx->nnodes;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_debug_math(mi3pt_ctx *ctx, int fn, const float *a, const float *b, float *out, size_t n)
-{
-    PT_GROUP(ctx, mi3pt_debug_math(group_member0(ctx), fn, a, b, out, n));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!a || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (n == 0) return MI3PT_OK;
-    DevBuf<float> d_a, d_b, d_o;
-    hipError_t e = d_a.alloc(n * 4);
-    if (e == hipSuccess) e = d_o.alloc(n * 4);
-    if (e == hipSuccess && b) e = d_b.alloc(n * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_a, a, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && b) e = hipMemcpyAsync(d_b, b, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        pt::launch_debug_math(fn, d_a, d_b, d_o, n, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = read_plane(ctx, d_o, n * 4, out);
-    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("debug_math: ") + hipGetErrorString(e));
-    return MI3PT_OK;
-}
-
-// =================================================================================================
-// Device groups: Renderer.create() over the GPUs of one node (the reference's seam is one adapter and
-// one device, renderer.ts:491-533, and one render() per frame, :366-395).
-//
-// A group handle behaves like a context: the same entry points, the same frame semantics, the same bits.  Behind it
-// stand one member context per listed device -- member i renders tile i of n (8-row blocks dealt round robin:
-// mi3pt_set_tile), the scene is replicated by every upload call, NOTHING is exchanged per frame -- and one
-// presenting context on the first device that holds the whole image.  The one exchange of a job is the GATHER: when
-// the accumulation image (or the canvas) is read, every member's HDR accumulation rows are copied into the presenting
-// context's image, de-interleaved on the way: one strided device-to-device copy per member (hipMemcpy2DAsync: peer
-// DMA over xGMI when the devices can reach each other, staged by the runtime otherwise), no host buffer, no
-// torch, no collective library -- a gather to one root is n - 1 point-to-point transfers on n - 1 distinct links.  The
-// fullscreen pass (the de-noise looks 6 rows up and down, so it cannot run per tile) runs on the gathered image; a
-// group therefore always presents lazily -- a FULLSCREEN submit is remembered and performed when the canvas is read
-// (MI3PT_PRESENT_LATEST; drawing the canvas from every frame would put a gather into every frame).
-// A group may list one device several times (tests: two members on the one GPU of the box).
-// =================================================================================================
-struct GroupState {
-    std::vector<mi3pt_ctx *> members;
-    mi3pt_ctx *present = nullptr;
-    int block_rows = 8;
-    int width = 0, height = 0;
-    bool gathered = false;        // the presenting context holds the members' current accumulation images
-    bool want_present = false;    // a fullscreen pass has been submitted since the canvas was last drawn
-    // The scene lives in member 0: uploads and the host-side analyses (packets, leaf ranks, the cull analysis) happen there once;
-    // the other members receive device-to-device copies of the finished buffers (group_sync_scene).
-    uint64_t cloned_epoch = 0;    // member 0's scene_epoch the other members' copies were made from
-    // Can the presenting device's copy engines address member i's memory directly?  (same device, or peer access enabled and
-    // confirmed at create).  Where not -- or after a direct gather failed -- the gather is staged through pinned host memory.
-    std::vector<char> peer_direct;
-    PinnedBuf<void> stage;        // pinned host buffer (allocated when first needed)
-    // first-hit feature images: which the members hold (rendered since the last resize), and which of those the presenting
-    // context's whole image is a current copy of
-    bool aov_rendered[MI3PT_AOV_COUNT] = {}, aov_gathered[MI3PT_AOV_COUNT] = {};
-};
-
-template <class F>
-static int group_each(mi3pt_ctx *g, bool with_present, F fn)
-{
-    for (mi3pt_ctx *m : g->group->members)
-        if (int rc = fn(m)) return rc;
-    if (with_present)
-        if (int rc = fn(g->group->present)) return rc;
-    return MI3PT_OK;
-}
-
-static mi3pt_ctx *group_member0(mi3pt_ctx *g) { return g->group->members[0]; }
-static int group_unsupported(const char *what) { return pt_set_error(MI3PT_ERR_STATE, what); }
-
-extern "C" int mi3pt_create_group(const int *devices, int ndevices, int block_rows, mi3pt_ctx **out_ctx)
-{
-    if (!devices || !out_ctx || ndevices < 1 || ndevices > 64) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_create_group: 1..64 devices");
-    if (block_rows < 1 || block_rows > 4096) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_create_group: block_rows must be in [1, 4096]");
-    *out_ctx = nullptr;
-    mi3pt_ctx *g = new (std::nothrow) mi3pt_ctx();
-    GroupState *gs = new (std::nothrow) GroupState();
-    if (!g || !gs) { delete g; delete gs; return pt_set_error(MI3PT_ERR_HIP, "out of host memory"); }
-    g->group = gs;
-    g->device = devices[0];
-    gs->block_rows = block_rows;
-    int rc = MI3PT_OK;
-    for (int i = 0; i < ndevices && rc == MI3PT_OK; i++) {
-        mi3pt_ctx *m = nullptr;
-        rc = mi3pt_create(devices[i], &m);
-        if (rc == MI3PT_OK) {
-            gs->members.push_back(m);
-            rc = mi3pt_set_tile(m, i, ndevices, block_rows);
-        }
-    }
-    if (rc == MI3PT_OK) rc = mi3pt_create(devices[0], &gs->present);
-    if (rc == MI3PT_OK) rc = mi3pt_set_present_mode(gs->present, MI3PT_PRESENT_EXACT);
-    if (rc == MI3PT_OK) {
-        // Let the first device's copy engines reach the others' memory -- and RECORD whether they can (round-3 advice: the return
-        // codes were dropped, so the gather could not tell a legal device-to-device rect copy from one that fails asynchronously).
-        gs->peer_direct.assign((size_t)ndevices, 0);
-        const bool on0 = hipSetDevice(devices[0]) == hipSuccess;
-        for (int i = 0; i < ndevices; i++) {
-            if (devices[i] == devices[0]) { gs->peer_direct[(size_t)i] = 1; continue; }
-            int can = 0;
-            if (!on0 || hipDeviceCanAccessPeer(&can, devices[0], devices[i]) != hipSuccess || !can) { (void)hipGetLastError(); continue; }
-            const hipError_t e = hipDeviceEnablePeerAccess(devices[i], 0);
-            if (e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled) gs->peer_direct[(size_t)i] = 1;
-            (void)hipGetLastError();
-        }
-        *out_ctx = g;
-        return MI3PT_OK;
-    }
-    const std::string msg = g_last_error;
-    group_destroy(g);
-    return pt_set_error(rc, msg);
-}
-
-extern "C" int mi3pt_group_size(mi3pt_ctx *ctx, int *members)
-{
-    if (!ctx || !members) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    *members = ctx->group ? (int)ctx->group->members.size() : 1;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_group_member(mi3pt_ctx *ctx, int index, mi3pt_ctx **member)
-{
-    if (!ctx || !member) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (!ctx->group) { if (index != 0) return pt_set_error(MI3PT_ERR_INVALID, "not a group: the only member is index 0"); *member = ctx; return MI3PT_OK; }
-    if (index == -1) { *member = ctx->group->present; return MI3PT_OK; }
-    if (index < 0 || (size_t)index >= ctx->group->members.size()) return pt_set_error(MI3PT_ERR_INVALID, "member index out of range");
-    *member = ctx->group->members[(size_t)index];
-    return MI3PT_OK;
-}
-
-static int group_destroy(mi3pt_ctx *g)
-{
-    GroupState *gs = g->group;
-    int rc = MI3PT_OK;
-    for (mi3pt_ctx *m : gs->members)
-        if (m) { const int r = mi3pt_destroy(m); if (r && !rc) rc = r; }
-    if (gs->present) { const int r = mi3pt_destroy(gs->present); if (r && !rc) rc = r; }
-    delete gs;
-    g->group = nullptr;
-    delete g;
-    return rc;
-}
-
-static int group_resize(mi3pt_ctx *g, int width, int height)
-{
-    GroupState *gs = g->group;
-    gs->width = gs->height = 0;
-    for (int k = 0; k < MI3PT_AOV_COUNT; k++) gs->aov_rendered[k] = gs->aov_gathered[k] = false;
-    gs->present->moments = false;      // (its resize frees the gathered moments image and must not allocate one of its own: group_gather_moments)
-    if (int rc = group_each(g, true, [&](mi3pt_ctx *m) { return mi3pt_resize(m, width, height); })) return rc;
-    gs->width = width;
-    gs->height = height;
-    g->width = width; g->height = height;
-    gs->gathered = true;          // every image is zero
-    gs->want_present = false;
-    for (int k = 0; k < MI3PT_AOV_COUNT; k++) gs->aov_rendered[k] = gs->aov_gathered[k] = false;
-    return MI3PT_OK;
-}
-
-static int group_reset(mi3pt_ctx *g)
-{
-    GroupState *gs = g->group;
-    if (int rc = group_each(g, true, [&](mi3pt_ctx *m) { return mi3pt_reset(m); })) return rc;
-    gs->gathered = true;
-    gs->want_present = false;
-    return MI3PT_OK;
-}
-
-static int group_set_uniforms(mi3pt_ctx *g, int pass, const void *bytes, size_t nbytes)
-{
-    if (pass == MI3PT_PASS_FULLSCREEN) return mi3pt_set_uniforms(g->group->present, pass, bytes, nbytes);
-    return group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_set_uniforms(m, pass, bytes, nbytes); });
-}
-
-// image row of local row `ly` of member i of n (mi3pt_set_tile's deal: rounds go back and forth)
-static size_t group_global_row(int ly, int i, int n, int br)
-{
-    const int b = ly / br;
-    return ((size_t)b * (size_t)n + (size_t)((b & 1) ? n - 1 - i : i)) * (size_t)br + (size_t)(ly % br);
-}
-
-// One scene buffer of `src` replicated into `dst` (another member, maybe another device): device to device, on dst's stream.
-static int clone_buffer(mi3pt_ctx *dst, DevBuf<void> &dbuf, const mi3pt_ctx *src, const DevBuf<void> &sbuf)
-{
-    dbuf.reset();
-    if (!sbuf) return MI3PT_OK;
-    HIP_TRY(dbuf.alloc(sbuf.bytes));
-    if (sbuf.bytes) HIP_TRY(hipMemcpyPeerAsync(dbuf, dst->device, sbuf, src->device, sbuf.bytes, dst->stream));
-    return MI3PT_OK;
-}
-
-// Everything mi3pt_upload_* and the scene analyses leave in a context, copied from `src` (a group's member 0) to `dst`.
-static int clone_scene(mi3pt_ctx *dst, const mi3pt_ctx *src)
-{
-    if (int rc = require_idle(dst)) return rc;
-    HIP_TRY(ctx_stream_sync(dst, dst->stream));
-    for (int k = 0; k < 2; k++) HIP_TRY(ctx_stream_sync(dst, dst->rt_stream[k]));
-    const auto from = SceneBuffers::all(*src);
-    const auto to = SceneBuffers::all(*dst);
-    for (size_t k = 0; k < from.size(); k++)
-        if (int rc = clone_buffer(dst, *to[k], src, *from[k])) return rc;
-    const size_t env_bytes = (size_t)MI3PT_ENV_WIDTH * MI3PT_ENV_HEIGHT * 16;
-    HIP_TRY(hipMemcpyPeerAsync(dst->d_env, dst->device, src->d_env, src->device, env_bytes, dst->stream));
-    HIP_TRY(hipMemcpyPeerAsync(dst->d_cdf, dst->device, src->d_cdf, src->device, env_bytes, dst->stream));
-    HIP_TRY(ctx_stream_sync(dst, dst->stream));
-    dst->scene_facts() = src->scene_facts();
-    // what does not come from `src`: the copy's own caches are of another scene, its streams have new work to order, its scene has a new version.
-    // (Nor do the options -- cull_enabled, wide_enabled, collapse, packet_order: set on every member -- the kept geometry and host_analyses.)
-    dst->cost_state = 0;
-    dst->sky_host_valid = false;
-    dst->main_dirty = true;
-    dst->scene_epoch++;
-    return MI3PT_OK;
-}
-
-// Before anything traces rays: member 0 compiles the scene (the host-side analyses run ONCE per scene change, whatever the
-// number of members -- round-3 verdict: config 5 on eight GPUs was eight uploads, eight 1.4 GB read-backs and eight analyses),
-// the other members get device copies.
-static int group_sync_scene(mi3pt_ctx *g)
-{
-    GroupState *gs = g->group;
-    mi3pt_ctx *m0 = gs->members[0];
-    if (int rc = require_ctx(m0)) return rc;
-    if (int rc = check_scene(m0)) return rc;
-    if (int rc = prepare_layout(m0)) return rc;
-    if (int rc = prepare_cull(m0)) return rc;
-    if (m0->scene_epoch == gs->cloned_epoch) return MI3PT_OK;
-    for (size_t i = 1; i < gs->members.size(); i++)
-        if (int rc = clone_scene(gs->members[i], m0)) return rc;
-    gs->cloned_epoch = m0->scene_epoch;
-    return MI3PT_OK;
-}
-
-static int group_submit_frames(mi3pt_ctx *g, unsigned pass_mask, uint32_t count)
-{
-    GroupState *gs = g->group;
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "submit before resize");
-    const unsigned sample = pass_mask & (MI3PT_SUBMIT_RAYTRACE | MI3PT_SUBMIT_ACCUMULATE);
-    if (pass_mask & MI3PT_SUBMIT_RAYTRACE)
-        if (int rc = group_sync_scene(g)) return rc;
-    if (sample) {
-        if (int rc = group_each(g, false, [&](mi3pt_ctx *m) { return count == 1 ? mi3pt_submit(m, sample) : mi3pt_submit_frames(m, sample, count); })) return rc;
-        if (sample & MI3PT_SUBMIT_ACCUMULATE) gs->gathered = false;
-    }
-    if (pass_mask & MI3PT_SUBMIT_FULLSCREEN) gs->want_present = true;      // performed when the canvas is read (see the header of this section)
-    return MI3PT_OK;
-}
-
-static int group_flush(mi3pt_ctx *g) { return group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_flush(m); }); }
-
-static int group_sync(mi3pt_ctx *g)
-{
-    // launch everything that is queued on every member first, THEN wait: the members run side by side
-    if (int rc = group_flush(g)) return rc;
-    return group_each(g, true, [&](mi3pt_ctx *m) { return mi3pt_sync(m); });
-}
-
-// The one exchange: members' accumulation rows -> the presenting context's whole image.
-// Member i's rows, de-interleaved into the whole image.  direct: one strided device-to-device copy (the de-interleave is the copy's
-// geometry: source pitch = one block, destination pitch = n blocks) on the presenting context's stream -- peer DMA over xGMI.
-// Otherwise: staged through pinned host memory (a device-to-host copy on the member's device, then the same strided copy from
-// the host buffer).
-// (member_plane: the member's rows of the image gathered; whole_plane: that image on the presenting context)
-static int gather_member(GroupState *gs, int i, bool direct, const float4 *member_plane, float4 *whole_plane)
-{
-    mi3pt_ctx *p = gs->present;
-    const mi3pt_ctx *m = gs->members[(size_t)i];
-    const int n = (int)gs->members.size(), br = gs->block_rows, W = gs->width, H = gs->height;
-    const size_t row_bytes = (size_t)W * 16, block_bytes = row_bytes * (size_t)br;
-    uint8_t *dst = reinterpret_cast<uint8_t *>(whole_plane);
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(member_plane);
-    const int rows = m->local_rows;
-    if (rows == 0) return MI3PT_OK;
-    const int full = rows / br, tail = rows - full * br;      // whole blocks, rows of a last partial block (the image's bottom edge)
-    const size_t grow = group_global_row(full * br, i, n, br);      // global row of the partial block
-    if (tail > 0 && (int)grow + tail > H) return pt_set_error(MI3PT_ERR_STATE, "gather: tile geometry mismatch");
-    hipMemcpyKind kind = hipMemcpyDeviceToDevice;
-    if (!direct) {
-        const size_t need = (size_t)rows * row_bytes;
-        if (gs->stage.bytes < need) HIP_TRY(gs->stage.alloc(need));
-        HIP_TRY(hipSetDevice(m->device));
-        HIP_TRY(hipMemcpy(gs->stage, src, need, hipMemcpyDeviceToHost));      // (synchronous: the one staging buffer is reused member by member)
-        HIP_TRY(hipSetDevice(p->device));
-        src = gs->stage.as<const uint8_t>();
-        kind = hipMemcpyHostToDevice;
-    }
-    // The deal goes back and forth: the member's even local blocks sit at image block (2 k n + i), its odd ones at
-    // ((2 k + 1) n + n - 1 - i) -- two strided sets, each ONE rect copy (source pitch = two blocks, destination pitch = 2 n blocks)
-    const int n_even = (full + 1) / 2, n_odd = full / 2;
-    if (n_even > 0)
-        HIP_TRY(hipMemcpy2DAsync(dst + (size_t)i * block_bytes, 2 * (size_t)n * block_bytes, src, 2 * block_bytes, block_bytes, (size_t)n_even, kind, p->stream));
-    if (n_odd > 0)
-        HIP_TRY(hipMemcpy2DAsync(dst + (size_t)(n + n - 1 - i) * block_bytes, 2 * (size_t)n * block_bytes, src + block_bytes, 2 * block_bytes, block_bytes, (size_t)n_odd, kind, p->stream));
-    if (tail > 0)
-        HIP_TRY(hipMemcpyAsync(dst + grow * row_bytes, src + (size_t)full * block_bytes, (size_t)tail * row_bytes, kind, p->stream));
-    if (!direct) HIP_TRY(ctx_stream_sync(p, p->stream));       // the staging buffer is free again
-    return MI3PT_OK;
-}
-
-// the copies of a gather (the members' work has been waited for); plane(ctx): the image gathered, as that context holds it
-template <class Plane> static int gather_copies(GroupState *gs, Plane plane)
-{
-    mi3pt_ctx *p = gs->present;
-    const int n = (int)gs->members.size();
-    for (int attempt = 0; attempt < 2; attempt++) {
-        // direct copies first, all in flight together on the presenting stream (n - 1 transfers on n - 1 links into one root) ...
-        for (int i = 0; i < n; i++) {
-            if (!gs->peer_direct[(size_t)i]) continue;
-            if (gather_member(gs, i, true, plane(gs->members[(size_t)i]), plane(p)) != MI3PT_OK) { (void)hipGetLastError(); gs->peer_direct[(size_t)i] = 0; }
-        }
-        if (ctx_stream_sync(p, p->stream) == hipSuccess) break;
-        // ... a rect copy between two devices can also fail asynchronously (round-3 advice): nothing this pass wrote is trusted;
-        // every member on another device goes through the host from now on, and the gather is done again, once
-        (void)hipGetLastError();
-        bool any = false;
-        for (int i = 0; i < n; i++)
-            if (gs->members[(size_t)i]->device != p->device && gs->peer_direct[(size_t)i]) { gs->peer_direct[(size_t)i] = 0; any = true; }
-        if (!any || attempt == 1) return pt_set_error(MI3PT_ERR_HIP, "group gather: the copies into the presenting context failed");
-    }
-    // ... then whatever cannot be addressed directly, staged through pinned host memory
-    for (int i = 0; i < n; i++)
-        if (!gs->peer_direct[(size_t)i])
-            if (int rc = gather_member(gs, i, false, plane(gs->members[(size_t)i]), plane(p))) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(ctx_stream_sync(p, p->stream));
-    return MI3PT_OK;
-}
-
-// A whole image the presenting context allocates when it is first gathered (a feature image, the moments image) and frees with its
-// textures.  wait_for_members: the members' work that writes the image, then the presenting context ready for the copies.
-template <class Plane, class Wait> static int gather_lazy_image(GroupState *gs, Plane plane, Wait wait_for_members)
-{
-    if (int rc = wait_for_members()) return rc;
-    mi3pt_ctx *p = gs->present;
-    if (!plane(p)) HIP_TRY(plane(p).alloc(plane_bytes(p)));
-    return gather_copies(gs, plane);
-}
-
-static int group_gather(mi3pt_ctx *g)
-{
-    GroupState *gs = g->group;
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "read before resize");
-    if (gs->gathered) return MI3PT_OK;
-    if (int rc = group_sync(g)) return rc;
-    mi3pt_ctx *p = gs->present;
-    if (int rc = require_idle(p)) return rc;
-    if (int rc = gather_copies(gs, [](mi3pt_ctx *c) -> float4 *& { return c->d_accum; })) return rc;
-    p->output_is_accum = true;      // like the copy-back of accumulate.ts:171-175
-    p->main_dirty = true;
-    p->accum_version++;
-    gs->gathered = true;
-    return MI3PT_OK;
-}
-
-// ---- first-hit feature images of a group: rendered by every member for its rows, gathered when read ----
-static int group_render_aovs(mi3pt_ctx *g, unsigned aov_mask)
-{
-    GroupState *gs = g->group;
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_render_aovs before resize");
-    if (aov_mask == 0 || (aov_mask >> MI3PT_AOV_COUNT)) return pt_set_error(MI3PT_ERR_INVALID, "aov_mask must be a non-empty OR of (1u << mi3pt_aov)");
-    if (int rc = group_sync_scene(g)) return rc;
-    if (int rc = group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_render_aovs(m, aov_mask); })) return rc;
-    for (int k = 0; k < MI3PT_AOV_COUNT; k++)
-        if ((aov_mask >> k) & 1u) { gs->aov_rendered[k] = true; gs->aov_gathered[k] = false; }
-    return MI3PT_OK;
-}
-
-static int group_gather_aov(mi3pt_ctx *g, int which, const char *what)
-{
-    GroupState *gs = g->group;
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
-    if (which < 0 || which >= MI3PT_AOV_COUNT) return pt_set_error(MI3PT_ERR_INVALID, "unknown feature image");
-    if (!gs->aov_rendered[which])
-        return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": this image has not been rendered since the last resize (mi3pt_render_aovs)");
-    if (gs->aov_gathered[which]) return MI3PT_OK;
-    // the members' passes (their own streams; their frame queues stay as they are), then the copies
-    auto members_streams = [&]() -> int {
-        for (mi3pt_ctx *m : gs->members) {
-            if (int rc = require_ctx(m)) return rc;
-            HIP_TRY(ctx_stream_sync(m, m->stream));
-        }
-        return require_ctx(gs->present);
-    };
-    if (int rc = gather_lazy_image(gs, [which](mi3pt_ctx *c) -> DevBuf<float4> & { return c->d_aov[which]; }, members_streams)) return rc;
-    gs->present->aov_valid[which] = true;
-    gs->aov_gathered[which] = true;
-    return MI3PT_OK;
-}
-
-static int group_read_aov(mi3pt_ctx *g, int which, void *dst, size_t nbytes)
-{
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (g->group->width && which >= 0 && which < MI3PT_AOV_COUNT && g->group->aov_rendered[which] &&
-        nbytes != (size_t)g->group->width * g->group->height * 16)
-        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (a group reads whole images: height x width x 16 bytes)");
-    if (int rc = group_gather_aov(g, which, "mi3pt_read_aov")) return rc;
-    return mi3pt_read_aov(g->group->present, which, dst, nbytes);
-}
-
-static int group_aov_ptr(mi3pt_ctx *g, int which, void **dev_ptr, size_t *nbytes)
-{
-    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = group_gather_aov(g, which, "mi3pt_aov_device_ptr")) return rc;
-    return mi3pt_aov_device_ptr(g->group->present, which, dev_ptr, nbytes);
-}
-
-// ---- the moments image of a group: kept by every member for its rows; the presenting context's whole image is allocated by the first read
-// (like a feature image: group_gather_aov), freed by its resize (free_textures) and by mi3pt_set_moments(0), and gathered whenever it is read.
-// While it holds the gathered copy the presenting context counts as having moments enabled, so that its own mi3pt_read_moments and
-// mi3pt_moments_device_ptr serve the image; it never runs an accumulate pass, so it never keeps moments of its own ----
-static int group_set_moments(mi3pt_ctx *g, int enabled)
-{
-    if (int rc = group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_set_moments(m, enabled); })) return rc;
-    mi3pt_ctx *p = g->group->present;
-    if (!enabled && p->d_moments) {
-        if (int rc = require_ctx(p)) return rc;
-        HIP_TRY(ctx_stream_sync(p, p->stream));
-        p->d_moments.reset();
-    }
-    if (!enabled) p->moments = false;
-    return MI3PT_OK;
-}
-
-static int group_gather_moments(mi3pt_ctx *g, const char *what)
-{
-    GroupState *gs = g->group;
-    if (!gs->members[0]->moments) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": the moments image is not enabled (mi3pt_set_moments)");
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
-    auto everything = [&]() -> int {
-        if (int rc = group_sync(g)) return rc;
-        return require_idle(gs->present);
-    };
-    if (int rc = gather_lazy_image(gs, [](mi3pt_ctx *c) -> DevBuf<float4> & { return c->d_moments; }, everything)) return rc;
-    gs->present->moments = true;
-    return MI3PT_OK;
-}
-
-static int group_read_moments(mi3pt_ctx *g, void *dst, size_t nbytes)
-{
-    GroupState *gs = g->group;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    const size_t need = (size_t)gs->width * gs->height * 16;
-    if (gs->width && gs->members[0]->moments && nbytes != need)
-        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (a group reads whole images: height x width x 16 bytes)");
-    if (int rc = group_gather_moments(g, "mi3pt_read_moments")) return rc;
-    return mi3pt_read_moments(gs->present, dst, nbytes);
-}
-
-static int group_moments_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes)
-{
-    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = group_gather_moments(g, "mi3pt_moments_device_ptr")) return rc;
-    return mi3pt_moments_device_ptr(g->group->present, dev_ptr, nbytes);
-}
-
-// ---- the error estimate: mi3pt_estimate_convergence goes to every member (PT_GROUP_ALL); the summaries combine on the host -- counts add,
-// max of max, min of min -- and so do the tile maps, which are kilobytes: no peer copies ----
-static int group_read_convergence(mi3pt_ctx *g, mi3pt_convergence *out)
-{
-    if (!out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    mi3pt_convergence all = {};
-    bool first = true;
-    for (mi3pt_ctx *m : g->group->members) {
-        mi3pt_convergence c;
-        if (int rc = mi3pt_read_convergence(m, &c)) return rc;
-        all.tiles += c.tiles; all.tiles_above += c.tiles_above; all.tiles_young += c.tiles_young; all.tiles_nonfinite += c.tiles_nonfinite;
-        all.texels += c.texels;
-        all.worst_tile = fmaxf(all.worst_tile, c.worst_tile);
-        all.worst_texel = fmaxf(all.worst_texel, c.worst_texel);
-        if (c.tiles) {
-            all.n_min = first ? c.n_min : fminf(all.n_min, c.n_min);
-            first = false;
-        }
-        all.threshold = c.threshold;
-    }
-    *out = all;
-    return MI3PT_OK;
-}
-
-static int group_read_convergence_tiles(mi3pt_ctx *g, float *dst, size_t nfloats)
-{
-    GroupState *gs = g->group;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_convergence_tiles before resize");
-    if (gs->block_rows % 8)
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_convergence_tiles: the members' tiles only form the image's tile map when the group's block_rows is a multiple of 8 (read each member's map: mi3pt_group_member)");
-    for (mi3pt_ctx *m : gs->members)
-        if (!m->conv_valid) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_convergence_tiles: nothing has been estimated since the last resize (mi3pt_estimate_convergence)");
-    const size_t tiles_x = ((size_t)gs->width + 7) / 8, tiles_y = ((size_t)gs->height + 7) / 8;
-    if (nfloats != tiles_x * tiles_y * 4)
-        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the tile map (a group reads the whole map: ceil(height / 8) x ceil(width / 8) x 4 floats)");
-    const int n = (int)gs->members.size();
-    std::vector<float> part;
-    for (int i = 0; i < n; i++) {
-        mi3pt_ctx *m = gs->members[(size_t)i];
-        const size_t rows = conv_tiles_y(m);
-        part.resize(rows * tiles_x * 4);
-        if (rows == 0) continue;
-        if (int rc = mi3pt_read_convergence_tiles(m, part.data(), part.size())) return rc;
-        for (size_t t = 0; t < rows; t++) {
-            const size_t gt = (size_t)mi3pt_tile_global_row((int)t, i, n, gs->block_rows / 8);
-            if (gt >= tiles_y) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_convergence_tiles: a member's tile row lies outside the image");
-            std::memcpy(dst + gt * tiles_x * 4, part.data() + t * tiles_x * 4, tiles_x * 16);
-        }
-    }
-    return MI3PT_OK;
-}
-
-// ---- the sample mask: the whole image's map in and out, scattered to / assembled from the members' maps on the host by the row rule of
-// group_read_convergence_tiles; the freeze rule runs on the WHOLE map, so its guard ring is the image's ----
-static int group_mask_shape(mi3pt_ctx *g, const char *what, size_t *tiles_x, size_t *tiles_y)
-{
-    GroupState *gs = g->group;
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
-    if (gs->block_rows % 8)
-        return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": the members' tiles only form the image's tile map when the group's block_rows is a multiple of 8 (use each member's mask: mi3pt_group_member)");
-    *tiles_x = ((size_t)gs->width + 7) / 8;
-    *tiles_y = ((size_t)gs->height + 7) / 8;
-    return MI3PT_OK;
-}
-
-static int group_set_sample_mask(mi3pt_ctx *g, const uint8_t *tiles, size_t ntiles)
-{
-    GroupState *gs = g->group;
-    size_t tiles_x = 0, tiles_y = 0;
-    if (int rc = group_mask_shape(g, "mi3pt_set_sample_mask", &tiles_x, &tiles_y)) return rc;
-    if (!tiles && ntiles == 0) return group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_set_sample_mask(m, nullptr, 0); });
-    if (!tiles) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (ntiles != tiles_x * tiles_y)
-        return pt_set_error(MI3PT_ERR_INVALID, "the mask's size does not match the tile map (a group takes the whole map: ceil(height / 8) x ceil(width / 8) bytes)");
-    const int n = (int)gs->members.size();
-    std::vector<uint8_t> part;
-    for (int i = 0; i < n; i++) {
-        mi3pt_ctx *m = gs->members[(size_t)i];
-        const size_t rows = conv_tiles_y(m);
-        part.assign(rows * tiles_x, 0);
-        for (size_t t = 0; t < rows; t++) {
-            const size_t gt = (size_t)mi3pt_tile_global_row((int)t, i, n, gs->block_rows / 8);
-            if (gt >= tiles_y) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_set_sample_mask: a member's tile row lies outside the image");
-            std::memcpy(part.data() + t * tiles_x, tiles + gt * tiles_x, tiles_x);
-        }
-        if (rows == 0) continue;
-        if (int rc = mi3pt_set_sample_mask(m, part.data(), part.size())) return rc;
-    }
-    return MI3PT_OK;
-}
-
-static int group_read_sample_mask(mi3pt_ctx *g, uint8_t *dst, size_t ntiles, uint32_t *sampled_out)
-{
-    GroupState *gs = g->group;
-    size_t tiles_x = 0, tiles_y = 0;
-    if (int rc = group_mask_shape(g, "mi3pt_read_sample_mask", &tiles_x, &tiles_y)) return rc;
-    if (ntiles != tiles_x * tiles_y)
-        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the tile map (a group reads the whole map: ceil(height / 8) x ceil(width / 8) bytes)");
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    const int n = (int)gs->members.size();
-    std::vector<uint8_t> part;
-    uint32_t sampled = 0;
-    for (int i = 0; i < n; i++) {
-        mi3pt_ctx *m = gs->members[(size_t)i];
-        const size_t rows = conv_tiles_y(m);
-        if (rows == 0) continue;
-        part.resize(rows * tiles_x);
-        uint32_t mine = 0;
-        if (int rc = mi3pt_read_sample_mask(m, part.data(), part.size(), &mine)) return rc;
-        sampled += mine;
-        for (size_t t = 0; t < rows; t++) {
-            const size_t gt = (size_t)mi3pt_tile_global_row((int)t, i, n, gs->block_rows / 8);
-            if (gt >= tiles_y) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_sample_mask: a member's tile row lies outside the image");
-            std::memcpy(dst + gt * tiles_x, part.data() + t * tiles_x, tiles_x);
-        }
-    }
-    if (sampled_out) *sampled_out = sampled;
-    return MI3PT_OK;
-}
-
-static int group_freeze_converged(mi3pt_ctx *g, int guard, uint32_t *sampled_out)
-{
-    GroupState *gs = g->group;
-    if (guard != 0 && guard != 1) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_freeze_converged: guard must be 0 or 1");
-    size_t tiles_x = 0, tiles_y = 0;
-    if (int rc = group_mask_shape(g, "mi3pt_freeze_converged", &tiles_x, &tiles_y)) return rc;
-    const size_t n = tiles_x * tiles_y;
-    std::vector<float> records(n * 4);
-    if (int rc = group_read_convergence_tiles(g, records.data(), records.size())) return rc;
-    std::vector<uint8_t> mask(n);
-    if (int rc = group_read_sample_mask(g, mask.data(), n, nullptr)) return rc;
-    const mi3pt_ctx *m0 = gs->members[0];
-    uint32_t sampled = 0;
-    if (int rc = mi3pt_host_freeze_tiles(records.data(), (int)tiles_x, (int)tiles_y, m0->conv_threshold, m0->conv_min_frames, guard, mask.data(), &sampled)) return rc;
-    if (int rc = group_set_sample_mask(g, mask.data(), n)) return rc;
-    if (sampled_out) *sampled_out = sampled;
-    return MI3PT_OK;
-}
-
-static int group_draw_canvas(mi3pt_ctx *g)
-{
-    GroupState *gs = g->group;
-    if (int rc = group_gather(g)) return rc;
-    if (gs->want_present) {
-        if (int rc = mi3pt_submit(gs->present, MI3PT_SUBMIT_FULLSCREEN)) return rc;
-        gs->want_present = false;
-    }
-    return MI3PT_OK;
-}
-
-static int group_read_texture(mi3pt_ctx *g, int which, float *dst, size_t nfloats)
-{
-    GroupState *gs = g->group;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "read before resize");
-    const size_t need = (size_t)gs->width * gs->height * 4;
-    if (nfloats != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the texture (a group reads whole images)");
-    if (which == MI3PT_TEX_ACCUMULATION) {
-        if (int rc = group_gather(g)) return rc;
-        return mi3pt_read_texture(gs->present, which, dst, nfloats);
-    }
-    if (which == MI3PT_TEX_CANVAS) {
-        if (int rc = group_draw_canvas(g)) return rc;
-        return mi3pt_read_texture(gs->present, which, dst, nfloats);
-    }
-    if (which != MI3PT_TEX_OUTPUT) return pt_set_error(MI3PT_ERR_INVALID, "unknown texture");
-    // the last frame's radiance: not part of any exchange -- read member by member and de-interleaved on the host
-    const int n = (int)gs->members.size(), br = gs->block_rows;
-    const size_t row = (size_t)gs->width * 4;
-    std::vector<float> part;
-    for (int i = 0; i < n; i++) {
-        mi3pt_ctx *m = gs->members[(size_t)i];
-        part.resize((size_t)m->local_rows * row);
-        if (int rc = mi3pt_read_texture(m, which, part.data(), part.size())) return rc;
-        for (int ly = 0; ly < m->local_rows; ly++) {
-            const size_t gy = group_global_row(ly, i, n, br);
-            std::memcpy(dst + gy * row, part.data() + (size_t)ly * row, row * 4);
-        }
-    }
-    return MI3PT_OK;
-}
-
-static int group_write_texture(mi3pt_ctx *g, int which, const float *src, size_t nfloats)
-{
-    GroupState *gs = g->group;
-    if (!src) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (gs->width == 0) return pt_set_error(MI3PT_ERR_STATE, "write before resize");
-    if (nfloats != (size_t)gs->width * gs->height * 4) return pt_set_error(MI3PT_ERR_INVALID, "source size does not match the texture (a group writes whole images)");
-    const int n = (int)gs->members.size(), br = gs->block_rows;
-    const size_t row = (size_t)gs->width * 4;
-    std::vector<float> part;
-    for (int i = 0; i < n; i++) {
-        mi3pt_ctx *m = gs->members[(size_t)i];
-        part.resize((size_t)m->local_rows * row);
-        for (int ly = 0; ly < m->local_rows; ly++) {
-            const size_t gy = group_global_row(ly, i, n, br);
-            std::memcpy(part.data() + (size_t)ly * row, src + gy * row, row * 4);
-        }
-        if (int rc = mi3pt_write_texture(m, which, part.data(), part.size())) return rc;
-    }
-    gs->gathered = false;
-    return MI3PT_OK;
-}
-
-static int group_read_canvas(mi3pt_ctx *g, uint8_t *dst, size_t nbytes)
-{
-    if (int rc = group_draw_canvas(g)) return rc;
-    return mi3pt_read_canvas_rgba8(g->group->present, dst, nbytes);
-}
-
-static int group_accumulation_ptr(mi3pt_ctx *g, void **dev_ptr, size_t *nbytes)
-{
-    if (int rc = group_gather(g)) return rc;
-    return mi3pt_accumulation_device_ptr(g->group->present, dev_ptr, nbytes);
-}
-
-// per-pass GPU time: the passes of the members run side by side -> the slowest member's; the fullscreen pass: the presenting context's
-static int group_pass_time(mi3pt_ctx *g, int pass, float *us)
-{
-    if (!us) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (pass == MI3PT_PASS_FULLSCREEN) return mi3pt_pass_time_us(g->group->present, pass, us);
-    float worst = 0.0f;
-    for (mi3pt_ctx *m : g->group->members) {
-        float t = 0.0f;
-        if (int rc = mi3pt_pass_time_us(m, pass, &t)) return rc;
-        if (t > worst) worst = t;
-    }
-    *us = worst;
-    return MI3PT_OK;
-}
-
-static int group_launch_stats(mi3pt_ctx *g, int reset, double *total_ms, uint64_t *launches, uint64_t *frames)
-{
-    double worst = 0.0;
-    uint64_t l0 = 0, f0 = 0;
-    bool first = true;
-    for (mi3pt_ctx *m : g->group->members) {
-        double t = 0.0;
-        uint64_t l = 0, f = 0;
-        if (int rc = mi3pt_raytrace_launch_stats(m, reset, &t, &l, &f)) return rc;
-        if (t > worst) worst = t;
-        if (first) { l0 = l; f0 = f; first = false; }
-    }
-    if (total_ms) *total_ms = worst;
-    if (launches) *launches = l0;
-    if (frames) *frames = f0;
-    return MI3PT_OK;
-}
-
-static int group_launch_span(mi3pt_ctx *g, double *span_ms)
-{
-    if (!span_ms) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    double worst = 0.0;
-    for (mi3pt_ctx *m : g->group->members) {
-        double t = 0.0;
-        if (int rc = mi3pt_raytrace_launch_span(m, &t)) return rc;
-        if (t > worst) worst = t;
-    }
-    *span_ms = worst;
-    return MI3PT_OK;
-}
-
-// MI3PT_OPT_HOST_ANALYSES: the sum over the members (one scene compile per scene change, whatever the group's size);
-// MI3PT_OPT_GATHER_STAGED: 1 = every member's rows reach the presenting context through pinned host memory (the path the gather falls
-// back to when peer access is unavailable or a direct copy failed: forced here so that it can be tested on one GPU)
-static int group_get_option(mi3pt_ctx *g, int option, int *value)
-{
-    if (!value) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    GroupState *gs = g->group;
-    if (option == MI3PT_OPT_HOST_ANALYSES) {
-        uint64_t n = 0;
-        for (mi3pt_ctx *m : gs->members) n += m->host_analyses;
-        *value = (int)n;
-        return MI3PT_OK;
-    }
-    if (option == MI3PT_OPT_GATHER_STAGED) {
-        int direct = 0;
-        for (char d : gs->peer_direct) direct += d ? 1 : 0;
-        *value = direct == 0 ? 1 : 0;
-        return MI3PT_OK;
-    }
-    return mi3pt_debug_get_option(gs->members[0], option, value);
-}
-
-static int group_set_option(mi3pt_ctx *g, int option, int value)
-{
-    GroupState *gs = g->group;
-    if (option == MI3PT_OPT_GATHER_STAGED) {
-        for (size_t i = 0; i < gs->peer_direct.size(); i++)
-            gs->peer_direct[i] = value ? 0 : (gs->members[i]->device == gs->present->device ? 1 : gs->peer_direct[i]);
-        gs->gathered = false;
-        for (bool &a : gs->aov_gathered) a = false;
-        return MI3PT_OK;
-    }
-    return group_each(g, false, [&](mi3pt_ctx *m) { return mi3pt_debug_set_option(m, option, value); });
-}
-
-static int group_counters(mi3pt_ctx *g, uint64_t *out)
-{
-    if (!out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    for (int k = 0; k < MI3PT_CNT_COUNT; k++) out[k] = 0;
-    for (mi3pt_ctx *m : g->group->members) {
-        uint64_t c[MI3PT_CNT_COUNT];
-        if (int rc = mi3pt_get_counters(m, c)) return rc;
-        for (int k = 0; k < MI3PT_CNT_COUNT; k++) out[k] += c[k];
-    }
     return MI3PT_OK;
 }

@@ -1,5 +1,5 @@
-// pt_ctx.h -- the context behind the C ABI of include/mi3pt.h (pt_context.hip): what it owns, by lifetime.  Host code only: no file that
-// defines a kernel includes this.
+// pt_ctx.h -- the context behind the C ABI of include/mi3pt.h (pt_context.hip and pt_ctx_*.hip; what those call of each other:
+// pt_ctx_calls.h): what it owns, by lifetime.  Host code only: no file that defines a kernel includes this.
 #pragma once
 #include "../../include/mi3pt.h"
 #include "pt_internal.h"
@@ -265,7 +265,7 @@ struct mi3pt_ctx : SceneBuffers, SceneFacts, ImageState {
     bool perm_used_valid[2] = { false, false };
     Stream cost_stream;
     uint8_t cost_key[MI3PT_RAYTRACE_UNIFORMS_SIZE] = {};
-    GroupState *group = nullptr;          // mi3pt_create_group: this handle fans every call out to member contexts (the end of pt_context.hip)
+    GroupState *group = nullptr;          // mi3pt_create_group: this handle fans every call out to member contexts (pt_ctx_group.hip)
     uint64_t scene_epoch = 1;             // bumped whenever the device's scene data or its analysis changes (uploads, prepare_layout, prepare_cull)
     uint64_t host_analyses = 0;           // scene compiles done on the host by THIS context: uploads that build packets + cull analyses (MI3PT_OPT_HOST_ANALYSES)
 

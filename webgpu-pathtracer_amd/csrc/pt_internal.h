@@ -4,6 +4,8 @@
 
 // Records `msg` as the calling thread's last error and returns `code`.
 int pt_set_error(int code, const std::string &msg);
+// The calling thread's last error as recorded (what mi3pt_last_error hands out); the string itself lives in pt_context.hip alone.
+const std::string &pt_last_error();
 
 // pt_lbvh.hip: device-side linear BVH over n 112-byte triangle records at d_tris; writes (2n - 1)
 // 48-byte node records to the HOST buffer nodes_out.  Returns 0, or -1 with `err` set.
@@ -21,7 +23,7 @@ int ploc_build(const void *d_tris, size_t n, int radius, int max_search_iteratio
 int refit_bvh(const void *d_tris, size_t ntris, const void *d_nodes, size_t n, void *nodes_out, float *refit_ms, hipStream_t stream, std::string &err);
 }
 
-// ---- host-side helpers shared by pt_context.hip and the pt_host_*.cpp files (plain C++: the CPU sanitizer builds cover them)
+// ---- host-side helpers shared by the context's units (pt_context.hip, pt_ctx_*.hip) and the pt_host_*.cpp files (plain C++: the CPU sanitizer builds cover them)
 #include <array>
 #include <cstdint>
 #include <cstring>

@@ -169,7 +169,7 @@ constexpr int SM_W8_OVERFLOW_NODES = 22;      // 64-bit node entries per lane in
 
 // 48-byte triangle record for intersection only: vertex a, the material index, and the two EDGES b - a and c - a as
 // Moller-Trumbore forms them first (raytrace.wgsl:82-83) -- one fp32 subtraction each, rounded to nearest, wherever it is
-// computed: at upload (pt_context.hip: tri_packet_of, the host's float subtraction) instead of per test (six vector
+// computed: at upload (pt_host_compile.cpp: tri_packet_of, the host's float subtraction) instead of per test (six vector
 // instructions of every triangle test).  The vertex normals (only needed for the one closest hit per ray) stay in the
 // uploaded 112-B records, like b and c themselves.
 struct TriPacket {
