@@ -1,5 +1,5 @@
 """The images of a context -- textures, canvas, feature images, filtered image, variance image, moments image -- behind one read /
-write / pointer path (pt_context.hip: read_plane, write_plane): what every entry point answers in every state, and a rank without rows.
+write / pointer path (pt_context.hip: read_plane; pt_ctx_image.hip: write_plane, hand_out_plane): what every entry point answers in every state, and a rank without rows.
 
 The codes of EXPECTED are what the library answered before the entry points shared that path: the table was printed by this loop on the
 library of the commit before (the separate copies of the plumbing) and committed as a literal, so that "the order of the checks is

@@ -47,7 +47,7 @@ def flags(built):
 
 
 def expected_variant(requested, f):
-    """pick_variant (csrc/pt_context.hip) from the compile's flags, for a context with its default options: the walk a requested
+    """pick_variant (csrc/pt_ctx_launch.hip) from the compile's flags, for a context with its default options: the walk a requested
     variant resolves to.  f: host_scene_compile's fields, with the 8-wide packets asked for when 14 is requested."""
     defer = f["leaf_cap"] >= 4                                   # leaves may be tested out of order: a proper tree, room in LDS
     cull = bool(f["cull_stack_ok"] and f["analysed"])            # the near-first walks: their stack bound holds and the analysis ran

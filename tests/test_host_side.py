@@ -78,7 +78,7 @@ def test_library_exports_every_declared_symbol(built):
 
 
 # the translation units of the context ("The context behind the boundary")
-CONTEXT_UNITS = {"pt_context.hip", "pt_ctx_probe.hip", "pt_ctx_group.hip"}
+CONTEXT_UNITS = {"pt_context.hip", "pt_ctx_scene.hip", "pt_ctx_launch.hip", "pt_ctx_image.hip", "pt_ctx_probe.hip", "pt_ctx_group.hip"}
 
 
 def test_makefile_lists_every_source_and_each_entry_point_has_one_body():
@@ -104,6 +104,36 @@ def test_makefile_lists_every_source_and_each_entry_point_has_one_body():
             bodies.setdefault(name, []).append(f)
     declared = _declared_symbols()          # (without the experiment build's own declarations, as the export test takes them)
     assert declared and {name: bodies.get(name, []) for name in declared if len(bodies.get(name, [])) != 1} == {}
+
+
+def test_context_units_cross_only_through_pt_ctx_calls_h():
+    """The rule of csrc/pt_ctx_calls.h ("The context behind the boundary"), on the text alone: every function the header declares
+    has its body in exactly one context unit, is named in at least one OTHER unit (directly, or through a static inline of the header: a
+    declaration nobody crosses with is dead), and no context unit declares any function ahead of its body -- a unit is ordered so that it
+    needs no forward declaration, and what another unit defines is declared in the header alone.  Needs no library."""
+    csrc = os.path.join(ROOT, "webgpu-pathtracer_amd", "csrc")
+    header = open(os.path.join(csrc, "pt_ctx_calls.h")).read()
+    units = {f: open(os.path.join(csrc, f)).read() for f in sorted(CONTEXT_UNITS)}
+    proto = r"^(?!static\b|template\b)[A-Za-z_][\w:]*[\s*&]+(\w+)\s*\([^;{}]*\)\s*;"
+    declared = re.findall(proto, header, flags=re.M)
+    assert len(declared) >= 39 and len(set(declared)) == len(declared)          # (this test reads one prototype per line, at the margin)
+    assert {"require_ctx", "ctx_wait", "scene_refs", "group_member0", "group_submit_frames"} <= set(declared)
+    # the header's one-liners: a unit that uses ctx_stream_sync calls ctx_wait
+    inline_uses = {m.group(1): set(re.findall(r"\b\w+\b", m.group(2)))
+                   for m in re.finditer(r"^static inline [^\n(]*?\b(\w+)\s*\(.*?\)\s*\{(.*)\}\s*$", header, flags=re.M)}
+    assert "ctx_stream_sync" in inline_uses and "ctx_wait" in inline_uses["ctx_stream_sync"]
+    wrong = {}
+    for name in declared:
+        homes = [f for f, text in units.items() if re.search(r"^[A-Za-z_][\w:\s*&]*?\b%s\s*\([^;{}]*\)\s*\{" % name, text, flags=re.M)]
+        if len(homes) != 1:
+            wrong[name] = "bodies in %s" % homes
+            continue
+        via = {name} | {inl for inl, used in inline_uses.items() if name in used}
+        if not any(re.search(r"\b%s\b" % v, text) for f, text in units.items() if f != homes[0] for v in via):
+            wrong[name] = "no unit but %s names it" % homes[0]
+    assert wrong == {}
+    ahead = {f: re.findall(r"^(?:static\s+)?[A-Za-z_][\w:\s*&<>]*?\b(\w+)\s*\([^;{}]*\)\s*;", text, flags=re.M) for f, text in units.items()}
+    assert {f: names for f, names in ahead.items() if names} == {}
 
 
 def test_release_library_reads_no_knobs(built):

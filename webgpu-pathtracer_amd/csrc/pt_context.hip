@@ -6,19 +6,17 @@
 // one HIP stream.  There is no CPU execution path in this file: every pass is a
 // kernel from pt_kernels.hip.
 //
-// The probes are pt_ctx_probe.hip, the device groups pt_ctx_group.hip; pt_ctx_calls.h declares what crosses those cuts.
+// This file is the core: the last error, the launch gate, create / destroy, the options, timing and counters.  The scene is pt_ctx_scene.hip,
+// the launch path pt_ctx_launch.hip, the images and their features pt_ctx_image.hip, the probes pt_ctx_probe.hip, the device groups
+// pt_ctx_group.hip; pt_ctx_calls.h declares what crosses those cuts.
 #include "../../include/mi3pt.h"
 #include "pt_ctx_calls.h"
 
 #include <hip/hip_runtime.h>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <array>
 #include <cstring>
 #include <string>
-#include <utility>
-#include <algorithm>
 #include <vector>
 #include <chrono>
 #include <thread>
@@ -33,15 +31,7 @@ int pt_set_error(int code, const std::string &msg)
 
 const std::string &pt_last_error() { return g_last_error; }
 
-// Most frames one launch may cover.  A single GPU batches 16 (the drain tail of a persistent
-// launch is then ~10 % of it); a rank of an N-way tile split renders 1/N of the image per frame,
-// so it batches N times as many frames for the same amount of work per launch.
-// Blocks of launch-invariant scalars for the raytrace kernel's service step (pt::RtService), one per batched launch.  Launches
-// alternate between two streams and at most two are in flight; a slot is rewritten (in stream order, by the setup kernel of
-// launch k + SERVICE_SLOTS) on the stream launch k ran on, i.e. after it.
 static_assert(MI3PT_ENV_WIDTH == pt::ENV_W && MI3PT_ENV_HEIGHT == pt::ENV_H, "the tuned kernels' environment size is the API's");
-static const int SERVICE_SLOTS = 8;
-static size_t service_slot_bytes() { return (pt::service_block_bytes() + 255) / 256 * 256; }
 
 int require_ctx(mi3pt_ctx *ctx)
 {
@@ -51,7 +41,6 @@ int require_ctx(mi3pt_ctx *ctx)
     return MI3PT_OK;
 }
 
-static int flush_pending(mi3pt_ctx *ctx);
 extern "C" int mi3pt_abi_version(void) { return MI3PT_ABI_VERSION; }
 extern "C" const char *mi3pt_last_error(void) { return g_last_error.c_str(); }
 
@@ -217,7 +206,6 @@ hipError_t ctx_wait(mi3pt_ctx *ctx, hipStream_t s, hipEvent_t ev, const char *wh
         else std::this_thread::sleep_for(std::chrono::microseconds(spins < 4096 ? 50 : 500));
     }
 }
-static hipError_t ctx_event_sync(mi3pt_ctx *ctx, hipEvent_t ev, const char *why = "event wait") { return ctx_wait(ctx, nullptr, ev, why); }
 
 int PassTimer::elapsed_us(mi3pt_ctx *ctx, float *us, const char *not_timed)
 {
@@ -238,23 +226,6 @@ hipError_t read_plane(mi3pt_ctx *ctx, const void *src, size_t nbytes, void *dst)
     if (e == hipSuccess) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
     return e;
-}
-
-static hipError_t write_plane(mi3pt_ctx *ctx, void *dst, const void *src, size_t nbytes)
-{
-    if (nbytes == 0) return hipSuccess;
-    hipError_t e = ctx_stream_sync(ctx, ctx->stream, "write-back");
-    if (e == hipSuccess) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);      // copy-on-call
-    return e;
-}
-
-// what every *_device_ptr entry point ends with
-static int hand_out_plane(const mi3pt_ctx *ctx, const void *plane, void **dev_ptr, size_t *nbytes)
-{
-    *dev_ptr = const_cast<void *>(plane);
-    if (nbytes) *nbytes = plane_bytes(ctx);
-    return MI3PT_OK;
 }
 
 extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
@@ -380,9 +351,6 @@ extern "C" int mi3pt_create(int device, mi3pt_ctx **out_ctx)
     return MI3PT_OK;
 }
 
-// A context without textures: everything that lives from resize to resize is let go of (what that is: ImageState's members).
-static void free_textures(mi3pt_ctx *ctx) { ctx->images() = ImageState(); }
-
 extern "C" int mi3pt_destroy(mi3pt_ctx *ctx)
 {
     PT_GROUP(ctx, group_destroy(ctx));
@@ -455,6 +423,9 @@ extern "C" int mi3pt_set_kernel_variant(mi3pt_ctx *ctx, int variant)
     return MI3PT_OK;
 }
 
+// Most frames one launch may cover.  A single GPU batches 16 (the drain tail of a persistent
+// launch is then ~10 % of it); a rank of an N-way tile split renders 1/N of the image per frame,
+// so it batches N times as many frames for the same amount of work per launch.
 // Frames one launch may cover for this context's tile (before the memory cap of mi3pt_resize).
 static int batch_limit(const mi3pt_ctx *ctx, int nranks)
 {
@@ -463,7 +434,7 @@ static int batch_limit(const mi3pt_ctx *ctx, int nranks)
     return (int)(b > ctx->batch_limit_frames ? ctx->batch_limit_frames : b);
 }
 
-static void recompute_batch_cap(mi3pt_ctx *ctx)
+void recompute_batch_cap(mi3pt_ctx *ctx)
 {
     if (ctx->width == 0) return;
     // (a band of 1 / k of the image batches k times as many frames per launch, like a rank of a k-way tile split)
@@ -619,464 +590,6 @@ extern "C" int mi3pt_set_tile(mi3pt_ctx *ctx, int rank, int nranks, int block_ro
     return MI3PT_OK;
 }
 
-// Replace *dst with a device copy of `bytes`.
-static int replace_buffer(mi3pt_ctx *ctx, DevBuf<void> &dst, const void *bytes, size_t nbytes)
-{
-    DevBuf<void> fresh;
-    HIP_TRY(fresh.alloc(nbytes));
-    hipError_t e = ctx_stream_sync(ctx, ctx->stream, "upload");      // (bounded; a large copy from pageable memory blocks the host until the stream gets there)
-    if (e == hipSuccess) e = hipMemcpyAsync(fresh, bytes, nbytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);   // copy-on-call: caller may reuse `bytes`
-    if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
-    dst = std::move(fresh);
-    ctx->scene_epoch++;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_upload_triangles(mi3pt_ctx *ctx, const void *bytes, size_t nbytes)
-{
-    PT_GROUP(ctx, mi3pt_upload_triangles(group_member0(ctx), bytes, nbytes));      // (a group's scene lives in member 0; the others receive device copies: group_sync_scene)
-    if (int rc = require_idle(ctx)) return rc;
-    if (!bytes || nbytes == 0 || nbytes % MI3PT_TRIANGLE_STRIDE)
-        return pt_set_error(MI3PT_ERR_INVALID, "triangle bytes must be a non-zero multiple of 112");
-    const size_t n = nbytes / MI3PT_TRIANGLE_STRIDE;
-    if (n > 0x7fffffffu) return pt_set_error(MI3PT_ERR_INVALID, "too many triangles");
-    std::vector<pt::TriPacket> pk;
-    int64_t max_mat = -1;
-    if (const char *e = pt::compile_triangles(static_cast<const uint8_t *>(bytes), n, pk, max_mat)) return pt_set_error(MI3PT_ERR_INVALID, e);
-    // (mi3pt_keep_geometry: the first upload after it hands the records over as the previous geometry instead of freeing them)
-    const bool hand_over = ctx->geometry_kept && !ctx->d_tris_kept;
-    DevBuf<void> tris;
-    if (int rc = replace_buffer(ctx, tris, bytes, nbytes)) return rc;
-    if (hand_over) ctx->d_tris_kept = std::move(ctx->d_tris);
-    ctx->d_tris = std::move(tris);
-    ctx->upload_epoch++;
-    if (int rc = replace_buffer(ctx, ctx->d_tripk, pk.data(), n * sizeof(pt::TriPacket))) return rc;
-    ctx->ntris = n;
-    ctx->host_analyses++;
-    ctx->max_mat_ref = max_mat;
-    ctx->cull_dirty = true;
-    ctx->cost_state = 0;            // (the tiles' costs were measured on another scene)
-    if (ctx->layout_active && ctx->nnodes > 0) {
-        // The device holds node packets, leaf ranks and the root reference in the visiting-order numbering of the debug
-        // layout, while the triangles just uploaded are in uploaded order again: rebuild the tree's side from the node
-        // records, which are kept as uploaded (round-2 advice: leaves referenced the wrong triangles after a
-        // triangles-only upload that followed mi3pt_debug_set_packet_layout(ctx, 0)).
-        std::vector<uint8_t> nodes(ctx->nnodes * MI3PT_BVHNODE_STRIDE);
-        HIP_TRY(hipMemcpy(nodes.data(), ctx->d_nodes, nodes.size(), hipMemcpyDeviceToHost));
-        ctx->layout_active = false;
-        return mi3pt_upload_bvh(ctx, nodes.data(), nodes.size());
-    }
-    ctx->layout_active = false;
-    ctx->layout_dirty = ctx->layout != 0;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_upload_materials(mi3pt_ctx *ctx, const void *bytes, size_t nbytes)
-{
-    PT_GROUP(ctx, mi3pt_upload_materials(group_member0(ctx), bytes, nbytes));      // (a group's scene lives in member 0; the others receive device copies: group_sync_scene)
-    if (int rc = require_idle(ctx)) return rc;
-    if (!bytes || nbytes == 0 || nbytes % MI3PT_MATERIAL_STRIDE)
-        return pt_set_error(MI3PT_ERR_INVALID, "material bytes must be a non-zero multiple of 64");
-    if (int rc = replace_buffer(ctx, ctx->d_mats, bytes, nbytes)) return rc;
-    ctx->upload_epoch++;
-    ctx->nmats = nbytes / MI3PT_MATERIAL_STRIDE;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_upload_bvh(mi3pt_ctx *ctx, const void *bytes, size_t nbytes)
-{
-    PT_GROUP(ctx, mi3pt_upload_bvh(group_member0(ctx), bytes, nbytes));      // (a group's scene lives in member 0; the others receive device copies: group_sync_scene)
-    if (int rc = require_idle(ctx)) return rc;
-    if (!bytes || nbytes == 0 || nbytes % MI3PT_BVHNODE_STRIDE)
-        return pt_set_error(MI3PT_ERR_INVALID, "BVH bytes must be a non-zero multiple of 48");
-    const size_t n = nbytes / MI3PT_BVHNODE_STRIDE;
-    if (n > 0x7fffffffu) return pt_set_error(MI3PT_ERR_INVALID, "too many BVH nodes");
-    const uint8_t *src = static_cast<const uint8_t *>(bytes);
-    pt::TreeCompile t;
-    if (const char *e = pt::compile_tree(src, n, t)) return pt_set_error(MI3PT_ERR_INVALID, e);
-    if (int rc = replace_buffer(ctx, ctx->d_nodes, bytes, nbytes)) return rc;
-    ctx->upload_epoch++;
-    if (int rc = replace_buffer(ctx, ctx->d_packets, t.packets.data(), t.packets.size() * sizeof(pt::NodePacket))) return rc;
-    if (int rc = replace_buffer(ctx, ctx->d_leaf_rank, t.leaf_rank.data(), t.leaf_rank.size() * sizeof(uint32_t))) return rc;
-    ctx->leaf_cap = t.leaf_cap;
-    ctx->cull_stack_ok = t.cull_stack_ok;
-    ctx->tree_proper = t.tree_proper;
-    ctx->nodes_reached = t.reached;
-    ctx->walk_stack_worst = t.walk_stack_worst;
-    ctx->nnodes = n;
-    ctx->npackets = t.npackets;
-    ctx->root_ref = t.root_ref;
-    ctx->scene_flags = t.scene_flags;
-    ctx->max_tri_ref = t.max_tri_ref;
-    // the cut behind the empty tiles of a view: the nesting of EVERY node's box is checked (the collapse checks it for the nodes it absorbs only)
-    ctx->sky_cut_ok = t.tree_proper && pt::sky_cut_of(src, n, ctx->sky_cut);
-    ctx->sky_host_valid = false;
-    ctx->cull_dirty = true;
-    ctx->cost_state = 0;            // (the tiles' costs were measured on another scene)
-    ctx->layout_active = false;
-    ctx->layout_dirty = ctx->layout != 0;
-    ctx->scene_epoch++;
-    ctx->host_analyses++;
-    return MI3PT_OK;
-}
-
-static int upload_env_like(mi3pt_ctx *ctx, void *dst, const float *rgba, int width, int height)
-{
-    if (int rc = require_idle(ctx)) return rc;
-    if (!rgba) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (width != MI3PT_ENV_WIDTH || height != MI3PT_ENV_HEIGHT)   // renderer.ts:133-137
-        return pt_set_error(MI3PT_ERR_INVALID,
-                            "Environment texture must be 1024x512 pixels. Please resize the texture and try again.");
-    const size_t nbytes = (size_t)width * height * 16;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "upload"));
-    HIP_TRY(hipMemcpyAsync(dst, rgba, nbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    ctx->scene_epoch++;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_upload_environment(mi3pt_ctx *ctx, const float *rgba, int width, int height)
-{
-    PT_GROUP(ctx, mi3pt_upload_environment(group_member0(ctx), rgba, width, height));      // (a group's scene lives in member 0; the others receive device copies: group_sync_scene)
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    return upload_env_like(ctx, ctx->d_env, rgba, width, height);
-}
-
-extern "C" int mi3pt_upload_environment_cdf(mi3pt_ctx *ctx, const float *rgba, int width, int height)
-{
-    PT_GROUP(ctx, mi3pt_upload_environment_cdf(group_member0(ctx), rgba, width, height));      // (a group's scene lives in member 0; the others receive device copies: group_sync_scene)
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    return upload_env_like(ctx, ctx->d_cdf, rgba, width, height);
-}
-
-static pt::Tile tile_of(const mi3pt_ctx *ctx)
-{
-    pt::Tile t;
-    t.tex_w = ctx->width; t.tex_h = ctx->height; t.local_rows = ctx->local_rows;
-    t.rank = ctx->rank; t.nranks = ctx->nranks; t.block_rows = ctx->block_rows;
-    return t;
-}
-
-static int zero_textures(mi3pt_ctx *ctx)
-{
-    const size_t tex_bytes = plane_bytes(ctx);
-    const size_t canvas_px = (size_t)ctx->width * ctx->height;
-    if (tex_bytes) {
-        // (the batch slots need no clearing: a launch writes every texel the ordered mean reads)
-        HIP_TRY(hipMemsetAsync(ctx->d_radiance, 0, tex_bytes, ctx->stream));
-        HIP_TRY(hipMemsetAsync(ctx->d_accum, 0, tex_bytes, ctx->stream));
-        if (ctx->d_moments) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, tex_bytes, ctx->stream));
-    }
-    if (canvas_px) {
-        HIP_TRY(hipMemsetAsync(ctx->d_canvas, 0, canvas_px * 16, ctx->stream));
-        HIP_TRY(hipMemsetAsync(ctx->d_canvas8, 0, canvas_px * 4, ctx->stream));
-    }
-    ctx->history_held = false;        // (mi3pt_reset, mi3pt_resize: a held history goes with the mean)
-    ctx->output_is_accum = false;
-    ctx->last_radiance = ctx->d_radiance;
-    ctx->main_dirty = true;
-    ctx->accum_version++;
-    ctx->presented_version = 0;       // the canvas was cleared
-    ctx->want_present = false;
-    return MI3PT_OK;
-}
-
-// mi3pt_resize / mi3pt_reset: no mask, every tile sampled (the queue has been launched under the old one)
-static void drop_sample_mask(mi3pt_ctx *ctx)
-{
-    ctx->mask.clear();
-    ctx->mask_epoch = 0;
-    ctx->mask_sampled = 0;
-}
-
-extern "C" int mi3pt_resize(mi3pt_ctx *ctx, int width, int height)
-{
-    PT_GROUP(ctx, group_resize(ctx, width, height));
-    if (int rc = require_idle(ctx)) return rc;
-    if (width <= 0 || height <= 0 || width > 32768 || height > 32768)
-        return pt_set_error(MI3PT_ERR_INVALID, "width/height must be in [1, 32768]");
-    drop_sample_mask(ctx);
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    for (int k = 0; k < 2; k++) HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[k]));
-    // Transactional: the new images are allocated into a local and the context only changes once
-    // every allocation has succeeded; a failure leaves it WITHOUT textures (width = height = 0,
-    // every later submit / read reports "before resize") instead of with dangling pointers.
-    free_textures(ctx);
-    const int rank = ctx->next_rank, nranks = ctx->next_nranks, block_rows = ctx->next_block_rows;
-    const int local_rows = mi3pt_tile_local_rows(height, rank, nranks, block_rows);
-    const size_t tex_bytes = (size_t)local_rows * width * 16;
-    const size_t canvas_px = (size_t)width * height;
-    pt::Tile t;
-    t.tex_w = width; t.tex_h = height; t.local_rows = local_rows; t.rank = rank; t.nranks = nranks; t.block_rows = block_rows;
-    // per-wave counter slots: one per tile for the per-pixel kernels' grids, one per resident wave for the persistent kernels'
-    // (whose grid is capped by the launch's JOBS -- tiles x frames -- and may exceed the tiles of one frame)
-    const int ntiles_frame = pt::raytrace_grid_blocks(t);
-    const int nblocks = ntiles_frame > 0 ? std::max(ntiles_frame, pt::PT_MAX_RESIDENT_WAVES) : 0;
-    // two counter sets: overlapping raytrace kernels of consecutive frames use alternate halves
-    const size_t cbytes = 2 * (size_t)(nblocks ? nblocks : 1) * pt::CNT_COUNT * sizeof(uint64_t);
-    ImageState fresh;
-    hipError_t e = fresh.d_radiance.alloc(tex_bytes);
-    if (e == hipSuccess) e = fresh.d_accum_own.alloc(tex_bytes);
-    if (e == hipSuccess) e = fresh.d_canvas.alloc(canvas_px * 16);
-    if (e == hipSuccess) e = fresh.d_canvas8.alloc(canvas_px * 4);
-    if (e == hipSuccess) e = fresh.d_block_counters.alloc(cbytes);
-    if (e == hipSuccess && ctx->moments) e = fresh.d_moments.alloc(tex_bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(fresh.d_block_counters, 0, cbytes, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return pt_set_error(MI3PT_ERR_HIP, std::string("mi3pt_resize: allocating the textures failed: ") + hipGetErrorString(e));
-    }
-    fresh.width = width; fresh.height = height; fresh.local_rows = local_rows;
-    fresh.d_accum = fresh.d_accum_own;
-    fresh.nblocks = nblocks;
-    ctx->rank = rank; ctx->nranks = nranks; ctx->block_rows = block_rows;
-    ctx->images() = std::move(fresh);
-    // batch depth: the limit for this tile split, capped so that the slot sets together take
-    // at most a quarter of the memory that is free now (slots are allocated when first needed)
-    recompute_batch_cap(ctx);
-    return zero_textures(ctx);
-}
-
-extern "C" int mi3pt_reset(mi3pt_ctx *ctx)
-{
-    PT_GROUP(ctx, group_reset(ctx));
-    if (int rc = require_idle(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "reset before resize");
-    drop_sample_mask(ctx);          // a new accumulation starts whole
-    return zero_textures(ctx);
-}
-
-extern "C" int mi3pt_set_uniforms(mi3pt_ctx *ctx, int pass, const void *bytes, size_t nbytes)
-{
-    PT_GROUP(ctx, group_set_uniforms(ctx, pass, bytes, nbytes));
-    if (!ctx || !bytes) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    switch (pass) {
-    case MI3PT_PASS_RAYTRACE:
-        if (nbytes != sizeof ctx->u_rt) return pt_set_error(MI3PT_ERR_INVALID, "raytrace uniforms are 96 bytes");
-        std::memcpy(ctx->u_rt, bytes, nbytes);
-        return MI3PT_OK;
-    case MI3PT_PASS_ACCUMULATE:
-        if (nbytes != sizeof ctx->u_acc) return pt_set_error(MI3PT_ERR_INVALID, "accumulate uniforms are 16 bytes");
-        std::memcpy(ctx->u_acc, bytes, nbytes);
-        return MI3PT_OK;
-    case MI3PT_PASS_FULLSCREEN:
-        if (nbytes != sizeof ctx->u_fs) return pt_set_error(MI3PT_ERR_INVALID, "fullscreen uniforms are 24 bytes");
-        std::memcpy(ctx->u_fs, bytes, nbytes);
-        return MI3PT_OK;
-    default:
-        return pt_set_error(MI3PT_ERR_INVALID, "unknown pass");
-    }
-}
-
-pt::SceneRefs scene_refs(const mi3pt_ctx *ctx)
-{
-    pt::SceneRefs s;
-    s.tris = (ctx->layout_active ? ctx->d_tris_perm : ctx->d_tris).as<const float4>();
-    s.nodes = ctx->d_nodes.as<const float4>();
-    s.mats = ctx->d_mats.as<const float4>();
-    s.env = ctx->d_env.as<const float4>();
-    s.packets = ctx->d_packets.as<const float4>();
-    s.tripk = ctx->d_tripk.as<const float4>();
-    s.leaf_rank = ctx->d_leaf_rank.as<const uint32_t>();
-    s.leaf_cap = ctx->leaf_cap;
-    s.wide = ctx->d_wide.as<const float4>();
-    s.cwide = ctx->cwide_ok ? ctx->d_cwide.as<const float4>() : nullptr;
-    s.tripk64 = ctx->cwide_ok ? ctx->d_tripk64.as<const float4>() : nullptr;
-    s.cw8 = ctx->cw8_ok ? ctx->d_cw8.as<const float4>() : nullptr;
-    s.tripk8 = ctx->cw8_ok ? ctx->d_tripk8.as<const float4>() : nullptr;
-    s.wide_leaf_cap = ctx->wide_ok ? ctx->wide_leaf_cap : 0;
-    s.wide_root = ctx->wide_root;
-    s.cdf = ctx->d_cdf.as<const float4>();
-    s.env_sampling = (ctx->env_sampling && ctx->d_cdf) ? 1 : 0;
-    s.ntris = (uint32_t)ctx->ntris; s.nnodes = (uint32_t)ctx->nnodes; s.nmats = (uint32_t)ctx->nmats;
-    s.npackets = (uint32_t)ctx->npackets;
-    s.root_ref = ctx->root_ref;
-    s.flags = ctx->scene_flags;
-    if ((ctx->wide_ok && ctx->wide_root_nested) || ctx->cw8_ok) s.flags |= 2u;      // (pt_kernels.h SceneRefs::flags bit 1; the 8-wide packets are only built for trees whose every box is nested)
-    if (ctx->wide_ok && ctx->auto_wide_variant == 12) s.flags |= 4u;  // (bit 2: the one-axis culling condition suits this scene -- variant 13 takes the hint)
-    s.cull_ka = ctx->cull_ka; s.cull_kb = ctx->cull_kb;
-#ifdef MI3PT_EXPERIMENTS
-    if (ctx->exp_force_slow_slab) s.flags = 0;
-#endif
-    s.env_w = MI3PT_ENV_WIDTH; s.env_h = MI3PT_ENV_HEIGHT;
-    return s;
-}
-
-// The scene is complete when the three buffers agree with each other.  An empty
-// scene (no BVH uploaded) is legal: every ray misses (raytrace.wgsl:206-207).
-int check_scene(const mi3pt_ctx *ctx)
-{
-    if (ctx->nnodes == 0) return MI3PT_OK;
-    if (ctx->max_tri_ref >= (int64_t)ctx->ntris)
-        return pt_set_error(MI3PT_ERR_STATE, "BVH references a triangle index beyond the triangle buffer");
-    if (ctx->max_tri_ref >= 0 && ctx->max_mat_ref >= (int64_t)ctx->nmats)
-        return pt_set_error(MI3PT_ERR_STATE, "a triangle references a material index beyond the material buffer");
-    return MI3PT_OK;
-}
-
-// Debug relabelling (mi3pt_debug_set_packet_layout(ctx, 1)): node packets numbered in the reference's
-// visiting order (node, right subtree, left subtree: left is pushed first, raytrace.wgsl:184-198)
-// and triangles -- 112-B records, 48-B packets, leaf ranks -- stored in leaf-visiting order.  Only
-// names change: every packet holds the same boxes, every leaf the same triangle, so images and
-// counters must be bit-identical to the breadth-first layout in every packet-walking kernel
-// (tests/test_gpu_parity.py::test_depth_first_relabelling_is_bit_identical).  Applied lazily
-// because it needs both uploads; needs a proper tree (tree_proper).  The distance-culling walk
-// is not offered in this layout (variant 0 / 9 run 7).
-int prepare_layout(mi3pt_ctx *ctx)
-{
-    if (!ctx->layout_dirty) return MI3PT_OK;
-    if (ctx->layout == 0 || ctx->nnodes == 0 || ctx->ntris == 0 || !ctx->tree_proper || ctx->max_tri_ref >= (int64_t)ctx->ntris)
-        return MI3PT_OK;       // stays dirty; the uploaded (breadth-first) arrangement is complete by itself
-    if (int rc = flush_pending(ctx)) return rc;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    for (int k = 0; k < 2; k++) HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[k]));
-    const size_t n = ctx->nnodes, nt = ctx->ntris;
-    std::vector<uint8_t> nodes(n * MI3PT_BVHNODE_STRIDE), tris(nt * MI3PT_TRIANGLE_STRIDE);
-    HIP_TRY(hipMemcpy(nodes.data(), ctx->d_nodes, nodes.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tris.data(), ctx->d_tris, tris.size(), hipMemcpyDeviceToHost));
-    const uint8_t *src = nodes.data();
-    std::vector<uint32_t> packet_of(n, pt::REF_NONE), tri_new(nt, 0xffffffffu);
-    uint32_t npk = 0, ntri = 0;
-    std::vector<uint32_t> st;
-    st.push_back(0);
-    while (!st.empty()) {
-        const uint32_t node = st.back();
-        st.pop_back();
-        const uint8_t *r = src + (size_t)node * MI3PT_BVHNODE_STRIDE;
-        if (ldi(r, 28) == 1) {
-            tri_new[(size_t)ldi(r, 40)] = ntri++;
-        } else {
-            packet_of[node] = npk++;
-            st.push_back((uint32_t)ldi(r, 32));
-            st.push_back((uint32_t)ldi(r, 36));
-        }
-    }
-    for (size_t i = 0; i < n; i++)        // internal nodes the root does not reach keep a packet (never walked)
-        if (ldi(src + i * MI3PT_BVHNODE_STRIDE, 28) != 1 && packet_of[i] == pt::REF_NONE) packet_of[i] = npk++;
-    for (size_t t = 0; t < nt; t++)
-        if (tri_new[t] == 0xffffffffu) tri_new[t] = ntri++;
-    if (npk != ctx->npackets || ntri != nt) return pt_set_error(MI3PT_ERR_STATE, "packet layout: counts do not match the upload");
-    std::vector<pt::NodePacket> pk;
-    pt::build_packets(src, n, packet_of, npk, tri_new.data(), pk);
-    std::vector<uint8_t> tris_perm(tris.size());
-    std::vector<pt::TriPacket> tripk(nt);
-    std::vector<uint32_t> rank(nt);
-    for (size_t t = 0; t < nt; t++) {
-        const uint8_t *rec = tris.data() + t * MI3PT_TRIANGLE_STRIDE;
-        const size_t to = tri_new[t];
-        std::memcpy(tris_perm.data() + to * MI3PT_TRIANGLE_STRIDE, rec, MI3PT_TRIANGLE_STRIDE);
-        tripk[to] = pt::tri_packet_of(rec);
-        rank[to] = (uint32_t)to;          // leaf-visiting order IS the new numbering
-    }
-    if (int rc = replace_buffer(ctx, ctx->d_packets, pk.data(), pk.size() * sizeof(pt::NodePacket))) return rc;
-    if (int rc = replace_buffer(ctx, ctx->d_tripk, tripk.data(), nt * sizeof(pt::TriPacket))) return rc;
-    if (int rc = replace_buffer(ctx, ctx->d_leaf_rank, rank.data(), nt * sizeof(uint32_t))) return rc;
-    if (int rc = replace_buffer(ctx, ctx->d_tris_perm, tris_perm.data(), tris_perm.size())) return rc;
-    ctx->root_ref = pt::child_ref(src, packet_of, tri_new.data(), 0);
-    ctx->layout_active = true;
-    ctx->layout_dirty = false;
-    ctx->scene_epoch++;
-    ctx->host_analyses++;
-    ctx->cull_ok = false;           // the analysis below works on the uploaded numbering
-    ctx->cull_dirty = true;
-    ctx->cost_state = 0;            // (the tiles' costs were measured on another scene)
-    ctx->main_dirty = true;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_debug_set_packet_layout(mi3pt_ctx *ctx, int layout)
-{
-    PT_GROUP(ctx, mi3pt_debug_set_packet_layout(group_member0(ctx), layout));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    if (layout != 0 && layout != 1) return pt_set_error(MI3PT_ERR_INVALID, "layout must be 0 (breadth-first) or 1 (visiting order)");
-    if (int rc = require_idle(ctx)) return rc;
-    // (switching back to 0 leaves a relabelled scene on the device as it is -- it is complete and
-    // consistent -- until the BVH or the triangles are uploaded again)
-    ctx->layout = layout;
-    ctx->layout_dirty = layout != 0 && !ctx->layout_active;
-    return MI3PT_OK;
-}
-
-// The lazy scene analysis behind the culling walks (kernel variants 9 .. 14): pt::compile_walk (pt_host_compile.cpp) on the device's own
-// copies of the tree and the vertices; runs when the triangles, the tree or an option that shapes the packets changed.
-int prepare_cull(mi3pt_ctx *ctx)
-{
-    if (!ctx->cull_dirty) return MI3PT_OK;
-    const bool wanted = (ctx->variant >= 9 && ctx->variant <= 14) || (ctx->variant == 0 && ctx->cull_enabled);
-    if (!wanted || ctx->layout_active || !ctx->cull_stack_ok || ctx->env_sampling || ctx->nnodes == 0 || ctx->ntris == 0 || ctx->npackets == 0)
-        return MI3PT_OK;       // stays dirty: pick_variant falls back to the reference-counter walk
-    if (int rc = flush_pending(ctx)) return rc;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    for (int k = 0; k < 2; k++) HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[k]));
-    const size_t n = ctx->nnodes, nt = ctx->ntris;
-    std::vector<uint8_t> nodes(n * MI3PT_BVHNODE_STRIDE);
-    // the three vertices of every triangle: the first 48 of every 112 bytes of the records, packed by a small kernel (the 48-B
-    // triangle packets hold edges, not b and c; uploaded numbering -- the analysis does not run on a relabelled scene)
-    std::vector<pt::TriVerts> tris(nt);
-    HIP_TRY(hipMemcpy(nodes.data(), ctx->d_nodes, nodes.size(), hipMemcpyDeviceToHost));
-    {
-        DevBuf<float4> packed;
-        HIP_TRY(packed.alloc(nt * sizeof(pt::TriVerts)));
-        pt::launch_pack_vertices(ctx->d_tris.as<const float4>(), packed, (uint32_t)nt, ctx->stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = read_plane(ctx, packed, nt * sizeof(pt::TriVerts), tris.data());
-        if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("cull analysis: reading the vertices back: ") + hipGetErrorString(e));
-    }
-    pt::WalkOptions opt;
-    opt.collapse = ctx->collapse;
-    opt.packet_order = ctx->packet_order;
-    // (the 8-wide packets only for a context that has asked for the walk: mi3pt_set_kernel_variant(ctx, 14) marks the analysis dirty when they are missing)
-    opt.eight_wide = ctx->variant == 14;
-#ifdef MI3PT_EXPERIMENTS
-    opt.cull_scale = ctx->exp_cull_scale;
-#endif
-    DevBuf<void> *const buffer_of[] = { nullptr, &ctx->d_wide, &ctx->d_cwide, &ctx->d_tripk64, &ctx->d_cw8, &ctx->d_tripk8 };
-    auto upload = [&](pt::WalkBuffer kind, const void *data, size_t bytes) -> int {
-        if (kind != pt::WALK_CULL) return replace_buffer(ctx, *buffer_of[kind], data, bytes);
-        // the first buffer out: from here on the device no longer holds the walks' packets of the scene before
-        ctx->wide_ok = ctx->cwide_ok = ctx->cw8_ok = false;
-        DevBuf<uint32_t> d_cull;
-        HIP_TRY(d_cull.alloc(bytes));
-        hipError_t e = hipMemcpyAsync(d_cull, data, bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            pt::launch_patch_cull(ctx->d_packets.as<float4>(), d_cull, (uint32_t)ctx->npackets, ctx->stream);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = ctx_stream_sync(ctx, ctx->stream);
-        if (e != hipSuccess) return pt_set_error(MI3PT_ERR_HIP, std::string("cull analysis: ") + hipGetErrorString(e));
-        return MI3PT_OK;
-    };
-    pt::WalkCompile w;
-    if (int rc = pt::compile_walk(nodes.data(), n, tris.data(), nt, ctx->npackets, opt, upload, w)) return rc;
-    if (!w.analysed) return MI3PT_OK;       // a leaf names a triangle that was not uploaded: check_scene reports it; stays dirty
-    ctx->cull_ka = w.cull_ka; ctx->cull_kb = w.cull_kb;
-    ctx->wide_ok = w.wide_ok;
-    ctx->cwide_ok = w.cwide_ok;
-    if (w.wide_ok) {
-        ctx->nwide = w.nwide;
-        ctx->wide_leaf_cap = pt::SM_CULL_LEAF_CAP;
-        ctx->wide_root = 0;
-        ctx->wide_stack_worst = w.wide_stack_worst;
-        ctx->wide_root_nested = w.wide_root_nested;
-    }
-    ctx->cw8_ok = w.cw8_ok;
-    ctx->cw8_tried = opt.eight_wide;
-    if (w.cw8_ok) {
-        ctx->ncw8 = w.ncw8;
-        ctx->cw8_height = w.cw8_height;
-        ctx->cw8_records = w.cw8_records;
-    }
-    ctx->auto_wide_variant = w.auto_wide_variant;
-    ctx->cull_ok = true;
-    ctx->deep_by_view = false;           // (another scene: judged anew from its first launch)
-    ctx->cull_dirty = false;
-    ctx->main_dirty = true;
-    ctx->scene_epoch++;
-    ctx->host_analyses++;
-    return MI3PT_OK;
-}
-
 extern "C" int mi3pt_set_present_mode(mi3pt_ctx *ctx, int mode)
 {
     PT_GROUP(ctx, (mode == MI3PT_PRESENT_EXACT || mode == MI3PT_PRESENT_LATEST) ? MI3PT_OK : pt_set_error(MI3PT_ERR_INVALID, "mode must be MI3PT_PRESENT_EXACT or MI3PT_PRESENT_LATEST"));      // (a group always presents lazily: see group_submit_frames)
@@ -1087,1648 +600,6 @@ extern "C" int mi3pt_set_present_mode(mi3pt_ctx *ctx, int mode)
     ctx->present_mode = mode;
     ctx->presented_version = 0;
     ctx->want_present = false;
-    return MI3PT_OK;
-}
-
-// the exact-packet wide walk `auto` falls back to where compressed packets could not be built: 10, 11 or 12 by the scene's statistics
-// in the experiment build; release builds carry 10 only (11 / 12 were superseded by 13; all of them render the same bits)
-static int auto_exact_wide(const mi3pt_ctx *ctx)
-{
-#ifdef MI3PT_EXPERIMENTS
-    return ctx->auto_wide_variant;
-#else
-    (void)ctx;
-    return 10;
-#endif
-}
-
-// 0 = auto -> the persistent kernel; the probes only know the two per-ray walks.
-static int pick_variant(const mi3pt_ctx *ctx)
-{
-    if (ctx->env_sampling) return 2;               // the dormant path lives in the per-pixel kernel only
-    const bool defer_ok = ctx->leaf_cap >= 4;      // see mi3pt_upload_bvh: leaves may be tested out of order
-    const bool cull_ok = ctx->cull_stack_ok && ctx->cull_ok && !ctx->cull_dirty;     // see prepare_cull (independent of defer_ok:
-                                                                                       // the culling walks have their own stack scheme)
-    const bool wide_ok = cull_ok && ctx->wide_ok;
-    // auto: the wide walk pays once the tree no longer sits in L1 / L2 (demo scene, 2 k nodes: binary packets 10.4, wide
-    // packets 10.2 Grays/s; dragon-class 8.5 -> 8.6; 10 M-triangle forest 24 -> 21 ms per frame)
-    // ... and on COMPRESSED wide packets (13) wherever they could be built (every box nested and finite: any tree of the reference's
-    // builder): half the bytes and half the loads per node step -- 10 M-triangle forest +29 %, the 870 k-triangle scene from close
-    // up +7 %, its stated view +0.5 %, the demo scene +-0 (profiles/r04_g_cwide_ab.log); 10 / 11 / 12 stay for the trees that do not
-    // admit it and as the diagnostic twin's walk
-    if (ctx->variant == 0)
-        return cull_ok && ctx->cull_enabled ? (wide_ok && ctx->wide_enabled ? (ctx->cwide_ok ? 13 : auto_exact_wide(ctx)) : 9) : (defer_ok ? 7 : 4);
-    if (ctx->variant == 14 && cull_ok && ctx->cw8_ok) return 14;      // (its own packets and its own stack bound: independent of the 4-ary walk's)
-    if ((ctx->variant == 13 || ctx->variant == 14) && wide_ok && ctx->cwide_ok) return 13;
-    if ((ctx->variant == 13 || ctx->variant == 14) && !(wide_ok && ctx->cwide_ok)) return wide_ok ? auto_exact_wide(ctx) : (cull_ok ? 9 : (defer_ok ? 7 : 4));
-    if (ctx->variant >= 10 && ctx->variant <= 12 && !wide_ok) return cull_ok ? 9 : (defer_ok ? 7 : 4);
-    if (ctx->variant == 9 && !cull_ok) return defer_ok ? 7 : 4;
-    if ((ctx->variant == 7 || ctx->variant == 8) && !defer_ok) return ctx->variant == 8 ? 6 : 4;
-    return ctx->variant;
-}
-
-static pt::AccUniforms acc_uniforms(const mi3pt_ctx *ctx)
-{
-    pt::AccUniforms a;
-    a.res_w = ldu(ctx->u_acc, 0); a.res_h = ldu(ctx->u_acc, 4);
-    a.frame = ldu(ctx->u_acc, 8); a.enabled = ldu(ctx->u_acc, 12);
-    return a;
-}
-
-static pt::RtLaunch build_launch(const mi3pt_ctx *ctx, const uint8_t *u, const pt::AccUniforms &acc)
-{
-    pt::RtLaunch L;
-    L.scene = scene_refs(ctx);
-    L.un.res_x = ldf(u, 0); L.un.res_y = ldf(u, 4); L.un.aspect = ldf(u, 8);
-    L.un.frame = ldu(u, 12);
-    L.un.max_bounces = ldi(u, 16); L.un.samples_per_frame = ldi(u, 20);
-    for (int k = 0; k < 3; k++) { L.un.cam_pos[k] = ldf(u, 32 + 4 * k); L.un.cam_dir[k] = ldf(u, 48 + 4 * k); }
-    L.un.fov = ldf(u, 60); L.un.focal_distance = ldf(u, 64); L.un.aperture = ldf(u, 68);
-    L.un.env_intensity = ldf(u, 80); L.un.env_rotation = ldf(u, 84);
-    L.acc = acc;
-    L.tile = tile_of(ctx);
-    L.radiance = ctx->d_radiance;
-    L.slot_pixels = plane_texels(ctx);
-    L.nframes = 1;
-    L.accum = ctx->d_accum;
-    L.block_counters = ctx->d_block_counters;
-    L.tile_counter = ctx->d_tile_counter;
-    L.job_chunk = ctx->job_chunk;
-    L.job_reverse = ctx->job_reverse;
-    L.tri_pair = ctx->tri_pair;
-    L.job_group = ctx->job_group;
-    if (ctx->job_group < 0) {
-        // jobs in groups of about an eighth of a frame's tiles (whole tile rows): all frames of a launch for
-        // these tiles, then the next group -- what the waves fetch for one frame of a band of the image is
-        // still in the L2s when they trace the next frame of it (1 GPU +1.7 %, a rank of an 8-way split +4.5 %)
-        const int tiles_x = (L.tile.tex_w + 7) / 8, ntiles = tiles_x * ((L.tile.local_rows + 7) / 8);
-        const int rows = ntiles / 8 / tiles_x;
-        L.job_group = (rows < 1 ? 1 : rows) * tiles_x;
-    }
-    L.wave_times = ctx->d_wave_times;
-    L.diag_lite = ctx->diag_lite;
-    L.stack_overflow = ctx->d_stack_overflow;
-    L.store_f16 = ctx->storage == MI3PT_STORAGE_F16;
-    // walk_min: deep walks gain from a higher threshold -- more node steps between two service steps -- short ones lose
-    // (profiles/r04_o_walkmin.log, 32 / 40 / 44 / 48: forest 1 678 / 1 756 / 1 792 / 1 806 Mrays/s, the 870 k-triangle scene from
-    // close up 5 484 / 5 589 / 5 600 / 5 495, its stated view 16 110 / 16 000 / 15 930 / 15 690, demo 25 500 / 25 350 / 24 270 / 23 560):
-    // 44 for trees of a million wide packets and more (deep walks from every camera) on compressed packets, 32 otherwise -- both
-    // compile-time constants of their lean builds (as a launch parameter the threshold cost the other scenes 0.8 .. 1.5 %)
-    L.walk_min = ctx->variant == 5 ? 48 : (ctx->walk_min > 0 ? ctx->walk_min
-                                           : ((pick_variant(ctx) == 13 ? (ctx->nwide >= (1u << 20) && ctx->wide_ok && ctx->cwide_ok) : (pick_variant(ctx) == 14 && ctx->ncw8 >= (1u << 19))) ? PT_DEEP_WALK_MIN : PT_DEFAULT_WALK_MIN));
-    L.leaf_min = ctx->leaf_min;
-    L.shade_split = ctx->shade_split;
-    L.tail_policy = ctx->tail_policy;
-    L.drain_flag = nullptr;
-    L.drain_seq = 0;
-    L.waves_per_cu = ctx->waves_per_cu;
-    L.num_cus = ctx->num_cus;
-    L.service = nullptr;          // (batched launches: a slot of the context's ring, see launch_batch)
-    L.cam_base = nullptr;         // (batched launches: launch_batch)
-    L.ntiles_active = 0;          // (batched launches: launch_batch, sky_prepare)
-    L.park = ctx->d_park;
-    L.six_waves = ctx->six_waves;
-    L.tile_cost = nullptr;        // (batched launches: launch_batch)
-    L.tile_perm = nullptr;
-    L.top_packets = ctx->top_packets;
-    if (pick_variant(ctx) == 13 && (size_t)L.top_packets > ctx->nwide) L.top_packets = (int)ctx->nwide;      // (A/B builds that stage compressed packets in LDS)
-    if (pick_variant(ctx) == 1) L.scene.tris = ctx->d_tris.as<const float4>();    // uploaded records, uploaded indices
-    return L;
-}
-
-static pt::AccUniforms acc_from(const uint8_t *u)
-{
-    pt::AccUniforms a;
-    a.res_w = ldu(u, 0); a.res_h = ldu(u, 4); a.frame = ldu(u, 8); a.enabled = ldu(u, 12);
-    return a;
-}
-
-// Folds a finished batch launch's event pair into the launch statistics.
-static int collect_rt_time(mi3pt_ctx *ctx, int par)
-{
-    if (!ctx->ev_rt_pending[par]) return MI3PT_OK;
-    HIP_TRY(ctx_event_sync(ctx, ctx->ev_rt[par][1]));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_rt[par][0], ctx->ev_rt[par][1]));
-    ctx->rt_total_ms += ms;
-    ctx->rt_last_ms = ms;
-    ctx->rt_launches++;
-    ctx->rt_frames += (uint64_t)ctx->ev_rt_frames[par];
-    ctx->ev_rt_pending[par] = false;
-    return MI3PT_OK;
-}
-
-// Makes sure parity `par`'s slot set can hold n frames.  One frame: a single slot (the interactive
-// hosts never need more).  Up to eight frames: eight.  More: the full batch_cap at once, so a batching caller allocates once.
-// Growing frees the old set (hipFree waits for the device, so nothing still reads it).
-static int ensure_slots(mi3pt_ctx *ctx, int par /* slot set */, int n)
-{
-    if (ctx->slots_alloc[par] >= n) return MI3PT_OK;
-    const size_t tex_bytes = plane_bytes(ctx);
-    // one frame: one slot; up to eight: eight (a host that queues a few frames at a time does not pay for -- or wait
-    // seconds for the allocation of -- 2 x 64 ... 256 full images it never fills); more: the full launch depth at
-    // once, so that a batching caller allocates once and not again in the middle of its job
-    int want = n <= 1 ? 1 : (n <= 8 ? 8 : ctx->batch_cap);
-    if (want > ctx->batch_cap) want = ctx->batch_cap;
-    if (want > n && tex_bytes) {
-        // the cap was computed at resize; what is free NOW decides whether the full depth (for every slot set) is taken
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t fit = (free_b / 2) / ((size_t)ctx->slot_sets * tex_bytes);
-            if ((size_t)want > fit) want = fit > (size_t)n ? (int)fit : n;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (want < n) want = n;
-    DevBuf<float4> fresh;
-    hipError_t e = fresh.alloc(tex_bytes * (size_t)want);
-    if (e != hipSuccess && want > n) {          // not enough memory for the full depth: take what this batch needs
-        (void)hipGetLastError();
-        want = n;
-        e = fresh.alloc(tex_bytes * (size_t)want);
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return pt_set_error(MI3PT_ERR_HIP, std::string("radiance slots: ") + hipGetErrorString(e));
-    }
-    ctx->d_slots[par] = std::move(fresh);
-    ctx->slots_alloc[par] = want;
-    // a caller that batches deeply will need the other set(s) at the same depth with its very next launch: allocate them
-    // now, outside its steady state (the allocation of a gigabyte took ~0.4 ms of a 12 ms job otherwise)
-    if (want == ctx->batch_cap && want > 8) {
-        for (int other = 0; other < ctx->slot_sets; other++) {
-            if (other == par || ctx->slots_alloc[other] >= want) continue;
-            DevBuf<float4> more;
-            if (more.alloc(tex_bytes * (size_t)want) != hipSuccess) { (void)hipGetLastError(); break; }
-            ctx->d_slots[other] = std::move(more);
-            ctx->slots_alloc[other] = want;
-        }
-    }
-    return MI3PT_OK;
-}
-
-// The measuring launch has finished (or `wait`): build this rank's job order from the segments its tiles' paths traced, into the
-// permutation buffer that is not in use.
-static int cost_order_collect(mi3pt_ctx *ctx, bool wait)
-{
-    if (ctx->cost_state != 1) return MI3PT_OK;
-    if (!wait) {
-        const hipError_t q = hipEventQuery(ctx->cost_event);
-        if (q == hipErrorNotReady) { (void)hipGetLastError(); return MI3PT_OK; }
-        if (q != hipSuccess) { (void)hipGetLastError(); ctx->cost_state = 0; return MI3PT_OK; }
-    }
-    const size_t n = ctx->cost_tiles;
-    const int target = ctx->perm_cur ^ 1;
-    ctx->cost_state = 0;        // (whatever goes wrong below: no order, measure again)
-    std::vector<uint32_t> cost(n), perm(n);
-    HIP_TRY(hipStreamWaitEvent(ctx->cost_stream, ctx->cost_event, 0));
-    HIP_TRY(hipMemcpyAsync(cost.data(), ctx->d_tile_cost, n * 4, hipMemcpyDeviceToHost, ctx->cost_stream));
-    HIP_TRY(hipStreamSynchronize(ctx->cost_stream));
-    if (ctx->perm_used_valid[target]) HIP_TRY(hipEventSynchronize(ctx->perm_used[target]));      // (long done: two orders ago)
-    // The order: the image's tiles from the bottom row up, as without the feature (what neighbouring waves fetch stays
-    // close together: sorting ALL tiles by cost scattered them and cost 5 % -- profiles/r03_h_cost_order.log), except that
-    // the cheapest quarter of the tiles is taken out and appended: the launch's last bands are then its cheapest tiles
-    // wherever they lie in the image.
-    std::vector<uint32_t> sorted(cost);
-    const size_t q = n / 4;
-    std::nth_element(sorted.begin(), sorted.begin() + (std::ptrdiff_t)q, sorted.end());
-    const uint32_t cut = sorted[q];          // tiles cheaper than this go last (ties stay in the main part)
-    size_t at = 0;
-    if (ctx->cost_order == 2) {
-        // every tile, costliest first (ties in image order): what a launch of ONE frame wants -- its time is its work plus its
-        // longest paths' dependent chains, which then start at once instead of when their tile's turn comes
-        for (size_t t = 0; t < n; t++) perm[t] = (uint32_t)t;
-        std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-        at = n;
-    } else {
-        for (size_t t = n; t-- > 0;) if (cost[t] >= cut) perm[at++] = (uint32_t)t;
-        for (size_t t = n; t-- > 0;) if (cost[t] < cut) perm[at++] = (uint32_t)t;
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->d_tile_perm[target], perm.data(), n * 4, hipMemcpyHostToDevice, ctx->cost_stream));
-    HIP_TRY(hipStreamSynchronize(ctx->cost_stream));
-    ctx->perm_cur = target;
-    ctx->cost_state = 2;
-    return MI3PT_OK;
-}
-
-// Sets the launch's cost-order fields; `*measuring` / `*ordered`: what to record behind the launch.
-static int cost_order_prepare(mi3pt_ctx *ctx, pt::RtLaunch &L, const uint8_t *u_rt, int variant, hipStream_t rs, bool *measuring, bool *ordered)
-{
-    *measuring = *ordered = false;
-    const size_t n = (size_t)pt::raytrace_grid_blocks(L.tile);
-    if (!ctx->cost_order || variant < 9 || variant > 13 || L.un.samples_per_frame != 1 || n < 2) return MI3PT_OK;
-    uint8_t key[MI3PT_RAYTRACE_UNIFORMS_SIZE];
-    std::memcpy(key, u_rt, sizeof key);
-    std::memset(key + 12, 0, 4);          // the frame counter
-    if (ctx->cost_tiles != n) {           // (resize / tile change: new arrays)
-        HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[0]));
-        HIP_TRY(ctx_stream_sync(ctx, ctx->rt_stream[1]));
-        for (DevBuf<uint32_t> *q : { &ctx->d_tile_cost, &ctx->d_tile_perm[0], &ctx->d_tile_perm[1] })
-            HIP_TRY(q->alloc(n * 4));
-        ctx->cost_tiles = n;
-        ctx->cost_state = 0;
-        ctx->perm_used_valid[0] = ctx->perm_used_valid[1] = false;
-    }
-    if (ctx->cost_state != 0 && std::memcmp(key, ctx->cost_key, sizeof key) != 0) ctx->cost_state = 0;      // the camera moved, bounces changed ...
-    if (int rc = cost_order_collect(ctx, false)) return rc;
-    if (ctx->cost_state == 0) {
-        std::memcpy(ctx->cost_key, key, sizeof key);
-        HIP_TRY(hipMemsetAsync(ctx->d_tile_cost, 0, n * 4, rs));
-        L.tile_cost = ctx->d_tile_cost;
-        *measuring = true;
-    } else if (ctx->cost_state == 2) {
-        L.tile_perm = ctx->d_tile_perm[ctx->perm_cur];
-        L.job_reverse = 0;                // the order is the permutation's: costliest first
-        *ordered = true;
-    }
-    return MI3PT_OK;
-}
-
-// One launch: frames [first, first + n) of the queue as one raytrace kernel over (frame slot,
-// tile) jobs on this parity's side stream, then the ordered multi-frame running mean on the
-// main stream.
-static int run_fullscreen(mi3pt_ctx *ctx, const uint8_t *u_fs);
-
-// The walk threshold by the view: reads what the most recent launch that has reported cost per ray (no wait: whatever has arrived).
-#define WALK_ADAPT_ENTER 40.0
-#define WALK_ADAPT_LEAVE 30.0
-static void adapt_walk(mi3pt_ctx *ctx)
-{
-    if (!ctx->walk_adapt || !ctx->h_walk_stats) { ctx->deep_by_view = false; return; }
-    volatile uint64_t *h = ctx->h_walk_stats;
-    uint64_t best_seq = ctx->walk_stats_seen, box = 0, rays = 0;
-    for (int par = 0; par < 2; par++) {
-        const uint64_t s0 = __atomic_load_n(&ctx->h_walk_stats[4 * par], __ATOMIC_ACQUIRE);
-        const uint64_t b = h[4 * par + 1], r = h[4 * par + 2];
-        const uint64_t s1 = __atomic_load_n(&ctx->h_walk_stats[4 * par], __ATOMIC_ACQUIRE);
-        if (s0 == s1 && s0 > best_seq && s0 <= ctx->walk_stats_seq) { best_seq = s0; box = b; rays = r; }
-    }
-    if (best_seq == ctx->walk_stats_seen) return;
-    ctx->walk_stats_seen = best_seq;
-    if (rays < 65536) return;              // (too small a launch to judge a view by)
-    const double per_ray = (double)box / (double)rays;
-    if (per_ray >= WALK_ADAPT_ENTER) ctx->deep_by_view = true;
-    else if (per_ray <= WALK_ADAPT_LEAVE) ctx->deep_by_view = false;
-}
-
-// The empty tiles of this launch's view: sets L.tile_perm / L.ntiles_active to the list of the other tiles and returns the device list
-// of the empty ones through *sky_list / *sky_count / *sky_samples (0: every tile is traced, the launch is what it was).  The split is
-// used by the lean builds of the culling walks only (variants 9 - 14: their box-test counter is not pinned; 1 - 8 keep the oracle's exact
-// counts and so trace every tile; the diagnostic twins and the per-pixel kernels keep tracing every pixel -- they are the on-device
-// check), with the camera base at hand, without a cost order.  The host's classification (a millisecond or two at 1080p) runs at
-// once for a launch of SKY_MIN_FRAMES frames or more, which hides it; a shallower launch -- an interactive host -- gets it once its camera
-// has stood still for a launch, so that a host that moves the camera every frame never pays for it.
-// With a sample mask (mi3pt_set_sample_mask) the same list carries the mask: [A: sampled and not empty | S: sampled and empty], composed by
-// pt::compose_tile_lists -- the persistent kernel gets A wherever the launch can take a list (the conditions above but for the ones the
-// empty tiles alone need: the cut, the camera base, two tiles or more), k_sky_samples gets S, and the ordered mean (k_accumulate_tiles)
-// gets all of it through *acc_list / *acc_count on EVERY route.  Without a classification S is empty; with A empty S is the job list.
-#define SKY_MIN_FRAMES 8
-static void tile_key_of(const pt::Tile &tile, uint64_t mask_epoch, uint8_t key[104])
-{
-    const int32_t tl[6] = { tile.tex_w, tile.tex_h, tile.local_rows, tile.rank, tile.nranks, tile.block_rows };
-    std::memcpy(key + 60, tl, sizeof tl);
-    std::memcpy(key + 96, &mask_epoch, 8);
-}
-
-// ctx->sky_host = the lists for `key` (the mask as it stands; the classification in ctx->sky_empty if `classified`)
-static void tile_lists_compose(mi3pt_ctx *ctx, const pt::Tile &tile, const uint8_t *u_rt, const uint8_t *key, bool classified)
-{
-    if (ctx->sky_list_valid && std::memcmp(key, ctx->sky_list_key, sizeof ctx->sky_list_key) == 0) return;
-    // the in-bounds pixels of the empty tiles (the refill's test, raytrace.wgsl:425-427): each is one ray, one miss, one pixel per frame
-    const double rx = u_rt ? ldf(u_rt, 0) : 0.0, ry = u_rt ? ldf(u_rt, 4) : 0.0;
-    pt::TileListInput in;
-    in.tex_w = tile.tex_w; in.tex_h = tile.tex_h; in.local_rows = tile.local_rows;
-    in.rank = tile.rank; in.nranks = tile.nranks; in.block_rows = tile.block_rows;
-    in.res_w = rx >= 1.0 ? (long long)std::min(rx, 4294967295.0) : 0;
-    in.res_h = ry >= 1.0 ? (long long)std::min(ry, 4294967295.0) : 0;
-    pt::TileLists out;
-    pt::compose_tile_lists(in, ctx->mask.empty() ? nullptr : ctx->mask.data(), classified ? ctx->sky_empty.data() : nullptr, out);
-    ctx->sky_host.swap(out.list);
-    ctx->sky_host_active = out.active;
-    ctx->sky_host_sky = out.sky;
-    ctx->sky_host_pixels = out.sky_pixels;
-    std::memcpy(ctx->sky_list_key, key, sizeof ctx->sky_list_key);
-    ctx->sky_list_valid = true;
-}
-
-// lists[slot] = ctx->sky_host (composed for `key`), copied on `s` unless the slot holds that list already.  *staged = false: no
-// memory for it (an unmasked launch then stays whole; under a mask the ordered mean cannot do without: `required`)
-static int tile_lists_stage(mi3pt_ctx *ctx, int slot, const uint8_t *key, size_t ntiles, hipStream_t s, bool required, bool *staged)
-{
-    *staged = true;
-    TileList &t = ctx->lists[slot];
-    if (t.dev_valid && std::memcmp(key, t.dev_key, sizeof t.dev_key) == 0) return MI3PT_OK;
-    if (!t.copied) HIP_TRY(hipEventCreateWithFlags(t.copied.put(), hipEventDisableTiming));
-    if (t.copied_valid) HIP_TRY(hipEventSynchronize(t.copied));      // (long done: this slot's previous list)
-    if (t.cap < ntiles) {
-        DevBuf<uint32_t> fresh;
-        if (fresh.alloc(ntiles * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            *staged = false;
-            return required ? pt_set_error(MI3PT_ERR_HIP, "no device memory for the sample mask's tile list") : MI3PT_OK;
-        }
-        t.d_list = std::move(fresh);          // (hipFree waits for the device: nothing still reads the old one)
-        t.cap = ntiles;
-    }
-    t.dev_valid = false;
-    t.staged = ctx->sky_host;
-    // (an ordered mean of an earlier launch may still read the slot's list from the context's stream)
-    if (t.read_valid) HIP_TRY(hipStreamWaitEvent(s, t.read, 0));
-    if (!t.staged.empty())
-        HIP_TRY(hipMemcpyAsync(t.d_list, t.staged.data(), t.staged.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(t.copied, s));
-    t.copied_valid = true;
-    std::memcpy(t.dev_key, key, sizeof t.dev_key);
-    t.dev_valid = true;
-    return MI3PT_OK;
-}
-
-static int sky_prepare(mi3pt_ctx *ctx, pt::RtLaunch &L, const uint8_t *u_rt, int par, int n, hipStream_t rs,
-                       const uint32_t **sky_list, int *sky_count, uint64_t *sky_samples, const uint32_t **acc_list, int *acc_count)
-{
-    *sky_list = nullptr; *sky_count = 0; *sky_samples = 0;
-    *acc_list = nullptr; *acc_count = 0;
-    const bool masked = !ctx->mask.empty();
-    const pt::RtRoute &r = ctx->last_route;
-    const int ntiles = pt::raytrace_grid_blocks(L.tile);
-    const bool takes_list = !L.tile_perm && !L.tile_cost && r.kind == 1 && r.lean && r.variant >= 9 && r.variant <= 14;
-    const bool sky_ok = takes_list && ctx->sky_tiles && ctx->sky_cut_ok && !ctx->env_sampling && L.cam_base && ntiles >= 2;
-    if (!masked && !sky_ok) return MI3PT_OK;
-    uint8_t key[104];
-    std::memset(key, 0, sizeof key);
-    bool classified = false;
-    if (sky_ok) {
-        std::memcpy(key, u_rt, 12);                       // resolution, aspect
-        std::memcpy(key + 12, u_rt + 32, 40);             // camera position, direction, fov, focal distance, aperture (32 .. 72)
-        std::memcpy(key + 52, u_rt + 16, 8);              // maxBounces, samplesPerFrame
-        tile_key_of(L.tile, 0, key);
-        std::memcpy(key + 88, &ctx->scene_epoch, 8);
-        classified = true;
-        if (!ctx->sky_host_valid || std::memcmp(key, ctx->sky_key, sizeof key) != 0) {
-            const bool stood_still = std::memcmp(key, ctx->sky_seen_key, sizeof key) == 0;
-            std::memcpy(ctx->sky_seen_key, key, sizeof key);
-            if (n < SKY_MIN_FRAMES && !stood_still) {
-                classified = false;
-            } else {
-                (void)pt::sky_classify(ctx->sky_cut, true, u_rt, L.tile.tex_w, L.tile.local_rows, L.tile.tex_h,
-                                       L.tile.rank, L.tile.nranks, L.tile.block_rows, ctx->sky_empty);
-                std::memcpy(ctx->sky_key, key, sizeof key);
-                ctx->sky_host_valid = true;
-            }
-        }
-        if (!classified) {
-            if (!masked) return MI3PT_OK;
-            std::memset(key, 0, sizeof key);              // (the list of the mask alone)
-        }
-    }
-    tile_key_of(L.tile, ctx->mask_epoch, key);
-    tile_lists_compose(ctx, L.tile, u_rt, key, classified);
-    const int active = ctx->sky_host_active, nsky = ctx->sky_host_sky;
-    if (!masked && (nsky <= 0 || active <= 0)) return MI3PT_OK;          // (nothing to take out -- or nothing left: such a launch stays whole)
-    if (active + nsky == 0) return MI3PT_OK;                             // (no tile is sampled: launch_batch launches nothing)
-    bool staged = false;
-    if (int rc = tile_lists_stage(ctx, par, key, (size_t)ntiles, rs, masked, &staged)) return rc;
-    if (!staged) return MI3PT_OK;                                        // no memory: no split
-    if (takes_list && active == 0) {                  // only empty tiles are sampled: they are the job list, no sky kernel
-        L.tile_perm = ctx->lists[par].d_list;
-        L.ntiles_active = nsky;
-    } else if (takes_list && (nsky > 0 || active < ntiles)) {
-        L.tile_perm = ctx->lists[par].d_list;
-        L.ntiles_active = active;
-        if (nsky > 0) {
-            *sky_list = ctx->lists[par].d_list + active;
-            *sky_count = nsky;
-            *sky_samples = ctx->sky_host_pixels * (uint64_t)n;
-        }
-    }
-    if (masked) {
-        *acc_list = ctx->lists[par].d_list;
-        *acc_count = active + nsky;
-    }
-    return MI3PT_OK;
-}
-
-// The list of the sampled tiles for an ordered mean that runs at once on the context's stream (mi3pt_submit's immediate path): slot 2
-static int mask_list_main(mi3pt_ctx *ctx, const pt::Tile &tile, const uint32_t **list, int *count)
-{
-    *list = nullptr; *count = 0;
-    uint8_t key[104];
-    std::memset(key, 0, sizeof key);
-    tile_key_of(tile, ctx->mask_epoch, key);
-    tile_lists_compose(ctx, tile, nullptr, key, false);
-    if (ctx->sky_host_active == 0) return MI3PT_OK;
-    bool staged = false;
-    if (int rc = tile_lists_stage(ctx, 2, key, (size_t)pt::raytrace_grid_blocks(tile), ctx->stream, true, &staged)) return rc;
-    *list = ctx->lists[2].d_list;
-    *count = ctx->sky_host_active;
-    return MI3PT_OK;
-}
-
-// behind an ordered mean that read lists[slot]
-static int mask_list_used(mi3pt_ctx *ctx, int slot)
-{
-    TileList &t = ctx->lists[slot];
-    if (!t.read) HIP_TRY(hipEventCreateWithFlags(t.read.put(), hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(t.read, ctx->stream));
-    t.read_valid = true;
-    return MI3PT_OK;
-}
-
-static int launch_batch(mi3pt_ctx *ctx, const mi3pt_ctx::PendingFrame *frames, int n)
-{
-    adapt_walk(ctx);
-    const mi3pt_ctx::PendingFrame &first = frames[0];
-    const pt::AccUniforms acc = acc_from(first.u_acc);
-    pt::RtLaunch L = build_launch(ctx, first.u_rt, acc);
-    const int variant = pick_variant(ctx);
-    const bool f16 = ctx->storage == MI3PT_STORAGE_F16;
-    const int par = (int)(ctx->seq & 1u);                        // stream, counters, queue head
-    const int set = (int)(ctx->seq % (uint64_t)ctx->slot_sets);   // radiance slots
-    if (int rc = ensure_slots(ctx, set, n)) {
-        // a single slot always fits where the textures did; fall back to it before giving up
-        if (n == 1 || ensure_slots(ctx, set, 1) != MI3PT_OK) return rc;
-        ctx->batch_cap = 1;
-        return MI3PT_ERR_STATE;      // caller re-chunks with the smaller cap
-    }
-    ctx->seq++;
-    hipStream_t rs = ctx->rt_stream[par];
-    if (ctx->main_dirty) {      // resets / rebinds queued on the main stream come first
-        HIP_TRY(hipEventRecord(ctx->main_mark, ctx->stream));
-        HIP_TRY(hipStreamWaitEvent(ctx->rt_stream[0], ctx->main_mark, 0));
-        HIP_TRY(hipStreamWaitEvent(ctx->rt_stream[1], ctx->main_mark, 0));
-        ctx->main_dirty = false;
-    }
-    // the ordered mean that last read this set of radiance slots (three batches ago) must be done
-    if (ctx->acc_done_valid[set]) HIP_TRY(hipStreamWaitEvent(rs, ctx->acc_done[set], 0));
-    L.radiance = ctx->d_slots[set];
-    L.nframes = n;
-    L.block_counters = ctx->d_block_counters + (size_t)par * ctx->nblocks * pt::CNT_COUNT;
-    L.tile_counter = ctx->d_tile_counter + par * 32;
-    L.stack_overflow = ctx->d_stack_overflow + (size_t)par * pt::PT_MAX_RESIDENT_WAVES * pt::SM_OVERFLOW_ENTRIES * 64;
-    L.park = ctx->d_park + (size_t)par * pt::PT_MAX_RESIDENT_WAVES * 6 * 64;
-    L.service = reinterpret_cast<pt::RtService *>(ctx->d_service + (size_t)((ctx->seq - 1) % SERVICE_SLOTS) * service_slot_bytes());
-    bool cost_measuring = false, cost_ordered = false;
-    if (int rc = cost_order_prepare(ctx, L, first.u_rt, variant, rs, &cost_measuring, &cost_ordered)) return rc;
-    if (ctx->timing)
-        if (int rc = collect_rt_time(ctx, par)) return rc;      // the launch of two batches ago
-    // Hold this launch until the previous one (on the other stream) has handed out its last job:
-    // its persistent waves then start to exit, and this launch's workgroups take the slots they
-    // free.  Enqueued earlier, the kernel would sit in the dispatcher for the previous launch's
-    // whole run -- same throughput, but event / profiler durations twice the execution time.
-    const uint32_t seq_before = ctx->launch_seq;
-    // (under a sample mask with no sampled tile -- mi3pt_set_sample_mask -- nothing is launched either: no raytrace, sky or accumulate kernel,
-    // and, like the empty tile, no sequence number is taken at the gate, so no later launch waits for a mark nobody publishes)
-    const bool masked = !ctx->mask.empty(), none_sampled = masked && ctx->mask_sampled == 0;
-    const bool launches = pt::raytrace_grid_blocks(L.tile) > 0 && !none_sampled;       // (an empty tile launches nothing)
-    // Only the state-machine kernel publishes a drain mark (pt_kernels.hip, the ticket draw).  A batch routed to the per-pixel
-    // kernels -- launches beyond the packing limits, maxBounces >= 65536 -- gets its mark from the host side of its stream after
-    // its last frame: left to a kernel that never stores it, the NEXT batch would wait for ever (round-4 advice).
-    ctx->last_route = pt::raytrace_route(L, variant);          // (does not depend on the two fields set below)
-    uint32_t publish_after = 0;
-    if (ctx->gate_enabled && launches) {
-        if (ctx->launch_seq != 0 &&
-            hipStreamWaitValue32(rs, ctx->d_drain_flag, ctx->launch_seq, hipStreamWaitValueGte, 0xffffffffu) != hipSuccess) {
-            // no stream memory operations here: launches simply queue behind each other from now on
-            (void)hipGetLastError();
-            ctx->gate_enabled = false;
-        } else if (ctx->last_route.kind == 1) {
-            ++ctx->launch_seq;
-            if (!ctx->debug_suppress_drain) { L.drain_flag = ctx->d_drain_flag; L.drain_seq = ctx->launch_seq; }
-        } else {
-            publish_after = ++ctx->launch_seq;
-        }
-    }
-    // The pixel-only part of the camera rays (RtLaunch::cam_base), formed once per camera / size / tile for this parity's stream:
-    // every frame of every later launch with the same camera loads it.  A host that moves the camera per frame pays one
-    // full-width pass over the pixels per launch instead of the same arithmetic at ~30 of 64 lanes inside the launch.
-    if (ctx->cam_base_enabled && ctx->last_route.kind == 1 && launches) {
-        uint8_t key[80];
-        std::memset(key, 0, sizeof key);
-        std::memcpy(key, first.u_rt, 12);                 // resolution, aspect
-        std::memcpy(key + 12, first.u_rt + 32, 36);       // camera position, direction, fov, focal distance (32 .. 68)
-        const int32_t tl[6] = { L.tile.tex_w, L.tile.tex_h, L.tile.local_rows, L.tile.rank, L.tile.nranks, L.tile.block_rows };
-        std::memcpy(key + 48, tl, sizeof tl);
-        if (!ctx->d_cam_base[par]) {
-            if (ctx->d_cam_base[par].alloc(L.slot_pixels * sizeof(float4)) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->cam_base_enabled = false;            // no memory for it: the kernel forms the rays itself, as before
-            }
-            ctx->cam_base_valid[par] = false;
-        }
-        if (ctx->d_cam_base[par]) {
-            if (!ctx->cam_base_valid[par] || std::memcmp(key, ctx->cam_base_key[par], sizeof key) != 0) {
-                pt::launch_camera_base(L, ctx->d_cam_base[par], rs);
-                std::memcpy(ctx->cam_base_key[par], key, sizeof key);
-                ctx->cam_base_valid[par] = true;
-            }
-            L.cam_base = ctx->d_cam_base[par];
-        }
-    }
-    // the tiles whose camera rays reach no geometry leave the job list
-    const uint32_t *sky_list = nullptr;
-    int sky_count = 0;
-    uint64_t sky_samples = 0;
-    const uint32_t *acc_list = nullptr;      // under a sample mask: the sampled tiles, for the ordered mean
-    int acc_count = 0;
-    if (launches)
-        if (int rc = sky_prepare(ctx, L, first.u_rt, par, n, rs, &sky_list, &sky_count, &sky_samples, &acc_list, &acc_count)) return rc;
-    // the walk threshold by the view (adapt_walk): the deep-walk build for a launch of the shipped walk long enough to run its six-wave form
-    // (>= 250 k jobs: a short launch -- an interactive host's single frames -- is all ramp and drain, and keeps the ordinary build.  Counted in
-    // tiles of the FRAME, empty ones included: which of the two builds a view gets does not depend on how much sky it shows --
-    // tests/test_gpu_configs.py::test_walk_threshold_follows_the_view pins the sequence; the grid and the six-wave choice count the real jobs)
-    if (ctx->deep_by_view && ctx->walk_min == 0 && L.walk_min == PT_DEFAULT_WALK_MIN && variant == 13 &&
-        (long long)pt::raytrace_grid_blocks(L.tile) * n >= 250000)
-        L.walk_min = PT_DEEP_WALK_MIN;
-    ctx->last_route = pt::raytrace_route(L, variant);          // (the grid and the build follow the number of jobs)
-    if (!none_sampled) pt::launch_raytrace_setup(L, ctx->last_route, rs);
-    if (ctx->timing) {
-        HIP_TRY(hipEventRecord(ctx->ev_rt[par][0], rs));
-        if (!ctx->span_started) { HIP_TRY(hipEventRecord(ctx->ev_span_start, rs)); ctx->span_started = true; }
-    }
-    // (in front of the persistent kernel: it runs while the predecessor's last paths drain -- +0.4 % over behind it, where it would follow this
-    // launch's own drain: profiles/sky_tiles_ab.log)
-    if (sky_count && ctx->sky_tiles != 2) pt::launch_sky_samples(L, sky_list, sky_count, sky_samples, rs);
-    if (!none_sampled) pt::launch_raytrace(L, ctx->last_route, false, rs);
-    if (sky_count && ctx->sky_tiles == 2) pt::launch_sky_samples(L, sky_list, sky_count, sky_samples, rs);
-    if (publish_after && !ctx->debug_suppress_drain && hipStreamWriteValue32(rs, ctx->d_drain_flag, publish_after, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->gate_enabled = false;          // (the next batch enqueues no wait; a batch already held is released by ctx_wait)
-    }
-    if (cost_measuring && launches) { HIP_TRY(hipEventRecord(ctx->cost_event, rs)); ctx->cost_state = 1; }
-    if (cost_ordered && launches) { HIP_TRY(hipEventRecord(ctx->perm_used[ctx->perm_cur], rs)); ctx->perm_used_valid[ctx->perm_cur] = true; }
-    if (hipError_t e = hipGetLastError()) {
-        // The kernel that would have published drain_seq never ran: publish it from the host side
-        // of the stream instead, so that neither a later launch nor mi3pt_destroy waits for it.
-        if (ctx->launch_seq != seq_before && hipStreamWriteValue32(rs, ctx->d_drain_flag, ctx->launch_seq, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->launch_seq = seq_before;
-            ctx->gate_enabled = false;
-        }
-        return pt_set_error(MI3PT_ERR_HIP, std::string("raytrace launch: ") + hipGetErrorString(e));
-    }
-    if (ctx->timing) {
-        HIP_TRY(hipEventRecord(ctx->ev_rt[par][1], rs));
-        ctx->ev_rt_pending[par] = true;
-        ctx->ev_rt_frames[par] = n;
-        ctx->ev_rt_newest = par;
-    }
-    // what this launch cost per ray, for the choice of a later launch's build (adapt_walk): behind the launch on its own stream, in front of the
-    // event the ordered mean waits for -- the report is there at every sync point (the rays of the empty tiles' samples are in the same counter set)
-    if (ctx->walk_adapt && ctx->h_walk_stats && launches && ctx->last_route.kind == 1 && ctx->last_route.lean && ctx->last_route.variant == 13 && ctx->walk_min == 0) {
-        pt::launch_walk_stats(L.block_counters, ctx->nblocks, ctx->d_walk_prev + 2 * par, ctx->d_walk_stats + 4 * par, ++ctx->walk_stats_seq, rs);
-        (void)hipGetLastError();
-    }
-    HIP_TRY(hipEventRecord(ctx->rt_done[par], rs));
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->rt_done[par], 0));
-    // The ordered mean, a run of frames at a time: a run ends with a frame whose canvas is wanted (EXACT presentation) or
-    // with the launch -- all n frames in one pass unless frames present, one pass + one fullscreen pass per presenting frame.
-    ctx->last_radiance = L.radiance + (size_t)(n - 1) * L.slot_pixels;
-    ctx->output_is_accum = true;
-    for (int k = 0; k < n;) {
-        int e = k;
-        while (e < n - 1 && !frames[e].present) e++;
-        const bool last_run = e == n - 1;
-        pt::AccUniforms a = acc;
-        a.frame = acc.frame + (uint32_t)k;
-        if (ctx->timing && last_run) HIP_TRY(ctx->pass_timer[1].begin(ctx->stream));
-        if (masked) {        // the sampled tiles only: a frozen tile's mean and moments keep their bits
-            pt::launch_accumulate_tiles(a, L.tile, acc_list, acc_count, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum,
-                                        ctx->d_moments, f16, ctx->by_count, ctx->stream);
-        } else {
-            pt::launch_accumulate_frames(a, L.tile, L.radiance + (size_t)k * L.slot_pixels, L.slot_pixels, e - k + 1, ctx->d_accum, ctx->d_moments, f16, ctx->by_count, 4096, ctx->stream);
-        }
-        HIP_TRY(hipGetLastError());
-        if (ctx->timing && last_run) HIP_TRY(ctx->pass_timer[1].end(ctx->stream));
-        ctx->accum_version++;
-        if (frames[e].present)
-            if (int rc = run_fullscreen(ctx, frames[e].u_fs)) return rc;
-        k = e + 1;
-    }
-    if (masked && acc_count)
-        if (int rc = mask_list_used(ctx, par)) return rc;
-    HIP_TRY(hipEventRecord(ctx->acc_done[set], ctx->stream));
-    ctx->acc_done_valid[set] = true;
-    return MI3PT_OK;
-}
-
-// Launches everything that is queued, batch_cap frames at a time.  The queue is emptied even on
-// failure (the frames are lost with the error; the context stays usable).
-static int flush_pending(mi3pt_ctx *ctx)
-{
-    if (ctx->pending.empty()) return MI3PT_OK;
-    std::vector<mi3pt_ctx::PendingFrame> q;
-    q.swap(ctx->pending);
-    size_t at = 0;
-    while (at < q.size()) {
-        int n = (int)(q.size() - at);
-        if (n > ctx->batch_cap) n = ctx->batch_cap;
-        const int rc = launch_batch(ctx, &q[at], n);
-        if (rc == MI3PT_ERR_STATE && n > 1) continue;       // the slot memory shrank batch_cap: retry smaller
-        if (rc != MI3PT_OK) return rc;
-        at += (size_t)n;
-    }
-    return MI3PT_OK;
-}
-
-// Every entry point that observes or changes device state goes through this.
-int require_idle(mi3pt_ctx *ctx)
-{
-    if (int rc = require_ctx(ctx)) return rc;
-    return flush_pending(ctx);
-}
-
-// Can `next` join the queued frames?  Same uniforms, consecutive frame numbers.
-static bool batch_compatible(const mi3pt_ctx::PendingFrame &last, const mi3pt_ctx::PendingFrame &next)
-{
-    if (std::memcmp(last.u_rt, next.u_rt, 12) || std::memcmp(last.u_rt + 16, next.u_rt + 16, 80)) return false;
-    if (std::memcmp(last.u_acc, next.u_acc, 8) || std::memcmp(last.u_acc + 12, next.u_acc + 12, 4)) return false;
-    return ldu(next.u_rt, 12) == ldu(last.u_rt, 12) + 1u && ldu(next.u_acc, 8) == ldu(last.u_acc, 8) + 1u;
-}
-
-static int run_fullscreen(mi3pt_ctx *ctx, const uint8_t *u_fs)
-{
-    pt::FsUniforms fs;
-    fs.res_x = ldf(u_fs, 0); fs.res_y = ldf(u_fs, 4); fs.aspect = ldf(u_fs, 8);
-    fs.scaling = ldf(u_fs, 12); fs.denoise = ldu(u_fs, 16); fs.tonemapping = ldu(u_fs, 20);
-    const float4 *tex = ctx->output_is_accum ? ctx->d_accum : ctx->last_radiance;
-    if (ctx->timing) HIP_TRY(ctx->pass_timer[2].begin(ctx->stream));
-    // (bit patterns compared: a NaN uniform must not rebuild the table every frame, and -0 is not +0 for a quotient)
-    const bool taps_current = ctx->fs_taps_valid && std::memcmp(ctx->fs_taps_res, &fs.res_x, 4) == 0 && std::memcmp(ctx->fs_taps_res + 1, &fs.res_y, 4) == 0;
-    pt::launch_fullscreen(fs, tex, ctx->width, ctx->height, ctx->width, ctx->height, ctx->d_fs_taps, taps_current, ctx->d_canvas,
-                          ctx->d_canvas8, ctx->stream);
-    if (hipError_t e = hipGetLastError()) {
-        ctx->fs_taps_valid = false;
-        return pt_set_error(MI3PT_ERR_HIP, std::string("fullscreen launch: ") + hipGetErrorString(e));
-    }
-    if (fs.denoise == 1u) { ctx->fs_taps_res[0] = fs.res_x; ctx->fs_taps_res[1] = fs.res_y; ctx->fs_taps_valid = true; }
-    if (ctx->timing) HIP_TRY(ctx->pass_timer[2].end(ctx->stream));
-    ctx->presented_version = ctx->accum_version;
-    std::memcpy(ctx->presented_fs, u_fs, sizeof ctx->presented_fs);
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_submit(mi3pt_ctx *ctx, unsigned pass_mask)
-{
-    PT_GROUP(ctx, group_submit_frames(ctx, pass_mask, 1));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "submit before resize");
-    if (pass_mask & ~(MI3PT_SUBMIT_RAYTRACE | MI3PT_SUBMIT_ACCUMULATE | MI3PT_SUBMIT_FULLSCREEN))
-        return pt_set_error(MI3PT_ERR_INVALID, "unknown bits in pass_mask");
-    const bool do_rt = pass_mask & MI3PT_SUBMIT_RAYTRACE, do_acc = pass_mask & MI3PT_SUBMIT_ACCUMULATE;
-    const bool do_fs = pass_mask & MI3PT_SUBMIT_FULLSCREEN;
-    if (do_fs && ctx->partial())
-        return pt_set_error(MI3PT_ERR_STATE,
-                            "the fullscreen pass needs the whole image: gather the tiles into a 1-rank context");
-    if (do_rt) {
-        if (int rc = check_scene(ctx)) return rc;
-        if (int rc = prepare_layout(ctx)) return rc;    // (no-ops unless the scene changed)
-        if (int rc = prepare_cull(ctx)) return rc;
-    }
-    const pt::Tile tile = tile_of(ctx);
-    const pt::AccUniforms acc = acc_uniforms(ctx);
-    const bool f16 = ctx->storage == MI3PT_STORAGE_F16;
-    const int variant = pick_variant(ctx);
-    const bool same_region = acc.res_w == (uint32_t)ldf(ctx->u_rt, 0) && acc.res_h == (uint32_t)ldf(ctx->u_rt, 4);
-    const bool lazy_present = ctx->present_mode == MI3PT_PRESENT_LATEST;
-    bool acc_done = false, drawn_with_frame = false;
-
-    if (do_rt && do_acc && same_region && ctx->pipeline && variant >= 4) {
-        // queued: runs with its neighbours as one batch (see flush_pending)
-        mi3pt_ctx::PendingFrame f;
-        std::memcpy(f.u_rt, ctx->u_rt, sizeof f.u_rt);
-        std::memcpy(f.u_acc, ctx->u_acc, sizeof f.u_acc);
-        if (!ctx->pending.empty() && !batch_compatible(ctx->pending.back(), f))
-            if (int rc = flush_pending(ctx)) return rc;
-        if (ctx->pending.empty()) for (PassTimer &t : ctx->pass_timer) t.forget();
-        int depth = ctx->batch_cap;
-        if (do_fs && !lazy_present) {          // EXACT: this frame's canvas is drawn behind its mean (launch_batch)
-            f.present = true;
-            std::memcpy(f.u_fs, ctx->u_fs, sizeof f.u_fs);
-            if (depth > ctx->present_depth) depth = ctx->present_depth;
-            drawn_with_frame = true;
-        }
-        ctx->pending.push_back(f);
-        if ((int)ctx->pending.size() >= depth)
-            if (int rc = flush_pending(ctx)) return rc;
-        acc_done = true;
-    } else {
-        if (int rc = flush_pending(ctx)) return rc;      // anything but a queued frame runs after the queue
-        for (PassTimer &t : ctx->pass_timer) t.forget();
-        if (do_rt) {
-            pt::RtLaunch L = build_launch(ctx, ctx->u_rt, acc);
-            // Fuse when the accumulate pass covers exactly the pixels the raytrace pass writes (the per-pixel kernels; the
-            // state-machine kernel writes the frame's radiance and the accumulate pass follows as a kernel of its own: same bits).
-            // (not with the moments image: the per-pixel kernels do not keep it, the two passes run separately -- same bits)
-            // (nor under a sample mask: the fused kernels step every texel)
-            const bool fused = do_acc && same_region && pt::raytrace_variant_fuses(variant) && !ctx->d_moments && ctx->mask.empty();
-            // (the service block of a launch that runs at once: its own slot -- launches on the main stream follow each other,
-            // and the batches launched before it are waited for by this stream)
-            L.service = reinterpret_cast<pt::RtService *>(ctx->d_service + (size_t)SERVICE_SLOTS * service_slot_bytes());
-            L.block_counters = ctx->d_block_counters;
-            ctx->last_route = pt::raytrace_route(L, variant);
-            pt::launch_raytrace_setup(L, ctx->last_route, ctx->stream);
-            if (ctx->timing) HIP_TRY(ctx->pass_timer[0].begin(ctx->stream));
-            pt::launch_raytrace(L, ctx->last_route, fused, ctx->stream);
-            HIP_TRY(hipGetLastError());
-            if (ctx->timing) HIP_TRY(ctx->pass_timer[0].end(ctx->stream));
-            ctx->last_radiance = ctx->d_radiance;
-            ctx->output_is_accum = fused;
-            ctx->main_dirty = true;     // a later batch must not overtake this kernel
-            ctx->accum_version++;
-            acc_done = fused;
-        }
-    }
-    if (do_acc && !acc_done) {
-        if (ctx->timing) HIP_TRY(ctx->pass_timer[1].begin(ctx->stream));
-        if (!ctx->mask.empty()) {
-            const uint32_t *list = nullptr;
-            int count = 0;
-            if (int rc = mask_list_main(ctx, tile, &list, &count)) return rc;
-            pt::launch_accumulate_tiles(acc, tile, list, count, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, ctx->by_count, ctx->stream);
-            if (count)
-                if (int rc = mask_list_used(ctx, 2)) return rc;
-        } else {
-            pt::launch_accumulate_frames(acc, tile, ctx->last_radiance, 0, 1, ctx->d_accum, ctx->d_moments, f16, ctx->by_count, 2048, ctx->stream);
-        }
-        HIP_TRY(hipGetLastError());
-        if (ctx->timing) HIP_TRY(ctx->pass_timer[1].end(ctx->stream));
-        ctx->output_is_accum = true;   // accumulate.ts:171-175 copies the mean into outputTexture
-        ctx->main_dirty = true;
-        ctx->accum_version++;
-    }
-    if (do_fs && !drawn_with_frame) {
-        // LATEST: frames may still be queued; the canvas is drawn from what has been launched, and
-        // only if that (or the pass's uniforms) changed since the last draw.  What is still queued
-        // is owed: a canvas read-back (or a FULLSCREEN-only submit) draws it.
-        const bool current = ctx->presented_version == ctx->accum_version &&
-                             std::memcmp(ctx->presented_fs, ctx->u_fs, sizeof ctx->u_fs) == 0;
-        if (lazy_present && current) {
-            if (!ctx->pending.empty()) ctx->want_present = true;
-            return MI3PT_OK;
-        }
-        if (int rc = run_fullscreen(ctx, ctx->u_fs)) return rc;
-        ctx->want_present = lazy_present && !ctx->pending.empty();
-    }
-    return MI3PT_OK;
-}
-
-// `count` consecutive frames in one call: what `count` calls of Renderer.render() submit while
-// nothing but the frame counter changes (renderer.ts:369-377 increments it before the uniforms
-// are written) -- frame i runs with raytrace `frame` = current + i and accumulate `frame` =
-// current + i, and both blocks are left at current + count, ready for the next call.
-extern "C" int mi3pt_submit_frames(mi3pt_ctx *ctx, unsigned pass_mask, uint32_t count)
-{
-    PT_GROUP(ctx, group_submit_frames(ctx, pass_mask, count));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    const bool queues_only = (pass_mask & ~(MI3PT_SUBMIT_RAYTRACE | MI3PT_SUBMIT_ACCUMULATE)) == 0;
-    for (uint32_t i = 0; i < count; i++) {
-        const size_t queued_before = ctx->pending.size();
-        if (int rc = mi3pt_submit(ctx, pass_mask)) return rc;
-        uint32_t f = ldu(ctx->u_rt, 12) + 1u, g = ldu(ctx->u_acc, 8) + 1u;
-        std::memcpy(ctx->u_rt + 12, &f, 4);
-        std::memcpy(ctx->u_acc + 8, &g, 4);
-        // That submit QUEUED its frame (the ordinary case: raytrace + accumulate, pipelined): the frames behind it differ from it in
-        // the frame counters alone and join the queue as copies -- what mi3pt_submit would do for each of them after checking the
-        // scene, the variant and the batch compatibility again (0.3 ms of a rank's 9.6 ms job for 256 frames, before anything was
-        // launched: profiles/r04_e_rank_job_host.log).  The queue is launched at the same depth as there.
-        // INVARIANT this fast path rests on (round-4 advice): between two frames INSIDE this call nothing can change -- no upload, no
-        // uniform other than the two frame counters, no option, no resize: single-threaded entry, and every such change is an entry
-        // point of its own -- so batch_compatible, check_scene and the prepare_* steps, which that first mi3pt_submit just ran, would
-        // give the same answers for every copy.  tests/test_gpu_gate.py holds it to `count` separate submits across a capacity
-        // boundary and with the cost-ordered job lists (whose per-launch state flush_pending advances, as for separate submits).
-        if (queues_only && ctx->pending.size() == queued_before + 1) {
-            while (i + 1 < count && (int)ctx->pending.size() < ctx->batch_cap) {
-                mi3pt_ctx::PendingFrame nf = ctx->pending.back();
-                std::memcpy(nf.u_rt + 12, &f, 4);
-                std::memcpy(nf.u_acc + 8, &g, 4);
-                ctx->pending.push_back(nf);
-                f++; g++; i++;
-                std::memcpy(ctx->u_rt + 12, &f, 4);
-                std::memcpy(ctx->u_acc + 8, &g, 4);
-            }
-            if ((int)ctx->pending.size() >= ctx->batch_cap)
-                if (int rc = flush_pending(ctx)) return rc;
-        }
-    }
-    return MI3PT_OK;
-}
-
-// LATEST presentation: the draw a queued frame asked for happens before the canvas is looked at.
-static int settle_canvas(mi3pt_ctx *ctx)
-{
-    if (ctx->present_mode != MI3PT_PRESENT_LATEST || !ctx->want_present || ctx->width == 0 || ctx->partial()) return MI3PT_OK;
-    ctx->want_present = false;
-    return run_fullscreen(ctx, ctx->u_fs);
-}
-
-extern "C" int mi3pt_flush(mi3pt_ctx *ctx)
-{
-    PT_GROUP(ctx, group_flush(ctx));
-    return require_idle(ctx);
-}
-
-extern "C" int mi3pt_batch_capacity(mi3pt_ctx *ctx, int *frames)
-{
-    PT_GROUP(ctx, mi3pt_batch_capacity(group_member0(ctx), frames));
-    if (!ctx || !frames) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "no textures before resize");
-    *frames = ctx->pipeline ? ctx->batch_cap : 1;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_sync(mi3pt_ctx *ctx)
-{
-    PT_GROUP(ctx, group_sync(ctx));
-    if (int rc = require_idle(ctx)) return rc;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    return cost_order_collect(ctx, false);      // (a measuring launch has finished by now: its job order is ready for the next launch)
-}
-
-extern "C" int mi3pt_read_texture(mi3pt_ctx *ctx, int which, float *dst, size_t nfloats)
-{
-    PT_GROUP(ctx, group_read_texture(ctx, which, dst, nfloats));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "read before resize");
-    const float4 *src;
-    size_t need;
-    switch (which) {
-    case MI3PT_TEX_OUTPUT:
-        src = ctx->output_is_accum ? ctx->d_accum : ctx->last_radiance;
-        need = plane_texels(ctx) * 4;
-        break;
-    case MI3PT_TEX_ACCUMULATION:
-        src = ctx->d_accum;
-        need = plane_texels(ctx) * 4;
-        break;
-    case MI3PT_TEX_CANVAS:
-        if (int rc = settle_canvas(ctx)) return rc;
-        src = ctx->d_canvas;
-        need = (size_t)ctx->height * ctx->width * 4;
-        break;
-    default:
-        return pt_set_error(MI3PT_ERR_INVALID, "unknown texture");
-    }
-    if (nfloats != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the texture");
-    HIP_TRY(read_plane(ctx, src, need * 4, dst));
-    return MI3PT_OK;
-}
-
-// Host -> device counterpart of mi3pt_read_texture for the accumulation image: restores a
-// saved running mean (checkpoint / resume) or hands a gathered multi-GPU image to a 1-rank
-// context for the fullscreen pass.
-extern "C" int mi3pt_write_texture(mi3pt_ctx *ctx, int which, const float *src, size_t nfloats)
-{
-    PT_GROUP(ctx, group_write_texture(ctx, which, src, nfloats));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!src) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "write before resize");
-    if (which != MI3PT_TEX_ACCUMULATION && which != MI3PT_TEX_OUTPUT)
-        return pt_set_error(MI3PT_ERR_INVALID, "only the accumulation / output image can be written");
-    const size_t need = plane_bytes(ctx);
-    if (nfloats != need / 4) return pt_set_error(MI3PT_ERR_INVALID, "source size does not match the texture");
-    if (ctx->d_moments && need) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, need, ctx->stream));      // (a mean from outside: its spread is unknown)
-    HIP_TRY(write_plane(ctx, ctx->d_accum, src, need));
-    ctx->output_is_accum = true;      // like the copy-back of accumulate.ts:171-175
-    ctx->main_dirty = true;
-    ctx->accum_version++;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_read_canvas_rgba8(mi3pt_ctx *ctx, uint8_t *dst, size_t nbytes)
-{
-    PT_GROUP(ctx, group_read_canvas(ctx, dst, nbytes));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "read before resize");
-    const size_t need = (size_t)ctx->width * ctx->height * 4;
-    if (nbytes != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the canvas");
-    if (int rc = settle_canvas(ctx)) return rc;
-    HIP_TRY(read_plane(ctx, ctx->d_canvas8, need, dst));
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_accumulation_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes)
-{
-    PT_GROUP(ctx, group_accumulation_ptr(ctx, dev_ptr, nbytes));
-    if (!ctx || !dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "no textures before resize");
-    if (int rc = require_idle(ctx)) return rc;
-    return hand_out_plane(ctx, ctx->d_accum, dev_ptr, nbytes);
-}
-
-extern "C" int mi3pt_bind_accumulation(mi3pt_ctx *ctx, void *dev_ptr, size_t nbytes)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_bind_accumulation: a device group gathers into its own image (mi3pt_accumulation_device_ptr)"));
-    if (int rc = require_idle(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "bind before resize");
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    ctx->main_dirty = true;
-    ctx->accum_version++;
-    // (another image becomes the mean: like a mean written from outside, its spread is unknown -- the moments start over)
-    auto zero_moments = [&]() -> int {
-        if (ctx->d_moments && plane_bytes(ctx)) HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, plane_bytes(ctx), ctx->stream));
-        return MI3PT_OK;
-    };
-    if (!dev_ptr) {
-        ctx->d_accum = ctx->d_accum_own;
-        return zero_moments();
-    }
-    if (nbytes != plane_bytes(ctx))
-        return pt_set_error(MI3PT_ERR_INVALID, "external accumulation buffer must be local_rows*width*16 bytes");
-    if (reinterpret_cast<uintptr_t>(dev_ptr) % 16)
-        return pt_set_error(MI3PT_ERR_INVALID, "external accumulation buffer must be 16-byte aligned");
-    ctx->d_accum = static_cast<float4 *>(dev_ptr);
-    return zero_moments();
-}
-
-// ---- first-hit feature images (include/mi3pt.h: mi3pt_aov, mi3pt_render_aovs) ----
-// Whether a first-hit pass walks the shipped walk's data (walk 13) -- after prepare_layout and prepare_cull: asked by mi3pt_render_aovs and
-// by the probe of that walk, mi3pt_debug_intersect_shipped.
-bool first_hit_walk_is_shipped(const mi3pt_ctx *ctx)
-{
-    return !ctx->env_sampling && !ctx->layout_active && ctx->cull_enabled && ctx->wide_enabled && ctx->cull_stack_ok &&
-           ctx->cull_ok && !ctx->cull_dirty && ctx->wide_ok && ctx->cwide_ok && ctx->d_leaf_rank;
-}
-
-// Not require_idle: the queued sample frames stay queued and keep their batching.  The pass is enqueued on the context's stream;
-// every path that frees or replaces a scene buffer waits for that stream first (replace_buffer, clone_scene, mi3pt_resize).
-extern "C" int mi3pt_render_aovs(mi3pt_ctx *ctx, unsigned aov_mask)
-{
-    PT_GROUP(ctx, group_render_aovs(ctx, aov_mask));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_render_aovs before resize");
-    if (aov_mask == 0 || (aov_mask >> MI3PT_AOV_COUNT)) return pt_set_error(MI3PT_ERR_INVALID, "aov_mask must be a non-empty OR of (1u << mi3pt_aov)");
-    if (int rc = check_scene(ctx)) return rc;
-    if (int rc = prepare_layout(ctx)) return rc;    // (what a raytrace submit does: no-ops unless the scene changed -- and then no frame is queued)
-    if (int rc = prepare_cull(ctx)) return rc;
-    const size_t tex_bytes = plane_bytes(ctx);
-    for (int k = 0; k < MI3PT_AOV_COUNT; k++)
-        if (((aov_mask >> k) & 1u) && !ctx->d_aov[k]) HIP_TRY(ctx->d_aov[k].alloc(tex_bytes));
-    pt::AovLaunch A;
-    A.scene = scene_refs(ctx);
-    const uint8_t *u = ctx->u_rt;
-    A.un.res_x = ldf(u, 0); A.un.res_y = ldf(u, 4); A.un.aspect = ldf(u, 8);
-    A.un.frame = 0; A.un.max_bounces = 0; A.un.samples_per_frame = 0;          // (do not enter)
-    for (int k = 0; k < 3; k++) { A.un.cam_pos[k] = ldf(u, 32 + 4 * k); A.un.cam_dir[k] = ldf(u, 48 + 4 * k); }
-    A.un.fov = ldf(u, 60); A.un.focal_distance = 0.0f; A.un.aperture = 0.0f; A.un.env_intensity = 0.0f; A.un.env_rotation = 0.0f;
-    A.tile = tile_of(ctx);
-    for (int k = 0; k < MI3PT_AOV_COUNT; k++) A.image[k] = ((aov_mask >> k) & 1u) ? ctx->d_aov[k] : nullptr;
-    // The walk.  Where `auto` would render sample frames with the shipped walk (variant 13: the scene admits distance culling and the
-    // compressed wide packets, MI3PT_OPT_CULL / MI3PT_OPT_WIDE are on, no debug layout), the first-hit walk on that walk's data.
-    // Else the reference's un-culled one on node / triangle packets with the prepared-reciprocal slab test (what the probe runs;
-    // bit-identical on every tree the context accepts).  The debug packet layout renumbers the triangles its packets name: there
-    // the walk on the uploaded records runs, so that the ids image holds uploaded indices.  One set of bits whichever runs.
-    int walk = 3, stack_worst = ctx->walk_stack_worst;
-    if (first_hit_walk_is_shipped(ctx)) { walk = 13; stack_worst = ctx->wide_stack_worst; }
-    else if (ctx->layout_active) { walk = 1; A.scene.tris = ctx->d_tris.as<const float4>(); }
-    if (tex_bytes) {
-        if (ctx->timing) HIP_TRY(ctx->aov_timer.begin(ctx->stream));
-        pt::launch_aovs(A, walk, stack_worst, ctx->leaf_min, ctx->stream);
-        HIP_TRY(hipGetLastError());
-        if (ctx->timing) HIP_TRY(ctx->aov_timer.end(ctx->stream));
-    }
-    for (int k = 0; k < MI3PT_AOV_COUNT; k++)
-        if ((aov_mask >> k) & 1u) {
-            ctx->aov_valid[k] = true;
-            std::memcpy(ctx->aov_u[k], ctx->u_rt, sizeof ctx->u_rt);      // (the view this image belongs to: mi3pt_reproject's old view)
-            ctx->aov_epoch[k] = ctx->upload_epoch;                       // (and the geometry: mi3pt_reproject_scene's previous one)
-        }
-    return MI3PT_OK;
-}
-
-static int aov_image(mi3pt_ctx *ctx, int which, const char *what)
-{
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
-    if (which < 0 || which >= MI3PT_AOV_COUNT) return pt_set_error(MI3PT_ERR_INVALID, "unknown feature image");
-    if (!ctx->aov_valid[which] || !ctx->d_aov[which])
-        return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": this image has not been rendered since the last resize (mi3pt_render_aovs)");
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_read_aov(mi3pt_ctx *ctx, int which, void *dst, size_t nbytes)
-{
-    PT_GROUP(ctx, group_read_aov(ctx, which, dst, nbytes));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = aov_image(ctx, which, "mi3pt_read_aov")) return rc;
-    if (nbytes != plane_bytes(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
-    HIP_TRY(read_plane(ctx, ctx->d_aov[which], nbytes, dst));
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_aov_device_ptr(mi3pt_ctx *ctx, int which, void **dev_ptr, size_t *nbytes)
-{
-    PT_GROUP(ctx, group_aov_ptr(ctx, which, dev_ptr, nbytes));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = aov_image(ctx, which, "mi3pt_aov_device_ptr")) return rc;
-    return hand_out_plane(ctx, ctx->d_aov[which], dev_ptr, nbytes);
-}
-
-// ---- the feature-guided a-trous de-noise of the running mean (include/mi3pt.h: mi3pt_denoise_guided; pt_guided.hip) ----
-// 1 / (sigma * sigma) in fp32; a sigma of 0 switches its term off
-static float guided_inv(float sigma) { return sigma == 0.0f ? 0.0f : 1.0f / (sigma * sigma); }
-
-extern "C" int mi3pt_denoise_guided(mi3pt_ctx *ctx, const mi3pt_guided_params *params)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_denoise_guided: not built for a device group (the members would have to exchange a 32-row halo)"));
-    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (params->levels < 1 || params->levels > 5) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: levels must be 1 .. 5");
-    for (float sigma : { params->sigma_color, params->sigma_normal, params->sigma_albedo, params->sigma_plane })
-        if (!(sigma >= 0.0f) || std::isinf(sigma)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: every sigma must be finite and >= 0");
-    // (a context that never opted into the moments image answers as it always did: the variance bit is unknown to it)
-    if (params->flags & ~(MI3PT_GUIDED_PRESENT | (ctx->moments_opted ? MI3PT_GUIDED_VARIANCE | MI3PT_GUIDED_YOUNG : 0u)))
-        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: unknown flag bits (MI3PT_GUIDED_VARIANCE, MI3PT_GUIDED_YOUNG: only on a context that has enabled the moments image, mi3pt_set_moments)");
-    const bool by_variance = (params->flags & MI3PT_GUIDED_VARIANCE) != 0, young = (params->flags & MI3PT_GUIDED_YOUNG) != 0;
-    if (young && !by_variance)
-        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_denoise_guided: MI3PT_GUIDED_YOUNG only together with MI3PT_GUIDED_VARIANCE (it changes that mode's initial variance)");
-    if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided before resize");
-    if (ctx->partial())
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided needs the whole image: not built for a rank of a tile split (a 32-row halo would have to be exchanged)");
-    for (int k = 0; k < MI3PT_AOV_COUNT; k++)
-        if (!ctx->aov_valid[k] || !ctx->d_aov[k])
-            return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided: the four feature images have not all been rendered since the last resize (mi3pt_render_aovs)");
-    if (by_variance && !ctx->d_moments)
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_denoise_guided: MI3PT_GUIDED_VARIANCE needs the moments image (mi3pt_set_moments(ctx, 1) before the frames are accumulated)");
-    if (int rc = flush_pending(ctx)) return rc;      // the mean a read-back would return now: the accumulate passes run on this stream
-    const size_t texels = plane_texels(ctx);
-    for (DevBuf<float4> *p : { &ctx->d_guided[0], &ctx->d_guided[1], &ctx->d_guided_nh })
-        if (!*p) HIP_TRY(p->alloc(plane_bytes(ctx)));
-    if (by_variance)
-        for (DevBuf<float> &p : ctx->d_guided_var)
-            if (!p) HIP_TRY(p.alloc(texels * 4));
-    pt::GuidedLaunch G;
-    G.normal_hit = ctx->d_guided_nh; G.position = ctx->d_aov[MI3PT_AOV_POSITION]; G.albedo = ctx->d_aov[MI3PT_AOV_ALBEDO];
-    G.width = ctx->width; G.rows = ctx->local_rows;
-    G.inv_color = guided_inv(params->sigma_color); G.inv_normal = guided_inv(params->sigma_normal);
-    G.inv_albedo = guided_inv(params->sigma_albedo); G.inv_plane = guided_inv(params->sigma_plane);
-    const bool despike = ctx->guided_despike;
-    if (despike) {
-        if (!ctx->d_guided_despike) HIP_TRY(ctx->d_guided_despike.alloc(plane_bytes(ctx)));
-        constexpr size_t count_bytes = (size_t)pt::DESPIKE_SLOTS * pt::DESPIKE_SLOT_WORDS * 4;
-        if (!ctx->d_guided_despike_count) HIP_TRY(ctx->d_guided_despike_count.alloc(count_bytes));
-        HIP_TRY(hipMemsetAsync(ctx->d_guided_despike_count, 0, count_bytes, ctx->stream));      // (outside the timed span: the pre-pass is one launch)
-    }
-    ctx->guided_despiked = false;
-    if (ctx->timing) HIP_TRY(ctx->guided_timer.begin(ctx->stream));
-    pt::launch_guided_pack(ctx->d_aov[MI3PT_AOV_NORMAL], ctx->d_aov[MI3PT_AOV_IDS], ctx->d_guided_nh, texels, ctx->stream);
-    const float4 *src = ctx->d_accum;
-    const float *var = nullptr;
-    float *scale = nullptr;
-    if (despike) {
-        // the pre-pass: c' in the accumulation image's place from here on; s into the variance image var_0 does not use (level 0 writes
-        // it after the var_0 kernel has read it)
-        if (by_variance) scale = ctx->d_guided_var[0];
-        pt::launch_guided_despike(src, ctx->d_aov[MI3PT_AOV_IDS], ctx->d_guided_despike, scale, ctx->d_guided_despike_count, ctx->width,
-                                  ctx->local_rows, ctx->stream);
-        src = ctx->d_guided_despike;
-    }
-    if (by_variance) {
-        // var_0 into the image level 0 does not write; level i then reads image (i + 1) & 1 and writes image i & 1
-        if (young)
-            pt::launch_guided_variance_young(G, src, ctx->d_moments, ctx->d_guided_var[1], scale, ctx->stream);
-        else
-            pt::launch_guided_variance(ctx->d_moments, ctx->d_guided_nh, ctx->d_guided_var[1], scale, ctx->width, ctx->local_rows, ctx->stream);
-        var = ctx->d_guided_var[1];
-    }
-    for (int level = 0; level < params->levels; level++) {
-        float4 *dst = ctx->d_guided[level & 1];
-        if (by_variance) {
-            float *var_dst = ctx->d_guided_var[level & 1];
-            pt::launch_guided_level_variance(G, src, dst, var, var_dst, level, params->sigma_color, ctx->stream);
-            var = var_dst;
-        } else {
-            pt::launch_guided_level(G, src, dst, level, ctx->stream);
-        }
-        src = dst;
-    }
-    HIP_TRY(hipGetLastError());
-    if (ctx->timing) HIP_TRY(ctx->guided_timer.end(ctx->stream));
-    ctx->guided_result = src;
-    ctx->guided_var_result = var;
-    ctx->guided_despiked = despike;
-    if (params->flags & MI3PT_GUIDED_PRESENT) {
-        // the fullscreen pass on the filtered image, with the pass's uniforms as they are and its own de-noiser off.  The canvas then shows
-        // no state of the running mean: the next fullscreen submit draws again whatever it showed before, and a draw still owed to queued
-        // frames (MI3PT_PRESENT_LATEST) is dropped -- those frames are in the mean this call filtered.
-        pt::FsUniforms fs;
-        const uint8_t *u_fs = ctx->u_fs;
-        fs.res_x = ldf(u_fs, 0); fs.res_y = ldf(u_fs, 4); fs.aspect = ldf(u_fs, 8);
-        fs.scaling = ldf(u_fs, 12); fs.denoise = 0u; fs.tonemapping = ldu(u_fs, 20);
-        pt::launch_fullscreen(fs, src, ctx->width, ctx->height, ctx->width, ctx->height, ctx->d_fs_taps, true, ctx->d_canvas, ctx->d_canvas8, ctx->stream);
-        HIP_TRY(hipGetLastError());
-        ctx->presented_version = 0;
-        ctx->want_present = false;
-    }
-    return MI3PT_OK;
-}
-
-static int guided_image(mi3pt_ctx *ctx, const char *what)
-{
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
-    if (!ctx->guided_result) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": nothing has been filtered since the last resize (mi3pt_denoise_guided)");
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_read_guided(mi3pt_ctx *ctx, void *dst, size_t nbytes)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_read_guided: mi3pt_denoise_guided is not built for a device group"));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = guided_image(ctx, "mi3pt_read_guided")) return rc;
-    if (nbytes != plane_bytes(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
-    HIP_TRY(read_plane(ctx, ctx->guided_result, nbytes, dst));
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_guided_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_guided_device_ptr: mi3pt_denoise_guided is not built for a device group"));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = guided_image(ctx, "mi3pt_guided_device_ptr")) return rc;
-    return hand_out_plane(ctx, ctx->guided_result, dev_ptr, nbytes);
-}
-
-extern "C" int mi3pt_read_guided_variance(mi3pt_ctx *ctx, float *dst, size_t nfloats)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_read_guided_variance: mi3pt_denoise_guided is not built for a device group"));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = guided_image(ctx, "mi3pt_read_guided_variance")) return rc;
-    if (!ctx->guided_var_result) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_guided_variance: the last filter ran without MI3PT_GUIDED_VARIANCE");
-    if (nfloats != plane_texels(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width floats)");
-    HIP_TRY(read_plane(ctx, ctx->guided_var_result, nfloats * 4, dst));
-    return MI3PT_OK;
-}
-
-// ---- the firefly pre-pass of the guided de-noise (include/mi3pt.h: mi3pt_set_guided_despike; pt_guided.hip: k_guided_despike) ----
-extern "C" int mi3pt_set_guided_despike(mi3pt_ctx *ctx, int enabled)
-{
-    PT_GROUP_ALL(ctx, false, mi3pt_set_guided_despike(m, enabled));
-    if (int rc = require_ctx(ctx)) return rc;
-    ctx->guided_despike = enabled != 0;      // (host state alone: read by the next mi3pt_denoise_guided, which allocates what it needs)
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_read_guided_despiked(mi3pt_ctx *ctx, uint32_t *texels)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_read_guided_despiked: mi3pt_denoise_guided is not built for a device group"));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (!texels) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = guided_image(ctx, "mi3pt_read_guided_despiked")) return rc;
-    if (!ctx->guided_despiked || !ctx->d_guided_despike_count)
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_guided_despiked: the last filter ran without the pre-pass (mi3pt_set_guided_despike)");
-    std::vector<uint32_t> slots((size_t)pt::DESPIKE_SLOTS * pt::DESPIKE_SLOT_WORDS);
-    HIP_TRY(read_plane(ctx, ctx->d_guided_despike_count, slots.size() * 4, slots.data()));
-    uint32_t sum = 0;
-    for (uint32_t k = 0; k < pt::DESPIKE_SLOTS; k++) sum += slots[(size_t)k * pt::DESPIKE_SLOT_WORDS];
-    *texels = sum;
-    return MI3PT_OK;
-}
-
-// ---- the moments image (include/mi3pt.h: mi3pt_set_moments; pt_kernels.hip: k_accumulate_frames<true>) ----
-extern "C" int mi3pt_set_moments(mi3pt_ctx *ctx, int enabled)
-{
-    PT_GROUP(ctx, group_set_moments(ctx, enabled));
-    if (int rc = require_idle(ctx)) return rc;
-    const bool on = enabled != 0;
-    if (on == ctx->moments) return MI3PT_OK;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));      // (the accumulate passes in flight read and write the image this frees)
-    if (!on) {
-        ctx->d_moments.reset();
-        for (DevBuf<float4> &p : ctx->d_hold) p.reset();      // (a held history is a mean WITH its moments)
-        ctx->history_held = false;
-        ctx->moments = false;
-        ctx->by_count = false;      // (the count is the image's n: the mode goes with it)
-        return MI3PT_OK;
-    }
-    if (ctx->width != 0) {
-        const size_t tex_bytes = plane_bytes(ctx);
-        DevBuf<float4> image;
-        HIP_TRY(image.alloc(tex_bytes));
-        if (tex_bytes) {
-            const hipError_t e = hipMemsetAsync(image, 0, tex_bytes, ctx->stream);
-            if (e != hipSuccess) {          // (nothing half enabled: the launches key on the pointer)
-                (void)hipGetLastError();
-                return pt_set_error(MI3PT_ERR_HIP, std::string("mi3pt_set_moments: clearing the image failed: ") + hipGetErrorString(e));
-            }
-        }
-        ctx->d_moments = std::move(image);
-        ctx->main_dirty = true;
-    }
-    ctx->moments = ctx->moments_opted = true;      // (before mi3pt_resize: the image comes with the textures)
-    return MI3PT_OK;
-}
-
-static int moments_image(mi3pt_ctx *ctx, const char *what)
-{
-    if (!ctx->moments) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": the moments image is not enabled (mi3pt_set_moments)");
-    if (ctx->width == 0 || !ctx->d_moments) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_read_moments(mi3pt_ctx *ctx, void *dst, size_t nbytes)
-{
-    PT_GROUP(ctx, group_read_moments(ctx, dst, nbytes));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = moments_image(ctx, "mi3pt_read_moments")) return rc;
-    if (nbytes != plane_bytes(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the image (rows x width x 16 bytes)");
-    HIP_TRY(read_plane(ctx, ctx->d_moments, nbytes, dst));
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_write_moments(mi3pt_ctx *ctx, const void *src, size_t nbytes)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_write_moments: a device group keeps its members' moments images (write each member's rows: mi3pt_group_member)"));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!src) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = moments_image(ctx, "mi3pt_write_moments")) return rc;
-    if (nbytes != plane_bytes(ctx)) return pt_set_error(MI3PT_ERR_INVALID, "source size does not match the image (rows x width x 16 bytes)");
-    if (nbytes == 0) return MI3PT_OK;
-    HIP_TRY(write_plane(ctx, ctx->d_moments, src, nbytes));
-    ctx->main_dirty = true;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_moments_device_ptr(mi3pt_ctx *ctx, void **dev_ptr, size_t *nbytes)
-{
-    PT_GROUP(ctx, group_moments_ptr(ctx, dev_ptr, nbytes));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!dev_ptr) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = moments_image(ctx, "mi3pt_moments_device_ptr")) return rc;
-    return hand_out_plane(ctx, ctx->d_moments, dev_ptr, nbytes);
-}
-
-// ---- the mean by count and the reprojection (include/mi3pt.h: mi3pt_set_mean_by_count, mi3pt_reproject; pt_accum.h, pt_reproject.hip) ----
-extern "C" int mi3pt_set_mean_by_count(mi3pt_ctx *ctx, int enabled)
-{
-    PT_GROUP_ALL(ctx, false, mi3pt_set_mean_by_count(m, enabled));
-    if (int rc = require_idle(ctx)) return rc;      // the frames queued so far were submitted under the old law
-    if (enabled && !ctx->moments)
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_set_mean_by_count needs the moments image: the count is its n (mi3pt_set_moments(ctx, 1) first)");
-    ctx->by_count = enabled != 0;
-    return MI3PT_OK;
-}
-
-// what mi3pt_reproject and mi3pt_reproject_scene share: the argument checks, the state checks and steps 1 - 7 of the header.  scene: the
-// kernel that follows a triangle back to the kept geometry (k_reproject_scene) takes k_reproject's place in step 5.
-struct ReprojectCall {
-    const char *who;
-    float plane_tolerance, normal_cos_min;
-    int max_history, max_history_moved;
-    unsigned flags;
-    bool scene;
-};
-
-static int reproject_run(mi3pt_ctx *ctx, const ReprojectCall &c)
-{
-    const std::string who = c.who;
-    if (!(c.plane_tolerance >= 0.0f) || std::isinf(c.plane_tolerance))
-        return pt_set_error(MI3PT_ERR_INVALID, who + ": plane_tolerance must be finite and >= 0");
-    if (!(c.normal_cos_min >= -1.0f && c.normal_cos_min <= 1.0f))
-        return pt_set_error(MI3PT_ERR_INVALID, who + ": normal_cos_min must lie in [-1, 1]");
-    if (c.max_history < 1 || c.max_history > (1 << 24)) return pt_set_error(MI3PT_ERR_INVALID, who + ": max_history must be 1 .. 2^24");
-    if (c.scene && (c.max_history_moved < 1 || c.max_history_moved > (1 << 24)))
-        return pt_set_error(MI3PT_ERR_INVALID, who + ": max_history_moved must be 1 .. 2^24");
-    if (c.flags) return pt_set_error(MI3PT_ERR_INVALID, who + ": unknown flag bits");
-    if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, who + " before resize");
-    if (!ctx->moments || !ctx->d_moments || !ctx->by_count)
-        return pt_set_error(MI3PT_ERR_STATE, who + " needs the moments image and the mean by count (mi3pt_set_moments, mi3pt_set_mean_by_count)");
-    if (ctx->partial())
-        return pt_set_error(MI3PT_ERR_STATE, who + ": not built for a rank of a tile split (a tap crosses the ranks' rows; no halo exchange)");
-    static const int old_set[3] = { MI3PT_AOV_POSITION, MI3PT_AOV_NORMAL, MI3PT_AOV_IDS };
-    const uint8_t *u0 = ctx->aov_u[MI3PT_AOV_POSITION];
-    for (int k : old_set) {
-        if (!ctx->aov_valid[k] || !ctx->d_aov[k])
-            return pt_set_error(MI3PT_ERR_STATE, who + ": the POSITION, NORMAL and IDS images of the old view have not been rendered since the last resize (mi3pt_render_aovs)");
-        // (resolution and aspect; camera position, direction and fov: what the first hit depends on)
-        if (std::memcmp(ctx->aov_u[k], u0, 12) || std::memcmp(ctx->aov_u[k] + 32, u0 + 32, 32))
-            return pt_set_error(MI3PT_ERR_STATE, who + ": the POSITION, NORMAL and IDS images were rendered from different views");
-    }
-    if (std::memcmp(ctx->u_rt, u0, 8))
-        return pt_set_error(MI3PT_ERR_STATE, who + ": the new view's resolution differs from the old view's");
-    if (c.scene) {
-        if (!ctx->geometry_kept) return pt_set_error(MI3PT_ERR_STATE, who + ": no previous geometry is kept (mi3pt_keep_geometry)");
-        if (!ctx->d_tris || ctx->ntris != ctx->ntris_kept)
-            return pt_set_error(MI3PT_ERR_STATE, who + ": the kept geometry and the current one differ in their number of triangles");
-        for (int k : old_set)
-            if (ctx->aov_epoch[k] != ctx->kept_epoch)
-                return pt_set_error(MI3PT_ERR_STATE, who + ": the POSITION, NORMAL and IDS images were not rendered from the kept geometry (an upload lies between them and mi3pt_keep_geometry)");
-    }
-    if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far belongs to the old view's mean
-    ctx->history_held = false;                       // (what was held belongs to the view before this one)
-    pt::ReprojectSceneLaunch S;
-    pt::ReprojectLaunch &R = S.view;
-    if (int rc = mi3pt_host_view_frame(u0, MI3PT_RAYTRACE_UNIFORMS_SIZE, R.f0)) return rc;
-    R.res0_x = ldf(u0, 0); R.res0_y = ldf(u0, 4);
-    const size_t tex_bytes = plane_bytes(ctx);
-    for (int k : old_set)
-        if (!ctx->d_aov_prev[k]) HIP_TRY(ctx->d_aov_prev[k].alloc(tex_bytes));
-    for (DevBuf<float4> &p : ctx->d_reproject)
-        if (!p) HIP_TRY(p.alloc(tex_bytes));
-    // the old features become the previous set; the new view's are rendered into the images the set before it held
-    for (int k : old_set) std::swap(ctx->d_aov[k], ctx->d_aov_prev[k]);
-    if (int rc = mi3pt_render_aovs(ctx, (1u << MI3PT_AOV_COUNT) - 1u)) {
-        for (int k : old_set) std::swap(ctx->d_aov[k], ctx->d_aov_prev[k]);      // (nothing was rendered: the old view's images stand)
-        return rc;
-    }
-    const pt::AccUniforms acc = acc_uniforms(ctx);
-    R.accum = ctx->d_accum; R.moments = ctx->d_moments;
-    R.accum_out = ctx->d_reproject[0]; R.moments_out = ctx->d_reproject[1];
-    R.pos1 = ctx->d_aov[MI3PT_AOV_POSITION]; R.nrm1 = ctx->d_aov[MI3PT_AOV_NORMAL]; R.ids1 = ctx->d_aov[MI3PT_AOV_IDS];
-    R.pos0 = ctx->d_aov_prev[MI3PT_AOV_POSITION]; R.nrm0 = ctx->d_aov_prev[MI3PT_AOV_NORMAL]; R.ids0 = ctx->d_aov_prev[MI3PT_AOV_IDS];
-    R.width = ctx->width; R.rows = ctx->local_rows;
-    R.res_w = acc.res_w; R.res_h = acc.res_h;
-    R.plane_tolerance = c.plane_tolerance; R.normal_cos_min = c.normal_cos_min; R.max_history = (float)c.max_history;
-    R.store_f16 = ctx->storage == MI3PT_STORAGE_F16;
-    if (ctx->timing) HIP_TRY(ctx->reproject_timer.begin(ctx->stream));
-    if (c.scene) {
-        // the records in upload order, which IDS indexes: the current ones, and the kept ones (the current ones until an upload handed them over)
-        S.tris1 = ctx->d_tris.as<const float4>();
-        S.tris0 = (ctx->d_tris_kept ? ctx->d_tris_kept : ctx->d_tris).as<const float4>();
-        S.ntris = (int32_t)ctx->ntris;
-        S.max_history_moved = (float)c.max_history_moved;
-        pt::launch_reproject_scene(S, ctx->stream);
-    } else {
-        pt::launch_reproject(R, ctx->stream);
-    }
-    HIP_TRY(hipGetLastError());
-    // the scratch pair takes the images' place: the context's own by a swap of pointers, a bound accumulation image by a copy on the stream
-    std::swap(ctx->d_moments, ctx->d_reproject[1]);
-    if (ctx->d_accum == ctx->d_accum_own) {
-        std::swap(ctx->d_accum_own, ctx->d_reproject[0]);
-        ctx->d_accum = ctx->d_accum_own;
-    } else if (tex_bytes) {
-        HIP_TRY(hipMemcpyAsync(ctx->d_accum, ctx->d_reproject[0], tex_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (ctx->timing) HIP_TRY(ctx->reproject_timer.end(ctx->stream));
-    drop_sample_mask(ctx);          // a new view starts whole
-    ctx->main_dirty = true;
-    ctx->accum_version++;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_reproject(mi3pt_ctx *ctx, const mi3pt_reproject_params *params)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_reproject: not built for a device group (a tap crosses the members' rows; no halo exchange)"));
-    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    return reproject_run(ctx, { "mi3pt_reproject", params->plane_tolerance, params->normal_cos_min, params->max_history, 1, params->flags, false });
-}
-
-// ---- the previous geometry and the reprojection across a scene change (include/mi3pt.h: mi3pt_keep_geometry, mi3pt_reproject_scene) ----
-extern "C" int mi3pt_keep_geometry(mi3pt_ctx *ctx, int keep)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_keep_geometry: not built for a device group (mi3pt_reproject_scene is not)"));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (keep && (!ctx->d_tris || ctx->ntris == 0))
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_keep_geometry: no triangles uploaded (mi3pt_upload_triangles)");
-    if (ctx->d_tris_kept) {        // (a second keep, or the release: behind whatever still reads the buffer)
-        HIP_TRY(ctx_stream_sync(ctx, ctx->stream, "mi3pt_keep_geometry"));
-        ctx->d_tris_kept.reset();
-    }
-    ctx->geometry_kept = keep != 0;
-    ctx->ntris_kept = keep ? ctx->ntris : 0;
-    ctx->kept_epoch = keep ? ctx->upload_epoch : 0;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_reproject_scene(mi3pt_ctx *ctx, const mi3pt_reproject_scene_params *params)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_reproject_scene: not built for a device group (a tap crosses the members' rows; no halo exchange)"));
-    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    return reproject_run(ctx, { "mi3pt_reproject_scene", params->plane_tolerance, params->normal_cos_min, params->max_history,
-                                params->max_history_moved, params->flags, true });
-}
-
-// ---- the held history and its validated merge (include/mi3pt.h: mi3pt_hold_history, mi3pt_merge_history; pt_history.hip) ----
-static int history_state(mi3pt_ctx *ctx, const std::string &who)
-{
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, who + " before resize");
-    if (!ctx->moments || !ctx->d_moments || !ctx->by_count)
-        return pt_set_error(MI3PT_ERR_STATE, who + " needs the moments image and the mean by count (mi3pt_set_moments, mi3pt_set_mean_by_count)");
-    if (ctx->partial())
-        return pt_set_error(MI3PT_ERR_STATE, who + ": not built for a rank of a tile split (a window crosses the ranks' rows; no halo exchange)");
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_hold_history(mi3pt_ctx *ctx)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_hold_history: not built for a device group (a window crosses the members' rows; no halo exchange)"));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (int rc = history_state(ctx, "mi3pt_hold_history")) return rc;
-    if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far belongs to the history that is held
-    const size_t tex_bytes = plane_bytes(ctx);
-    for (DevBuf<float4> &p : ctx->d_hold)
-        if (!p) HIP_TRY(p.alloc(tex_bytes));
-    ctx->history_held = false;        // (a failure below leaves nothing half held)
-    // the images become the held pair: the context's own by a swap of pointers, a bound accumulation image by a copy on the stream
-    std::swap(ctx->d_moments, ctx->d_hold[1]);
-    if (ctx->d_accum == ctx->d_accum_own) {
-        std::swap(ctx->d_accum_own, ctx->d_hold[0]);
-        ctx->d_accum = ctx->d_accum_own;
-    } else if (tex_bytes) {
-        HIP_TRY(hipMemcpyAsync(ctx->d_hold[0], ctx->d_accum, tex_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    ctx->main_dirty = true;
-    ctx->accum_version++;
-    if (tex_bytes) {                  // the live pair as mi3pt_reset leaves it
-        HIP_TRY(hipMemsetAsync(ctx->d_accum, 0, tex_bytes, ctx->stream));
-        HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, tex_bytes, ctx->stream));
-    }
-    ctx->history_held = true;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_merge_history(mi3pt_ctx *ctx, const mi3pt_history_params *params)
-{
-    PT_GROUP(ctx, group_unsupported("mi3pt_merge_history: not built for a device group (a window crosses the members' rows; no halo exchange)"));
-    if (!ctx || !params) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (params->radius < 0 || params->radius > 3) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_merge_history: radius must be 0 .. 3");
-    if (!(params->z_keep >= 0.0f) || std::isinf(params->z_keep))
-        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_merge_history: z_keep must be finite and >= 0");
-    if (!(params->z_drop > params->z_keep) || std::isinf(params->z_drop))
-        return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_merge_history: z_drop must be finite and above z_keep");
-    if (params->flags) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_merge_history: unknown flag bits");
-    if (int rc = require_ctx(ctx)) return rc;
-    if (int rc = history_state(ctx, "mi3pt_merge_history")) return rc;
-    if (!ctx->history_held || !ctx->d_hold[0] || !ctx->d_hold[1])
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_merge_history: no history is held (mi3pt_hold_history; a reset, a resize and a reprojection drop it)");
-    if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far is a fresh sample of the test
-    const size_t tex_bytes = plane_bytes(ctx);
-    for (DevBuf<float4> &p : ctx->d_reproject)
-        if (!p) HIP_TRY(p.alloc(tex_bytes));
-    const pt::AccUniforms acc = acc_uniforms(ctx);
-    pt::HistoryLaunch L;
-    L.accum = ctx->d_accum; L.moments = ctx->d_moments;
-    L.accum_held = ctx->d_hold[0]; L.moments_held = ctx->d_hold[1];
-    L.accum_out = ctx->d_reproject[0]; L.moments_out = ctx->d_reproject[1];
-    L.width = ctx->width; L.rows = ctx->local_rows;
-    L.res_w = acc.res_w; L.res_h = acc.res_h;
-    L.radius = params->radius; L.z_keep = params->z_keep; L.z_drop = params->z_drop;
-    L.store_f16 = ctx->storage == MI3PT_STORAGE_F16;
-    if (ctx->timing) HIP_TRY(ctx->history_timer.begin(ctx->stream));
-    pt::launch_history(L, ctx->stream);
-    HIP_TRY(hipGetLastError());
-    // the scratch pair takes the images' place: the context's own by a swap of pointers, a bound accumulation image by a copy on the stream
-    std::swap(ctx->d_moments, ctx->d_reproject[1]);
-    if (ctx->d_accum == ctx->d_accum_own) {
-        std::swap(ctx->d_accum_own, ctx->d_reproject[0]);
-        ctx->d_accum = ctx->d_accum_own;
-    } else if (tex_bytes) {
-        HIP_TRY(hipMemcpyAsync(ctx->d_accum, ctx->d_reproject[0], tex_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (ctx->timing) HIP_TRY(ctx->history_timer.end(ctx->stream));
-    ctx->history_held = false;
-    ctx->main_dirty = true;
-    ctx->accum_version++;
-    return MI3PT_OK;
-}
-
-// ---- the per-tile error estimate of the running mean (include/mi3pt.h: mi3pt_estimate_convergence; pt_converge.hip) ----
-
-extern "C" int mi3pt_estimate_convergence(mi3pt_ctx *ctx, float threshold, int min_frames)
-{
-    PT_GROUP_ALL(ctx, false, mi3pt_estimate_convergence(m, threshold, min_frames));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    if (!(threshold >= 0.0f) || std::isinf(threshold)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_estimate_convergence: the threshold must be finite and >= 0");
-    if (min_frames < 0 || min_frames > (1 << 24)) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_estimate_convergence: min_frames must be 0 .. 2^24");
-    if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_estimate_convergence before resize");
-    if (!ctx->moments || !ctx->d_moments)
-        return pt_set_error(MI3PT_ERR_STATE, "mi3pt_estimate_convergence needs the moments image (mi3pt_set_moments(ctx, 1) before the frames are accumulated)");
-    if (int rc = flush_pending(ctx)) return rc;      // every frame submitted so far: the accumulate passes run on this stream
-    const size_t ntiles = conv_tiles_x(ctx) * conv_tiles_y(ctx);
-    if (!ctx->d_conv_tiles) HIP_TRY(ctx->d_conv_tiles.alloc(ntiles * 16));
-    if (!ctx->d_conv_parts) HIP_TRY(ctx->d_conv_parts.alloc((size_t)pt::converge_blocks(ctx->width, ctx->local_rows) * sizeof(pt::ConvergePart)));
-    if (!ctx->d_conv_summary) HIP_TRY(ctx->d_conv_summary.alloc(sizeof(pt::ConvergeSummary)));
-    if (!ctx->h_conv_summary) HIP_TRY(ctx->h_conv_summary.alloc(sizeof(pt::ConvergeSummary)));
-    if (!ctx->conv_done) HIP_TRY(hipEventCreateWithFlags(ctx->conv_done.put(), hipEventDisableTiming));
-    const float t2 = (threshold * threshold) * 3.0f;
-    if (ctx->timing) HIP_TRY(ctx->conv_timer.begin(ctx->stream));
-    pt::launch_converge(ctx->d_accum, ctx->d_moments, ctx->d_conv_tiles, ctx->d_conv_parts, ctx->d_conv_summary, ctx->width, ctx->local_rows, t2,
-                        (float)min_frames, ctx->stream);
-    HIP_TRY(hipGetLastError());
-    if (ctx->timing) HIP_TRY(ctx->conv_timer.end(ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->h_conv_summary, ctx->d_conv_summary, sizeof(pt::ConvergeSummary), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->conv_done, ctx->stream));
-    ctx->conv_valid = true;
-    ctx->conv_threshold = threshold;
-    ctx->conv_min_frames = min_frames;
-    return MI3PT_OK;
-}
-
-// what both reads start with: the state, then the wait for the estimate's event -- not for the stream, and the queue is not launched
-static int conv_wait(mi3pt_ctx *ctx, const char *what)
-{
-    if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + " before resize");
-    if (!ctx->conv_valid) return pt_set_error(MI3PT_ERR_STATE, std::string(what) + ": nothing has been estimated since the last resize (mi3pt_estimate_convergence)");
-    HIP_TRY(ctx_event_sync(ctx, ctx->conv_done, "convergence estimate"));
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_read_convergence(mi3pt_ctx *ctx, mi3pt_convergence *out)
-{
-    PT_GROUP(ctx, group_read_convergence(ctx, out));
-    if (!ctx || !out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = conv_wait(ctx, "mi3pt_read_convergence")) return rc;
-    const pt::ConvergeSummary s = *ctx->h_conv_summary;
-    auto as_float = [](uint32_t bits) { float f; std::memcpy(&f, &bits, 4); return f; };
-    out->tiles = s.tiles;
-    out->tiles_above = s.above;
-    out->tiles_young = s.young;
-    out->tiles_nonfinite = s.nonfinite;
-    out->texels = s.texels;
-    out->worst_tile = as_float(s.worst_tile);
-    out->worst_texel = as_float(s.worst_texel);
-    out->n_min = out->tiles ? as_float(~s.n_min_inv) : 0.0f;
-    out->threshold = ctx->conv_threshold;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_read_convergence_tiles(mi3pt_ctx *ctx, float *dst, size_t nfloats)
-{
-    PT_GROUP(ctx, group_read_convergence_tiles(ctx, dst, nfloats));
-    if (!ctx || !dst) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width != 0 && ctx->conv_valid && nfloats != conv_tiles_x(ctx) * conv_tiles_y(ctx) * 4)
-        return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the tile map (ceil(rows / 8) x ceil(width / 8) x 4 floats)");
-    if (int rc = conv_wait(ctx, "mi3pt_read_convergence_tiles")) return rc;
-    if (nfloats == 0) return MI3PT_OK;
-    // the map is the estimate's until the next estimate: copied beside the context's stream, which may be busy with later frames
-    if (!ctx->conv_read_stream) HIP_TRY(hipStreamCreateWithFlags(ctx->conv_read_stream.put(), hipStreamNonBlocking));
-    HIP_TRY(hipMemcpyAsync(dst, ctx->d_conv_tiles, nfloats * 4, hipMemcpyDeviceToHost, ctx->conv_read_stream));
-    HIP_TRY(hipStreamSynchronize(ctx->conv_read_stream));
-    return MI3PT_OK;
-}
-
-// ---- adaptive sampling: the per-tile sample mask (include/mi3pt.h: mi3pt_set_sample_mask; pt_host_adapt.cpp, pt_accumulate_tiles.hip) ----
-extern "C" int mi3pt_set_sample_mask(mi3pt_ctx *ctx, const uint8_t *tiles, size_t ntiles)
-{
-    PT_GROUP(ctx, group_set_sample_mask(ctx, tiles, ntiles));
-    if (int rc = require_ctx(ctx)) return rc;
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_set_sample_mask before resize");
-    const bool clear = !tiles && ntiles == 0;
-    if (!clear && !tiles) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (!clear && ntiles != conv_tiles_x(ctx) * conv_tiles_y(ctx))
-        return pt_set_error(MI3PT_ERR_INVALID, "the mask's size does not match the tile map (ceil(rows / 8) x ceil(width / 8) bytes)");
-    if (int rc = flush_pending(ctx)) return rc;      // the frames queued so far were submitted under the old mask
-    if (clear || ntiles == 0) {                       // (a rank without rows has nothing to mask)
-        drop_sample_mask(ctx);
-        return MI3PT_OK;
-    }
-    ctx->mask.resize(ntiles);
-    uint32_t sampled = 0;
-    for (size_t t = 0; t < ntiles; t++) {
-        ctx->mask[t] = tiles[t] ? 1 : 0;
-        sampled += tiles[t] ? 1u : 0u;
-    }
-    ctx->mask_sampled = sampled;
-    ctx->mask_epoch = ++ctx->mask_epochs;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_read_sample_mask(mi3pt_ctx *ctx, uint8_t *dst, size_t ntiles, uint32_t *sampled_out)
-{
-    PT_GROUP(ctx, group_read_sample_mask(ctx, dst, ntiles, sampled_out));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    if (ctx->width == 0) return pt_set_error(MI3PT_ERR_STATE, "mi3pt_read_sample_mask before resize");
-    const size_t need = conv_tiles_x(ctx) * conv_tiles_y(ctx);
-    if (ntiles != need) return pt_set_error(MI3PT_ERR_INVALID, "destination size does not match the tile map (ceil(rows / 8) x ceil(width / 8) bytes)");
-    if (!dst && need) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (ctx->mask.empty()) {
-        if (need) std::memset(dst, 1, need);
-        if (sampled_out) *sampled_out = (uint32_t)need;
-        return MI3PT_OK;
-    }
-    std::memcpy(dst, ctx->mask.data(), need);
-    if (sampled_out) *sampled_out = ctx->mask_sampled;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_freeze_converged(mi3pt_ctx *ctx, int guard, uint32_t *sampled_out)
-{
-    PT_GROUP(ctx, group_freeze_converged(ctx, guard, sampled_out));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    if (guard != 0 && guard != 1) return pt_set_error(MI3PT_ERR_INVALID, "mi3pt_freeze_converged: guard must be 0 or 1");
-    if (int rc = conv_wait(ctx, "mi3pt_freeze_converged")) return rc;
-    const size_t tiles_x = conv_tiles_x(ctx), tiles_y = conv_tiles_y(ctx), n = tiles_x * tiles_y;
-    std::vector<float> records(n * 4);
-    if (n)
-        if (int rc = mi3pt_read_convergence_tiles(ctx, records.data(), records.size())) return rc;
-    std::vector<uint8_t> mask(n, 1);
-    if (!ctx->mask.empty()) mask = ctx->mask;
-    uint32_t sampled = 0;
-    if (int rc = mi3pt_host_freeze_tiles(records.data(), (int)tiles_x, (int)tiles_y, ctx->conv_threshold, ctx->conv_min_frames, guard, mask.data(), &sampled)) return rc;
-    if (n)
-        if (int rc = mi3pt_set_sample_mask(ctx, mask.data(), n)) return rc;
-    if (sampled_out) *sampled_out = sampled;
     return MI3PT_OK;
 }
 
@@ -2763,42 +634,6 @@ extern "C" int mi3pt_pass_time_us(mi3pt_ctx *ctx, int pass, float *microseconds)
     return ctx->pass_timer[pass].elapsed_us(ctx, microseconds, "pass was not timed in the last submit");
 }
 
-extern "C" int mi3pt_raytrace_launch_stats(mi3pt_ctx *ctx, int reset, double *total_ms, uint64_t *launches,
-                                           uint64_t *frames)
-{
-    PT_GROUP(ctx, group_launch_stats(ctx, reset, total_ms, launches, frames));
-    if (int rc = require_idle(ctx)) return rc;
-    if (int rc = collect_rt_time(ctx, ctx->ev_rt_newest ^ 1)) return rc;
-    if (int rc = collect_rt_time(ctx, ctx->ev_rt_newest)) return rc;
-    if (total_ms) *total_ms = ctx->rt_total_ms;
-    if (launches) *launches = ctx->rt_launches;
-    if (frames) *frames = ctx->rt_frames;
-    if (reset) { ctx->rt_total_ms = 0.0; ctx->rt_launches = 0; ctx->rt_frames = 0; ctx->span_started = false; }
-    return MI3PT_OK;
-}
-
-// Wall-clock span of the batched raytrace launches since the last reset of the launch statistics:
-// from the start of the first to the end of the last, on the GPU's clock.  Consecutive launches
-// overlap at their tails (the next one starts while the last paths of this one drain), so the
-// sum of the per-launch durations exceeds this; span / launches is the non-overlapped time a
-// launch costs.
-extern "C" int mi3pt_raytrace_launch_span(mi3pt_ctx *ctx, double *span_ms)
-{
-    PT_GROUP(ctx, group_launch_span(ctx, span_ms));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!span_ms) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    *span_ms = 0.0;
-    if (!ctx->span_started) return MI3PT_OK;
-    for (int par = 0; par < 2; par++) {
-        if (!ctx->ev_rt_frames[par]) continue;              // this parity never ran a timed launch
-        HIP_TRY(ctx_event_sync(ctx, ctx->ev_rt[par][1]));
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ctx->ev_span_start, ctx->ev_rt[par][1]) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if ((double)ms > *span_ms) *span_ms = ms;
-    }
-    return MI3PT_OK;
-}
-
 extern "C" int mi3pt_get_counters(mi3pt_ctx *ctx, uint64_t out[MI3PT_CNT_COUNT])
 {
     PT_GROUP(ctx, group_counters(ctx, out));
@@ -2820,103 +655,5 @@ extern "C" int mi3pt_reset_counters(mi3pt_ctx *ctx)
     if (ctx->nblocks == 0) return MI3PT_OK;
     HIP_TRY(hipMemsetAsync(ctx->d_block_counters, 0, 2 * (size_t)ctx->nblocks * pt::CNT_COUNT * 8, ctx->stream));
     ctx->main_dirty = true;
-    return MI3PT_OK;
-}
-
-// Which kernel variant a raytrace submit would run right now (after the lazy scene analyses): the
-// selected one, or what it falls back to when the scene does not admit it.
-extern "C" int mi3pt_debug_active_variant(mi3pt_ctx *ctx, int *variant)
-{
-    PT_GROUP(ctx, mi3pt_debug_active_variant(group_member0(ctx), variant));
-    if (!ctx || !variant) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = require_idle(ctx)) return rc;
-    if (int rc = check_scene(ctx)) return rc;
-    if (int rc = prepare_layout(ctx)) return rc;
-    if (int rc = prepare_cull(ctx)) return rc;
-    *variant = pick_variant(ctx);
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_debug_last_launch(mi3pt_ctx *ctx, int *kind, int *variant, int *lean, int *workgroups)
-{
-    PT_GROUP(ctx, mi3pt_debug_last_launch(group_member0(ctx), kind, variant, lean, workgroups));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    if (kind) *kind = ctx->last_route.kind;
-    if (variant) *variant = ctx->last_route.variant;
-    if (lean) *lean = ctx->last_route.lean ? 1 : 0;
-    if (workgroups) *workgroups = ctx->last_route.blocks;
-    return MI3PT_OK;
-}
-
-extern "C" int mi3pt_device_build_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t nodes_capacity_bytes, size_t *nnodes_out, float *build_ms)
-{
-    PT_GROUP(ctx, mi3pt_device_build_bvh(group_member0(ctx), nodes_out, nodes_capacity_bytes, nnodes_out, build_ms));
-    if (int rc = require_idle(ctx)) return rc;
-    if (!nodes_out || !nnodes_out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (!ctx->d_tris || ctx->ntris == 0) return pt_set_error(MI3PT_ERR_STATE, "no triangles uploaded (mi3pt_upload_triangles)");
-    const size_t nodes = 2 * ctx->ntris - 1;
-    if (nodes_capacity_bytes < nodes * MI3PT_BVHNODE_STRIDE) return pt_set_error(MI3PT_ERR_INVALID, "node buffer too small");
-    std::string err;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    if (pt::lbvh_build(ctx->d_tris, ctx->ntris, nodes_out, build_ms, ctx->stream, err) != 0)
-        return pt_set_error(MI3PT_ERR_HIP, "device BVH build: " + err);
-    *nnodes_out = nodes;
-    return MI3PT_OK;
-}
-
-// The device builders by name (pt_lbvh.hip, pt_ploc.hip).  Reads d_tris, writes temporaries of its own: no field of the context moves.
-extern "C" int mi3pt_device_build_bvh_ex(mi3pt_ctx *ctx, const mi3pt_bvh_build_params *params, void *nodes_out, size_t nodes_capacity_bytes,
-                                         size_t *nnodes_out, mi3pt_bvh_build_info *info)
-{
-    PT_GROUP(ctx, mi3pt_device_build_bvh_ex(group_member0(ctx), params, nodes_out, nodes_capacity_bytes, nnodes_out, info));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    if (!params || !nodes_out || !nnodes_out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (params->method != MI3PT_BVH_METHOD_LBVH && params->method != MI3PT_BVH_METHOD_PLOC)
-        return pt_set_error(MI3PT_ERR_INVALID, "device BVH build: unknown method");
-    if (params->flags != 0) return pt_set_error(MI3PT_ERR_INVALID, "device BVH build: flags must be 0");
-    if (params->method == MI3PT_BVH_METHOD_PLOC) {
-        if (params->radius < 1 || params->radius > 64) return pt_set_error(MI3PT_ERR_INVALID, "device BVH build: radius must be 1 .. 64");
-        if (params->max_search_iterations < 0 || params->max_search_iterations > 65535)
-            return pt_set_error(MI3PT_ERR_INVALID, "device BVH build: max_search_iterations must be 0 .. 65535");
-    }
-    if (int rc = require_idle(ctx)) return rc;
-    if (!ctx->d_tris || ctx->ntris == 0) return pt_set_error(MI3PT_ERR_STATE, "no triangles uploaded (mi3pt_upload_triangles)");
-    const size_t nodes = 2 * ctx->ntris - 1;
-    if (nodes_capacity_bytes < nodes * MI3PT_BVHNODE_STRIDE) return pt_set_error(MI3PT_ERR_INVALID, "node buffer too small");
-    std::string err;
-    mi3pt_bvh_build_info got = { 0.0f, 0u, 0u };
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    const int rc = params->method == MI3PT_BVH_METHOD_LBVH
-        ? pt::lbvh_build(ctx->d_tris, ctx->ntris, nodes_out, &got.build_ms, ctx->stream, err)
-        : pt::ploc_build(ctx->d_tris, ctx->ntris, params->radius, params->max_search_iterations, nodes_out, &got.build_ms,
-                         &got.search_iterations, &got.forced_iterations, ctx->stream, err);
-    if (rc != 0) return pt_set_error(MI3PT_ERR_HIP, "device BVH build: " + err);
-    *nnodes_out = nodes;
-    if (info) *info = got;
-    return MI3PT_OK;
-}
-
-// The boxes of the uploaded tree re-fitted to the uploaded triangles (pt_refit.hip).  Reads d_nodes and d_tris, writes temporaries of its own:
-// no field of the context moves.
-extern "C" int mi3pt_device_refit_bvh(mi3pt_ctx *ctx, void *nodes_out, size_t nodes_capacity_bytes, size_t *nnodes_out, float *refit_ms)
-{
-    PT_GROUP(ctx, mi3pt_device_refit_bvh(group_member0(ctx), nodes_out, nodes_capacity_bytes, nnodes_out, refit_ms));
-    if (!ctx) return pt_set_error(MI3PT_ERR_INVALID, "null context");
-    if (!nodes_out || !nnodes_out) return pt_set_error(MI3PT_ERR_INVALID, "null argument");
-    if (int rc = require_idle(ctx)) return rc;
-    if (!ctx->d_nodes || ctx->nnodes == 0) return pt_set_error(MI3PT_ERR_STATE, "no BVH uploaded (mi3pt_upload_bvh)");
-    if (!ctx->d_tris || ctx->ntris == 0) return pt_set_error(MI3PT_ERR_STATE, "no triangles uploaded (mi3pt_upload_triangles)");
-    if (!ctx->tree_proper)
-        return pt_set_error(MI3PT_ERR_STATE, "refit needs a proper tree: every node reached once from node 0, one leaf per triangle, depth under 64");
-    if (ctx->nodes_reached != ctx->nnodes)
-        return pt_set_error(MI3PT_ERR_STATE, "refit needs every record of the buffer within reach of node 0: the uploaded tree holds records the root does not reach");
-    if (ctx->max_tri_ref >= (int64_t)ctx->ntris)
-        return pt_set_error(MI3PT_ERR_STATE, "BVH references a triangle index beyond the triangle buffer");
-    if (nodes_capacity_bytes < ctx->nnodes * MI3PT_BVHNODE_STRIDE) return pt_set_error(MI3PT_ERR_INVALID, "node buffer too small");
-    std::string err;
-    HIP_TRY(ctx_stream_sync(ctx, ctx->stream));
-    if (pt::refit_bvh(ctx->d_tris, ctx->ntris, ctx->d_nodes, ctx->nnodes, nodes_out, refit_ms, ctx->stream, err) != 0)
-        return pt_set_error(MI3PT_ERR_HIP, "device BVH refit: " + err);
-    *nnodes_out = ctx->nnodes;
     return MI3PT_OK;
 }

@@ -4,17 +4,25 @@
 #pragma once
 #include "pt_ctx.h"
 
-// ================================================ pt_context.hip: the core, the scene, the launch path, the images ================================================
+// ================================================ pt_context.hip: the core ================================================
 // (the last error: pt_set_error / pt_last_error, pt_internal.h)
 
 // A context, and its device current: MI3PT_ERR_INVALID for a null handle, MI3PT_ERR_HIP where hipSetDevice fails.
 int require_ctx(mi3pt_ctx *ctx);
-// require_ctx + flush of the deferred frame queue: every entry point that observes or changes device state goes through this.
-int require_idle(mi3pt_ctx *ctx);
 // Every wait of a blocking entry point: for the event, or (ev == nullptr) for the stream; bounded while the launch gate is armed (a held
 // launch is released from the host after gate_timeout_ms without progress).  `why` goes into the warning.
 hipError_t ctx_wait(mi3pt_ctx *ctx, hipStream_t s, hipEvent_t ev, const char *why);
 static inline hipError_t ctx_stream_sync(mi3pt_ctx *ctx, hipStream_t s, const char *why = "stream wait") { return ctx_wait(ctx, s, nullptr, why); }
+static inline hipError_t ctx_event_sync(mi3pt_ctx *ctx, hipEvent_t ev, const char *why = "event wait") { return ctx_wait(ctx, nullptr, ev, why); }
+// ctx->batch_cap from the options and the tile split, capped by a quarter of the memory that is free now: after mi3pt_resize and after a
+// batch option changed.  Nothing to do before the first resize.
+void recompute_batch_cap(mi3pt_ctx *ctx);
+
+// Blocks of launch-invariant scalars for the raytrace kernel's service step (pt::RtService), one per batched launch.  Launches
+// alternate between two streams and at most two are in flight; a slot is rewritten (in stream order, by the setup kernel of
+// launch k + SERVICE_SLOTS) on the stream launch k ran on, i.e. after it.
+static const int SERVICE_SLOTS = 8;
+static inline size_t service_slot_bytes() { return (pt::service_block_bytes() + 255) / 256 * 256; }
 
 // ---- image planes: the local_rows x width images of a context (radiance, mean, feature images, filter images, moments) ----
 static inline size_t plane_texels(const mi3pt_ctx *ctx) { return (size_t)ctx->local_rows * ctx->width; }
@@ -26,6 +34,7 @@ hipError_t read_plane(mi3pt_ctx *ctx, const void *src, size_t nbytes, void *dst)
 static inline size_t conv_tiles_x(const mi3pt_ctx *ctx) { return ((size_t)ctx->width + 7) / 8; }
 static inline size_t conv_tiles_y(const mi3pt_ctx *ctx) { return ((size_t)ctx->local_rows + 7) / 8; }
 
+// ================================================ pt_ctx_scene.hip: the scene and its lazy analyses ================================================
 // The device's scene as the kernels take it: the buffers of the active layout, counts, flags.  After prepare_layout and prepare_cull.
 pt::SceneRefs scene_refs(const mi3pt_ctx *ctx);
 // The scene is complete when the three buffers agree with each other (MI3PT_ERR_STATE otherwise); an empty scene is legal.
@@ -35,6 +44,22 @@ int prepare_layout(mi3pt_ctx *ctx);
 // The lazy scene analysis behind the culling walks (kernel variants 9 .. 14); runs when the triangles, the tree or an option that shapes
 // the packets changed.
 int prepare_cull(mi3pt_ctx *ctx);
+
+// ================================================ pt_ctx_launch.hip: the launch path ================================================
+// require_ctx + flush of the deferred frame queue: every entry point that observes or changes device state goes through this.
+int require_idle(mi3pt_ctx *ctx);
+// Launches everything that is queued, batch_cap frames at a time; the queue is emptied even on failure.  The device is current already
+// (require_ctx): the lazy scene analyses and the features that work on the mean call this.
+int flush_pending(mi3pt_ctx *ctx);
+// The accumulate pass's uniforms as mi3pt_set_uniforms left them, and the tile of the image this context holds.
+pt::AccUniforms acc_uniforms(const mi3pt_ctx *ctx);
+pt::Tile tile_of(const mi3pt_ctx *ctx);
+// Folds parity `par`'s finished batch launch (its event pair, waited for) into the launch statistics; nothing pending: nothing done.
+int collect_rt_time(mi3pt_ctx *ctx, int par);
+// The fullscreen pass on the context's stream, from the mean (or the last radiance) into the canvas, with the uniforms `u_fs`.
+int run_fullscreen(mi3pt_ctx *ctx, const uint8_t *u_fs);
+
+// ================================================ pt_ctx_image.hip: the images and their features ================================================
 // Whether a first-hit pass walks the shipped walk's data (walk 13) -- after prepare_layout and prepare_cull.
 bool first_hit_walk_is_shipped(const mi3pt_ctx *ctx);
 

@@ -3116,7 +3116,7 @@ void launch_sky_samples(const RtLaunch &L, const uint32_t *tiles, int ntiles, ui
     hipLaunchKernelGGL(k_sky_samples, dim3((unsigned)ntiles, (unsigned)((L.nframes + 3) / 4)), dim3(256), 0, s, L, tiles, samples);
 }
 
-// What the launch that has just run COST per ray, for the host's choice of the next launch's build (pt_context.hip: adapt_walk): the
+// What the launch that has just run COST per ray, for the host's choice of the next launch's build (pt_ctx_launch.hip: adapt_walk): the
 // counter set's box tests and rays, summed over its blocks, as the difference to the previous call for that set.  A reset of the
 // counters in between (sums below the previous ones) restarts the difference.  One block; microseconds.
 __global__ void __launch_bounds__(256) k_walk_stats(const uint64_t *__restrict__ counters, int nblocks, uint64_t *prev, uint64_t *out, uint64_t seq)
